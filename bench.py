@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - SCF-iteration time and ERI shell-quartet throughput of the MI355X Hartree-Fock path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started plainly - then this process,
@@ -16,13 +16,21 @@ starts again at pass 0 (the runs' set-up - one-electron integrals, S^-1/2, guess
 Workloads (BASELINE.json configs; inputs are the fixture files under data/, nothing is random):
   N = 1  -> H2O / cc-pVTZ RHF (configs[2], the configuration the metric is quoted on; 58 bf, 32 131 unique quartets)
   N > 1  -> C6H6 / cc-pVDZ RHF (configs[4]): the class-sorted quartet list is dealt across the ranks, every rank digests its
-            shard and the partial Fock matrices are summed by one RCCL all-reduce per build (strong scaling).  The N = 1 line
-            carries the same workload's single-GPU numbers under "scaling_reference", and every N > 1 line under
+            shard and the partial Fock matrices are summed by one RCCL all-reduce per build (strong scaling).  With --full the N = 1
+            line carries the same workload's single-GPU numbers under "scaling_reference", and every N > 1 line under
             "same_workload_1gpu" (rank 0 times the unsharded workload on its own GPU before the sharded run, with the speed-up).
 `value` = unique shell quartets enumerated per step x K / elapsed (max over ranks), whole job.  `ms_per_step` = SCF-iteration time.
 
-Extra objects on the JSON line: "roofline" (the Fock build: hipEvent-timed inside the timed passes on the library's stream,
-binding roof first) and "cpu_baseline" (the oracle - a CPU restatement of the reference algorithm - on this host's cores).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the JSON line, whose "roofline" (the Fock build:
+hipEvent-timed inside the timed passes on the library's stream, binding roof first) is computed from those steps.  Everything that takes
+runs of its own is behind --full: the measured FP64 / HBM peaks and every launch of a build timed alone (roofline), the accumulation A/B,
+a cold SCF, the stored-tensor mode, the benzene scaling reference and, for N > 1, the same workload on one GPU, and "cpu_baseline" (the
+oracle - a CPU restatement of the reference algorithm - on this host's cores).  --no-extras, --no-scaling-reference and --no-cpu-baseline
+leave parts of that out again.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller (qc_scf_iterate's electronic energy and rms, the
+state's density and orbital energies, float64) as DIR/<name>.npy.  The inputs are the fixture files, so two builds of the project run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +39,8 @@ import socket
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -73,7 +83,8 @@ class Host:
 
 
 def timed_scf_passes(q, sysh, host, sync, steps, warmup, world_single=True):
-    """`steps` timed passes of real SCF runs (see the module docstring); returns elapsed seconds and what the passes were."""
+    """`steps` timed passes of real SCF runs (see the module docstring); returns elapsed seconds, what the passes were and what the
+    last of them computed."""
     # warm-up: one whole SCF run (code upload, stream tuning, Schwarz pass), at least `warmup` passes; it also tells how many
     # runs the timed region needs
     st = q.ScfStepper(sysh, stop_rule=EPS)
@@ -107,7 +118,7 @@ def timed_scf_passes(q, sysh, host, sync, steps, warmup, world_single=True):
     done, cur, passes, restarts = 0, 0, [], 0
     k_in_run = 0
     while done < steps:
-        _, rms = runs[cur].iterate()            # synchronises the library's stream at the end of every pass
+        e, rms = runs[cur].iterate()            # synchronises the library's stream at the end of every pass
         passes.append(k_in_run)
         done += 1; k_in_run += 1
         if rms < EPS and done < steps and cur + 1 < len(runs):
@@ -118,6 +129,8 @@ def timed_scf_passes(q, sysh, host, sync, steps, warmup, world_single=True):
     fock = sum(c["fock"] for c in cs) / max(1.0, sum(c["builds_timed"] for c in cs))          # hipEvent ms inside the passes
     linalg = sum(c["linalg"] for c in cs) / steps
     D = runs[0].density(0)
+    outputs = {"electronic_energy": np.array([e]), "rms": np.array([rms]), "density": runs[cur].density(0),
+               "orbital_energies": runs[cur].orbital_energies(0)}
     for r in runs:
         r.close()
     info = {"passes_timed": "SCF passes %s of %d run(s) from the Hueckel guess, stopping rule rms < %g (converges at pass %s)"
@@ -125,7 +138,7 @@ def timed_scf_passes(q, sysh, host, sync, steps, warmup, world_single=True):
             "warmup_runs": warm_runs, "assignment_search_ended": bool(frozen),
             "speculative_builds": {"consumed": int(sum(c["spec_hits"] for c in cs)), "discarded": int(sum(c["spec_lost"] for c in cs)),
                                    "builds_timed": int(sum(c["builds_timed"] for c in cs))}}
-    return dt, fock, linalg, D, info
+    return dt, fock, linalg, D, info, outputs
 
 
 _PEAKS = None
@@ -273,13 +286,13 @@ def cpu_baseline(mol, budget_s=12.0):
     return out
 
 
-def measure(torch, q, host, key, steps, warmup, world, rank, uid=None, with_units=True):
+def measure(torch, q, host, key, steps, warmup, world, rank, uid=None, with_units=True, with_peaks=True):
     mol = load(q, key)
     sysh = q.System(mol)
     if world > 1:
         sysh.comm_init(uid, rank, world)        # shard the quartet list, RCCL communicator for the partial-Fock all-reduce
     nq_total = sysh.n_quartets()
-    dt, fock_ms, linalg_ms, D, info = timed_scf_passes(q, sysh, host, torch.cuda.synchronize, steps, warmup, world == 1)
+    dt, fock_ms, linalg_ms, D, info, outputs = timed_scf_passes(q, sysh, host, torch.cuda.synchronize, steps, warmup, world == 1)
     ws = sysh.work_stats()
     res = {
         "value": nq_total * steps / dt, "ms_per_step": dt * 1e3 / steps, "steps": steps,
@@ -289,7 +302,7 @@ def measure(torch, q, host, key, steps, warmup, world, rank, uid=None, with_unit
         "iter_breakdown_ms": {"fock_build": fock_ms, "diis_eig_density": linalg_ms},
         "timed": info,
     }
-    res["roofline"] = roofline_of(ws, fock_ms, 0, measured_peaks(q))
+    res["roofline"] = roofline_of(ws, fock_ms, 0, measured_peaks(q) if with_peaks else None)
     if with_units:
         up = unit_profile(torch, q, sysh, D, reps=3)      # collective when sharded: every rank calls it
         res["roofline"]["kernel"] = "qc_fock_tier_kernel<LAB, TIER> + qc_fock_bm_kernel<LCD, HI>: %d concurrent launches = one Fock build" % len(up["units_alone"])
@@ -307,10 +320,22 @@ def measure(torch, q, host, key, steps, warmup, world, rank, uid=None, with_unit
         res["roofline"]["traffic_source"] = src
         res["committed_counters"] = {"source": src, "fock_build": pmc.get("fock_build"), "eigensolve": pmc.get("eigensolve")}
     sysh.close()
-    return res, mol
+    return res, mol, outputs
 
 
 MAX_LINE_BYTES = 4096      # the driver keeps an ~8 KB tail of stdout: the record must fit with room to spare
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every array as float64 in `path`/<name>.npy (the whole outputs: about 100 KB at the largest workload)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > MAX_DUMP_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, MAX_DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _r(x, sig=6):
@@ -459,9 +484,12 @@ def main():
     ap.add_argument("--steps", type=int, default=30)      # (two whole SCF runs of the headline workload: passes 0..14 twice)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="auto", choices=["auto"] + sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scaling-reference", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline (module docstring): peaks, per-launch "
+                    "profile, accumulation A/B, cold SCF, stored mode, scaling reference, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-scaling-reference", action="store_true", help="with --full: no scaling reference / one-GPU run of the workload")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline measurement and the measured peaks (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true", help="harness test without a GPU (not a measurement)")
     args = ap.parse_args()
 
@@ -492,18 +520,21 @@ def main():
 
     key = args.workload if args.workload != "auto" else ("h2o_ccpvtz" if world == 1 else "c6h6_ccpvdz")
     same_workload_1gpu = None
-    if world > 1 and not args.no_scaling_reference:
+    if world > 1 and args.full and not args.no_scaling_reference:
         # The N = 1 line of this benchmark is H2O/cc-pVTZ (the configuration the metric is quoted on), the N > 1 lines are the sharded
         # benzene workload: rank 0 first times the SAME workload unsharded on its own GPU (outside the timed region, the other ranks wait),
         # so that every multi-GPU line carries the single-GPU figure its speed-up is measured against.
         if rank == 0:
             # (bounded: the other ranks sit in the barrier below meanwhile)
-            r1, _ = measure(torch, q, Host(1, torch, dist), key, max(8, min(args.steps, 12)), 2, 1, 0, None, with_units=False)
+            r1, _, _ = measure(torch, q, Host(1, torch, dist), key, max(8, min(args.steps, 12)), 2, 1, 0, None, with_units=False)
             same_workload_1gpu = {"workload": WORKLOADS[key][2] + " direct-SCF iteration", "n_gpus": 1, "value": r1["value"],
                                   "ms_per_step": r1["ms_per_step"], "fock_build_ms": r1["iter_breakdown_ms"]["fock_build"],
                                   "diis_eig_density_ms": r1["iter_breakdown_ms"]["diis_eig_density"]}
         host.barrier()
-    res, mol = measure(torch, q, host, key, args.steps, args.warmup, world, rank, uid, with_units=not args.no_extras)
+    res, mol, outputs = measure(torch, q, host, key, args.steps, args.warmup, world, rank, uid,
+                                with_units=args.full and not args.no_extras, with_peaks=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     line = {
         "metric": "ERI shell-quartets/sec through one SCF iteration (ms_per_step = SCF iter time), RHF",
         "value": res["value"], "unit": "shell-quartets/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -524,12 +555,12 @@ def main():
         if same_workload_1gpu:
             same_workload_1gpu["speedup"] = res["value"] / same_workload_1gpu["value"]
             line["same_workload_1gpu"] = same_workload_1gpu
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         line["accumulation"] = accumulation_ab(q, mol)
         line["cold_scf"] = cold_scf(q, mol, EPS)
         if not args.no_scaling_reference and key == "h2o_ccpvtz":
             k2 = max(8, min(args.steps, 24))
-            r2, m2 = measure(torch, q, host, "c6h6_ccpvdz", k2, 2, 1, 0, None, with_units=True)
+            r2, m2, _ = measure(torch, q, host, "c6h6_ccpvdz", k2, 2, 1, 0, None, with_units=True)
             line["scaling_reference"] = {"workload": WORKLOADS["c6h6_ccpvdz"][2] + " direct-SCF iteration", "n_gpus": 1,
                                          "value": r2["value"], "ms_per_step": r2["ms_per_step"], "steps": k2,
                                          "passes": r2["timed"]["passes_timed"], "converges_at_pass": r2["timed"]["converges_at_pass"],

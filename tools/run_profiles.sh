@@ -1,7 +1,7 @@
 # Round profile set (run on the GPU box through gpurun): bash tools/run_profiles.sh <round tag, e.g. r03>
 # Per workload: (1) the bench line itself, (2) rocprofv3 --kernel-trace --stats of the same command, (3) PMC passes in their own
 # runs (separate --pmc passes, nothing but --kernel-trace beside them).  Under rocprofv3 the program goes directly after `--`.
-# Then, in the SAME invocation: the summaries (tools/make_profile_summary.py -> profiles/<tag>_*) and the default `python bench.py` line,
+# Then, in the SAME invocation: the summaries (tools/make_profile_summary.py -> profiles/<tag>_*) and the `python bench.py --full` line,
 # which quotes its HBM traffic from the PMC summary just written - so the two cannot disagree.  Everything lands under
 # gpurun_out/prof_<tag>/ (profiles/ of the box copy is mirrored into gpurun_out/prof_<tag>/profiles/ for the way back).
 TAG=${1:-r04}
@@ -26,7 +26,7 @@ cat $O/summary.txt
 WARM_RUNS=40 python tools/timeline_probe.py 2> $O/device_timeline_raw.txt || exit 1
 { echo "# tools/timeline_probe.py (QC_DEV_TIMELINE=1): H2O/cc-pVTZ RHF, one SCF run after 40 warm-up runs; microseconds on the device's 100 MHz clock,"; echo "# from the end of the previous pass's last kernel; unitN = launch unit N of the build (qc_unit_of), small2 = second launch of a cold pass"; grep "timeline\]\|events of the same" $O/device_timeline_raw.txt | tail -17; } > profiles/${TAG}_device_timeline.txt
 python tools/open_shell_fused_probe.py > profiles/${TAG}_o2_triplet_linear_algebra.txt 2>&1 || exit 1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 cp bench_detail.json $O/bench_default_detail.json
 cp $O/bench_default.json profiles/${TAG}_bench_default.json; cp $O/bench_default_detail.json profiles/${TAG}_bench_default_detail.json
 mkdir -p $O/profiles && cp profiles/${TAG}_* $O/profiles/
