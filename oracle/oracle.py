@@ -53,6 +53,7 @@ def lib():
         L.orc_g_rhf.argtypes = [C.c_int, _dp, _dp, _dp]
         L.orc_g_uhf.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
         L.orc_g_rhf_quartets.argtypes = [C.c_void_p, C.c_long, _ip, _dp, _dp]
+        L.orc_jk_quartets.argtypes = [C.c_void_p, C.c_long, _ip, _dp, _dp, _dp, _dp]
         L.orc_qr_solve.argtypes = [C.c_int, _dp, _dp, _dp]; L.orc_qr_solve.restype = C.c_int
         L.orc_core_guess.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
         L.orc_boys.argtypes = [C.c_int, C.c_double, _dp]
@@ -135,6 +136,39 @@ class Oracle:
         abcd = np.ascontiguousarray(abcd, np.int32).reshape(-1)
         lib().orc_g_rhf_quartets(self.h, len(abcd) // 4, abcd, np.ascontiguousarray(D, np.float64), G)
         return G
+
+    def jk_quartets(self, DJ, DK, abcd):
+        """(J, K) from a list of unique shell quartets: J contracted with DJ, K with DK (orc_jk_quartets).  Releases the GIL:
+        disjoint lists may be contracted from several threads at once."""
+        J, K = np.zeros((self.n, self.n)), np.zeros((self.n, self.n))
+        abcd = np.ascontiguousarray(abcd, np.int32).reshape(-1)
+        lib().orc_jk_quartets(self.h, len(abcd) // 4, abcd, np.ascontiguousarray(DJ, np.float64),
+                              np.ascontiguousarray(DK, np.float64), J, K)
+        return J, K
+
+    def unique_quartets(self):
+        """Every unique shell quartet (A >= B, C >= D, pair AB >= pair CD) as an int32 array of shape (nq, 4), built from the shell
+        count alone, in the order of orc_eri_full_strided."""
+        ns = lib().orc_nshells(self.h)
+        a, b = np.tril_indices(ns)                          # pair p = a (a + 1) / 2 + b, b <= a
+        p, q = np.tril_indices(len(a))                      # ket pair q <= bra pair p
+        out = np.empty((len(p), 4), np.int32)
+        out[:, 0], out[:, 1], out[:, 2], out[:, 3] = a[p], b[p], a[q], b[q]
+        assert len(out) == self.n_unique_quartets()
+        return out
+
+    def jk_all_quartets(self, DJ, DK, abcd=None, nthreads=None):
+        """(J, K) of every unique shell quartet (or of `abcd`), contracted by orc_jk_quartets in `nthreads` threads - one interleaved
+        chunk per thread, the chunks' matrices summed.  Default: min(16, the cores this process may use)."""
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        abcd = self.unique_quartets() if abcd is None else np.asarray(abcd, np.int32).reshape(-1, 4)
+        nt = max(1, min(nthreads or min(16, len(os.sched_getaffinity(0))), len(abcd)))
+        self.eri_shell_quartet(0, 0, 0, 0)                  # (the integral code's index tables are built before the threads start)
+        chunks = [np.ascontiguousarray(abcd[t::nt]) for t in range(nt)]
+        with ThreadPoolExecutor(nt) as ex:
+            parts = list(ex.map(lambda c: self.jk_quartets(DJ, DK, c), chunks))
+        return sum(P[0] for P in parts), sum(P[1] for P in parts)
 
     def g_uhf(self, D1, D2, eri):
         n = self.n

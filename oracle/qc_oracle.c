@@ -766,6 +766,37 @@ void orc_g_rhf_quartets(const Basis *B, long nq, const int *abcd, const double *
     free(buf);
 }
 
+/* The same digestion with J and K kept apart and each contracted with a density of its own: J[i,j] = sum_kl (ij|kl) DJ[k,l],
+ * K[i,j] = sum_kl (ik|jl) DK[k,l].  RHF: G = J(D) - K(D)/2; UHF (uhf.rs:210-227): G_a = J(D_a + D_b) - K(D_a).  J and K are
+ * overwritten.  Touches nothing shared, so disjoint sub-lists may be contracted in parallel threads and summed. */
+void orc_jk_quartets(const Basis *B, long nq, const int *abcd, const double *DJ, const double *DK, double *J, double *K) {
+    int n = B->nbasis;
+    double *buf = (double *)malloc(sizeof(double) * 15 * 15 * 15 * 15);
+    memset(J, 0, sizeof(double) * n * n);
+    memset(K, 0, sizeof(double) * n * n);
+    for (long t = 0; t < nq; t++) {
+        int sa = abcd[4 * t], sb = abcd[4 * t + 1], sc = abcd[4 * t + 2], sd = abcd[4 * t + 3];
+        const Shell *SA = &B->sh[sa], *SB = &B->sh[sb], *SC = &B->sh[sc], *SD = &B->sh[sd];
+        orc_eri_shell_quartet(B, sa, sb, sc, sd, buf);
+        double shellw = 1.0;                                  /* as in orc_g_rhf_quartets */
+        if (sa == sb) shellw *= 0.5;
+        if (sc == sd) shellw *= 0.5;
+        if (sa == sc && sb == sd) shellw *= 0.5;
+        for (int fa = 0; fa < SA->nfunc; fa++) for (int fb = 0; fb < SB->nfunc; fb++)
+        for (int fc = 0; fc < SC->nfunc; fc++) for (int fd = 0; fd < SD->nfunc; fd++) {
+            double v = shellw * buf[((fa * SB->nfunc + fb) * SC->nfunc + fc) * SD->nfunc + fd];
+            int i = SA->off + fa, j = SB->off + fb, k = SC->off + fc, l = SD->off + fd;
+            int cand[8][4] = {{i,j,k,l},{j,i,k,l},{i,j,l,k},{j,i,l,k},{k,l,i,j},{l,k,i,j},{k,l,j,i},{l,k,j,i}};
+            for (int c = 0; c < 8; c++) {
+                int *x = cand[c];
+                J[x[0] * n + x[1]] += DJ[x[2] * n + x[3]] * v;
+                K[x[0] * n + x[2]] += DK[x[1] * n + x[3]] * v;
+            }
+        }
+    }
+    free(buf);
+}
+
 static double energy_half_trace(int n, const double *D, const double *H, const double *G) {
     /* 0.5 * tr(D (2H + G)) (rhf.rs:84-85) */
     double e = 0.0;

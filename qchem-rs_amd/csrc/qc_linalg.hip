@@ -200,7 +200,7 @@ __global__ __launch_bounds__(QC_EIG_THREADS) void qc_jacobi_kernel(int n, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One-sided (Hestenes) Jacobi for matrices whose A and V do not both fit in LDS (98 < n <= 128).
+// One-sided (Hestenes) Jacobi for matrices whose A and V do not both fit in LDS (100 < n <= 128; n = 100 needs 163 072 bytes for both).
 // B = A + sigma I is made positive definite with a Gershgorin shift; the columns of G (initially B) are rotated
 // pairwise to mutual orthogonality, G <- G J.  At convergence G = U Sigma: the normalised columns are the
 // eigenvectors and ||g_i|| - sigma the eigenvalues, so only ONE n x n matrix has to live in LDS (column-major,
@@ -419,7 +419,7 @@ int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, dou
     const size_t lds2 = 2 * (size_t)m * ld * sizeof(double) + tail, lds1 = (size_t)m * ld * sizeof(double) + tail;
     const bool v_in_lds = lds2 <= 160 * 1024;
     static const bool force1 = getenv("QC_EIG_ONESIDED") != nullptr;
-    if ((!v_in_lds || force1) && n <= QC_EIG1_ROWS * QC_EIG1_TEAM) {   // 98 < n <= 128: one-sided variant, a single matrix in LDS
+    if ((!v_in_lds || force1) && n <= QC_EIG1_ROWS * QC_EIG1_TEAM) {   // 100 < n <= 128: one-sided variant, a single matrix in LDS
         const size_t l1 = ((size_t)m * (n | 1) + 32 + m) * sizeof(double) + (size_t)(m + 4) * sizeof(int) + 16;
         if (l1 <= 160 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(qc_jacobi1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);

@@ -334,7 +334,9 @@ def test_sym_eig_warm_start_regimes():
 
 
 def test_rhf_chloroform_sto3g_third_row_and_large_basis():
-    """Cl (6-primitive contractions, 33 functions) and a basis beyond the in-LDS eigensolver limit (benzene/6-311++G**, n = 174)."""
+    """Cl (6-primitive contractions, 33 functions) and a basis beyond the in-LDS eigensolver limit (benzene/6-311++G**, n = 174).
+    The G(2D) = 2 G(D) line holds by construction under fixed-point accumulation (the scale drops by one, every contribution doubles
+    exactly): it is no parity check - test_fock_above_n64_matches_the_oracle_quartet_contraction compares that build with the oracle."""
     q, s, o = _sys("chloroform", "STO-3G")
     out = q.restricted_hartree_fock(s, q.HartreeFockConfig(200, 1e-9))
     ref = o.rhf(200, 1e-9)
@@ -775,14 +777,18 @@ def test_schwarz_factors_and_screening():
     assert np.abs(G_all - G).max() < TOL_INT * max(1.0, np.abs(G_ref).max())
 
 
-@pytest.mark.parametrize("mol,basis,na,nb", [("water", "cc-pVDZ", 0, 0), ("oxygen", "cc-pVDZ", 9, 7), ("water", "cc-pVTZ", 0, 0), ("ethylene", "6-31G_st_st", 0, 0)])
+@pytest.mark.parametrize("mol,basis,na,nb", [("water", "cc-pVDZ", 0, 0), ("oxygen", "cc-pVDZ", 9, 7), ("water", "cc-pVTZ", 0, 0), ("ethylene", "6-31G_st_st", 0, 0),
+                                             ("ethylene", "cc-pVTZ", 0, 0)])
 def test_uhf_passes_match_oracle_one_by_one(mol, basis, na, nb):
     """The UHF loop body (uhf.rs:80-163) pass by pass: both Fock matrices from the OLD densities, per-spin DIIS(2,8), the averaged
     rms of uhf.rs:137 and the energy expression of uhf.rs:145-153 - closed shell under the reference's N/2 rule, and the open-shell
-    extension while its trajectory is still well conditioned (the first passes; later it amplifies rounding, see the triplet test)."""
+    extension while its trajectory is still well conditioned (the first passes; later it amplifies rounding, see the triplet test).
+    (ethylene/cc-pVTZ, n = 116: the generic launch sequence with f functions and the one-sided rotation kernel in LDS.)"""
     q, s, o = _sys(mol, basis)
     npass = 12 if na else 100
-    ref = o.uhf(npass if na else 100, 1e-10 if not na else 1e-30, n_alpha=na or -1, n_beta=nb or -1, trace=True)
+    I, _ = o.eri_strided_mt(0, 1, min(16, len(os.sched_getaffinity(0))))
+    ref = o.uhf(npass if na else 100, 1e-10 if not na else 1e-30, n_alpha=na or -1, n_beta=nb or -1, eri=I, trace=True)
+    del I
     st = q.ScfStepper(s, uhf=True, n_alpha=na, n_beta=nb)
     for k in range(min(len(ref["trace_energy"]), npass if na else 1000)):
         e, rms = st.iterate()
@@ -1014,4 +1020,188 @@ def test_fock_cartesian_f_shells_wide_ket_blocks():
     assert np.abs(Ga - o.g_uhf(Da, Db, I)).max() < TOL_INT * scale
     assert np.abs(Gb - o.g_uhf(Db, Da, I)).max() < TOL_INT * scale
     assert np.abs(s.eri() - I).max() < TOL_INT
+    s.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Shapes above n = 64: Fock builds against the oracle's contraction of the complete quartet list, the rotation eigensolvers at every
+# size regime, open-shell SCF on the generic launch sequence.
+
+def _jk_refs(o, Da, Db):
+    """RHF G(Da), UHF G_alpha and G_beta of every unique shell quartet, from the oracle's J and K (orc_jk_quartets): J is linear in
+    the density, so two contractions serve all three - G = J(Da) - K(Da)/2, G_a = J(Da + Db) - K(Da), G_b = J(Da + Db) - K(Db)."""
+    Ja, Ka = o.jk_all_quartets(Da, Da)
+    Jb, Kb = o.jk_all_quartets(Db, Db)
+    return Ja - 0.5 * Ka, Ja + Jb - Ka, Ja + Jb - Kb
+
+
+def _column_classes(s, n):
+    """{class id: quartets} of one instrumented build (qc_fock_profile; id = (BM << 12) | (LAB << 8) | (LCD << 4) | LGC).  The device
+    buffers come from the HIP runtime the library is bound to: the system's, or - if torch was loaded first - the copy torch bundles
+    (a second runtime in the process may not find the device once the first has opened it)."""
+    import ctypes as C
+    import sys
+    import qchem_rs_amd as q
+    q.hf.lib()
+    other = os.path.dirname(sys.modules["torch"].__file__) if "torch" in sys.modules else None
+    with open("/proc/self/maps") as f:
+        paths = sorted({l.split()[-1] for l in f if "libamdhip64.so" in l})
+    hip = C.CDLL(([p for p in paths if not (other and p.startswith(other))] or paths)[0])
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    D = np.ascontiguousarray(_rand_sym(n, 0))
+    dD, dG = C.c_void_p(), C.c_void_p()
+    assert hip.hipMalloc(C.byref(dD), D.nbytes) == 0 and hip.hipMalloc(C.byref(dG), D.nbytes) == 0
+    try:
+        assert hip.hipMemcpy(dD, D.ctypes.data_as(C.c_void_p), D.nbytes, 1) == 0          # hipMemcpyHostToDevice
+        assert hip.hipMemset(dG, 0, D.nbytes) == 0
+        pr = s.fock_profile(dD.value, dG.value, 1)
+    finally:
+        hip.hipFree(dD); hip.hipFree(dG)
+    return {int(c): int(k) for c, k in zip(pr["class_id"], pr["quartets"])}
+
+
+def _valu_fket_quartets(classes):
+    """Quartets of the d.d / f.p-ket column classes (LCD = 4) with a d.p ... f.f bra (LAB >= 3) in their 32-lane VALU form (LGC = 5) -
+    the lists longer than QC_MFMA4_MAX (qc_system.cpp); shorter ones run as matrix-core tiles in the 64-lane instance (LGC = 6)."""
+    return [k for c, k in classes.items() if not c >> 12 and (c >> 8) & 15 >= 3 and (c >> 4) & 15 == 4 and c & 15 == 5]
+
+
+@pytest.mark.parametrize("mol,basis", [("benzene", "6-311++G_st_st"), ("ethylene", "cc-pVTZ"), ("benzene", "cc-pVDZ")])
+def test_fock_above_n64_matches_the_oracle_quartet_contraction(mol, basis):
+    """RHF G and UHF G_alpha, G_beta (Da != Db) at n = 174 (benzene/6-311++G**: diffuse sp shells, 8.4 M quartets, beyond every in-LDS
+    eigensolver), 116 (ethylene/cc-pVTZ: f functions in a build above the bra-major merge limit, d.p / f.s and d.d / f.p bras whose
+    d.d / f.p-ket lists are too long for the matrix-core form) and 114 (benzene/cc-pVDZ: UHF with the bra-major workgroups' LDS rows
+    sized for two spins) against the oracle's J and K of the complete unique quartet list - built on the oracle side, not from the
+    product's plan - and bitwise repeatable on the same handle."""
+    q, s, o = _sys(mol, basis)
+    assert s.n > 64
+    if basis == "cc-pVTZ":
+        assert max(_valu_fket_quartets(_column_classes(s, s.n)), default=0) > 1024, "the VALU route of the f-basis build is gone"
+    Da, Db = _rand_sym(s.n, 71), _rand_sym(s.n, 72)
+    G = s.fock_rhf(Da)
+    Ga, Gb = s.fock_uhf(Da, Db)
+    G_ref, Ga_ref, Gb_ref = _jk_refs(o, Da, Db)
+    for X, R in ((G, G_ref), (Ga, Ga_ref), (Gb, Gb_ref)):
+        assert np.abs(X - R).max() < TOL_INT * max(1.0, np.abs(R).max())
+    assert np.array_equal(s.fock_rhf(Da), G)
+    Ga2, Gb2 = s.fock_uhf(Da, Db)
+    assert np.array_equal(Ga2, Ga) and np.array_equal(Gb2, Gb)
+    s.close()
+
+
+@pytest.mark.parametrize("which", ["water", "oxygen-cartesian"])
+def test_fock_f_basis_valu_route_on_small_systems(which, monkeypatch, tmp_path):
+    """QC_MFMA4_MAX = 0 (read per system): every d.d / f.p-ket list of a d.p ... f.f bra takes the 32-lane VALU form inside the
+    f-capable wide-ket kernels - the route of long lists (ethylene/cc-pVTZ and larger) - on water/cc-pVTZ and on O2/cc-pVTZ with
+    Cartesian d and f shells, where the dense tensor is cheap.  RHF and UHF against the dense contraction, bitwise repeatable."""
+    import json
+    import qchem_rs_amd as q
+    from oracle.oracle import Oracle
+    from conftest import data
+    if which == "water":
+        m = load_system("water", "cc-pVTZ")
+    else:
+        b = json.load(open(data("basis", "cc-pVTZ.json")))
+        for el in b["elements"].values():
+            for sh in el["electron_shells"]:
+                if sh["angular_momentum"][0] >= 2:
+                    sh["function_type"] = "gto_cartesian"
+        f = tmp_path / "cc-pVTZ-cart.json"
+        f.write_text(json.dumps(b))
+        m = q.MolecularSystem.load(data("mol", "oxygen.json"), q.BasisSet.load(str(f)))
+    o = Oracle(m)
+    s_def = q.System(m)
+    nq_def = sum(_valu_fket_quartets(_column_classes(s_def, s_def.n)))
+    s_def.close()
+    monkeypatch.setenv("QC_MFMA4_MAX", "0")
+    s = q.System(m)
+    monkeypatch.delenv("QC_MFMA4_MAX")
+    nq = sum(_valu_fket_quartets(_column_classes(s, s.n)))
+    assert nq > nq_def, (nq, nq_def)
+    I = o.eri()
+    D, Da, Db = _rand_sym(s.n, 81), _rand_sym(s.n, 82), _rand_sym(s.n, 83)
+    G_ref = o.g_rhf(D, I)
+    G = s.fock_rhf(D)
+    assert np.abs(G - G_ref).max() < TOL_INT * max(1.0, np.abs(G_ref).max())
+    Ga, Gb = s.fock_uhf(Da, Db)
+    Ga_ref, Gb_ref = o.g_uhf(Da, Db, I), o.g_uhf(Db, Da, I)
+    assert np.abs(Ga - Ga_ref).max() < TOL_INT * max(1.0, np.abs(Ga_ref).max())
+    assert np.abs(Gb - Gb_ref).max() < TOL_INT * max(1.0, np.abs(Gb_ref).max())
+    assert np.array_equal(s.fock_rhf(D), G)
+    Ga2, Gb2 = s.fock_uhf(Da, Db)
+    assert np.array_equal(Ga2, Ga) and np.array_equal(Gb2, Gb)
+    s.close()
+
+
+@pytest.mark.parametrize("n", [24, 64, 100, 101, 114, 128, 129, 174, 230])
+def test_rotation_eigensolvers_at_every_size_regime(n):
+    """The single-workgroup Jacobi kernels of qc_eig_device - two-sided with A and V in LDS up to n = 100 (qc_jacobi_kernel<true>),
+    one-sided in LDS for 101..128 (qc_jacobi1_kernel), one-sided in global memory above (qc_jacobi1g_kernel) - every eigensolve of
+    open-shell UHF and the fallback of the tridiagonal path.  Reached through sym_eig_warm(A, I): the refinement finds a dense A far
+    from diagonal (emax > 0.1), falls back to rotations on X^T A X = A exactly, and V = I Q is exact.  Dense random spectra and
+    Q diag(w) Q^T with exactly repeated eigenvalues and 1e-9 clusters, with the bars of test_sym_eig; at n = 114 and 174 also the
+    near-eigenvector start of an open-shell pass (perturbation 0.3), with the bars of test_sym_eig_warm_start_regimes."""
+    import qchem_rs_amd as q
+    s = q.System(load_system("hydrogen", "STO-3G"))
+    rng = np.random.default_rng(500 + n)
+    d = np.sort(rng.uniform(-10, 10, n))
+    for k in range(0, n - 7, 12):
+        d[k + 1] = d[k]                                        # exactly repeated
+        d[k + 5] = d[k + 4] + 1e-9; d[k + 6] = d[k + 4] + 2e-9     # a 1e-9 cluster
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    A2 = (Q * d) @ Q.T; A2 = 0.5 * (A2 + A2.T)
+    for A in (_rand_sym(n, 900 + n), A2):
+        V, w = s.sym_eig_warm(A, np.eye(n))
+        w_ref = np.linalg.eigvalsh(A)
+        assert np.all(np.diff(w) >= 0)
+        assert np.abs(w - w_ref).max() < 1e-12 * max(1.0, np.abs(w_ref).max())
+        assert np.abs(V.T @ V - np.eye(n)).max() < 1e-12
+        assert np.abs(A @ V - V * w).max() < 1e-11 * max(1.0, np.abs(w_ref).max())
+    if n in (114, 174):
+        _, V0 = np.linalg.eigh(A2)
+        P = rng.standard_normal((n, n)); B = A2 + 0.3 * (P + P.T)
+        V, w = s.sym_eig_warm(B, V0)
+        assert np.all(np.diff(w) >= 0)
+        assert np.abs(w - np.linalg.eigvalsh(B)).max() < 1e-11
+        assert np.abs(V.T @ V - np.eye(n)).max() < 1e-12
+        assert np.abs(B @ V - V * w).max() < 1e-10
+    s.close()
+
+
+@pytest.mark.parametrize("basis", ["6-311++G_st_st", "cc-pVTZ"])
+def test_open_shell_passes_above_n64_match_oracle(basis):
+    """Triplet ethylene (n_alpha = 9, n_beta = 7) at n = 72 (6-311++G**: the generic launch sequence - GEMMs, device DIIS - with the
+    two-sided rotation kernel) and n = 116 (cc-pVTZ: f functions, the one-sided LDS rotation kernel) pass by pass against the oracle's
+    trace.  The oracle does not converge either case in 200 passes (never-reset DIIS, as for O2), so the first 12 passes are compared,
+    with the open-shell bars of test_uhf_passes_match_oracle_one_by_one; pass 0 to 1e-9.  Then <S^2> against numpy on the densities,
+    and a second run repeats the first bit for bit."""
+    q, s, o = _sys("ethylene", basis)
+    assert s.n > 64
+    I, _ = o.eri_strided_mt(0, 1, min(16, len(os.sched_getaffinity(0))))
+    ref = o.uhf(12, 1e-30, n_alpha=9, n_beta=7, eri=I, trace=True)
+    del I
+    assert len(ref["trace_energy"]) >= 12
+
+    def run():
+        st = q.ScfStepper(s, uhf=True, n_alpha=9, n_beta=7)
+        tr = [st.iterate() for _ in range(12)]
+        out = tr, st.density(0), st.density(1), st.spin_square()
+        st.close()
+        return out
+
+    tr, Da, Db, s2 = run()
+    for k, (e, rms) in enumerate(tr):
+        tol = 1e-9 if k == 0 else 1e-7
+        assert abs(e - ref["trace_energy"][k]) < tol * max(1.0, abs(e)), k
+        if k == 0:
+            assert abs(rms - ref["trace_rms"][0]) < 1e-9 * max(1.0, ref["trace_rms"][0])
+        else:
+            assert abs(rms - ref["trace_rms"][k]) < tol + 1e-4 * ref["trace_rms"][k], k
+    S = o.overlap()
+    assert abs(s2 - (1.0 * 2.0 + 7 - np.trace(Da @ S @ Db @ S))) < 1e-10
+    tr2, Da2, Db2, s2b = run()
+    assert tr2 == tr and np.array_equal(Da2, Da) and np.array_equal(Db2, Db) and s2b == s2
     s.close()
