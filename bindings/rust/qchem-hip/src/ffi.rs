@@ -29,6 +29,19 @@ pub struct QcHfOutput {
     pub ms_tuner: f64,
 }
 
+/// MP2 correlation energy (`qc_scf_mp2` / `qc_mp2`).
+#[repr(C)]
+pub struct QcMp2Output {
+    pub e_os: f64,
+    pub e_ss: f64,
+    pub e_corr: f64,
+    pub ms_tensor: f64,
+    pub ms_transform: f64,
+    pub ms_energy: f64,
+    pub n_frozen: i32,
+    pub reserved: [i32; 7],
+}
+
 pub const QC_OK: c_int = 0;
 pub const QC_NOT_CONVERGED: c_int = 1;
 pub const QC_DIIS_SINGULAR: c_int = 2;
@@ -62,6 +75,13 @@ extern "C" {
     pub fn qc_scf_set_stop_rule(st: *mut QcScfState, epsilon: f64) -> c_int;
     pub fn qc_scf_counters(st: *mut QcScfState, out: *mut f64, n: c_int) -> c_int;
     pub fn qc_scf_end(st: *mut QcScfState);
+    /// MO coefficients of the last Roothaan step, row-major n x n: out[i*n+k] = component i of MO k (ascending energies).
+    pub fn qc_scf_coefficients(st: *mut QcScfState, spin: c_int, out: *mut f64) -> c_int;
+    /// MP2 from the state's last orbitals; the state is left as it was.
+    pub fn qc_scf_mp2(st: *mut QcScfState, n_frozen: i32, out: *mut QcMp2Output) -> c_int;
+    /// MP2 from caller orbitals: nspin 1 (C n*n, eps n, nocc[0]) or 2 (C 2*n*n, eps 2*n, nocc = [n_alpha, n_beta]).
+    pub fn qc_mp2(sys: *mut QcSystem, nspin: c_int, c: *const f64, eps: *const f64, nocc: *const i32, n_frozen: i32,
+                  out: *mut QcMp2Output) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

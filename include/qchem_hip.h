@@ -154,6 +154,35 @@ int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon);
 int qc_scf_counters(qc_scf_state *st, double *out, int n);
 void qc_scf_end(qc_scf_state *st);
 
+/* ---- after SCF (not in the reference).  MO coefficients of the state's last Roothaan step, n*n to the host, V[i*n+k] = component i of
+ * MO k (the layout of qc_sym_eig), columns in the order of qc_scf_orbital_energies (ascending).  spin 0 / 1 (UHF beta).  QC_ERR_INVALID
+ * before the first qc_scf_iterate. */
+int qc_scf_coefficients(qc_scf_state *st, int spin, double *out_nxn);
+
+/* ---- MP2 correlation energy, conventional: the AO tensor is built in HBM, transformed to (ia|jb) by four f64 MFMA quarter
+ * transformations and freed at the end of the call.  Needs ~8 (n^4 + o n^3 + o v n^2 + ...) bytes of free HBM (QC_ERR_UNSUPPORTED
+ * otherwise, and on a sharded handle).  With D = e_i + e_j - e_a - e_b over active orbitals (the lowest n_frozen of each spin take no part):
+ *   RHF: e_os = sum (ia|jb)^2 / D,  e_ss = sum (ia|jb) [(ia|jb) - (ib|ja)] / D
+ *   UHF: e_os = sum (i_a a_a|j_b b_b)^2 / D,  e_ss = sum over both spins of 1/2 sum (ia|jb) [(ia|jb) - (ib|ja)] / D
+ * QC_ERR_INVALID for null pointers, n_frozen < 0 or > min(nocc), or any D >= 0 (checked on the host from the orbital energies, before
+ * the device is touched).  Empty blocks (no electrons or no virtuals in one spin) contribute 0.  The result is bitwise reproducible. */
+typedef struct {
+    double e_os;          /* opposite-spin part of the MP2 correlation energy */
+    double e_ss;          /* same-spin part */
+    double e_corr;        /* e_os + e_ss */
+    double ms_tensor, ms_transform, ms_energy;   /* wall time of the phases (stream-synchronised) */
+    int32_t n_frozen;
+    int32_t reserved[7];
+} qc_mp2_output;
+
+/* MP2 from the state's last C and orbital energies (what qc_scf_coefficients / qc_scf_orbital_energies report).  The state is left
+ * exactly as it was: qc_scf_iterate may be called again. */
+int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out);
+
+/* The same from caller-supplied orbitals (host pointers).  nspin 1: C n*n, eps n, nocc[0] doubly occupied.
+ * nspin 2: C = [Ca; Cb] 2*n*n, eps 2*n, nocc = {n_alpha, n_beta}. */
+int qc_mp2(qc_system *sys, int nspin, const double *C, const double *eps, const int32_t *nocc, int32_t n_frozen, qc_mp2_output *out);
+
 /* ---- Fock mode of the SCF drivers on this handle.  0 (default): direct - quartets are evaluated and digested every pass.
  * 1: stored - the reference's own conventional algorithm with the tensor resident in HBM: molint::eri once (rhf.rs:45),
  * electron_terms (rhf.rs:58-62), then one streaming GEMV per pass (rhf.rs:152-167 / uhf.rs:216-226).  Needs ~18 n^4 bytes

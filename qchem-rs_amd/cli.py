@@ -2,11 +2,13 @@
 
 Same sub-commands, flags, defaults and printed lines as `qchem-cli` (main.rs:20-62 flags, :98-105 / :143-151 output: three
 decimals, Rust's `{:3.3}` / `{:3.3?}` / Duration `{:0.2?}` formats), so a user of the reference finds the contract unchanged.
-Two additions, both opt-in:
+Three additions, all opt-in:
   * `--json` prints one JSON object with full-precision fields after the reference's lines;
   * `uhf -c/--charge -s/--spin-multiplicity` are honoured (the reference parses and ignores them, main.rs:111 "TODO"):
     with either given, n_alpha / n_beta follow from charge and multiplicity and an `<S^2>` line is added.  With both left at
-    0 the behaviour is the reference's N/2 rule (uhf.rs:43-45).
+    0 the behaviour is the reference's N/2 rule (uhf.rs:43-45);
+  * `--mp2 [--frozen-core N]` adds the MP2 correlation energy of the converged determinant after the reference's lines (the SCF
+    then runs pass by pass through hf.ScfStepper; its lines are those of the run without the flag).
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -67,7 +69,30 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--max-iterations", type=int, default=100)
         s.add_argument("--epsilon", type=float, default=1e-6)
         s.add_argument("--json", action="store_true", help="also print one JSON object with full-precision fields")
+        s.add_argument("--mp2", action="store_true", help="also compute the MP2 correlation energy of the converged determinant")
+        s.add_argument("--frozen-core", type=int, default=None, metavar="N",
+                       help="leave the lowest N orbitals of each spin out of the MP2 sums (requires --mp2)")
     return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.frozen_core is not None and not args.mp2:
+        p.error("--frozen-core requires --mp2")
+    if args.frozen_core is not None and args.frozen_core < 0:
+        p.error("--frozen-core must not be negative")
+    return args
+
+
+def _print_mp2(mp2: "hf.Mp2Output", e_hf: float) -> None:
+    print("mp2 correlation energy: " + fmt_f(mp2.e_corr))
+    print("mp2 total energy: " + fmt_f(e_hf + mp2.e_corr))
+
+
+def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
+    return {"e_os": mp2.e_os, "e_ss": mp2.e_ss, "e_corr": mp2.e_corr, "e_total": e_hf + mp2.e_corr, "n_frozen": mp2.n_frozen,
+            "timings_ms": {"tensor": mp2.ms_tensor, "transform": mp2.ms_transform, "energy": mp2.ms_energy}}
 
 
 def occupations(n_electrons_neutral: int, charge: int, multiplicity: int) -> Tuple[int, int]:
@@ -93,7 +118,13 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    out = hf.restricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
+    mp2 = None
+    config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
+    if args.mp2:
+        res = hf.restricted_mp2(system, config, args.frozen_core or 0)
+        out, mp2 = res if res is not None else (None, None)
+    else:
+        out = hf.restricted_hartree_fock(system, config)
     elapsed = time.perf_counter() - start
     if out is None:
         return _not_converged()
@@ -102,10 +133,15 @@ def run_rhf(args) -> int:
     print("nuclear repulsion energy: " + fmt_f(out.nuclear_repulsion))
     print("hartree fock energy: " + fmt_f(out.total_energy()))
     print("orbital energies: " + fmt_vec(out.orbital_energies))
+    if mp2 is not None:
+        _print_mp2(mp2, out.total_energy())
     if args.json:
-        print(json.dumps({"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
-                          "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
-                          "orbital_energies": list(out.orbital_energies), "seconds": elapsed, "timings_ms": out.timings_ms}))
+        doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
+               "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
+               "orbital_energies": list(out.orbital_energies), "seconds": elapsed, "timings_ms": out.timings_ms}
+        if mp2 is not None:
+            doc["mp2"] = _mp2_json(mp2, out.total_energy())
+        print(json.dumps(doc))
     return 0
 
 
@@ -117,11 +153,11 @@ def run_uhf(args) -> int:
     if extension:
         n_alpha, n_beta = occupations(system.n_electrons, args.charge, args.spin_multiplicity)
     start = time.perf_counter()
-    s2 = None
-    if not extension:
+    s2 = mp2 = None
+    if not extension and not args.mp2:
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
-        # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> of the final determinant can be read
+        # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
         handle = hf.System(system)
         st = hf.ScfStepper(handle, uhf=True, n_alpha=n_alpha, n_beta=n_beta)
         out = None
@@ -129,9 +165,12 @@ def run_uhf(args) -> int:
             for it in range(args.max_iterations + 1):                       # 0..=max_iterations, uhf.rs:82
                 e, rms = st.iterate()
                 if rms / 2.0 < args.epsilon:                                # uhf.rs:139
-                    s2 = st.spin_square()
+                    if extension:
+                        s2 = st.spin_square()
                     out = hf.UnrestrictedHartreeFockOutput(list(st.orbital_energies(0)), list(st.orbital_energies(1)), e,
                                                            handle.nuclear_repulsion(), it)
+                    if args.mp2:
+                        mp2 = st.mp2(args.frozen_core or 0)
                     break
         finally:
             st.close()
@@ -147,17 +186,22 @@ def run_uhf(args) -> int:
     print("orbital energies beta spin: " + fmt_vec(out.orbital_energies_beta))
     if s2 is not None:
         print("<S^2>: %s (n_alpha %d, n_beta %d)" % (fmt_f(s2), n_alpha, n_beta))
+    if mp2 is not None:
+        _print_mp2(mp2, out.total_energy())
     if args.json:
-        print(json.dumps({"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
-                          "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
-                          "orbital_energies_alpha": list(out.orbital_energies_alpha),
-                          "orbital_energies_beta": list(out.orbital_energies_beta), "n_alpha": n_alpha, "n_beta": n_beta,
-                          "spin_square": s2, "seconds": elapsed, "timings_ms": out.timings_ms}))
+        doc = {"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
+               "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
+               "orbital_energies_alpha": list(out.orbital_energies_alpha),
+               "orbital_energies_beta": list(out.orbital_energies_beta), "n_alpha": n_alpha, "n_beta": n_beta,
+               "spin_square": s2, "seconds": elapsed, "timings_ms": out.timings_ms}
+        if mp2 is not None:
+            doc["mp2"] = _mp2_json(mp2, out.total_energy())
+        print(json.dumps(doc))
     return 0
 
 
 def main(argv: Optional[List[str]] = None) -> int:
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     return run_rhf(args) if args.command == "rhf" else run_uhf(args)
 
 

@@ -1146,6 +1146,39 @@ int qc_scf_density(qc_scf_state *st, int spin, double *out) {
     QC_HIP_CHECK(hipMemcpy(out, st->D[spin].p, nn * sizeof(double), hipMemcpyDeviceToHost));
     return QC_OK;
 }
+int qc_scf_coefficients(qc_scf_state *st, int spin, double *out) {
+    if (!st || !out || spin < 0 || spin > (st->uhf ? 1 : 0) || st->passes == 0) return QC_ERR_INVALID;
+    const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;
+    QC_HIP_CHECK(hipStreamSynchronize(st->S->stream));
+    QC_HIP_CHECK(hipMemcpy(out, st->Cs.p + spin * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
+    return QC_OK;
+}
+int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out) {
+    if (!st || !out || st->passes == 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    const int n = S->nbasis, nspin = st->uhf ? 2 : 1;
+    std::vector<double> eps((size_t)nspin * n);
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    QC_HIP_CHECK(hipMemcpy(eps.data(), st->ws.p, eps.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int32_t nocc[2] = {st->nocc[0], st->nocc[1]};
+    int rc = qc_mp2_validate(n, nspin, eps.data(), nocc, n_frozen);
+    if (rc != QC_OK) return rc;
+    return qc_mp2_device(S, nspin, st->Cs.p, st->ws.p, nocc, n_frozen, out);   // (reads Cs / ws, writes nothing of the state)
+}
+int qc_mp2(qc_system *S, int nspin, const double *C, const double *eps, const int32_t *nocc, int32_t n_frozen, qc_mp2_output *out) {
+    if (!S || !C || !eps || !nocc || !out || (nspin != 1 && nspin != 2)) return QC_ERR_INVALID;
+    const int n = S->nbasis;
+    int rc = qc_mp2_validate(n, nspin, eps, nocc, n_frozen);
+    if (rc != QC_OK) return rc;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if ((rc = qc_device_init(S)) != QC_OK) return rc;
+    const size_t nn = (size_t)n * n;
+    DevBuf dC, dE;
+    if (dC.alloc(nspin * nn) != QC_OK || dE.alloc((size_t)nspin * n) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dC.p, C, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(dE.p, eps, nspin * n * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    return qc_mp2_device(S, nspin, dC.p, dE.p, nocc, n_frozen, out);
+}
 int qc_scf_matrix(qc_scf_state *st, int which, double *out) {
     if (!st || !out || which < 0 || which > 2) return QC_ERR_INVALID;
     const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;

@@ -291,6 +291,11 @@ struct QcFockArgs {
     bool fold_joins = false;
 };
 int qc_launch_eri_full(qc_system *S, double *d_out);
+// MP2 (qc_mp2.hip).  validate: host-side argument and denominator checks of qc_mp2 / qc_scf_mp2 (eps: nspin n-vectors on the host).
+// device: the energies from orbitals in HBM (dC: nspin n x n blocks, dEps: nspin n-vectors), on the handle's stream; the AO tensor and
+// the intermediates live for the duration of the call.
+int qc_mp2_validate(int n, int nspin, const double *eps, const int32_t *nocc, int n_frozen);
+int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps, const int32_t *nocc, int n_frozen, qc_mp2_output *out);
 int qc_schwarz_device(qc_system *S);     // fills pairQ / imax from the (P|P) quartets, then screens the work lists
 // fixed-point scale of a build from its densities: out[0] = 2^S, out[1] = 2^-S, S = min(QC_FX_MAXBITS, 60 - ceil(log2(4 imax sum|D|)))
 void qc_fx_scale(hipStream_t st, int n, const double *Da, const double *Db /*nullable*/, double imax, double *out);

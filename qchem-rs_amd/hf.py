@@ -43,7 +43,8 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_comm_init", "qc_set_shard", "qc_plan_shard", "qc_set_stream", "qc_device_ready", "qc_work_stats_get",
            "qc_fock_profile", "qc_plan_shard_quartets", "qc_scf_begin_rhf", "qc_scf_begin_uhf", "qc_scf_iterate",
            "qc_scf_orbital_energies", "qc_scf_density", "qc_scf_spin_square", "qc_scf_timings", "qc_scf_end", "qc_fock_profile_tiers", "qc_unit_quartets", "qc_sym_eig_warm", "qc_set_fock_mode", "qc_scf_tensor_ms", "qc_set_accumulation", "qc_set_schwarz", "qc_scf_matrix", "qc_rccl_info", "qc_measure_peaks",
-           "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment"]
+           "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment",
+           "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2"]
 
 
 class QcError(RuntimeError):
@@ -60,6 +61,27 @@ class _Output(C.Structure):
                 ("electronic_energy", C.c_double), ("nuclear_repulsion", C.c_double), ("iterations", C.c_size_t),
                 ("ms_setup", C.c_double), ("ms_fock_total", C.c_double), ("ms_linalg_total", C.c_double),
                 ("ms_total", C.c_double), ("ms_tuner", C.c_double)]
+
+
+class _Mp2Output(C.Structure):
+    _fields_ = [("e_os", C.c_double), ("e_ss", C.c_double), ("e_corr", C.c_double), ("ms_tensor", C.c_double),
+                ("ms_transform", C.c_double), ("ms_energy", C.c_double), ("n_frozen", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+@dataclass
+class Mp2Output:
+    """qc_mp2_output: the MP2 correlation energy split by spin, and the wall time of its three phases (ms)."""
+    e_os: float
+    e_ss: float
+    e_corr: float
+    ms_tensor: float
+    ms_transform: float
+    ms_energy: float
+    n_frozen: int
+
+    @classmethod
+    def _from(cls, o: "_Mp2Output") -> "Mp2Output":
+        return cls(o.e_os, o.e_ss, o.e_corr, o.ms_tensor, o.ms_transform, o.ms_energy, int(o.n_frozen))
 
 
 class WorkStats(C.Structure):
@@ -134,6 +156,9 @@ def lib():
         L.qc_scf_end.argtypes = [vp]; L.qc_scf_end.restype = None
         L.qc_scf_set_stop_rule.argtypes = [vp, C.c_double]
         L.qc_scf_counters.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+        L.qc_scf_coefficients.argtypes = [vp, C.c_int, _dp]
+        L.qc_scf_mp2.argtypes = [vp, C.c_int32, C.POINTER(_Mp2Output)]
+        L.qc_mp2.argtypes = [vp, C.c_int, _dp, _dp, _ip, C.c_int32, C.POINTER(_Mp2Output)]
         _lib = L
     return _lib
 
@@ -213,6 +238,19 @@ class System:
         A = np.ascontiguousarray(A, np.float64); n = A.shape[0]
         V = np.zeros((n, n)); w = np.zeros(n)
         _check(lib().qc_sym_eig_warm(self._h, n, A, np.ascontiguousarray(V0, np.float64), V, w), "qc_sym_eig_warm"); return V, w
+
+    def mp2(self, C_mo, eps, nocc, n_frozen: int = 0) -> "Mp2Output":
+        """MP2 correlation energy from caller-supplied orbitals (qc_mp2).  RHF: C n x n, eps n, nocc an int (doubly occupied).
+        UHF: C (2, n, n) = [Ca, Cb], eps (2, n), nocc (n_alpha, n_beta).  Columns of C are MOs, in the order of eps."""
+        nocc = np.atleast_1d(np.asarray(nocc, np.int32))
+        nspin = len(nocc)
+        Cm = np.ascontiguousarray(C_mo, np.float64).reshape(-1)
+        e = np.ascontiguousarray(eps, np.float64).reshape(-1)
+        if nspin not in (1, 2) or Cm.size != nspin * self.n * self.n or e.size != nspin * self.n:
+            raise QcError("qc_mp2: %d spin(s) need C of %d and eps of %d doubles" % (nspin, nspin * self.n * self.n, nspin * self.n))
+        o = _Mp2Output()
+        _check(lib().qc_mp2(self._h, nspin, Cm, e, np.ascontiguousarray(nocc), int(n_frozen), C.byref(o)), "qc_mp2")
+        return Mp2Output._from(o)
 
     def set_fock_mode(self, mode: str):
         """'direct' (default) or 'stored' (the reference's conventional algorithm, tensor resident in HBM)."""
@@ -330,6 +368,17 @@ class ScfStepper:
 
     def density(self, spin=0):
         D = np.zeros((self.system.n, self.system.n)); _check(lib().qc_scf_density(self._st, spin, D), "qc_scf_density"); return D
+
+    def coefficients(self, spin=0):
+        """MO coefficients of the last Roothaan step: column k is the MO of orbital_energies(spin)[k]."""
+        Cm = np.zeros((self.system.n, self.system.n))
+        _check(lib().qc_scf_coefficients(self._st, spin, Cm), "qc_scf_coefficients"); return Cm
+
+    def mp2(self, n_frozen: int = 0) -> "Mp2Output":
+        """MP2 correlation energy from the state's last orbitals (qc_scf_mp2); the state is left as it was."""
+        o = _Mp2Output()
+        _check(lib().qc_scf_mp2(self._st, int(n_frozen), C.byref(o)), "qc_scf_mp2")
+        return Mp2Output._from(o)
 
     def matrix(self, which: str):
         """Set-up matrix of the state: 'S' (overlap), 'H' (core Hamiltonian) or 'X' (S^-1/2, rhf.rs:124-131)."""
@@ -452,3 +501,38 @@ def restricted_hartree_fock(system, config: HartreeFockConfig) -> Optional[Restr
 
 def unrestricted_hartree_fock(system, config: HartreeFockConfig) -> Optional[UnrestrictedHartreeFockOutput]:
     return _run("qc_scf_uhf", system, config, True)
+
+
+def _stepped_mp2(system, config: HartreeFockConfig, n_frozen: int, uhf: bool):
+    """The reference's loop (rhf.rs:67-108 / uhf.rs:82-167) driven pass by pass, as cli.run_uhf does, then MP2 on the converged state."""
+    sysh = _as_system(system)
+    if uhf:
+        n_alpha, n_beta = int(config.n_alpha), int(config.n_beta)
+        st = ScfStepper(sysh, uhf=True, n_alpha=n_alpha, n_beta=n_beta, stop_rule=float(config.epsilon))
+    else:
+        st = ScfStepper(sysh, stop_rule=float(config.epsilon))
+    try:
+        for it in range(int(config.max_iterations) + 1):                   # 0..=max_iterations, rhf.rs:67 / uhf.rs:82
+            e, rms = st.iterate()
+            if (rms / 2.0 if uhf else rms) < config.epsilon:                # uhf.rs:139 / rhf.rs:94
+                t = st.timings()
+                if uhf:
+                    out = UnrestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), st.orbital_energies(1).tolist(), e,
+                                                        sysh.nuclear_repulsion(), it, t)
+                else:
+                    out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, t)
+                return out, st.mp2(n_frozen)
+        return None
+    finally:
+        st.close()
+
+
+def restricted_mp2(system, config: HartreeFockConfig, n_frozen: int = 0):
+    """(RestrictedHartreeFockOutput, Mp2Output), or None when the SCF does not converge."""
+    return _stepped_mp2(system, config, n_frozen, False)
+
+
+def unrestricted_mp2(system, config: HartreeFockConfig, n_frozen: int = 0):
+    """(UnrestrictedHartreeFockOutput, Mp2Output), or None when the SCF does not converge.  config.n_alpha / n_beta as for
+    unrestricted_hartree_fock."""
+    return _stepped_mp2(system, config, n_frozen, True)
