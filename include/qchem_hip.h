@@ -73,8 +73,9 @@ int qc_nuclear(const qc_system *sys, double *out);
 int qc_one_electron_gpu(qc_system *sys, int which, double *out);
 
 /* ---- two-electron integrals: replaces molint::eri (rhf.rs:45, uhf.rs:55).  GPU.  out = n^4 doubles on the host,
- * row-major (i,j,k,l), chemists' notation (ij|kl) - the index order rhf.rs:60-61 reads.  Plumbing/tests only: the SCF
- * drivers below never materialise this tensor. */
+ * row-major (i,j,k,l), chemists' notation (ij|kl) - the index order rhf.rs:60-61 reads.  The same device tensor feeds
+ * every MP2 energy (qc_mp2, qc_scf_mp2) and the stored Fock mode (qc_set_fock_mode); the direct SCF drivers never
+ * materialise it. */
 int qc_eri_full(qc_system *sys, double *out);
 
 /* ---- Fock build: replaces compute_electronic_hamiltonian (rhf.rs:152-167 incl. the tensor of rhf.rs:58-62;

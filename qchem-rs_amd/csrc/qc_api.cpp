@@ -846,11 +846,11 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         if (st->uhf) {   // uhf.rs:216-226: G_s = <I, D_s + D_s'> - <I^x, D_s>
             qc_axpby(sm, n, 1.0, st->D[0].p, 1.0, st->D[1].p, st->Dtot.p);
             qc_axpby(sm, n, -1.0, st->D[0].p, 0.0, nullptr, W.t1[0].p);
-            qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur);
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur)) != QC_OK) return rc;
             qc_axpby(sm, n, -1.0, st->D[1].p, 0.0, nullptr, W.t1[0].p);
-            qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur + nn);
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur + nn)) != QC_OK) return rc;
         } else {
-            qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, Gcur);   // rhf.rs:152-167
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, Gcur)) != QC_OK) return rc;   // rhf.rs:152-167
         }
         st->cur_build_tuned = false; st->cur_build_gen = S->assign_gen;
     } else {

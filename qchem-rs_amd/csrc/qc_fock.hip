@@ -1599,7 +1599,7 @@ int qc_schwarz_device(qc_system *S) {
     return QC_OK;
 }
 
-// molint::eri replacement for tests/plumbing: unsplit slots (every quartet complete in one slot) + plain stores
+// molint::eri replacement (qc_eri_full, MP2, stored Fock mode): unsplit slots (every quartet complete in one slot) + plain stores
 int qc_launch_eri_full(qc_system *S, double *d_out) {
     QcFockArgs fa{};
     fa.eri_out = d_out;

@@ -405,7 +405,7 @@ __device__ __forceinline__ void qc_bm_body(const QcKernelArgs &a, const double *
         return;
     }
     if (a.eri_out != nullptr) {
-        // materialise (ij|kl) with its 8 symmetry images (tests / stored-tensor mode; bundles are not cut along ij there)
+        // materialise (ij|kl) with its 8 symmetry images (qc_eri_full, MP2, stored-tensor mode; bundles are not cut along ij there)
         if (active) {
             const size_t n1 = n, n2 = n1 * n1, n3 = n2 * n1;
             double *o = a.eri_out;

@@ -797,8 +797,8 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                 for (int o = C / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, C));
                 if (li == 0) a.schwarz_out[sl.bra] = sqrt(m);
             } else if (a.eri_out != nullptr) {
-                // materialise (ij|kl) with its 8 symmetry images: the tensor molint::eri returns (tests / plumbing only;
-                // the host hands this mode unsplit slots, so plain stores are complete values)
+                // materialise (ij|kl) with its 8 symmetry images: the tensor molint::eri returns (qc_eri_full, MP2, stored Fock
+                // mode; the host hands this mode unsplit slots, so plain stores are complete values)
                 const size_t n1 = n, n2 = n1 * n1, n3 = n2 * n1;
                 for (int x = li; x < nab * ncd; x += C) {
                     const int ab = x / ncd, cd = x - ab * ncd;

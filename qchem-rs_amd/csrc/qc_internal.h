@@ -355,7 +355,7 @@ int qc_eig_cold_async(hipStream_t st, int n, double *dA, double *dX0, double *tr
 int qc_eig_cold_sync(hipStream_t st, int n, double *dA, double *dX0, double *triwork, double *dV, double *dw, double *d_work, double *t1, double *t2,
                      double *t3, double *t4, double *small, int *ctl, int *notconv = nullptr);
 void qc_permute_tensor(hipStream_t st, int n, const double *I, double c_direct, double c_exch, double *T);
-void qc_tensor_gemv(hipStream_t st, int n, const double *T1, const double *D1, const double *T2, const double *D2, double *G);
+int qc_tensor_gemv(hipStream_t st, int n, const double *T1, const double *D1, const double *T2, const double *D2, double *G);   // QC_OK or QC_ERR_HIP
 void qc_axpby(hipStream_t st, int n, double a, const double *x, double b, const double *y, double *out);
 void qc_sub_transpose(hipStream_t st, int n, const double *M, double *out);              // out = M - M^T
 // (fxs non-null: Gt = [hi | lo] planes of 64-bit fixed-point integers, lo_off doubles apart, units fxs[1] = 2^-S and 2^-(S+32))

@@ -1285,17 +1285,25 @@ __global__ __launch_bounds__(QC_GEMV_THREADS) void qc_tensor_gemv_kernel(int n, 
         __syncthreads();
     }
 }
-void qc_tensor_gemv(hipStream_t st, int n, const double *T1, const double *D1, const double *T2, const double *D2, double *G) {
+// Three forms: D in LDS within the default 48 KB (RHF n <= 78, UHF n <= 55), D in LDS above it after raising the kernel's limit
+// (RHF n <= 138, UHF n <= 97), D read through L2.  Returns QC_ERR_HIP if the limit cannot be raised or the launch fails: G is
+// then not written.
+int qc_tensor_gemv(hipStream_t st, int n, const double *T1, const double *D1, const double *T2, const double *D2, double *G) {
     const size_t nn = (size_t)n * n, lds = (T2 ? 2 : 1) * (nn + 1) * sizeof(double);
     const int nrows = n * (n + 1) / 2;
     if (lds <= 150 * 1024) {
         static size_t allowed = 48 * 1024;
-        if (lds > allowed) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(qc_tensor_gemv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); allowed = lds; }
+        if (lds > allowed) {
+            QC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(qc_tensor_gemv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            allowed = lds;
+        }
         const int per_cu = std::max<int>(1, std::min<int>(4, (int)(150 * 1024 / lds)));
         hipLaunchKernelGGL(qc_tensor_gemv_kernel<true>, dim3(std::min(nrows, 256 * per_cu)), dim3(QC_GEMV_THREADS), lds, st, n, T1, D1, T2, D2, G);
     } else {
         hipLaunchKernelGGL(qc_tensor_gemv_kernel<false>, dim3(std::min(nrows, 256 * 4)), dim3(QC_GEMV_THREADS), 0, st, n, T1, D1, T2, D2, G);
     }
+    QC_HIP_CHECK(hipGetLastError());
+    return QC_OK;
 }
 
 // out[j] = <x, ys[j]>, one workgroup per j (diis.rs:43-45)

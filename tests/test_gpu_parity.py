@@ -208,8 +208,8 @@ def test_fock_linearity_and_symmetry_benzene_ccpvdz():
 
 def test_fock_benzene_equals_contraction_of_the_materialised_tensor():
     """Full size (BASELINE config 5, 1.1 M quartets): the fused digestion (row buffers, MFMA step 3, atomics, replicas) against
-    a plain numpy contraction of the tensor the same integral code materialises (qc_eri_full; the integrals themselves are
-    pinned against the oracle on the smaller systems above)."""
+    a plain numpy contraction of the tensor the same integral code materialises (qc_eri_full; that tensor is pinned against the
+    oracle element by element at this size in test_eri_tensor_above_n64_matches_oracle)."""
     q, s, o = _sys("benzene", "cc-pVDZ")
     n = s.n
     I = s.eri()
@@ -1205,3 +1205,141 @@ def test_open_shell_passes_above_n64_match_oracle(basis):
     tr2, Da2, Db2, s2b = run()
     assert tr2 == tr and np.array_equal(Da2, Da) and np.array_equal(Db2, Db) and s2b == s2
     s.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The materialised tensor above n = 64 (qc_eri_full: the tensor behind MP2 and the stored Fock mode) and the stored-tensor SCF in every
+# launch form of qc_tensor_gemv, against the oracle.
+
+def _oracle_tensor(o):
+    I, _ = o.eri_strided_mt(0, 1, min(16, len(os.sched_getaffinity(0))))
+    return I
+
+
+def _pp_bm_unit(q):
+    names = [u for u in range(q.hf.PROFILE_UNITS) if q.hf.unit_name(u) == "qc_fock_bm_kernel<2, 0>"]
+    assert len(names) == 1
+    return names[0]
+
+
+@pytest.mark.parametrize("mol,basis,n", [("chloroform", "6-31G_st_st", 77), ("benzene", "cc-pVDZ", 114), ("ethylene", "cc-pVTZ", 116)])
+def test_eri_tensor_above_n64_matches_oracle(mol, basis, n):
+    """qc_eri_full element by element against the oracle's tensor at n = 77 (chloroform/6-31G**: Cl, odd n), 114 (benzene/cc-pVDZ: its
+    p.p-ket bra-major class, which tensor mode hands to the column kernels) and 116 (ethylene/cc-pVTZ: f functions, d.d / f.p-ket lists
+    in their 32-lane VALU form, LGC = 5) - compared one slab of the first index at a time.  The 8 symmetry images agree to rounding, and
+    a second call on the same handle repeats the first bit for bit (MP2's reproducibility rests on it)."""
+    q, s, o = _sys(mol, basis)
+    assert s.n == n
+    if basis == "cc-pVTZ":
+        assert max(_valu_fket_quartets(_column_classes(s, s.n)), default=0) > 1024, "the VALU route of the f-basis tensor is gone"
+    if mol == "benzene":
+        s.fock_rhf(_rand_sym(n, 0))
+        assert s.unit_quartets()[_pp_bm_unit(q)] > 0, "benzene/cc-pVDZ has no p.p-ket bra-major class any more"
+    I = s.eri()
+    R = _oracle_tensor(o)
+    for a in range(n):
+        assert np.abs(I[a] - R[a]).max() < TOL_INT, a
+    del R
+    scale = np.abs(I).max()
+    for a in range(n):
+        X = I[a]                                                       # X[j, k, l] = (aj|kl)
+        assert np.abs(X - I[:, a]).max() <= 1e-14 * scale, a          # (ja|kl)
+        assert np.abs(X - X.transpose(0, 2, 1)).max() <= 1e-14 * scale, a        # (aj|lk)
+        assert np.abs(X - I[:, :, a, :].transpose(2, 0, 1)).max() <= 1e-14 * scale, a     # (kl|aj)
+    assert np.array_equal(s.eri(), I)
+    s.close()
+
+
+@pytest.mark.parametrize("route", ["valu-fket", "pp-bm-to-column"])
+def test_eri_tensor_routes_on_small_systems(route, monkeypatch):
+    """The tensor-mode stores of two routes the default plans of small systems never take, against the dense oracle tensor:
+    QC_MFMA4_MAX = 0 on water/cc-pVTZ (every d.d / f.p-ket list of a d.p ... f.f bra in the 32-lane VALU form, LGC = 5) and
+    QC_BM_PP_MIN = 1 on water/cc-pVDZ (p.p-ket bra-major classes, which qc_launch_eri_full runs in the column kernels)."""
+    import qchem_rs_amd as q
+    from oracle.oracle import Oracle
+    mol, basis, var = ("water", "cc-pVTZ", "QC_MFMA4_MAX") if route == "valu-fket" else ("water", "cc-pVDZ", "QC_BM_PP_MIN")
+    m = load_system(mol, basis)
+    o = Oracle(m)
+    monkeypatch.setenv(var, "0" if route == "valu-fket" else "1")
+    s = q.System(m)
+    monkeypatch.delenv(var)
+    if route == "valu-fket":
+        assert sum(_valu_fket_quartets(_column_classes(s, s.n))) > 0
+    else:
+        s.fock_rhf(_rand_sym(s.n, 0))
+        assert s.unit_quartets()[_pp_bm_unit(q)] > 0
+    I = s.eri()
+    assert np.abs(I - o.eri()).max() < TOL_INT
+    assert np.array_equal(s.eri(), I)
+    s.close()
+
+
+def _gemv_form(n, nspin):
+    """Launch form of qc_tensor_gemv for n and 1 (RHF) or 2 (UHF) tensors: D in LDS within 48 KB, in LDS above 48 KB, or through L2."""
+    lds = nspin * (n * n + 1) * 8
+    return "lds" if lds <= 48 * 1024 else ("lds-raised" if lds <= 150 * 1024 else "l2")
+
+
+@pytest.mark.parametrize("mol,basis,n,form", [("benzene", "cc-pVDZ", 114, "lds-raised"), ("benzene", "6-311++G_st_st", 174, "l2")])
+def test_stored_tensor_rhf_passes_above_n64(mol, basis, n, form):
+    """Stored-tensor RHF (qc_tensor_gemv on T = I - I^x / 2) pass by pass in the GEMV forms with D in LDS above 48 KB (n = 114) and with
+    D read through L2 (n = 174), against the direct build on the same handle - which
+    test_fock_above_n64_matches_the_oracle_quartet_contraction pins to the oracle at these sizes - and at n = 114 also against the
+    oracle's trace on its own tensor (no 7.3 GB oracle SCF at n = 174): energy to 1e-9 relative, rms to 2e-8 + 1e-5 relative - both
+    modes are 6.5e-9 from the oracle's rms at pass 11 (measured; benzene's near-degenerate orbitals, see
+    test_benzene_ccpvdz_energy_matches_oracle), and 6e-11 from each other.
+
+    benzene/6-311++G**: the Hueckel start in a basis with diffuse shells is poorly conditioned (density rms 1.6e6 after pass 0), so the
+    last digits of G - each mode agrees with the oracle to 1e-10 of the largest element - reach the energies of the first passes at up
+    to 8e-9 relative and the rms at up to 1e-2 (measured); by pass 8 DIIS has damped them to 1e-10 in the energy and 3e-4 in the rms.
+    Bars there: energy 2e-8 relative through pass 7, 1e-9 from pass 8 on; rms 1e-3 relative from pass 8 on."""
+    q, s, o = _sys(mol, basis)
+    assert s.n == n and _gemv_form(n, 1) == form
+    ref = None
+    if n <= 128:
+        I = _oracle_tensor(o)
+        ref = o.rhf(12, 1e-30, eri=I, trace=True)
+        del I
+        assert len(ref["trace_energy"]) >= 12
+    s.set_fock_mode("stored")
+    st = q.ScfStepper(s)
+    s.set_fock_mode("direct")
+    st2 = q.ScfStepper(s)
+    for k in range(12):
+        e1, r1 = st.iterate(); e2, r2 = st2.iterate()
+        if ref is not None:
+            assert abs(e1 - ref["trace_energy"][k]) < 1e-9 * max(1.0, abs(e1)), k
+            assert abs(r1 - ref["trace_rms"][k]) < 2e-8 + 1e-5 * ref["trace_rms"][k], k
+            assert abs(e1 - e2) < 1e-9 * max(1.0, abs(e2)), k
+            assert abs(r1 - r2) < 1e-9 + 1e-6 * r2, k
+        elif k < 8:
+            assert abs(e1 - e2) < 2e-8 * abs(e2), k
+        else:
+            assert abs(e1 - e2) < 1e-9 * abs(e2), k
+            assert abs(r1 - r2) < 1e-3 * r2, k
+    st.close(); st2.close(); s.close()
+
+
+@pytest.mark.parametrize("mol,basis,n,na,nb,form", [("chloroform", "6-31G_st_st", 77, 30, 28, "lds-raised"),
+                                                    ("ethylene", "cc-pVTZ", 116, 9, 7, "l2")])
+def test_stored_tensor_uhf_passes_match_oracle_above_n64(mol, basis, n, na, nb, form):
+    """Stored-tensor UHF (two tensors, I and its exchange permutation, Da != Db) pass by pass against the oracle's trace on its own tensor:
+    triplet chloroform at n = 77 (D in LDS above 48 KB, odd n: the n^2 tail of the GEMV) and triplet ethylene at n = 116 (D through L2).
+    The first 12 passes, with the bars of test_open_shell_passes_above_n64_match_oracle."""
+    q, s, o = _sys(mol, basis)
+    assert s.n == n and _gemv_form(n, 2) == form
+    I = _oracle_tensor(o)
+    ref = o.uhf(12, 1e-30, n_alpha=na, n_beta=nb, eri=I, trace=True)
+    del I
+    assert len(ref["trace_energy"]) >= 12
+    s.set_fock_mode("stored")
+    st = q.ScfStepper(s, uhf=True, n_alpha=na, n_beta=nb)
+    for k in range(12):
+        e, rms = st.iterate()
+        tol = 1e-9 if k == 0 else 1e-7
+        assert abs(e - ref["trace_energy"][k]) < tol * max(1.0, abs(e)), k
+        if k == 0:
+            assert abs(rms - ref["trace_rms"][0]) < 1e-9 * max(1.0, ref["trace_rms"][0])
+        else:
+            assert abs(rms - ref["trace_rms"][k]) < tol + 1e-4 * ref["trace_rms"][k], k
+    st.close(); s.close()

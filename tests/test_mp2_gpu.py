@@ -61,9 +61,10 @@ def _sys(mol, basis):
 def _oracle_eri(mol, basis):
     key = (mol, basis)
     if key not in _CACHE:
+        import os
         from oracle.oracle import Oracle
-        _CACHE.clear()
-        _CACHE[key] = Oracle(load_system(mol, basis)).eri()
+        _CACHE.clear()                                # (before the next tensor exists: one at a time, 7.3 GB at n = 174)
+        _CACHE[key] = Oracle(load_system(mol, basis)).eri_strided_mt(0, 1, min(16, len(os.sched_getaffinity(0))))[0]
     return _CACHE[key]
 
 
@@ -115,6 +116,44 @@ def test_kernels_uhf_synthetic_orbitals(basis, na, nb, nf):
     assert abs(got.e_os - e_os) <= TOL and abs(got.e_ss - (aa + bb)) <= TOL, (got, e_os, aa, bb)
 
 
+# Above n = 64, against the oracle's tensor.  chloroform/6-31G** (n = 77, odd): every GEMM's B rows unaligned (the non-VEC loads);
+# ethylene/cc-pVTZ (n = 116): the tensor of the VALU f-ket route; benzene/6-311++G** (n = 174): two 128-wide N tiles in steps 3 (N = n)
+# and 4 (N = v >= 141) with their masked edges, the batched (b, nt) tiles of step 3, o = 16 / 17 on the edge of the second MFMA row band,
+# o = 33 with a one-row second M tile, and both B alignments of step 4 (B = C + nocc: even and odd nocc).
+BIG = [("chloroform", "6-31G_st_st", 77, (29,), 0), ("chloroform", "6-31G_st_st", 77, (29,), 5), ("chloroform", "6-31G_st_st", 77, (30, 28), 0),
+       ("ethylene", "cc-pVTZ", 116, (8,), 2), ("ethylene", "cc-pVTZ", 116, (9, 7), 0),
+       ("benzene", "6-311++G_st_st", 174, (16,), 0), ("benzene", "6-311++G_st_st", 174, (17,), 0),
+       ("benzene", "6-311++G_st_st", 174, (21,), 6), ("benzene", "6-311++G_st_st", 174, (33,), 0),
+       ("benzene", "6-311++G_st_st", 174, (22, 21), 0), ("benzene", "6-311++G_st_st", 174, (17, 16), 6)]
+
+
+@pytest.mark.parametrize("mol,basis,n,nocc,nf", BIG)
+def test_kernels_synthetic_orbitals_above_n64(mol, basis, n, nocc, nf):
+    s = _sys(mol, basis)
+    assert s.n == n
+    if n == 174:
+        assert n > 128 and n - max(nocc) > 128                    # two N tiles in steps 3 and 4
+    I = _oracle_eri(mol, basis)
+    Cs, es = _synthetic(n, nocc, seed=sum(nocc) + 13 * nf + n)
+    if len(nocc) == 1:
+        got = s.mp2(Cs[0], es[0], nocc[0], nf)
+        e_os, e_ss = ref_rmp2(I, Cs[0], es[0], nocc[0], nf)
+    else:
+        got = s.mp2(np.stack(Cs), np.stack(es), list(nocc), nf)
+        e_os, aa, bb = ref_ump2(I, Cs[0], Cs[1], es[0], es[1], nocc[0], nocc[1], nf)
+        e_ss = aa + bb
+    s.close()
+    assert abs(got.e_os - e_os) <= TOL and abs(got.e_ss - e_ss) <= TOL, (got, e_os, e_ss)
+
+
+def test_mp2_n174_is_bitwise_reproducible():
+    s = _sys("benzene", "6-311++G_st_st")
+    (C,), (e,) = _synthetic(s.n, [17], seed=3)
+    m1, m2 = s.mp2(C, e, 17, 6), s.mp2(C, e, 17, 6)
+    s.close()
+    assert (m1.e_os, m1.e_ss, m1.e_corr) == (m2.e_os, m2.e_ss, m2.e_corr)
+
+
 # ---- 2. RHF states ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mol,basis,nf", [("water", "STO-3G", 0), ("water", "6-31G_st_st", 0), ("water", "cc-pVDZ", 0),
                                           ("water", "cc-pVTZ", 0), ("water", "cc-pVTZ", 1), ("ethylene", "cc-pVDZ", 0)])
@@ -138,10 +177,38 @@ def test_rhf_state_mp2_benzene_ccpvdz_beyond_one_workgroup():
     got = st.mp2(6)
     C, e = st.coefficients(), st.orbital_energies()
     st.close()
-    I = s.eri()
-    e_os, e_ss = ref_rmp2(I, C, e, 21, 6)
-    del I
+    e_os, e_ss = ref_rmp2(_oracle_eri("benzene", "cc-pVDZ"), C, e, 21, 6)
     assert abs(got.e_os - e_os) <= TOL and abs(got.e_ss - e_ss) <= TOL, (got, e_os, e_ss)
+
+
+def test_rhf_state_mp2_ethylene_ccpvtz():
+    """A converged RHF state at n = 116 (f functions), two frozen core orbitals, against numpy on its own orbitals and the oracle's tensor."""
+    import qchem_rs_amd as q
+    s = _sys("ethylene", "cc-pVTZ")
+    assert s.n == 116
+    st = q.ScfStepper(s)
+    _converge(st, 1e-8)
+    got = st.mp2(2)
+    C, e = st.coefficients(), st.orbital_energies()
+    st.close()
+    e_os, e_ss = ref_rmp2(_oracle_eri("ethylene", "cc-pVTZ"), C, e, s.n_electrons() // 2, 2)
+    assert abs(got.e_os - e_os) <= TOL and abs(got.e_ss - e_ss) <= TOL, (got, e_os, e_ss)
+
+
+def test_uhf_state_mp2_triplet_ethylene_ccpvtz():
+    """Triplet ethylene (n_alpha = 9, n_beta = 7) at n = 116 after 12 passes - not converged (see test_open_shell_passes_above_n64_match_oracle),
+    but its orbitals are those of a pass, and both spins' highest occupied orbital lies below the lowest virtual one (qc_mp2_validate;
+    gaps of 0.31 and 0.37 Eh) - against numpy on that state's coefficients and orbital energies."""
+    import qchem_rs_amd as q
+    s = _sys("ethylene", "cc-pVTZ")
+    st = q.ScfStepper(s, uhf=True, n_alpha=9, n_beta=7)
+    for _ in range(12):
+        st.iterate()
+    got = st.mp2()
+    Ca, Cb, ea, eb = st.coefficients(0), st.coefficients(1), st.orbital_energies(0), st.orbital_energies(1)
+    st.close()
+    e_os, aa, bb = ref_ump2(_oracle_eri("ethylene", "cc-pVTZ"), Ca, Cb, ea, eb, 9, 7)
+    assert abs(got.e_os - e_os) <= TOL and abs(got.e_ss - (aa + bb)) <= TOL, (got, e_os, aa, bb)
 
 
 # ---- 3. known answer ----------------------------------------------------------------------------------------------------------------
