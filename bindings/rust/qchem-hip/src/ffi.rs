@@ -82,6 +82,13 @@ extern "C" {
     /// MP2 from caller orbitals: nspin 1 (C n*n, eps n, nocc[0]) or 2 (C 2*n*n, eps 2*n, nocc = [n_alpha, n_beta]).
     pub fn qc_mp2(sys: *mut QcSystem, nspin: c_int, c: *const f64, eps: *const f64, nocc: *const i32, n_frozen: i32,
                   out: *mut QcMp2Output) -> c_int;
+    /// Nuclear gradient terms for fixed densities: terms = 4 x natoms x 3 (nuclear repulsion, core Hamiltonian, overlap,
+    /// two-electron), Eh/bohr.  nspin 1: D n*n (qc_fock_rhf convention); nspin 2: D = [Da; Db].  W: energy-weighted density n*n.
+    pub fn qc_gradient(sys: *mut QcSystem, nspin: c_int, d: *const f64, w: *const f64, terms: *mut f64) -> c_int;
+    /// Total gradient (natoms x 3) at the state's last Roothaan step; the state is left as it was.
+    pub fn qc_scf_gradient(st: *mut QcScfState, grad: *mut f64) -> c_int;
+    /// Phase times (ms) of the handle's last gradient: transform, one-electron, two-electron, sum.
+    pub fn qc_gradient_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

@@ -184,6 +184,30 @@ int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out);
  * nspin 2: C = [Ca; Cb] 2*n*n, eps 2*n, nocc = {n_alpha, n_beta}. */
 int qc_mp2(qc_system *sys, int nspin, const double *C, const double *eps, const int32_t *nocc, int32_t n_frozen, qc_mp2_output *out);
 
+/* ---- nuclear gradient (after SCF, not in the reference).  dE/dX in Eh/bohr, atoms in input order, components x, y, z:
+ *   dE/dX = sum P_t dh/dX + 1/2 sum d(mn|ls)/dX [P_t,mn P_t,ls - P_a,ml P_a,ns - P_b,ml P_b,ns] - sum W dS/dX + dVnn/dX
+ * with P_t = P_a + P_b and h = T + V (dV includes the derivative of the operator: the nuclei move too).  This equals the derivative of the
+ * energy only at a converged state; at any other state it is the formula above evaluated at the current orbitals.  Shells s to f, pure
+ * and Cartesian.  The two-electron quartets follow qc_set_schwarz.  Bitwise reproducible from call to call and across fresh handles.
+ * QC_ERR_INVALID for null pointers or nspin not 1 / 2 (checked before the device is touched), QC_ERR_NO_DEVICE without a device,
+ * QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator, for more than 682 atoms (the per-workgroup atom rows are held in
+ * 32 KB of LDS), and when one quartet class's tables would exceed the 160 KB of LDS of a workgroup (not reached by s..f shells). */
+
+/* The fixed-density contraction from host pointers (the gradient counterpart of qc_fock_rhf / qc_fock_uhf).  nspin 1: D n*n in the
+ * qc_fock_rhf convention (the factor 2 included; P_a = P_b = D/2).  nspin 2: D = [Da; Db] 2*n*n.  W: the energy-weighted density, n*n.
+ * terms receives 4 x natoms x 3 doubles: nuclear repulsion, core Hamiltonian (kinetic + nuclear attraction, Hellmann-Feynman part
+ * included), overlap (-W.S'), two-electron.  The gradient is their sum. */
+int qc_gradient(qc_system *sys, int nspin, const double *D, const double *W, double *terms);
+
+/* natoms x 3 doubles: the total gradient at the state's last Roothaan step, RHF or UHF.  P is the state's density (what qc_scf_density
+ * returns), W = sum_spin sum_{i occ} n_i e_i c_i c_i^T from the C and orbital energies of qc_scf_coefficients / qc_scf_orbital_energies,
+ * both on the device.  QC_ERR_INVALID before the first qc_scf_iterate.  The state is left exactly as it was. */
+int qc_scf_gradient(qc_scf_state *st, double *grad);
+
+/* Phase times (ms) of the handle's last gradient call: P/W build (qc_scf_gradient; qc_gradient: the spin combination of the uploaded
+ * densities) + Cartesian transform, one-electron terms, two-electron term, sum. */
+int qc_gradient_timings(const qc_system *sys, double *ms4);
+
 /* ---- Fock mode of the SCF drivers on this handle.  0 (default): direct - quartets are evaluated and digested every pass.
  * 1: stored - the reference's own conventional algorithm with the tensor resident in HBM: molint::eri once (rhf.rs:45),
  * electron_terms (rhf.rs:58-62), then one streaming GEMV per pass (rhf.rs:152-167 / uhf.rs:216-226).  Needs ~18 n^4 bytes

@@ -2,4 +2,5 @@
 from .loader import Atom, BasisSet, MolecularSystem, ShellDef  # noqa: F401
 from .hf import (HartreeFockConfig, Mp2Output, QcError, RestrictedHartreeFockOutput, ScfStepper, System,  # noqa: F401
                  UnrestrictedHartreeFockOutput, build_library, comm_unique_id, device_ready, lib, measure_peaks, rccl_info,
-                 restricted_hartree_fock, restricted_mp2, unrestricted_hartree_fock, unrestricted_mp2)
+                 restricted_gradient, restricted_hartree_fock, restricted_mp2, unrestricted_gradient, unrestricted_hartree_fock,
+                 unrestricted_mp2)

@@ -8,7 +8,9 @@ Three additions, all opt-in:
     with either given, n_alpha / n_beta follow from charge and multiplicity and an `<S^2>` line is added.  With both left at
     0 the behaviour is the reference's N/2 rule (uhf.rs:43-45);
   * `--mp2 [--frozen-core N]` adds the MP2 correlation energy of the converged determinant after the reference's lines (the SCF
-    then runs pass by pass through hf.ScfStepper; its lines are those of the run without the flag).
+    then runs pass by pass through hf.ScfStepper; its lines are those of the run without the flag);
+  * `--gradient` adds the analytic nuclear gradient of the converged determinant (Eh/bohr), one line per atom - index, Z, gx, gy,
+    gz - after the reference's lines and any MP2 lines; `--json` then carries a "gradient" array.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -72,6 +74,7 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--mp2", action="store_true", help="also compute the MP2 correlation energy of the converged determinant")
         s.add_argument("--frozen-core", type=int, default=None, metavar="N",
                        help="leave the lowest N orbitals of each spin out of the MP2 sums (requires --mp2)")
+        s.add_argument("--gradient", action="store_true", help="also print the analytic nuclear gradient (Eh/bohr) of the converged determinant")
     return p
 
 
@@ -93,6 +96,11 @@ def _print_mp2(mp2: "hf.Mp2Output", e_hf: float) -> None:
 def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
     return {"e_os": mp2.e_os, "e_ss": mp2.e_ss, "e_corr": mp2.e_corr, "e_total": e_hf + mp2.e_corr, "n_frozen": mp2.n_frozen,
             "timings_ms": {"tensor": mp2.ms_tensor, "transform": mp2.ms_transform, "energy": mp2.ms_energy}}
+
+
+def _print_gradient(system: MolecularSystem, g) -> None:
+    for i, (atom, row) in enumerate(zip(system.atoms, g)):
+        print("%d %d %.10f %.10f %.10f" % (i, atom.ordinal, row[0], row[1], row[2]))
 
 
 def occupations(n_electrons_neutral: int, charge: int, multiplicity: int) -> Tuple[int, int]:
@@ -118,9 +126,12 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = None
+    mp2 = grad = None
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.mp2:
+    if args.gradient:
+        res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
+        out, (mp2, grad) = res if res is not None else (None, (None, None))
+    elif args.mp2:
         res = hf.restricted_mp2(system, config, args.frozen_core or 0)
         out, mp2 = res if res is not None else (None, None)
     else:
@@ -135,12 +146,16 @@ def run_rhf(args) -> int:
     print("orbital energies: " + fmt_vec(out.orbital_energies))
     if mp2 is not None:
         _print_mp2(mp2, out.total_energy())
+    if grad is not None:
+        _print_gradient(system, grad)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
                "orbital_energies": list(out.orbital_energies), "seconds": elapsed, "timings_ms": out.timings_ms}
         if mp2 is not None:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
+        if grad is not None:
+            doc["gradient"] = grad.tolist()
         print(json.dumps(doc))
     return 0
 
@@ -153,8 +168,8 @@ def run_uhf(args) -> int:
     if extension:
         n_alpha, n_beta = occupations(system.n_electrons, args.charge, args.spin_multiplicity)
     start = time.perf_counter()
-    s2 = mp2 = None
-    if not extension and not args.mp2:
+    s2 = mp2 = grad = None
+    if not extension and not args.mp2 and not args.gradient:
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
@@ -171,6 +186,8 @@ def run_uhf(args) -> int:
                                                            handle.nuclear_repulsion(), it)
                     if args.mp2:
                         mp2 = st.mp2(args.frozen_core or 0)
+                    if args.gradient:
+                        grad = st.gradient()
                     break
         finally:
             st.close()
@@ -188,6 +205,8 @@ def run_uhf(args) -> int:
         print("<S^2>: %s (n_alpha %d, n_beta %d)" % (fmt_f(s2), n_alpha, n_beta))
     if mp2 is not None:
         _print_mp2(mp2, out.total_energy())
+    if grad is not None:
+        _print_gradient(system, grad)
     if args.json:
         doc = {"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -196,6 +215,8 @@ def run_uhf(args) -> int:
                "spin_square": s2, "seconds": elapsed, "timings_ms": out.timings_ms}
         if mp2 is not None:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
+        if grad is not None:
+            doc["gradient"] = grad.tolist()
         print(json.dumps(doc))
     return 0
 

@@ -1179,6 +1179,53 @@ int qc_mp2(qc_system *S, int nspin, const double *C, const double *eps, const in
     QC_HIP_CHECK(hipMemcpyAsync(dE.p, eps, nspin * n * sizeof(double), hipMemcpyHostToDevice, S->stream));
     return qc_mp2_device(S, nspin, dC.p, dE.p, nocc, n_frozen, out);
 }
+int qc_gradient(qc_system *S, int nspin, const double *D, const double *W, double *terms) {
+    if (!S || !D || !W || !terms || (nspin != 1 && nspin != 2)) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const int na3 = 3 * S->natoms;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf dP, dW;
+    if (dP.alloc(nspin * nn) != QC_OK || dW.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dP.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(dW.p, W, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    qc_nuclear_gradient(S, terms);
+    return qc_gradient_device(S, nspin, dP.p, dW.p, terms + na3, S->grad_ms);
+}
+int qc_scf_gradient(qc_scf_state *st, double *grad) {
+    if (!st || !grad || st->passes == 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const int n = S->nbasis, nspin = st->uhf ? 2 : 1, na3 = 3 * S->natoms;
+    const size_t nn = (size_t)n * n;
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    DevBuf dP, dW;
+    if (dP.alloc(nspin * nn) != QC_OK || dW.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    hipEvent_t ev[2];
+    for (auto &e : ev) QC_HIP_CHECK(hipEventCreate(&e));
+    struct EvDel { hipEvent_t *e; ~EvDel() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } evdel{ev};
+    // P: the state's own density, exactly what qc_scf_density returns; W from the C and orbital energies the state reports
+    QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
+    for (int s = 0; s < nspin; ++s) QC_HIP_CHECK(hipMemcpyAsync(dP.p + s * nn, st->D[s].p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+    const int nocc[2] = {st->nocc[0], st->nocc[1]};
+    int rc = qc_gradient_w_device(S, nspin, st->Cs.p, st->ws.p, nocc, dW.p);   // (reads Cs / ws, writes nothing of the state)
+    if (rc != QC_OK) return rc;
+    QC_HIP_CHECK(hipEventRecord(ev[1], S->stream));
+    std::vector<double> t((size_t)4 * na3);
+    qc_nuclear_gradient(S, t.data());
+    if ((rc = qc_gradient_device(S, nspin, dP.p, dW.p, t.data() + na3, S->grad_ms)) != QC_OK) return rc;
+    float pw = 0.f;
+    QC_HIP_CHECK(hipEventElapsedTime(&pw, ev[0], ev[1]));
+    S->grad_ms[0] += pw;                                                    // (phase 0: P/W build + Cartesian transform)
+    for (int k = 0; k < na3; ++k) grad[k] = ((t[k] + t[na3 + k]) + t[2 * na3 + k]) + t[3 * na3 + k];
+    return QC_OK;
+}
+int qc_gradient_timings(const qc_system *S, double *ms) {
+    if (!S || !ms) return QC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = S->grad_ms[i];
+    return QC_OK;
+}
 int qc_scf_matrix(qc_scf_state *st, int which, double *out) {
     if (!st || !out || which < 0 || which > 2) return QC_ERR_INVALID;
     const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;

@@ -142,6 +142,7 @@ struct qc_system {
     std::vector<double> pspack;                 // ps pairs, 8 doubles per primitive: [q, Q(3), E_0[x,y,z], E_1] (see qc_fock_bm.hip)
     std::vector<double> pairdataT;              // same blocks with the expansion stored [ab][h] (bra side of the bra-major kernels)
     std::vector<QcClass> classes;
+    double grad_ms[4] = {0, 0, 0, 0};         // phase times of the last gradient call (qc_gradient_timings)
     std::vector<double> pairQ;                  // Schwarz factor sqrt(max_ab (ab|ab)) of each stored pair (empty until the device pass has run)
     double imax = 0.0;                          // max pairQ^2: bound on every |(ij|kl)|
     double schwarz_tau = QC_SCHWARZ_TAU;        // 0: no screening
@@ -296,6 +297,11 @@ int qc_launch_eri_full(qc_system *S, double *d_out);
 // the intermediates live for the duration of the call.
 int qc_mp2_validate(int n, int nspin, const double *eps, const int32_t *nocc, int n_frozen);
 int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps, const int32_t *nocc, int n_frozen, qc_mp2_output *out);
+// nuclear gradient (qc_grad.hip): terms3 = [core | overlap | two-electron] x 3 natoms (host) from device densities dP (RHF D, UHF [Da; Db])
+// and dW; ms[4] = phase times (transform, one-electron, two-electron, sum) or null.  w: W of an SCF state's orbitals (enqueued).
+int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *dW, double *terms3, double *ms);
+int qc_gradient_w_device(qc_system *S, int nspin, const double *dC, const double *dEps, const int *nocc, double *dW);
+void qc_nuclear_gradient(const qc_system *S, double *g);
 int qc_schwarz_device(qc_system *S);     // fills pairQ / imax from the (P|P) quartets, then screens the work lists
 // fixed-point scale of a build from its densities: out[0] = 2^S, out[1] = 2^-S, S = min(QC_FX_MAXBITS, 60 - ceil(log2(4 imax sum|D|)))
 void qc_fx_scale(hipStream_t st, int n, const double *Da, const double *Db /*nullable*/, double imax, double *out);

@@ -44,7 +44,7 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_fock_profile", "qc_plan_shard_quartets", "qc_scf_begin_rhf", "qc_scf_begin_uhf", "qc_scf_iterate",
            "qc_scf_orbital_energies", "qc_scf_density", "qc_scf_spin_square", "qc_scf_timings", "qc_scf_end", "qc_fock_profile_tiers", "qc_unit_quartets", "qc_sym_eig_warm", "qc_set_fock_mode", "qc_scf_tensor_ms", "qc_set_accumulation", "qc_set_schwarz", "qc_scf_matrix", "qc_rccl_info", "qc_measure_peaks",
            "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment",
-           "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2"]
+           "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings"]
 
 
 class QcError(RuntimeError):
@@ -159,6 +159,9 @@ def lib():
         L.qc_scf_coefficients.argtypes = [vp, C.c_int, _dp]
         L.qc_scf_mp2.argtypes = [vp, C.c_int32, C.POINTER(_Mp2Output)]
         L.qc_mp2.argtypes = [vp, C.c_int, _dp, _dp, _ip, C.c_int32, C.POINTER(_Mp2Output)]
+        L.qc_gradient.argtypes = [vp, C.c_int, _dp, _dp, _dp]
+        L.qc_scf_gradient.argtypes = [vp, _dp]
+        L.qc_gradient_timings.argtypes = [vp, _dp]
         _lib = L
     return _lib
 
@@ -251,6 +254,23 @@ class System:
         o = _Mp2Output()
         _check(lib().qc_mp2(self._h, nspin, Cm, e, np.ascontiguousarray(nocc), int(n_frozen), C.byref(o)), "qc_mp2")
         return Mp2Output._from(o)
+
+    def gradient(self, D, W, Db=None):
+        """The four terms of the nuclear gradient for fixed densities (qc_gradient), each a (natoms, 3) array in Eh/bohr: nuclear
+        repulsion, core Hamiltonian, overlap (-W.S'), two-electron.  RHF: D in the qc_fock_rhf convention; UHF: D = D_alpha, Db = D_beta."""
+        n = self.n
+        Dm = np.ascontiguousarray(D if Db is None else np.concatenate([np.asarray(D).reshape(n, n), np.asarray(Db).reshape(n, n)]), dtype=np.float64)
+        Wm = np.ascontiguousarray(W, dtype=np.float64)
+        if Dm.size != (1 if Db is None else 2) * n * n or Wm.size != n * n:
+            raise QcError("qc_gradient: D and W must be n x n")
+        natoms = len(self.mol.atoms)
+        t = np.zeros((4, natoms, 3))
+        _check(lib().qc_gradient(self._h, 1 if Db is None else 2, Dm, Wm, t), "qc_gradient")
+        return t[0], t[1], t[2], t[3]
+
+    def gradient_timings(self):
+        """Phase times (ms) of the handle's last gradient: density transform, one-electron terms, two-electron term, sum."""
+        ms = np.zeros(4); _check(lib().qc_gradient_timings(self._h, ms), "qc_gradient_timings"); return ms
 
     def set_fock_mode(self, mode: str):
         """'direct' (default) or 'stored' (the reference's conventional algorithm, tensor resident in HBM)."""
@@ -380,6 +400,11 @@ class ScfStepper:
         _check(lib().qc_scf_mp2(self._st, int(n_frozen), C.byref(o)), "qc_scf_mp2")
         return Mp2Output._from(o)
 
+    def gradient(self):
+        """Total nuclear gradient (natoms, 3), Eh/bohr, at the state's last Roothaan step (qc_scf_gradient); the state is left as it was."""
+        g = np.zeros((len(self.system.mol.atoms), 3))
+        _check(lib().qc_scf_gradient(self._st, g), "qc_scf_gradient"); return g
+
     def matrix(self, which: str):
         """Set-up matrix of the state: 'S' (overlap), 'H' (core Hamiltonian) or 'X' (S^-1/2, rhf.rs:124-131)."""
         M = np.zeros((self.system.n, self.system.n))
@@ -503,8 +528,9 @@ def unrestricted_hartree_fock(system, config: HartreeFockConfig) -> Optional[Unr
     return _run("qc_scf_uhf", system, config, True)
 
 
-def _stepped_mp2(system, config: HartreeFockConfig, n_frozen: int, uhf: bool):
-    """The reference's loop (rhf.rs:67-108 / uhf.rs:82-167) driven pass by pass, as cli.run_uhf does, then MP2 on the converged state."""
+def _stepped(system, config: HartreeFockConfig, uhf: bool, after):
+    """The reference's loop (rhf.rs:67-108 / uhf.rs:82-167) driven pass by pass, as cli.run_uhf does, then `after` (MP2, gradient) on the
+    converged state."""
     sysh = _as_system(system)
     if uhf:
         n_alpha, n_beta = int(config.n_alpha), int(config.n_beta)
@@ -521,7 +547,7 @@ def _stepped_mp2(system, config: HartreeFockConfig, n_frozen: int, uhf: bool):
                                                         sysh.nuclear_repulsion(), it, t)
                 else:
                     out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, t)
-                return out, st.mp2(n_frozen)
+                return out, after(st)
         return None
     finally:
         st.close()
@@ -529,10 +555,21 @@ def _stepped_mp2(system, config: HartreeFockConfig, n_frozen: int, uhf: bool):
 
 def restricted_mp2(system, config: HartreeFockConfig, n_frozen: int = 0):
     """(RestrictedHartreeFockOutput, Mp2Output), or None when the SCF does not converge."""
-    return _stepped_mp2(system, config, n_frozen, False)
+    return _stepped(system, config, False, lambda st: st.mp2(n_frozen))
 
 
 def unrestricted_mp2(system, config: HartreeFockConfig, n_frozen: int = 0):
     """(UnrestrictedHartreeFockOutput, Mp2Output), or None when the SCF does not converge.  config.n_alpha / n_beta as for
     unrestricted_hartree_fock."""
-    return _stepped_mp2(system, config, n_frozen, True)
+    return _stepped(system, config, True, lambda st: st.mp2(n_frozen))
+
+
+def restricted_gradient(system, config: HartreeFockConfig):
+    """(RestrictedHartreeFockOutput, gradient (natoms, 3) in Eh/bohr), or None when the SCF does not converge."""
+    return _stepped(system, config, False, lambda st: st.gradient())
+
+
+def unrestricted_gradient(system, config: HartreeFockConfig, n_alpha: int, n_beta: int):
+    """(UnrestrictedHartreeFockOutput, gradient (natoms, 3) in Eh/bohr), or None when the SCF does not converge."""
+    cfg = HartreeFockConfig(config.max_iterations, config.epsilon, int(n_alpha), int(n_beta))
+    return _stepped(system, cfg, True, lambda st: st.gradient())
