@@ -143,13 +143,11 @@ int qc_scf_matrix(qc_scf_state *st, int which, double *out_nxn);
 int qc_scf_spin_square(qc_scf_state *st, double *s2);
 int qc_scf_timings(qc_scf_state *st, double *ms_setup, double *ms_fock, double *ms_linalg);
 /* The stopping rule of the host's loop, told to the library: "I stop calling qc_scf_iterate once rms < epsilon (RHF, rhf.rs:94) /
- * rms / 2 < epsilon (UHF, uhf.rs:139)".  Optional, and it changes no result.  qc_scf_iterate issues the NEXT pass's Fock build behind
- * the pass it is asked for, before it knows how that pass ends (the host is then off the pass boundary); with the rule known, the
- * kernel that ends a pass evaluates it on the device and empties the build queued behind a converging pass instead of running it for
- * nothing.  A host that goes on regardless gets a regular build.  epsilon = 0 (default): no rule; qc_scf_rhf / qc_scf_uhf set theirs. */
+ * rms / 2 < epsilon (UHF, uhf.rs:139)".  Kept for hosts that call it: a null state or a negative / NaN epsilon is QC_ERR_INVALID,
+ * anything else is accepted and ignored (nothing in the library acts on the rule any more). */
 int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon);
 /* out[0 .. n) of: ms_setup, ms_fock (builds that contained a tuner run are left out), ms_linalg, builds counted in ms_fock, host ms of
- * the first build's timing passes, passes done, speculative builds consumed, speculative builds discarded, passes whose eigensolve was
+ * the first build's timing passes, passes done, two slots that are reserved, always 0, passes whose eigensolve was
  * repeated, trials of the online stream-assignment search so far (handle-wide), 1 once that search has ended */
 #define QC_SCF_NCOUNTERS 11
 int qc_scf_counters(qc_scf_state *st, double *out, int n);

@@ -106,11 +106,6 @@ struct DeviceDiis {
         slots.push_front(s);
         *d_err = pool[2 * s]; *d_fock = pool[2 * s + 1];
     }
-    // the buffers next_sample will hand out next (the speculative build of the next pass writes its F = H + G there)
-    void peek_next(double **d_err, double **d_fock) const {
-        const int s = (int)slots.size() == maxlen ? slots.back() : (int)slots.size();
-        *d_err = pool[2 * s]; *d_fock = pool[2 * s + 1];
-    }
     // enqueues: new row of B, coefficient solve, extrapolated Fock matrix into d_out
     int extrapolate(hipStream_t st, double *d_out, int *d_flag) {
         const int m = (int)slots.size();
@@ -264,8 +259,7 @@ int roothaan_enqueue(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *d
 
 // The same step for n <= QC_SMALL_MAXN, density / energy / rms of rhf.rs:78-88 included: one launch when the eigensolve is a refinement from
 // the previous vectors, pre | tridiagonal start | refine + post when it starts cold, pre | Jacobi kernel | post for the rotation-only runs.
-struct SmallTail { int nocc; double dfac; double *Dn; const double *Dold; double *scal_out; int *ctl_all, *ctl_out; double *fxs_out; unsigned *seq_out = nullptr; unsigned seq = 0;
-                   unsigned *fork_words = nullptr; unsigned fork_seq = 0; double eps = 0.0; unsigned *h_cancel = nullptr; };
+struct SmallTail { int nocc; double dfac; double *Dn; const double *Dold; double *scal_out; int *ctl_all, *ctl_out; double *fxs_out; unsigned *seq_out = nullptr; unsigned seq = 0; };
 int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG, const double *dD, double *dw_out, double *dC, int spin,
                    double *dE, double *dF, bool have_F, const SmallTail &tl, hipStream_t st_in = nullptr, int b = 0) {
     const int n = S->nbasis;
@@ -284,7 +278,6 @@ int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG,
     a.Cp_out = W.CpNew[spin].p; a.w_out = dw_out; a.C_out = dC; a.Dn = tl.Dn; a.Dold = tl.Dold; a.nocc = tl.nocc; a.dfac = tl.dfac;
     a.scal_out = tl.scal_out; a.ctl_all = tl.ctl_all; a.ctl_out = tl.ctl_out; a.fxs_out = tl.fxs_out; a.imax = S->imax;
     a.seq_out = tl.seq_out; a.seq = tl.seq;
-    a.fork_words = tl.fork_words; a.fork_seq = tl.fork_seq; a.eps = tl.eps; a.h_cancel = tl.h_cancel;
     a.tl = S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
     W.cold[spin] = false;
     static const bool force_jacobi = getenv("QC_EIG_JACOBI") != nullptr;
@@ -294,7 +287,7 @@ int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG,
         return qc_scf_small_launch(st, a);
     }
     QcSmallArgs pre = a;
-    pre.phases = 1; pre.ctl_all = nullptr; pre.seq_out = nullptr; pre.fork_words = nullptr;
+    pre.phases = 1; pre.ctl_all = nullptr; pre.seq_out = nullptr;
     if (a.tl) a.tl += QC_TL_W;                              // (the second launch of the pass has its own slot)
     if ((rc = qc_scf_small_launch(st, pre)) != QC_OK) return rc;
     if (qc_tri_ok(n) && !force_jacobi && !W.rotations_only) {
@@ -457,7 +450,7 @@ int qc_fock_prepare_device(qc_system *S, const double *dDa, const double *dDb, b
 }
 
 int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, double *dGa, double *dGb, bool uhf, int *twin_cache,
-                         const double *dH, double *dFa, double *dFb, bool *f_done, const void *owner, unsigned fork_seq) {
+                         const double *dH, double *dFa, double *dFb, bool *f_done, const void *owner) {
     const int n = S->nbasis;
     const size_t nn = (size_t)n * n;
     hipStream_t st = S->stream;
@@ -488,9 +481,6 @@ int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, dou
     const size_t plane = (size_t)QC_NREP * nspin * nn;          // one accumulator plane: [replica][spin][n*n]
     const bool ready = fx && S->prepared && owner != nullptr && S->prep_owner == owner && S->prep_Da == dDa && S->prep_Db == (uhf ? dDb : nullptr);   // qc_fock_prepare_device ran for these
     S->prepared = false;
-    // (a speculative build starts on the device's word, not on the host's: its preliminaries must be in the stream in front of the
-    // kernel that releases the fork word - qc_fock_prepare_device for exactly these densities - and the planes clean)
-    if (fork_seq && !(ready && S->gt_clean)) return QC_ERR_INVALID;
     QcFockArgs a{};
     // Replicas in use (the planes keep their layout): 8 for n <= 64, all 32 above.  Replicas spread the atomics of hot elements, and the
     // closing fold reads and zeroes every one of them: at n = 58 that is 1.7 MB with 32 replicas, and the H2O/cc-pVTZ iteration takes 0.308 ms
@@ -499,7 +489,7 @@ int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, dou
     const char *nrep_s = getenv("QC_NREP_USE");                 // (read per build: a test switches it inside one process)
     const int nrep_env = nrep_s ? std::max(1, std::min(QC_NREP, atoi(nrep_s))) : 0;
     const int nrep_use = nrep_env ? nrep_env : (n <= 64 ? 8 : QC_NREP);
-    a.nrep = nrep_use; a.rep_stride = nspin * nn; a.fxs = fxs; a.fx_lo = plane; a.fork_seq = fork_seq;
+    a.nrep = nrep_use; a.rep_stride = nspin * nn; a.fxs = fxs; a.fx_lo = plane;
     if (!ready) {
         QC_HIP_CHECK(hipMemsetAsync(S->d_Gtmp, 0, (fx ? 2 : 1) * plane * sizeof(double), st));
         if (fx) qc_fx_scale(st, n, dDa, uhf ? dDb : nullptr, S->imax, S->d_fxs);      // this build's fixed-point unit, from its densities
@@ -512,20 +502,11 @@ int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, dou
         a.Dj = dDa; a.Dk0 = dDa; a.Dk1 = nullptr; a.cK = 0.5;
     }
     a.G0 = S->d_Gtmp; a.G1 = S->d_Gtmp + nn;
-    // (QC_FOLD_JOIN: the closing fold waits for the side streams' markers itself instead of sitting behind the one-lane waiting kernel - one
-    // dependent launch less, 1 us per H2O/cc-pVTZ pass on the device timeline, nothing measurable per iteration (five alternating runs);
-    // OFF by default: every workgroup of the fold then polls one word, 813 of them at n = 114, and three of nine benzene/cc-pVDZ runs
-    // with that many pollers next to an experimental replica count lost a marker for 20 s - not understood, not reproduced since, not shipped)
-    static const bool fold_join = getenv("QC_FOLD_JOIN") != nullptr;
-    a.fold_joins = fx && !S->comm && S->nranks == 1 && fold_join;
     int rc = qc_launch_fock_classes(S, a, nullptr, nullptr, ready);
     if (rc != QC_OK) return rc;
     if (fx && !S->comm && S->nranks == 1) {
-        // (one launch instead of fold + symmetrise: nothing needs the folded planes; and the join of the side streams in the same launch)
-        const bool fj = S->fold_join_pending;
-        S->fold_join_pending = false;
-        qc_fold_symmetrize(st, n, nrep_use, nspin * nn, S->d_Gtmp, plane, dGa, dH, dH ? dFa : nullptr, fxs, S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 1) : nullptr,
-                           fj ? S->d_join : nullptr, S->join_target, S->h_join_timeout, S->wait_limit);
+        // (one launch instead of fold + symmetrise: nothing needs the folded planes)
+        qc_fold_symmetrize(st, n, nrep_use, nspin * nn, S->d_Gtmp, plane, dGa, dH, dH ? dFa : nullptr, fxs, S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 1) : nullptr);
         if (two) qc_fold_symmetrize(st, n, nrep_use, nspin * nn, S->d_Gtmp + nn, plane, dGb, dH, dH ? dFb : nullptr, fxs);
         else if (uhf) QC_HIP_CHECK(hipMemcpyAsync(dGb, dGa, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
         S->gt_clean = true; S->gt_clean_nspin = nspin;      // every replica element of the planes in use was read and zeroed
@@ -627,15 +608,8 @@ struct qc_scf_state {
     bool uhf = false;
     int nocc[2] = {0, 0};
     ScfWork W;
-    DevBuf D[2], Dn[2], Gb[2], Cs, ws;         // densities are double-buffered per spin: D <-> Dn swap when a pass is accepted
-    int g_cur = 0;                             // G of this pass lives in Gb[g_cur]; the speculative build of the next pass writes Gb[g_cur ^ 1]
-    double eps_hint = 0.0;                     // > 0: the host stops once the reference's stopping rule holds at this epsilon (qc_scf_set_stop_rule)
-    unsigned *h_cancel = nullptr;              // pinned: number of the speculative build the device cancelled (the pass in front of it met the rule)
-    // Speculative build of the next pass behind this pass's Roothaan step (scf_iterate).  OFF by default: built, parity-tested, and
-    // measured SLOWER on MI355X (H2O/cc-pVTZ 0.38-0.44 ms per iteration against 0.31) - DESIGN.md 3.1 says why.  QC_SPEC=1 (read per
-    // SCF state) switches it on.
-    bool spec_on = getenv("QC_SPEC") != nullptr && getenv("QC_NO_SPEC") == nullptr;
-    int64_t spec_hits = 0, spec_lost = 0, builds_timed = 0, passes = 0, redos = 0;
+    DevBuf D[2], Dn[2], G, Cs, ws;             // densities are double-buffered per spin: D <-> Dn swap when a pass is accepted
+    int64_t builds_timed = 0, passes = 0, redos = 0;
     bool spin_parallel = getenv("QC_NO_SPIN_PARALLEL") == nullptr;      // (A/B switch, read per SCF state)
     double warm_rms_env = getenv("QC_EIG_WARM_RMS") ? atof(getenv("QC_EIG_WARM_RMS")) : 0.0;   // (read per SCF state: tests reach the repeat branch with it)
     double ms_tuner = 0;
@@ -657,10 +631,8 @@ struct qc_scf_state {
     ~qc_scf_state() {
         if (S && S->prep_owner == this) { S->prepared = false; S->prep_owner = nullptr; }
         delete diis[0]; delete diis[1];
-        if (S && S->spec.owner == this) { S->spec.pending = false; S->spec.owner = nullptr; }
         if (S && S->stream) { (void)hipStreamSynchronize(S->stream); qc_gate_quiet(S); qc_tl_dump(S); }
         for (auto &set : evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        if (h_cancel) (void)hipHostFree(h_cancel);
     }
 };
 static void system_free(qc_system *S);
@@ -703,9 +675,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     st->W.small_fused = n <= QC_SMALL_MAXN && (!st->W.rotations_only || open_fused) && getenv("QC_NO_SMALL_FUSED") == nullptr;
     if ((rc = st->W.init(n, uhf ? 2 : 1)) != QC_OK) return rc;
     for (int s = 0; s < nspin; ++s) if (st->D[s].alloc(nn) != QC_OK || st->Dn[s].alloc(nn) != QC_OK) return QC_ERR_HIP;
-    if (st->Gb[0].alloc(nspin * nn) != QC_OK || st->Gb[1].alloc(nspin * nn) != QC_OK || st->Cs.alloc(nspin * nn) != QC_OK || st->ws.alloc(nspin * n) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipHostMalloc(&st->h_cancel, sizeof(unsigned), hipHostMallocDefault));
-    *st->h_cancel = 0;
+    if (st->G.alloc(nspin * nn) != QC_OK || st->Cs.alloc(nspin * nn) != QC_OK || st->ws.alloc(nspin * n) != QC_OK) return QC_ERR_HIP;
     std::vector<double> h_eht;
     lap("state buffers");
     if ((rc = scf_setup(S, st->W, h_eht)) != QC_OK) return rc;           // rhf.rs:41-49
@@ -794,21 +764,7 @@ static hipError_t wait_event(hipEvent_t ev) {
 // The whole pass is enqueued without looking at the device; one synchronisation at its end returns the energy, the rms
 // and the control words (DIIS failure, eigen-refinement outcome).  Launch latency of ~50 small kernels then overlaps with
 // their execution instead of adding to it.
-//
-// Round 4: the host leaves the pass boundary.  Behind the pass's Roothaan step - before waiting for it - the NEXT pass's Fock build is
-// issued speculatively from the density buffer the step is about to fill: its side streams start with a one-lane kernel that waits for
-// the fork word which the step's last kernel releases (qc_fock.hip, "Device-side fork"), the handle's own chain simply follows in
-// stream order.  All launches of build k + 1 then sit in their queues when pass k's densities become final (before: 26 us of idle GPU per
-// pass while the host saw the pass end and turned around, and launches arriving 8 us apart).  The next call of this function finds its
-// build in flight and goes straight to the Roothaan step.  What makes it safe:
-//  * G is double-buffered (the repeat branch below still needs the old G for the energy); F = H + G goes to the DIIS slot the next pass
-//    will claim, which this pass only reads in front of it in stream order;
-//  * a repeat of the eigensolve (rotations wanted) changes the density: the speculative build is then discarded - it ran into the
-//    accumulator planes and its closing kernel left them clean - and the next pass builds again;
-//  * when the host has said where it stops (qc_scf_set_stop_rule; scf_run does), the kernel that ends the pass evaluates the same
-//    rule and cancels the build behind a converged pass on the device: its class kernels return at once;
-//  * may_continue = false (scf_run's last allowed pass): nothing is issued behind the pass.
-static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool may_continue = true) {
+static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     qc_system *S = st->S;
     ScfWork &W = st->W;
     const int n = S->nbasis;
@@ -822,35 +778,21 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
     st->ev_cur ^= 1;
     hipEvent_t *const ev = st->evs[st->ev_cur];
     hipEvent_t const ev0 = ev[0], ev1 = ev[1], ev2 = ev[2];
-    double *const Gcur = st->Gb[st->g_cur].p, *const Gnext = st->Gb[st->g_cur ^ 1].p;
+    double *const dG = st->G.p;
     double *dE[2] = {nullptr, nullptr}, *dF[2] = {nullptr, nullptr};       // this pass's DIIS sample buffers (error, Fock matrix) per spin
     for (int s = 0; s < nspin; ++s) st->diis[s]->next_sample(&dE[s], &dF[s]);
     bool have_F = false;
-    // the build of this pass may be in flight already (issued speculatively by the previous pass)
-    bool spec_hit = false;
-    {
-        qc_system::QcSpec &sp = S->spec;
-        if (sp.pending && sp.owner == st) {
-            const bool cancelled = __atomic_load_n(st->h_cancel, __ATOMIC_ACQUIRE) == sp.seq;     // (the host goes on although its own rule held: build again)
-            spec_hit = !st->stored && !cancelled && sp.Da == st->D[0].p && sp.Db == (st->uhf ? st->D[1].p : nullptr) && sp.Ga == Gcur;
-            sp.pending = false;
-            if (spec_hit) { have_F = sp.f_done; st->spec_hits += 1; }
-            else { st->spec_lost += 1; S->prepared = false; }      // (its kernels may still run: the build below forks off the handle's stream)
-        }
-    }
     // G of every spin from the *old* densities
-    if (spec_hit) {
-        // (ev0 / ev1 of this set were recorded around the build when it was issued)
-    } else if (st->stored) {
+    if (st->stored) {
         QC_HIP_CHECK(hipEventRecord(ev0, sm));
         if (st->uhf) {   // uhf.rs:216-226: G_s = <I, D_s + D_s'> - <I^x, D_s>
             qc_axpby(sm, n, 1.0, st->D[0].p, 1.0, st->D[1].p, st->Dtot.p);
             qc_axpby(sm, n, -1.0, st->D[0].p, 0.0, nullptr, W.t1[0].p);
-            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur)) != QC_OK) return rc;
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, dG)) != QC_OK) return rc;
             qc_axpby(sm, n, -1.0, st->D[1].p, 0.0, nullptr, W.t1[0].p);
-            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, Gcur + nn)) != QC_OK) return rc;
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.t1[0].p, dG + nn)) != QC_OK) return rc;
         } else {
-            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, Gcur)) != QC_OK) return rc;   // rhf.rs:152-167
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, dG)) != QC_OK) return rc;   // rhf.rs:152-167
         }
         st->cur_build_tuned = false; st->cur_build_gen = S->assign_gen;
     } else {
@@ -858,7 +800,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         qc_stamp("ev0");
         const int tunes0 = S->tune_count;
         const double tt0 = now_ms();
-        if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, Gcur, st->uhf ? Gcur + nn : nullptr, st->uhf,
+        if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dG + nn : nullptr, st->uhf,
                                        &st->twin, W.H.p, dF[0], dF[1], &have_F, st)) != QC_OK) return rc;
         st->cur_build_tuned = S->tune_count != tunes0;
         if (st->cur_build_tuned) st->ms_tuner += now_ms() - tt0;
@@ -866,7 +808,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
     }
     qc_stamp("build out");
     scf_flush_timing(st);                                                 // (the previous pass's times, now that this pass's build is out)
-    if (!spec_hit) QC_HIP_CHECK(hipEventRecord(ev1, sm));
+    QC_HIP_CHECK(hipEventRecord(ev1, sm));
     qc_stamp("flush timing, ev1");
     // UHF: the two spins' steps are independent (uhf.rs:84-135 runs them one after the other) - the beta step goes to a side stream on
     // another dispatch pipe, behind an event of the build's closing kernel, and meets the handle's stream again before the scalars
@@ -877,7 +819,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         if (spin_par && !side) return QC_ERR_HIP;
         for (int s = 0; s < nspin; ++s) {                                 // (the control words were cleared by the previous pass)
             const bool on_side = spin_par && s == 1;
-            if ((rc = roothaan_enqueue(S, W, *st->diis[s], Gcur + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F,
+            if ((rc = roothaan_enqueue(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F,
                                        on_side ? side : sm, on_side ? 1 : 0)) != QC_OK) return rc;
             if (on_side) {    // the beta density on the side stream as well; then the streams meet
                 if (st->nocc[s] > 0) qc_gemm(side, n, n, st->nocc[s], 1.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
@@ -901,7 +843,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         else if (st->nocc[s] > 0) qc_gemm(sm, n, n, st->nocc[s], st->uhf ? 1.0 : 2.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
         else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), sm));
         // energy and rms straight into pinned host memory; the last spin's kernel also hands over and clears the control words
-        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, Gcur + s * nn, scal_out + 2 * s, hand_over ? W.ctl : nullptr, ctl_out);
+        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, dG + s * nn, scal_out + 2 * s, hand_over ? W.ctl : nullptr, ctl_out);
         return QC_OK;
     };
     auto publish_scalars = [&]() -> int {
@@ -922,23 +864,17 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
     // Single-rank runs on the one-workgroup path: the kernel that ends the pass stores the pass's sequence number into pinned memory
     // after the scalars and control words, and the host polls THAT instead of the event behind it (a few microseconds earlier per pass).
     unsigned *h_seq = reinterpret_cast<unsigned *>(W.h_scal + 2 * QC_SYNC_WORDS);
-    // speculative build of the next pass: decided before the Roothaan step goes out (the one-workgroup kernel releases the fork word itself)
-    const bool want_spec = may_continue && st->spec_on && !st->stored && qc_fock_can_speculate(S);
-    // (with a speculative build behind the pass every launch sequence ends in a kernel that can store the word - the release kernel - and
-    // should: the event behind a kernel that retires while the next build's side chains start is signalled up to 100 us late)
-    const bool seq_wait = ((W.small_fused && !multi) || want_spec) && !st->event_wait;
-    const unsigned spec_seq = want_spec ? ++S->fork_seq : 0;
-    const bool release_in_kernel = want_spec && W.small_fused && !st->uhf && !multi && !st->event_wait;
+    const bool seq_wait = W.small_fused && !multi && !st->event_wait;
     // UHF on the one-workgroup path: the two spins' kernels side by side as well - beta on a side stream of another dispatch pipe behind an
     // event of the build's closing kernel, with the second set of work buffers; the kernel that joins the streams on the device also hands
     // the control words over and stores the sequence word (qc_spin_join_end).  Same kernels per spin: bit for bit the serial order.
-    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events && !multi && !want_spec;
+    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events && !multi;
     if (small_par) {
         hipStream_t side = qc_spin_fork(S);
         if (!side) return QC_ERR_HIP;
         for (int s = 0; s < nspin; ++s) {
             SmallTail tl{st->nocc[s], 1.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, nullptr, ctl_out, nullptr};
-            if ((rc = roothaan_small(S, W, *st->diis[s], Gcur + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl,
+            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl,
                                      s == 1 ? side : nullptr, s)) != QC_OK) return rc;
         }
         if ((rc = qc_spin_join_end(S, W.ctl, ctl_out, seq_wait ? h_seq : nullptr, st->pass_seq + 1)) != QC_OK) return rc;
@@ -949,11 +885,8 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
             scale_in_kernel = scale_here;
             SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl : nullptr, ctl_out,
                          scale_here ? S->d_fxs : nullptr};
-            // (when a release kernel follows - closed-shell UHF with a speculative build behind the pass - IT stores the sequence word:
-            // the host must not look at the cancel word before the kernel that writes it has run)
-            if (seq_wait && s == nspin - 1 && !(want_spec && !release_in_kernel)) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
-            if (release_in_kernel) { tl.fork_words = S->d_join; tl.fork_seq = spec_seq; tl.eps = st->eps_hint; tl.h_cancel = st->h_cancel; }
-            if ((rc = roothaan_small(S, W, *st->diis[s], Gcur + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
+            if (seq_wait && s == nspin - 1) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
+            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
         }
     } else
         for (int s = 0; s < nspin; ++s) if ((rc = density_and_scalars(s, s == nspin - 1)) != QC_OK) return rc;
@@ -961,29 +894,9 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
     // the next pass's build starts from Dn: its density-only preliminaries run while the host turns around
     auto prepare_next = [&]() -> int { return st->stored ? QC_OK : qc_fock_prepare_device(S, st->Dn[0].p, st->uhf ? st->Dn[1].p : nullptr, st->uhf, st, scale_in_kernel); };
     if ((rc = prepare_next()) != QC_OK) return rc;
-    // (the pass's scalars as the device sees them: pinned host memory, or the all-reduced words of a multi-rank run)
-    if (want_spec && !release_in_kernel)
-        qc_spec_release(sm, S->d_join, spec_seq, multi ? reinterpret_cast<const double *>(W.d_sync) : W.h_scal, n, nspin, st->eps_hint, st->h_cancel,
-                        seq_wait ? h_seq : nullptr, st->pass_seq + 1);
     qc_stamp("roothaan out");
     QC_HIP_CHECK(hipEventRecord(ev2, sm));
     qc_stamp("ev2");
-    if (want_spec) {
-        // the next pass's build, behind everything above in the handle's stream and behind the fork word on the side streams
-        hipEvent_t *const evn = st->evs[st->ev_cur ^ 1];
-        double *nE[2] = {nullptr, nullptr}, *nF[2] = {nullptr, nullptr};
-        for (int s = 0; s < nspin; ++s) st->diis[s]->peek_next(&nE[s], &nF[s]);
-        bool f_done = false;
-        scf_flush_timing(st);                       // (the other event set is about to be recorded again)
-        QC_HIP_CHECK(hipEventRecord(evn[0], sm));
-        rc = qc_fock_build_device(S, st->Dn[0].p, st->uhf ? st->Dn[1].p : nullptr, Gnext, st->uhf ? Gnext + nn : nullptr, st->uhf,
-                                  &st->twin, W.H.p, nF[0], nF[1], &f_done, st, spec_seq);
-        if (rc != QC_OK) return rc;
-        QC_HIP_CHECK(hipEventRecord(evn[1], sm));
-        qc_system::QcSpec &sp = S->spec;
-        sp.pending = true; sp.owner = st; sp.Da = st->Dn[0].p; sp.Db = st->uhf ? st->Dn[1].p : nullptr; sp.Ga = Gnext; sp.Gb = st->uhf ? Gnext + nn : nullptr;
-        sp.f_done = f_done; sp.seq = spec_seq;
-    }
     const double th1 = now_ms();
     if (seq_wait) {
         const unsigned want = st->pass_seq + 1;
@@ -1003,20 +916,20 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         }
         st->pass_seq = want;
         // The word says that the pass's last kernel is through.  If the preliminaries of the next build were put behind it (UHF: density
-        // sum and fixed-point unit; a memset after a mode change), a NON-speculative next build's side streams - which start without a
-        // fork event - must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there:
-        // the kernel leaves the fixed-point unit itself and the fold left the planes clean.  A speculative build waits on the device.)
-        if (!st->stored && S->prep_enqueued && !want_spec) QC_HIP_CHECK(wait_event(ev2));
+        // sum and fixed-point unit; a memset after a mode change), the next build's side streams - which start without a fork event -
+        // must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there: the kernel
+        // leaves the fixed-point unit itself and the fold left the planes clean.)
+        if (!st->stored && S->prep_enqueued) QC_HIP_CHECK(wait_event(ev2));
     } else QC_HIP_CHECK(wait_event(ev2));
     const double th2 = now_ms();
     qc_stamp("pass seen");
     if ((rc = qc_join_check(S)) != QC_OK) return rc;                     // (the join of this pass's build is in front of everything waited for)
-    if (!want_spec) qc_gate_quiet(S);                                    // (nothing of this handle waits on the device any more)
+    qc_gate_quiet(S);                                                    // (nothing of this handle waits on the device any more)
     if (!ranks_agree()) { fprintf(stderr, "qchem_hip: rank %d: the ranks' SCF scalars differ - replicated state diverged\n", S->rank); return QC_ERR_RCCL; }
     if (h_ctl[8] != 0) return QC_DIIS_SINGULAR;                          // "DIIS failed", rhf.rs:73
     if (h_ctl[9] != 0) return QC_EIG_NOT_CONVERGED;
     static const bool dbg = getenv("QC_SCF_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[scf] ctl a: %d %d %d %d  b: %d %d %d %d  npass %d %d have_prev %d mode %d cold %d spec %s/%s | host enqueue %.0f us, then waited %.0f us\n", h_ctl[0], h_ctl[1], h_ctl[2], h_ctl[3], h_ctl[4], h_ctl[5], h_ctl[6], h_ctl[7], W.npass[0], W.npass[1], (int)W.have_prev[0], W.mode[0], (int)W.cold[0], spec_hit ? "hit" : "-", want_spec ? "issued" : "-", (th1 - th0) * 1e3, (th2 - th1) * 1e3);
+    if (dbg) fprintf(stderr, "[scf] ctl a: %d %d %d %d  b: %d %d %d %d  npass %d %d have_prev %d mode %d cold %d | host enqueue %.0f us, then waited %.0f us\n", h_ctl[0], h_ctl[1], h_ctl[2], h_ctl[3], h_ctl[4], h_ctl[5], h_ctl[6], h_ctl[7], W.npass[0], W.npass[1], (int)W.have_prev[0], W.mode[0], (int)W.cold[0], (th1 - th0) * 1e3, (th2 - th1) * 1e3);
     if (dbg) {   // the pass's DIIS coefficients (diis.rs:50-51), newest sample first
         double c[12] = {0};
         const int m = (int)st->diis[0]->slots.size();
@@ -1026,11 +939,9 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         fprintf(stderr, "\n");
     }
     // the pass's event times are read by the next pass (scf_flush_timing): the last event may still be in flight when the host has seen
-    // the sequence word, and with a speculative build behind the pass nothing should keep the host here
+    // the sequence word
     st->timing_pending = true; st->pending_set = st->ev_cur;
     st->pend_build_tuned = st->cur_build_tuned; st->pend_build_gen = st->cur_build_gen;
-    // (what the NEXT pass's timing set will describe, if its build is the one just issued)
-    st->cur_build_tuned = false; st->cur_build_gen = S->assign_gen;
     bool redo = false;
     for (int s = 0; s < nspin; ++s) {
         const bool refined = W.cold[s] || (W.have_prev[s] && W.mode[s] == 0);       // the eigensolve reported through the control word
@@ -1038,12 +949,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         if (h_ctl[4 * s] == 1) { W.npass[s] = W.cold[s] ? 3 : std::max(1, std::min(3, h_ctl[4 * s + 3])); continue; }
         W.npass[s] = 3;
         // the refinement wanted rotations (large step, or a degenerate cluster): repeat this spin's eigensolve the careful way
-        if (!redo) {
-            // (the density is about to change: a speculative build from the old one is worthless - it is left to run out, its closing
-            // kernel leaves the accumulator planes clean, and everything below queues behind it on the handle's stream)
-            if (S->spec.pending && S->spec.owner == st) { S->spec.pending = false; st->spec_lost += 1; }
-            scf_flush_timing(st); QC_HIP_CHECK(hipEventRecord(ev1, sm));
-        }
+        if (!redo) { scf_flush_timing(st); QC_HIP_CHECK(hipEventRecord(ev1, sm)); }
         if ((rc = roothaan_redo_eig(S, W, st->ws.p + s * n, st->Cs.p + s * nn, s)) != QC_OK) return rc;
         if ((rc = density_and_scalars(s, false)) != QC_OK) return rc;
         redo = true;
@@ -1082,7 +988,6 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out, bool m
         std::swap(W.CpPrev[s].p, W.CpNew[s].p);
         W.have_prev[s] = true;
     }
-    st->g_cur ^= 1;
     st->passes += 1;
     qc_stamp("pass end");
     qc_stamp_flush();
@@ -1103,10 +1008,9 @@ static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, boo
     out->nuclear_repulsion = qc_nuclear_repulsion(S);                    // rhf.rs:39
     out->electronic_energy = 0.0; out->iterations = 0;
     int status = QC_NOT_CONVERGED;
-    st->eps_hint = cfg->epsilon;                                         // (the rule below, told to the device: see scf_iterate)
     for (size_t it = 0; it <= cfg->max_iterations; ++it) {               // inclusive range, rhf.rs:66 / uhf.rs:80
         double e = 0.0, rms = 0.0;
-        rc = scf_iterate(st, &e, &rms, it < cfg->max_iterations);
+        rc = scf_iterate(st, &e, &rms);
         if (rc != QC_OK) { status = rc; break; }
         // the reference's per-iteration log line (rhf.rs:90-92, uhf.rs:138; `log::info!`, silent unless a logger is installed): QC_LOG=1
         static const bool log_info = getenv("QC_LOG") != nullptr;
@@ -1309,14 +1213,13 @@ int qc_dispatch_lanes(qc_system *S, int32_t *nlanes, int32_t slot_stream[8]) {
 }
 int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon) {
     if (!st || !(epsilon >= 0.0)) return QC_ERR_INVALID;
-    st->eps_hint = epsilon;
-    return QC_OK;
+    return QC_OK;                                                        // (nothing acts on the rule: see the header)
 }
 int qc_scf_counters(qc_scf_state *st, double *out, int n) {
     if (!st || !out || n < 0) return QC_ERR_INVALID;
     scf_flush_timing(st);
     const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->ms_fock, st->ms_linalg, (double)st->builds_timed, st->ms_tuner, (double)st->passes,
-                                        (double)st->spec_hits, (double)st->spec_lost, (double)st->redos,
+                                        0.0, 0.0 /* reserved */, (double)st->redos,
                                         (double)st->S->on.trials, st->S->on.settled ? 1.0 : 0.0};
     for (int i = 0; i < n && i < QC_SCF_NCOUNTERS; ++i) out[i] = v[i];
     return QC_OK;

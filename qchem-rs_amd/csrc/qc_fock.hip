@@ -5,13 +5,10 @@
 #include <vector>
 
 #include "qc_fock_kernel.h"
+#include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <memory>
 #include <mutex>
-#include <thread>
 #include "qc_fock_bm.h"
 
 int qc_launch_tier_lab0(int, int, size_t, hipStream_t, const QcTierArgs &);
@@ -130,7 +127,6 @@ int qc_device_reshard(qc_system *S) {
     S->unit_ms.clear(); S->unit_stream.clear();
     S->cand_skip = false; S->tune_count = 0; S->on = qc_system::QcOnline{};
     S->assign_gen += 1;
-    if (S->spec.pending) { if (S->stream) (void)hipStreamSynchronize(S->stream); S->spec.pending = false; }     // (it digests the old lists)
     qc_build_shards(S, !S->device_ready);         // (a handle without its device part builds its lists behind the Schwarz pass, or on demand)
     if (!S->device_ready) return QC_OK;
     return upload_slots(S);
@@ -204,7 +200,6 @@ static bool qc_stream_pool_take(qc_system *S);
 static bool qc_stream_pool_give(qc_system *S);
 __global__ void qc_join_mark_kernel(unsigned *cnt);
 static void qc_gate_forget(qc_system *S);
-static void qc_issue_pool_drop(qc_system *S);
 void qc_online_reset(qc_system *S, bool frozen);
 void qc_assign_cache_lookup(qc_system *S);
 static void qc_assign_cache_store(const qc_system *S);
@@ -285,7 +280,6 @@ int qc_device_init(qc_system *S) {
         int prc = qc_join_probe(S, &concurrent);
         if (prc != QC_OK) return prc;
         S->join_by_events = !concurrent || getenv("QC_EVENT_JOIN") != nullptr;      // (A/B switch, read per handle: the event join of rounds 1-2)
-        S->issue_threads = getenv("QC_ISSUE_THREADS") ? atoi(getenv("QC_ISSUE_THREADS")) : -1;    // (0: never; n: always n helpers; read per handle)
         if (!concurrent && getenv("QC_SCF_DEBUG")) fprintf(stderr, "qchem_hip: kernels of different streams do not run concurrently here (profiler counters?): event join\n");
         if (concurrent && !lanes_known) { prc = qc_lane_probe(S); if (prc != QC_OK) return prc; S->lanes_probed = getenv("QC_NO_LANES") == nullptr; }
     }
@@ -326,11 +320,9 @@ int qc_device_init(qc_system *S) {
 void qc_device_free(qc_system *S) {
     if (S->stream) (void)hipStreamSynchronize(S->stream);
     qc_gate_forget(S);
-    S->spec.pending = false;
     drop_lists(S);
     void *ptrs[] = {S->d_rplan, S->d_gidx, S->d_shells, S->d_pairdata, S->d_pairdataT, S->d_pspack, S->d_pairs, S->d_boys, S->d_D, S->d_G, S->d_Gtmp, S->d_Gred, S->d_Dj, S->d_flag, S->d_fxs};
     S->d_flag = nullptr; S->d_fxs = nullptr;
-    qc_issue_pool_drop(S);
     drop_launch_plan(S);
     if (S->d_join) { (void)hipFree(S->d_join); S->d_join = nullptr; }
     if (S->h_join_timeout) { (void)hipHostFree(S->h_join_timeout); S->h_join_timeout = nullptr; }
@@ -348,77 +340,6 @@ void qc_device_free(qc_system *S) {
     S->ev_fork = nullptr;
     S->stream = nullptr; S->own_stream = false; S->device_ready = false;
 }
-
-// ---- Issuing a build from several host threads.  The runtime needs 5-8 us of host time per launch; a build of H2O/cc-pVTZ is 13 launches
-// and 5 markers, so the last one left the caller ~100 us after the first - half the length of the build itself, and every stream's first
-// kernel started 6-7 us after the previous stream's.  Launches into DIFFERENT streams are independent in the runtime (one lock per
-// stream), so the side streams are shared out between a few helper threads that issue them while the caller issues the handle's own
-// chain.  A helper spins for its next job for a few milliseconds after the last one (a pass of a small molecule is 0.35 ms: a parked
-// thread's wake-up would cost more than it saves) and sleeps on a condition variable after that.
-struct QcIssuePool {
-    struct Worker {
-        std::thread th;
-        std::mutex m;
-        std::condition_variable cv;
-        bool sleeping = false;
-        std::atomic<int> go{0}, done{0};
-        std::atomic<bool> quit{false};
-        std::function<int()> job;
-        int rc = QC_OK;
-    };
-    std::vector<std::unique_ptr<Worker>> w;
-    int gen = 0;
-    static void relax() { __builtin_ia32_pause(); }
-    static void run(Worker *W, int device) {
-        (void)hipSetDevice(device);
-        int seen = 0;
-        for (;;) {
-            int spins = 0;
-            while (W->go.load(std::memory_order_acquire) == seen && !W->quit.load(std::memory_order_acquire)) {
-                if (++spins < 400000) relax();
-                else {
-                    std::unique_lock<std::mutex> lk(W->m);
-                    W->sleeping = true;
-                    W->cv.wait_for(lk, std::chrono::milliseconds(100), [&] { return W->go.load(std::memory_order_acquire) != seen || W->quit.load(std::memory_order_acquire); });
-                    W->sleeping = false;
-                    spins = 0;
-                }
-            }
-            if (W->quit.load(std::memory_order_acquire)) return;
-            seen = W->go.load(std::memory_order_acquire);
-            W->rc = W->job();
-            W->done.store(seen, std::memory_order_release);
-        }
-    }
-    explicit QcIssuePool(int n, int device) {
-        for (int i = 0; i < n; ++i) {
-            w.emplace_back(new Worker());
-            Worker *W = w.back().get();
-            W->th = std::thread(run, W, device);
-        }
-    }
-    void start(int i, std::function<int()> job) {
-        Worker *W = w[i].get();
-        W->job = std::move(job);
-        W->go.store(gen, std::memory_order_release);
-        std::lock_guard<std::mutex> lk(W->m);
-        if (W->sleeping) W->cv.notify_one();
-    }
-    int wait(int i) {
-        Worker *W = w[i].get();
-        while (W->done.load(std::memory_order_acquire) != gen) relax();
-        return W->rc;
-    }
-    ~QcIssuePool() {
-        for (auto &W : w) {
-            W->quit.store(true, std::memory_order_release);
-            { std::lock_guard<std::mutex> lk(W->m); W->cv.notify_one(); }
-            if (W->th.joinable()) W->th.join();
-        }
-    }
-};
-
-static void qc_issue_pool_drop(qc_system *S) { delete S->issue_pool; S->issue_pool = nullptr; }
 
 // ---- One handle at a time may have device-side waits in flight on a device.  A waiting kernel sits at the head of its hardware queue
 // until the kernel that releases it has run; the argument that this cannot deadlock - every wait is issued after everything it depends
@@ -647,11 +568,6 @@ static int qc_lane_probe(qc_system *S) {
 // side stream ends with a one-lane marker kernel that counts itself (in-queue dependency: a few us), and the handle's stream runs a
 // one-lane kernel that waits for the count of this build (monotonic counter, signed comparison) before the fold.
 //
-// Device-side fork (round 4): the side streams of a SPECULATIVE build - the next SCF pass's build, issued behind this pass's Roothaan step
-// before the host has seen the pass end (scf_iterate) - start with the same one-lane waiting kernel, on the fork word (d_join[1]) that the
-// kernel which leaves the pass's densities releases.  The host is then off the pass boundary: all launches of the next build sit in their
-// queues when the densities become final.
-//
 // A wait gives up after S->wait_limit ticks of the constant 100 MHz clock (qc_wait_limit: 20 s, or fifty times the build's serial time if
 // that is longer) - only possible when the launches it waits for never complete - and says so in pinned memory.  Every host wait that
 // follows looks at that word (qc_join_check) and fails THAT call: a build whose join gave up has folded an incomplete matrix.
@@ -661,14 +577,12 @@ __global__ void qc_join_mark_kernel(unsigned *cnt) {
 // (the poll is a RELAXED agent-scope load - it goes past the non-coherent cache levels without invalidating anything; an acquire load
 // in the loop invalidates the waiter's L2 every time round, and five waiters doing that every 100 ns through a whole Roothaan step cost
 // the kernels running beside them 30 % - measured: iteration 0.33 -> 0.46 ms.  One acquire fence once the word is there.)
-// (`delay`, ticks of the 100 MHz clock: a fork waiter lets that much time pass after the word has arrived - the side chains of a build
-// start a few microseconds apart, heaviest first, as they do when the host issues them one by one: released all at once they take each
-// other's wave slots from the first cycle and the chain that ends the build loses its head start - measured, see launch_concurrent)
-__global__ void qc_join_wait_kernel(unsigned *cnt, unsigned target, int *timeout_flag, long long limit, int delay, unsigned long long *tl = nullptr) {
+// (`gentle`: the join of the two spins' Roothaan steps and the concurrency probe - qc_spin_join, qc_join_probe - against the join of a build)
+__global__ void qc_join_wait_kernel(unsigned *cnt, unsigned target, int *timeout_flag, long long limit, bool gentle, unsigned long long *tl = nullptr) {
     if (threadIdx.x != 0) return;
     qc_tl_stamp(tl, 0);
-    if (delay < 0) {
-        // the join of a build (delay = -1): nothing runs next to this lane that its polling could disturb for long, and every 1.7 us step
+    if (!gentle) {
+        // the join of a build: nothing runs next to this lane that its polling could disturb for long, and every 1.7 us step
         // of the gentle loop below is 0.85 us, on average, between the last marker and the fold - one load per ~0.2 us here
         long long t0 = 0;
         unsigned it = 0;
@@ -684,8 +598,8 @@ __global__ void qc_join_wait_kernel(unsigned *cnt, unsigned target, int *timeout
         qc_tl_stamp(tl, 1);
         return;
     }
-    // (poll gently: one load per ~1.7 us, the clock only every 16th time round - a fork waiter spins through a whole Roothaan step next to
-    // the one workgroup that runs it, and whatever it does to the memory system of its CU that workgroup pays)
+    // (poll gently: one load per ~1.7 us, the clock only every 16th time round - this waiter spins through the other spin's whole Roothaan
+    // step, and whatever it does to the memory system of its CU the workgroups of that step pay)
     long long t0 = 0;
     unsigned it = 0;
     while ((int)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
@@ -696,39 +610,8 @@ __global__ void qc_join_wait_kernel(unsigned *cnt, unsigned target, int *timeout
             else if (t - t0 > limit) { __hip_atomic_store(timeout_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); break; }
         }
     }
-    if (delay > 0) {
-        const long long t1 = wall_clock64();
-        while (wall_clock64() - t1 < delay) __builtin_amdgcn_s_sleep(8);
-    }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     qc_tl_stamp(tl, 1);
-}
-// The word that ends an SCF pass on the device, for the launch sequences that have no kernel of their own to do it in (the one-workgroup
-// Roothaan kernel of small closed-shell runs does the same at its end, qc_scf_small.hip): decide whether the host - which has promised to
-// stop once the reference's stopping rule holds at `eps` (rhf.rs:94 / uhf.rs:139) - will take another pass; if not, the speculative build
-// behind this kernel is cancelled (cancel word = its number: the class kernels return at once), and the host is told so in pinned memory
-// before it sees the pass end; then release the fork word.  scal: [0.5 tr(D(2H+G)), sum_i dD_ii^2] per spin, wherever the pass left them.
-__global__ void qc_spec_release_kernel(unsigned *words, unsigned seq, const double *scal, int n, int nspin, double eps, unsigned *h_cancel,
-                                       unsigned *h_seq, unsigned seqval) {
-    if (threadIdx.x != 0) return;
-    bool stop = false;
-    if (eps > 0.0) {
-        double rms = 0.0;
-        for (int s = 0; s < nspin; ++s) rms += sqrt(scal[2 * s + 1] / n);
-        // (uhf.rs:137-139: density_rms = (rms_a + rms_b) / 2, test rms / 2 < eps;  rhf.rs:94: rms < eps)
-        stop = nspin == 2 ? (rms / 2.0 / 2.0 < eps) : (rms < eps);
-    }
-    if (stop) {
-        __hip_atomic_store(words + 2, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (h_cancel) __hip_atomic_store(h_cancel, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __hip_atomic_store(words + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    // (h_seq: this kernel also ends the pass for a host that polls the pinned sequence word - after the cancel word it may look at)
-    if (h_seq) __hip_atomic_store(h_seq, seqval, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-void qc_spec_release(hipStream_t st, unsigned *words, unsigned seq, const double *scal, int n, int nspin, double eps, unsigned *h_cancel,
-                     unsigned *h_seq, unsigned seqval) {
-    hipLaunchKernelGGL(qc_spec_release_kernel, dim3(1), dim3(64), 0, st, words, seq, scal, n, nspin, eps, h_cancel, h_seq, seqval);
 }
 
 // twenty seconds of the 100 MHz clock, or fifty times the serial time of the build's launches when that is longer (a side chain of a
@@ -754,7 +637,7 @@ int qc_spin_join(qc_system *S) {
     S->spin_target += 1;
     S->wait_limit = qc_wait_limit(S);
     hipLaunchKernelGGL(qc_join_mark_kernel, dim3(1), dim3(64), 0, side, S->d_join + 4);
-    hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join + 4, S->spin_target, S->h_join_timeout, S->wait_limit, 0, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join + 4, S->spin_target, S->h_join_timeout, S->wait_limit, true, (unsigned long long *)nullptr);
     gate.waits = true;
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
@@ -803,19 +686,17 @@ int qc_spin_join_end(qc_system *S, int *ctl_all, int *ctl_out, unsigned *h_seq, 
 // again, and this handle joins through events from now on.
 int qc_join_check(qc_system *S) {
     if (!S->h_join_timeout || !__atomic_load_n(S->h_join_timeout, __ATOMIC_ACQUIRE)) return QC_OK;
-    const int who = __atomic_load_n(S->h_join_timeout, __ATOMIC_ACQUIRE);         // (1: a waiting kernel, 2: the closing fold)
     S->last_error = "a device-side wait of the Fock build gave up (QC_WAIT_LIMIT_MS): a launch it depended on never finished; "
                     "this handle joins its streams through events from now on";
     fprintf(stderr, "qchem_hip: %s\n", S->last_error.c_str());
     (void)hipDeviceSynchronize();
     unsigned c[5] = {0, 0, 0, 0, 0};
     if (hipMemcpy(c, S->d_join, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess) {
-        fprintf(stderr, "qchem_hip: join counter %u, the wait wanted %u (%s); fork word %u, spin counter %u / %u\n", c[0], S->join_target,
-                who == 2 ? "by the closing fold" : "by a waiting kernel", c[1], c[4], S->spin_target);
-        S->join_target = c[0]; S->fork_seq = std::max(S->fork_seq, c[1]); S->spin_target = c[4]; }
+        fprintf(stderr, "qchem_hip: join counter %u, the wait wanted %u; spin counter %u / %u\n", c[0], S->join_target, c[4], S->spin_target);
+        S->join_target = c[0]; S->spin_target = c[4]; }
     __atomic_store_n(S->h_join_timeout, 0, __ATOMIC_RELEASE);
     S->join_by_events = true;
-    S->gt_clean = false; S->prepared = false; S->spec.pending = false;
+    S->gt_clean = false; S->prepared = false;
     return QC_ERR_HIP;
 }
 
@@ -827,7 +708,7 @@ static int qc_join_probe(qc_system *S, bool *concurrent) {
     QcGateHold hold(S);
     *S->h_join_timeout = 0;
     S->join_target += 1;
-    hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join, S->join_target, S->h_join_timeout, 200000LL, 0, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join, S->join_target, S->h_join_timeout, 200000LL, true, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(qc_join_mark_kernel, dim3(1), dim3(64), 0, S->side[0], S->d_join);
     if (hipGetLastError() != hipSuccess) return QC_ERR_HIP;
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
@@ -842,7 +723,6 @@ static QcKernelArgs base_args(qc_system *S, const QcFockArgs &fa) {
     a.pairs = S->d_pairs; a.pairdata = S->d_pairdata; a.pairdataT = S->d_pairdataT; a.boys = S->d_boys; a.rplan = reinterpret_cast<const int2 *>(S->d_rplan); a.gidx = reinterpret_cast<const uint4 *>(S->d_gidx); a.n = S->nbasis;
     a.Dj = fa.Dj; a.Dk0 = fa.Dk0; a.Dk1 = fa.Dk1; a.G0 = fa.G0; a.G1 = fa.G1; a.cK = fa.cK; a.eri_out = fa.eri_out;
     a.nrep = fa.nrep > 0 ? fa.nrep : 1; a.rep_stride = fa.rep_stride; a.fxs = fa.fxs; a.fx_lo = fa.fx_lo; a.schwarz_out = fa.schwarz_out;
-    a.cancel = fa.fork_seq ? S->d_join + 2 : nullptr; a.cancel_seq = fa.fork_seq;
     return a;
 }
 
@@ -976,14 +856,19 @@ static void tier_units(qc_system *S, std::vector<std::vector<int>> &units) {
         });
 }
 
-// Normal mode: the (at most 14) tier launches are independent (they only meet in the atomically accumulated Gt
-// replicas), so each goes to its own side stream forked from / joined to the handle's stream.
-// Profiling mode (class_ms != nullptr): one single-segment launch per class bucket, serial on the handle's stream with
-// a hipEvent between consecutive launches; unit_ms (optional, 14 entries) times the real tier launches the same way.
-int qc_launch_fock_classes(qc_system *S, const QcFockArgs &fa, float *class_ms, float *unit_ms, bool nofork) {
-    const QcKernelArgs a0 = base_args(S, fa);
-    const QcKernelArgs &a = a0;
-    // (the launch units and their segments only change with the work lists: kept between builds, dropped by upload_slots)
+// What the functions of one build share: the handle, the caller's arguments, the kernels' arguments made of them, the launch plan.
+struct QcBuild {
+    qc_system *S;
+    const QcFockArgs &fa;
+    const QcKernelArgs a;
+    const QcLaunchPlan &plan;
+    // from the first replica of the hi plane to the last replica in use of the lo plane: the planes keep the layout of QC_NREP replicas
+    // whatever the number in use
+    size_t accum_bytes() const { return ((fa.fxs ? fa.fx_lo : 0) + (size_t)a.nrep * a.rep_stride) * sizeof(double); }
+};
+
+// (the launch units and their segments only change with the work lists: kept between builds, dropped by upload_slots)
+static const QcLaunchPlan &launch_plan_of(qc_system *S) {
     if (!S->launch_plan) {
         S->launch_plan = new QcLaunchPlan();
         tier_units(S, S->launch_plan->units);
@@ -993,428 +878,404 @@ int qc_launch_fock_classes(qc_system *S, const QcFockArgs &fa, float *class_ms, 
             S->launch_plan->segs.push_back(std::move(v));
         }
     }
-    const std::vector<std::vector<int>> &units = S->launch_plan->units;
-    auto segs_of = [&](const std::vector<int> &u) -> const std::vector<Seg> & { return S->launch_plan->segs[&u - units.data()]; };
-    if (class_ms || unit_ms) {
-        const size_t nev = (class_ms ? S->classes.size() : units.size()) + 1;
-        EventList evl;
-        if (evl.create(nev) != QC_OK) return QC_ERR_HIP;
-        std::vector<hipEvent_t> &ev = evl.ev;
-        QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
-        if (class_ms) {
-            for (size_t ci = 0; ci < S->classes.size(); ++ci) {
-                const QcClass &c = S->classes[ci];
-                if (!c.slots.empty() || !c.bundles.empty()) {
-                    int rc = launch_segments(S, qc_unit_of(c.LAB, c.LCD, c.bm), {seg_of(c)}, S->stream, a);
-                    if (rc != QC_OK) return rc;
-                }
-                QC_HIP_CHECK(hipEventRecord(ev[ci + 1], S->stream));
+    return *S->launch_plan;
+}
+
+// Profiling mode: one single-segment launch per class bucket (class_ms), or the real tier launches (unit_ms, QC_NUNITS entries), serial on
+// the handle's stream with a hipEvent between consecutive launches.
+static int time_units_serial(const QcBuild &b, float *class_ms, float *unit_ms) {
+    qc_system *S = b.S;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    const size_t nev = (class_ms ? S->classes.size() : units.size()) + 1;
+    EventList evl;
+    if (evl.create(nev) != QC_OK) return QC_ERR_HIP;
+    std::vector<hipEvent_t> &ev = evl.ev;
+    QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
+    if (class_ms) {
+        for (size_t ci = 0; ci < S->classes.size(); ++ci) {
+            const QcClass &c = S->classes[ci];
+            if (!c.slots.empty() || !c.bundles.empty()) {
+                int rc = launch_segments(S, qc_unit_of(c.LAB, c.LCD, c.bm), {seg_of(c)}, S->stream, b.a);
+                if (rc != QC_OK) return rc;
             }
-        } else {
-            for (size_t u = 0; u < units.size(); ++u) {
-                if (!units[u].empty()) { int rc = launch_segments(S, (int)u, segs_of(units[u]), S->stream, a); if (rc != QC_OK) return rc; }
-                QC_HIP_CHECK(hipEventRecord(ev[u + 1], S->stream));
-            }
+            QC_HIP_CHECK(hipEventRecord(ev[ci + 1], S->stream));
         }
-        QC_HIP_CHECK(hipEventSynchronize(ev.back()));
-        float *out = class_ms ? class_ms : unit_ms;
-        for (size_t i = 0; i + 1 < nev; ++i) QC_HIP_CHECK(hipEventElapsedTime(&out[i], ev[i], ev[i + 1]));
-        return QC_OK;
+    } else {
+        for (size_t u = 0; u < units.size(); ++u) {
+            if (!units[u].empty()) { int rc = launch_segments(S, (int)u, b.plan.segs[u], S->stream, b.a); if (rc != QC_OK) return rc; }
+            QC_HIP_CHECK(hipEventRecord(ev[u + 1], S->stream));
+        }
     }
-    // Launch units are independent; they go to QC_NSTREAMS side streams (one hardware queue each next to the main
-    // stream's, GPU_MAX_HW_QUEUES=8).  Kernels on one stream run in order, so the assignment matters: the first build
-    // of a handle times every unit alone (density-independent), then units are placed longest-first on the least
-    // loaded stream.
-    // (`head_start`, ms: stream 0 is given that much more work than the others.  The most loaded stream becomes the handle's own stream,
-    // and a build that ends on the handle's stream goes straight on to the fold, while one that ends on a side stream first pays the
-    // cross-queue signal - event packet, barrier packets, ~20 us on the H2O/cc-pVTZ trace.)
-    auto lpt = [&](const std::vector<float> &w, int nstreams, float head_start = 0.f, bool bm_on_second = false) {
-        nstreams = std::min(nstreams, S->nlanes);              // (slots beyond the dispatch lanes share a pipe with an earlier one)
-        std::vector<int> ord;
-        for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) ord.push_back((int)u);
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return w[x] > w[y]; });
-        std::vector<float> load(nstreams, 0.f);
-        load[0] = -head_start;
-        S->unit_stream.assign(units.size(), 0);
-        // (bm_on_second: the bra-major launches - persistent grids that are dispatched at once and do not hold their pipe - on the SECOND
-        // streams of the pipes, every one its own chain, next to the column launches on the lanes.  H2O/cc-pVTZ without any search:
-        // 0.341 against 0.350 ms per iteration, benzene 1.730 against 1.718; as a proposal of the search, with moves onto the second
-        // streams allowed, the search ended on assignments that were fast back to back and slow inside SCF passes (0.199 ms builds
-        // against 0.192) and found nothing for benzene.  QC_BM_PAIRED keeps the experiment.)
-        static const bool bm_env = getenv("QC_BM_PAIRED") != nullptr;
-        const bool bm_paired = bm_on_second || bm_env;
-        int nextb = S->nlanes;
-        for (int u : ord) {
-            if (bm_paired && u >= 2 * (QC_LPAIR + 1) && S->nlanes == nstreams && nextb < QC_NSTREAMS) { S->unit_stream[u] = nextb++; continue; }
-            const int k = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            S->unit_stream[u] = k;
-            load[k] += w[u];
-        }
-        S->unit_weight = w;
-    };
-    // one concurrent build: fork the side streams off the handle's stream, launch every unit on its stream (heaviest
-    // first), join.  `ev` (tuning only): [0] fork, [1] join, [2 + 2u], [3 + 2u] around unit u.
-    auto launch_concurrent = [&](hipEvent_t *ev, bool per_unit, unsigned fork_seq, bool fold_joins = false) -> int {
-        S->fold_join_pending = false;
-        qc_stamp("to launch_concurrent");
-        QcGateHold gate(S);
-        qc_stamp("gate");
-        QcKernelArgs a = a0;                       // (a speculative / spec-form build carries its number: the cancel word may empty it)
-        a.cancel = fork_seq ? S->d_join + 2 : nullptr; a.cancel_seq = fork_seq;                        // (cross-stream dependencies are created here and nowhere else: see QcGate)
-        if (ev) QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
-        // (nofork: everything the launches depend on has completed - the host waited for the handle's stream after it was enqueued)
-        static const bool force_fork = getenv("QC_FORCE_FORK") != nullptr;          // (A/B switch)
-        // device-side fork (speculative build): the side streams' first kernels wait for the fork word instead of an event of the
-        // handle's stream - what they depend on has not even started when they are issued
-        const bool devfork = fork_seq != 0;
-        const bool fork = !devfork && (ev != nullptr || !nofork || force_fork);
-        if (fork) QC_HIP_CHECK(hipEventRecord(S->ev_fork, S->stream));
-        S->wait_limit = qc_wait_limit(S);
-        // Issue order (the host needs ~8 us per launch, so it matters): inside a stream heaviest first; across streams the
-        // first launch of every stream before any second one, streams in the order of their total load - the chain that
-        // ends the build gets going first and no stream sits empty while another one's queue is being filled.
-        std::vector<int> q[QC_NSTREAMS];
-        int ks[QC_NSTREAMS];
-        {
-            std::vector<int> byw;
-            for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) byw.push_back((int)u);
-            // (an entry of unit_stream is lane | rank << 3: inside a lane the launches go out by rank, then heaviest first - the rank is how
-            // the assignment search puts a lighter launch in front of a heavier one)
-            std::stable_sort(byw.begin(), byw.end(), [&](int x, int y) {
-                const int rx = S->unit_stream[x] >> 3, ry = S->unit_stream[y] >> 3;
-                return rx != ry ? rx < ry : S->unit_weight[x] > S->unit_weight[y];
-            });
-            float load[QC_NSTREAMS] = {};
-            for (int u : byw) { q[S->unit_stream[u] & 7].push_back(u); load[S->unit_stream[u] & 7] += S->unit_weight[u]; }
-            for (int k = 0; k < QC_NSTREAMS; ++k) ks[k] = k;
-            std::stable_sort(ks, ks + QC_NSTREAMS, [&](int x, int y) { return load[x] > load[y]; });
-        }
-        // the most loaded chain runs on the handle's own stream: no fork hop before it, no join after it.
-        // NOT in a speculative build: there the kernel in front of the build - the Roothaan step that releases the fork word before it
-        // ends - retires slowly once the side chains have started (its end-of-kernel cache write-back competes with their traffic: 100 us
-        // instead of 5 on the H2O/cc-pVTZ trace), and a chain queued behind it on the handle's stream starts that much later.  All chains
-        // of a speculative build go to side streams; the handle's stream carries the wait and the fold, which have to wait anyway.
-        // (with the dispatch lanes known, slot 0 is the slot on the pipe of the handle's own stream: its chain is the one that runs there -
-        // any other choice would put two chains on one pipe; the longest-first rule gives slot 0 the heaviest launch anyway)
-        const int kmain = devfork ? -1 : (S->lane0_is_main ? (q[0].empty() ? -1 : 0) : ks[0]);
-        // (a speculative build keeps the pipe of the handle's own stream free of its waiting kernels: a queue whose head packet waits
-        // behind a running kernel slows the other queue of its pipe - the Roothaan step on the handle's stream ran 1.2-1.7x longer with
-        // a waiter next door - so the chain of slot 0 goes to the second stream of lane 1's pipe)
-        static const bool spec_keep_lane0 = getenv("QC_SPEC_LANE0") != nullptr;      // (A/B switch)
-        auto side_slot = [&](int k) { return (devfork && S->lane0_is_main && !spec_keep_lane0 && k == 0 && S->nlanes + 0 < QC_NSTREAMS) ? S->nlanes : k; };
-        const bool event_join = S->join_by_events;                   // (QC_EVENT_JOIN, or dispatches are serialised here: qc_device_init)
-        if (devfork && event_join) return QC_ERR_INVALID;            // (the caller asks qc_fock_can_speculate first)
-        // an earlier ASYNCHRONOUS build's wait gave up (qc_fock_*_device return before their build has run; every call that waits on the
-        // host has looked at the word itself, qc_join_check): its result was not complete, and this is the first call that can say so
-        if (!event_join) { int jrc = qc_join_check(S); if (jrc != QC_OK) return jrc; }
-        qc_stamp("sorted");
-        // launches of a set of streams, interleaved (first launch of every stream of the set before any second one), then the
-        // streams' markers of the device-side join
-        auto issue = [&](const int *set, int nset) -> int {
-            size_t longest = 0;
-            for (int i = 0; i < nset; ++i) longest = std::max(longest, q[set[i]].size());
-            for (size_t pos = 0; pos < longest; ++pos)
-                for (int i = 0; i < nset; ++i) {
-                    const int k = set[i];
-                    if (pos >= q[k].size()) continue;
-                    const int u = q[k][pos];
-                    hipStream_t st = k == kmain ? S->stream : S->side[S->slot_side[side_slot(k)]];
-                    if (pos == 0 && k != kmain && fork) QC_HIP_CHECK(hipStreamWaitEvent(st, S->ev_fork, 0));
-                    if (pos == 0 && k != kmain && devfork) {
-                        // (side chains in the order of their load, QC_FORK_STAGGER_US apart - default 6 us, the host's own issue rate)
-                        static const double stagger_us = getenv("QC_FORK_STAGGER_US") ? atof(getenv("QC_FORK_STAGGER_US")) : 6.0;
-                        const int delay = (int)(stagger_us * 100.0 * (double)i);
-                        hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, st, S->d_join + 1, fork_seq, S->h_join_timeout, S->wait_limit, delay, (unsigned long long *)nullptr);
-                    }
-                    if (ev && per_unit) QC_HIP_CHECK(hipEventRecord(ev[2 + 2 * u], st));
-                    int rc = launch_segments(S, u, segs_of(units[u]), st, a);
-                    if (rc != QC_OK) return rc;
-                    qc_stamp("launch");
-                    if (ev && per_unit) QC_HIP_CHECK(hipEventRecord(ev[3 + 2 * u], st));
-                }
-            if (!event_join) {
-                // (test hook QC_JOIN_FAULT: the first side stream's marker is left out - a join that can never complete, as if a launch on
-                // that stream had died: the waiting kernel runs into its limit and the call that waits for this build must fail)
-                const bool fault = getenv("QC_JOIN_FAULT") != nullptr;
-                for (int i = 0; i < nset; ++i)
-                    if (set[i] != kmain && !q[set[i]].empty() && !(fault && i == (set[0] == kmain ? 1 : 0))) hipLaunchKernelGGL(qc_join_mark_kernel, dim3(1), dim3(64), 0, S->side[S->slot_side[side_slot(set[i])]], S->d_join);
-                if (hipGetLastError() != hipSuccess) return QC_ERR_HIP;
-                qc_stamp("markers");
-            }
-            return QC_OK;
-        };
-        int nused = 0;
-        unsigned nside = 0;
-        for (int k = 0; k < QC_NSTREAMS; ++k) if (!q[k].empty()) { ++nused; if (k != kmain) ++nside; }
-        // Measured (alternating runs on one box): H2O/cc-pVTZ builds 0.227 ms with three helpers against 0.204 ms issued by the caller
-        // alone (means of six) - its 13 launches of 30-70 us each do better when they start 6-7 us apart than all at once; benzene/cc-pVDZ
-        // iterations 1.646 against 1.641 ms (means of four; 1.470 against 1.494 ms of build in a first pair of runs), and on another box two
-        // of six runs with helpers showed 0.1-0.16 ms per pass outside the build and linear-algebra intervals.  Nothing gained: the
-        // helpers are OFF unless QC_ISSUE_THREADS asks for them (the code stays for larger systems, where the issue time of dozens of
-        // long launches could matter).
-        const int nhelp_env = std::min(S->issue_threads, QC_NSTREAMS - 1);
-        float serial_ms = 0.f;
-        for (float x : S->unit_ms) serial_ms += x;
-        const int nhelp_want = nhelp_env >= 0 ? nhelp_env : 0;
-        (void)serial_ms;
-        const int nhelp = (event_join || devfork || (ev && per_unit) || nused < 3) ? 0 : std::min(nhelp_want, nused - 1);
-        if (nhelp <= 0) {
-            int used_set[QC_NSTREAMS], n = 0;
-            for (int k : ks) if (!q[k].empty()) used_set[n++] = k;
-            int rc = issue(used_set, n);
+    QC_HIP_CHECK(hipEventSynchronize(ev.back()));
+    float *out = class_ms ? class_ms : unit_ms;
+    for (size_t i = 0; i + 1 < nev; ++i) QC_HIP_CHECK(hipEventElapsedTime(&out[i], ev[i], ev[i + 1]));
+    return QC_OK;
+}
+
+// Launch units are independent (they only meet in the atomically accumulated Gt replicas); they go to the side streams of the dispatch
+// lanes.  Kernels on one stream run in order, so the assignment matters: units are placed longest-first on the least loaded stream.
+// (`head_start`, ms: stream 0 is given that much more work than the others.  The most loaded stream becomes the handle's own stream,
+// and a build that ends on the handle's stream goes straight on to the fold, while one that ends on a side stream first pays the
+// cross-queue signal - event packet, barrier packets, ~20 us on the H2O/cc-pVTZ trace.)
+static void assign_longest_first(const QcBuild &b, const std::vector<float> &w, int nstreams, float head_start = 0.f) {
+    qc_system *S = b.S;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    nstreams = std::min(nstreams, S->nlanes);              // (slots beyond the dispatch lanes share a pipe with an earlier one)
+    std::vector<int> ord;
+    for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) ord.push_back((int)u);
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return w[x] > w[y]; });
+    std::vector<float> load(nstreams, 0.f);
+    load[0] = -head_start;
+    S->unit_stream.assign(units.size(), 0);
+    for (int u : ord) {
+        const int k = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        S->unit_stream[u] = k;
+        load[k] += w[u];
+    }
+    S->unit_weight = w;
+}
+
+// one concurrent build: fork the side streams off the handle's stream, launch every unit on its stream (heaviest
+// first), join.  `ev` (tuning only): [0] fork, [1] join, [2 + 2u], [3 + 2u] around unit u.
+// (nofork: everything the launches depend on has completed - the host waited for the handle's stream after it was enqueued)
+static int issue_build(const QcBuild &b, hipEvent_t *ev, bool per_unit, bool nofork) {
+    qc_system *S = b.S;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    qc_stamp("to launch_concurrent");
+    QcGateHold gate(S);                        // (cross-stream dependencies are created here and nowhere else: see QcGate)
+    qc_stamp("gate");
+    if (ev) QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
+    static const bool force_fork = getenv("QC_FORCE_FORK") != nullptr;          // (A/B switch)
+    const bool fork = ev != nullptr || !nofork || force_fork;
+    if (fork) QC_HIP_CHECK(hipEventRecord(S->ev_fork, S->stream));
+    S->wait_limit = qc_wait_limit(S);
+    // Issue order (the host needs ~8 us per launch, so it matters): inside a stream heaviest first; across streams the
+    // first launch of every stream before any second one, streams in the order of their total load - the chain that
+    // ends the build gets going first and no stream sits empty while another one's queue is being filled.
+    std::vector<int> q[QC_NSTREAMS];
+    int ks[QC_NSTREAMS];
+    {
+        std::vector<int> byw;
+        for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) byw.push_back((int)u);
+        // (an entry of unit_stream is lane | rank << 3: inside a lane the launches go out by rank, then heaviest first - the rank is how
+        // the assignment search puts a lighter launch in front of a heavier one)
+        std::stable_sort(byw.begin(), byw.end(), [&](int x, int y) {
+            const int rx = S->unit_stream[x] >> 3, ry = S->unit_stream[y] >> 3;
+            return rx != ry ? rx < ry : S->unit_weight[x] > S->unit_weight[y];
+        });
+        float load[QC_NSTREAMS] = {};
+        for (int u : byw) { q[S->unit_stream[u] & 7].push_back(u); load[S->unit_stream[u] & 7] += S->unit_weight[u]; }
+        for (int k = 0; k < QC_NSTREAMS; ++k) ks[k] = k;
+        std::stable_sort(ks, ks + QC_NSTREAMS, [&](int x, int y) { return load[x] > load[y]; });
+    }
+    // the most loaded chain runs on the handle's own stream: no fork hop before it, no join after it.
+    // (with the dispatch lanes known, slot 0 is the slot on the pipe of the handle's own stream: its chain is the one that runs there -
+    // any other choice would put two chains on one pipe; the longest-first rule gives slot 0 the heaviest launch anyway)
+    const int kmain = S->lane0_is_main ? (q[0].empty() ? -1 : 0) : ks[0];
+    const bool event_join = S->join_by_events;                   // (QC_EVENT_JOIN, or dispatches are serialised here: qc_device_init)
+    // an earlier ASYNCHRONOUS build's wait gave up (qc_fock_*_device return before their build has run; every call that waits on the
+    // host has looked at the word itself, qc_join_check): its result was not complete, and this is the first call that can say so
+    if (!event_join) { int jrc = qc_join_check(S); if (jrc != QC_OK) return jrc; }
+    qc_stamp("sorted");
+    // the launches of the streams in use, interleaved (first launch of every stream before any second one), then the streams' markers of
+    // the device-side join
+    int set[QC_NSTREAMS], nset = 0;
+    unsigned nside = 0;
+    for (int k : ks) if (!q[k].empty()) { set[nset++] = k; if (k != kmain) ++nside; }
+    size_t longest = 0;
+    for (int i = 0; i < nset; ++i) longest = std::max(longest, q[set[i]].size());
+    for (size_t pos = 0; pos < longest; ++pos)
+        for (int i = 0; i < nset; ++i) {
+            const int k = set[i];
+            if (pos >= q[k].size()) continue;
+            const int u = q[k][pos];
+            hipStream_t st = k == kmain ? S->stream : S->side[S->slot_side[k]];
+            if (pos == 0 && k != kmain && fork) QC_HIP_CHECK(hipStreamWaitEvent(st, S->ev_fork, 0));
+            if (ev && per_unit) QC_HIP_CHECK(hipEventRecord(ev[2 + 2 * u], st));
+            int rc = launch_segments(S, u, b.plan.segs[u], st, b.a);
             if (rc != QC_OK) return rc;
-        } else {
-            if (!S->issue_pool || (int)S->issue_pool->w.size() < nhelp) { delete S->issue_pool; S->issue_pool = new QcIssuePool(std::max(nhelp, nhelp_want), S->device); }
-            QcIssuePool &P = *S->issue_pool;
-            ++P.gen;
-            int sets[QC_NSTREAMS][QC_NSTREAMS], nset[QC_NSTREAMS] = {};
-            {   // side streams in the order of their load, dealt round the helpers
-                int h = 0;
-                for (int k : ks) if (k != kmain && !q[k].empty()) { sets[h][nset[h]++] = k; h = (h + 1) % nhelp; }
-            }
-            for (int h = 0; h < nhelp; ++h) P.start(h, [&, h]() -> int { return issue(sets[h], nset[h]); });
-            int rc = kmain >= 0 ? issue(&kmain, 1) : QC_OK;
-            for (int h = 0; h < nhelp; ++h) { const int r = P.wait(h); if (rc == QC_OK) rc = r; }       // (every helper is waited for, whatever happened)
-            if (rc != QC_OK) {
-                // some markers of this build may be out, others not: the counter and the host's target meet again before anything else waits
-                unsigned c = 0;
-                if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(&c, S->d_join, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess) S->join_target = c;
-                return rc;
-            }
+            qc_stamp("launch");
+            if (ev && per_unit) QC_HIP_CHECK(hipEventRecord(ev[3 + 2 * u], st));
         }
-        if (event_join) {
-            for (int k = 0; k < QC_NSTREAMS; ++k) {
-                if (q[k].empty() || k == kmain) continue;
-                QC_HIP_CHECK(hipEventRecord(S->ev_join[k], S->side[S->slot_side[side_slot(k)]]));
-                QC_HIP_CHECK(hipStreamWaitEvent(S->stream, S->ev_join[k], 0));
-            }
-        } else if (nside) {
+    if (event_join) {
+        for (int k = 0; k < QC_NSTREAMS; ++k) {
+            if (q[k].empty() || k == kmain) continue;
+            QC_HIP_CHECK(hipEventRecord(S->ev_join[k], S->side[S->slot_side[k]]));
+            QC_HIP_CHECK(hipStreamWaitEvent(S->stream, S->ev_join[k], 0));
+        }
+    } else {
+        // (test hook QC_JOIN_FAULT: the first side stream's marker is left out - a join that can never complete, as if a launch on
+        // that stream had died: the waiting kernel runs into its limit and the call that waits for this build must fail)
+        const bool fault = getenv("QC_JOIN_FAULT") != nullptr;
+        for (int i = 0; i < nset; ++i)
+            if (set[i] != kmain && !(fault && i == (set[0] == kmain ? 1 : 0))) hipLaunchKernelGGL(qc_join_mark_kernel, dim3(1), dim3(64), 0, S->side[S->slot_side[set[i]]], S->d_join);
+        if (hipGetLastError() != hipSuccess) return QC_ERR_HIP;
+        qc_stamp("markers");
+        if (nside) {
             S->join_target += nside;
-            if (fold_joins) S->fold_join_pending = true;
-            else hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join, S->join_target, S->h_join_timeout, S->wait_limit, -1, S->tl_cur ? S->tl_cur + QC_TL_W * QC_NUNITS : nullptr);
+            hipLaunchKernelGGL(qc_join_wait_kernel, dim3(1), dim3(64), 0, S->stream, S->d_join, S->join_target, S->h_join_timeout, S->wait_limit, false, S->tl_cur ? S->tl_cur + QC_TL_W * QC_NUNITS : nullptr);
             if (hipGetLastError() != hipSuccess) return QC_ERR_HIP;
             gate.waits = true;
             qc_stamp("wait kernel");
         }
-        if (ev) QC_HIP_CHECK(hipEventRecord(ev[1], S->stream));
-        static const bool join_check = getenv("QC_JOIN_CHECK") != nullptr;       // (diagnostic: after every build the device counter is the host's target)
-        if (join_check && !event_join) {
-            unsigned c = 0;
-            QC_HIP_CHECK(hipDeviceSynchronize());
-            QC_HIP_CHECK(hipMemcpy(&c, S->d_join, sizeof(c), hipMemcpyDeviceToHost));
-            if (c != S->join_target) { fprintf(stderr, "qchem_hip: join counter %u, target %u (%u side streams)\n", c, S->join_target, nside); return QC_ERR_HIP; }
-        }
-        return QC_OK;
-    };
-    // Kernels that overlap stretch each other by class-dependent factors (the bra-major launches 1.8x next to the one-wave-per-SIMD
-    // launches, those hardly at all), which the durations alone do not show: three concurrent builds with events around every launch,
-    // each proposing the longest-first assignment of the durations seen INSIDE it.  These proposals are the first trials of the online
-    // search and are made when it starts (its first instalment): a handle that runs one SCF does not pay for them.
-    auto seed_proposals = [&]() -> int {
-        const size_t gb = ((fa.fxs ? fa.fx_lo : 0) + (size_t)a.nrep * a.rep_stride) * sizeof(double);
-        const std::vector<int> keep = S->unit_stream;
-        EventList evl;
-        if (evl.create(2 + 2 * units.size()) != QC_OK) return QC_ERR_HIP;
-        std::vector<hipEvent_t> &ev = evl.ev;
-        int rc = QC_OK;
-        for (int round = 0; round < 3 && rc == QC_OK; ++round) {
-            if (fa.G0) QC_HIP_CHECK(hipMemsetAsync(fa.G0, 0, gb, S->stream));
-            if ((rc = launch_concurrent(ev.data(), true, 0)) != QC_OK) break;
-            QC_HIP_CHECK(hipEventSynchronize(ev[1]));
-            if ((rc = qc_join_check(S)) != QC_OK) break;
-            std::vector<float> dur(units.size(), 0.f);
-            for (size_t u = 0; u < units.size(); ++u)
-                if (!units[u].empty()) { QC_HIP_CHECK(hipEventSynchronize(ev[3 + 2 * u])); QC_HIP_CHECK(hipEventElapsedTime(&dur[u], ev[2 + 2 * u], ev[3 + 2 * u])); }
-            lpt(dur, QC_NSTREAMS, round == 1 ? 0.015f : 0.f);
-            if (std::find(S->on.cands.begin(), S->on.cands.end(), S->unit_stream) == S->on.cands.end() && S->unit_stream != keep) S->on.cands.push_back(S->unit_stream);
-            S->on.spent += 1;
-        }
-        S->unit_stream = keep; S->unit_weight = S->unit_ms;
-        return rc;
-    };
-    if (S->unit_ms.size() != units.size()) {
-        // First build of a shard.  No tuner run (round 4): the launches are timed alone once (two serial passes: the first pays the code
-        // upload), placed longest-first on the dispatch lanes, and the assignment is refined ONLINE from the build times the SCF passes
-        // report anyway (qc_fock_feedback) - a neighbouring assignment is tried for a few passes and kept when it is faster.  The offline
-        // tuner of rounds 1-3 (25 + up to 256 extra builds and a local search, 55 ms for H2O/cc-pVTZ) cost ten times the 15-pass SCF it
-        // served and won 6 % of its builds; a process that has seen the same work lists before starts from what it learned (qc_assign_cache).
-        S->unit_ms.assign(units.size(), 0.f);
-        struct Untuned { qc_system *S; bool keep = false; ~Untuned() { if (!keep) { S->unit_ms.clear(); S->unit_stream.clear(); } } } untuned{S};
-        // (from the first replica of the hi plane to the last replica in use of the lo plane: the planes keep the layout of QC_NREP replicas
-        // whatever the number in use)
-        const size_t gbytes = ((fa.fxs ? fa.fx_lo : 0) + (size_t)a.nrep * a.rep_stride) * sizeof(double);
-        // (the warm-up pass only where this process has not launched these units before: their first launches pay the code upload)
-        static std::atomic<unsigned long long> units_warm{0};
-        unsigned long long mine = 0;
-        for (size_t u = 0; u < units.size() && u < 62; ++u) if (!units[u].empty()) mine |= 1ull << u;
-        if (S->merge_bm) mine |= 1ull << 62;                 // (the merged launches are kernels of their own)
-        if (S->merge_t1) mine |= 1ull << 63;
-        int rc = QC_OK;
-        if ((units_warm.load(std::memory_order_acquire) & mine) != mine) rc = qc_launch_fock_classes(S, fa, nullptr, S->unit_ms.data());
-        if (rc == QC_OK) rc = qc_launch_fock_classes(S, fa, nullptr, S->unit_ms.data());   // serial, timed
-        if (rc == QC_OK) units_warm.fetch_or(mine, std::memory_order_acq_rel);
-        if (rc != QC_OK) return rc;
-        static const int fixed_w = getenv("QC_TUNE_FIXED") ? atoi(getenv("QC_TUNE_FIXED")) : 0;      // (experiment switch: lanes used, no online search)
-        lpt(S->unit_ms, fixed_w >= 1 && fixed_w <= QC_NSTREAMS ? fixed_w : QC_NSTREAMS, 0.015f);
-        S->tune_count += 1; S->assign_gen += 1;
-        const bool no_search = fixed_w >= 1 || getenv("QC_TUNE_OFF") != nullptr;
-        qc_online_reset(S, no_search);
-        qc_assign_cache_lookup(S);
-        if (fa.G0) QC_HIP_CHECK(hipMemsetAsync(fa.G0, 0, gbytes, S->stream));
-        nofork = false;                                  // the side streams must see that memset (and the timing passes) finished
-        untuned.keep = true;
     }
-    // an instalment of the assignment search (see above): not in a speculative build, not in the builds of a profiling call
-    S->on.builds += 1;
-    if (!S->on.frozen && fa.fork_seq == 0 && fa.G0 && S->on.builds >= QC_SEARCH_FIRST_BUILD && S->on.spent + 2 * QC_SEARCH_CHUNK <= S->on.builds) {
-        const size_t gbytes = ((fa.fxs ? fa.fx_lo : 0) + (size_t)a.nrep * a.rep_stride) * sizeof(double);
-        EventList evl;
-        if (evl.create(2) != QC_OK) return QC_ERR_HIP;
-        qc_system::QcOnline &o = S->on;
-        static const bool dbg = getenv("QC_TUNE_DEBUG") != nullptr;
-        int rc = QC_OK;
-        auto measure = [&](const std::vector<int> &assign, float &t) -> int {
-            S->unit_stream = assign;
-            t = 1e30f;
-            for (int rep = 0; rep < 2; ++rep) {
-                QC_HIP_CHECK(hipMemsetAsync(fa.G0, 0, gbytes, S->stream));
-                int r = launch_concurrent(evl.ev.data(), false, 0);
-                if (r != QC_OK) return r;
-                QC_HIP_CHECK(hipEventSynchronize(evl.ev[1]));
-                if ((r = qc_join_check(S)) != QC_OK) return r;
-                float x = 0.f;
-                QC_HIP_CHECK(hipEventElapsedTime(&x, evl.ev[0], evl.ev[1]));
-                t = std::min(t, x);
-                o.spent += 1;
+    if (ev) QC_HIP_CHECK(hipEventRecord(ev[1], S->stream));
+    static const bool join_check = getenv("QC_JOIN_CHECK") != nullptr;       // (diagnostic: after every build the device counter is the host's target)
+    if (join_check && !event_join) {
+        unsigned c = 0;
+        QC_HIP_CHECK(hipDeviceSynchronize());
+        QC_HIP_CHECK(hipMemcpy(&c, S->d_join, sizeof(c), hipMemcpyDeviceToHost));
+        if (c != S->join_target) { fprintf(stderr, "qchem_hip: join counter %u, target %u (%u side streams)\n", c, S->join_target, nside); return QC_ERR_HIP; }
+    }
+    return QC_OK;
+}
+
+// First build of a shard.  No tuner run (round 4): the launches are timed alone once (two serial passes: the first pays the code
+// upload), placed longest-first on the dispatch lanes, and the assignment is refined ONLINE from the build times the SCF passes
+// report anyway (qc_fock_feedback) - a neighbouring assignment is tried for a few passes and kept when it is faster.  The offline
+// tuner of rounds 1-3 (25 + up to 256 extra builds and a local search, 55 ms for H2O/cc-pVTZ) cost ten times the 15-pass SCF it
+// served and won 6 % of its builds; a process that has seen the same work lists before starts from what it learned (qc_assign_cache).
+static int first_build(const QcBuild &b) {
+    qc_system *S = b.S;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    S->unit_ms.assign(units.size(), 0.f);
+    struct Untuned { qc_system *S; bool keep = false; ~Untuned() { if (!keep) { S->unit_ms.clear(); S->unit_stream.clear(); } } } untuned{S};
+    // (the warm-up pass only where this process has not launched these units before: their first launches pay the code upload)
+    static std::atomic<unsigned long long> units_warm{0};
+    unsigned long long mine = 0;
+    for (size_t u = 0; u < units.size() && u < 62; ++u) if (!units[u].empty()) mine |= 1ull << u;
+    if (S->merge_bm) mine |= 1ull << 62;                 // (the merged launches are kernels of their own)
+    if (S->merge_t1) mine |= 1ull << 63;
+    int rc = QC_OK;
+    if ((units_warm.load(std::memory_order_acquire) & mine) != mine) rc = time_units_serial(b, nullptr, S->unit_ms.data());
+    if (rc == QC_OK) rc = time_units_serial(b, nullptr, S->unit_ms.data());   // serial, timed
+    if (rc == QC_OK) units_warm.fetch_or(mine, std::memory_order_acq_rel);
+    if (rc != QC_OK) return rc;
+    static const int fixed_w = getenv("QC_TUNE_FIXED") ? atoi(getenv("QC_TUNE_FIXED")) : 0;      // (experiment switch: lanes used, no online search)
+    assign_longest_first(b, S->unit_ms, fixed_w >= 1 && fixed_w <= QC_NSTREAMS ? fixed_w : QC_NSTREAMS, 0.015f);
+    S->tune_count += 1; S->assign_gen += 1;
+    const bool no_search = fixed_w >= 1 || getenv("QC_TUNE_OFF") != nullptr;
+    qc_online_reset(S, no_search);
+    qc_assign_cache_lookup(S);
+    if (b.fa.G0) QC_HIP_CHECK(hipMemsetAsync(b.fa.G0, 0, b.accum_bytes(), S->stream));
+    untuned.keep = true;
+    return QC_OK;
+}
+
+// Kernels that overlap stretch each other by class-dependent factors (the bra-major launches 1.8x next to the one-wave-per-SIMD
+// launches, those hardly at all), which the durations alone do not show: three concurrent builds with events around every launch,
+// each proposing the longest-first assignment of the durations seen INSIDE it.  These proposals are the first trials of the online
+// search and are made when it starts (its first instalment): a handle that runs one SCF does not pay for them.
+static int seed_proposals(const QcBuild &b) {
+    qc_system *S = b.S;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    const std::vector<int> keep = S->unit_stream;
+    EventList evl;
+    if (evl.create(2 + 2 * units.size()) != QC_OK) return QC_ERR_HIP;
+    std::vector<hipEvent_t> &ev = evl.ev;
+    int rc = QC_OK;
+    for (int round = 0; round < 3 && rc == QC_OK; ++round) {
+        if (b.fa.G0) QC_HIP_CHECK(hipMemsetAsync(b.fa.G0, 0, b.accum_bytes(), S->stream));
+        if ((rc = issue_build(b, ev.data(), true, false)) != QC_OK) break;
+        QC_HIP_CHECK(hipEventSynchronize(ev[1]));
+        if ((rc = qc_join_check(S)) != QC_OK) break;
+        std::vector<float> dur(units.size(), 0.f);
+        for (size_t u = 0; u < units.size(); ++u)
+            if (!units[u].empty()) { QC_HIP_CHECK(hipEventSynchronize(ev[3 + 2 * u])); QC_HIP_CHECK(hipEventElapsedTime(&dur[u], ev[2 + 2 * u], ev[3 + 2 * u])); }
+        assign_longest_first(b, dur, QC_NSTREAMS, round == 1 ? 0.015f : 0.f);
+        if (std::find(S->on.cands.begin(), S->on.cands.end(), S->unit_stream) == S->on.cands.end() && S->unit_stream != keep) S->on.cands.push_back(S->unit_stream);
+        S->on.spent += 1;
+    }
+    S->unit_stream = keep; S->unit_weight = S->unit_ms;
+    return rc;
+}
+
+// the better of two back-to-back builds under `assign` (`ev`: two events, around the build)
+static int measure_assignment(const QcBuild &b, hipEvent_t *ev, const std::vector<int> &assign, float &t) {
+    qc_system *S = b.S;
+    S->unit_stream = assign;
+    t = 1e30f;
+    for (int rep = 0; rep < 2; ++rep) {
+        QC_HIP_CHECK(hipMemsetAsync(b.fa.G0, 0, b.accum_bytes(), S->stream));
+        int r = issue_build(b, ev, false, false);
+        if (r != QC_OK) return r;
+        QC_HIP_CHECK(hipEventSynchronize(ev[1]));
+        if ((r = qc_join_check(S)) != QC_OK) return r;
+        float x = 0.f;
+        QC_HIP_CHECK(hipEventElapsedTime(&x, ev[0], ev[1]));
+        t = std::min(t, x);
+        S->on.spent += 1;
+    }
+    return QC_OK;
+}
+
+// The neighbourhood of the current best, in full and in a fixed order: every launch moved to every other lane, every pair of
+// launches on different lanes swapped - launches of the most loaded lane first (they are the ones whose move can shorten the
+// build).  The search ends when a whole sweep has found nothing (a local optimum of the FULL neighbourhood: ten random
+// neighbours in a row, the rule before, left most of it unseen and ended anywhere between 0.172 and 0.192 ms on H2O/cc-pVTZ).
+static void neighbours(const QcBuild &b) {
+    qc_system *S = b.S;
+    qc_system::QcOnline &o = S->on;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    o.nb.clear(); o.nb_pos = 0;
+    std::vector<int> act;
+    for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) act.push_back((int)u);
+    const int nl = std::min(QC_NSTREAMS, S->nlanes);
+    if (act.size() < 2 || nl < 2) return;
+    float load[QC_NSTREAMS] = {};
+    int cnt[QC_NSTREAMS] = {}, maxrank[QC_NSTREAMS] = {};
+    for (int u : act) { const int k = o.best[u] & 7; load[k] += S->unit_ms[u]; cnt[k] += 1; maxrank[k] = std::max(maxrank[k], o.best[u] >> 3); }
+    std::stable_sort(act.begin(), act.end(), [&](int x, int y) { return load[o.best[x] & 7] > load[o.best[y] & 7]; });
+    for (int u : act)
+        for (int k = 0; k < nl; ++k)
+            if (k != (o.best[u] & 7)) { std::vector<int> t = o.best; t[u] = k; o.nb.push_back(std::move(t)); }
+    for (size_t i = 0; i < act.size(); ++i)
+        for (size_t j = i + 1; j < act.size(); ++j)
+            if ((o.best[act[i]] & 7) != (o.best[act[j]] & 7)) {
+                std::vector<int> t = o.best;
+                const int ki = t[act[i]] & 7, kj = t[act[j]] & 7;
+                t[act[i]] = kj; t[act[j]] = ki;
+                o.nb.push_back(std::move(t));
             }
-            return QC_OK;
-        };
-        // The neighbourhood of the current best, in full and in a fixed order: every launch moved to every other lane, every pair of
-        // launches on different lanes swapped - launches of the most loaded lane first (they are the ones whose move can shorten the
-        // build).  The search ends when a whole sweep has found nothing (a local optimum of the FULL neighbourhood: ten random
-        // neighbours in a row, the rule before, left most of it unseen and ended anywhere between 0.172 and 0.192 ms on H2O/cc-pVTZ).
-        auto neighbours = [&]() {
-            o.nb.clear(); o.nb_pos = 0;
-            std::vector<int> act;
-            for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) act.push_back((int)u);
-            const int nl = std::min(QC_NSTREAMS, S->nlanes);
-            if (act.size() < 2 || nl < 2) return;
-            float load[QC_NSTREAMS] = {};
-            int cnt[QC_NSTREAMS] = {}, maxrank[QC_NSTREAMS] = {};
-            for (int u : act) { const int k = o.best[u] & 7; load[k] += S->unit_ms[u]; cnt[k] += 1; maxrank[k] = std::max(maxrank[k], o.best[u] >> 3); }
-            std::stable_sort(act.begin(), act.end(), [&](int x, int y) { return load[o.best[x] & 7] > load[o.best[y] & 7]; });
-            for (int u : act)
-                for (int k = 0; k < nl; ++k)
-                    if (k != (o.best[u] & 7)) { std::vector<int> t = o.best; t[u] = k; o.nb.push_back(std::move(t)); }
-            for (size_t i = 0; i < act.size(); ++i)
-                for (size_t j = i + 1; j < act.size(); ++j)
-                    if ((o.best[act[i]] & 7) != (o.best[act[j]] & 7)) {
-                        std::vector<int> t = o.best;
-                        const int ki = t[act[i]] & 7, kj = t[act[j]] & 7;
-                        t[act[i]] = kj; t[act[j]] = ki;
-                        o.nb.push_back(std::move(t));
-                    }
-            // order inside a lane: a launch sent to the back of its lane (the heavier-first rule is not always the better one: which kernel
-            // of a chain meets which kernels of the other chains decides how far they stretch each other)
-            for (int u : act) {
-                const int k = o.best[u] & 7;
-                if (cnt[k] >= 2 && maxrank[k] < 14) { std::vector<int> t = o.best; t[u] = k | ((maxrank[k] + 1) << 3); o.nb.push_back(std::move(t)); }
+    // order inside a lane: a launch sent to the back of its lane (the heavier-first rule is not always the better one: which kernel
+    // of a chain meets which kernels of the other chains decides how far they stretch each other)
+    for (int u : act) {
+        const int k = o.best[u] & 7;
+        if (cnt[k] >= 2 && maxrank[k] < 14) { std::vector<int> t = o.best; t[u] = k | ((maxrank[k] + 1) << 3); o.nb.push_back(std::move(t)); }
+    }
+}
+// the next assignment to try, in o.trial: the proposals of the first build, then the neighbours not measured yet
+static bool propose(const QcBuild &b) {
+    qc_system::QcOnline &o = b.S->on;
+    if (!o.cands.empty()) { o.trial = o.cands.back(); o.cands.pop_back(); return true; }
+    if (o.nb.empty() && o.nb_pos == 0) neighbours(b);
+    while (o.nb_pos < o.nb.size()) {
+        o.trial = o.nb[o.nb_pos++];
+        bool seen = false;
+        for (const auto &e : o.tried) if (e == o.trial) { seen = true; break; }
+        if (!seen) { o.tried.push_back(o.trial); return true; }
+    }
+    return false;
+}
+// the three fastest assignments measured so far
+static void note_top(qc_system::QcOnline &o, const std::vector<int> &a, float t) {
+    for (auto &e : o.top) if (e.second == a) { e.first = std::min(e.first, t); return; }
+    o.top.push_back({t, a});
+    std::sort(o.top.begin(), o.top.end(), [](const std::pair<float, std::vector<int>> &x, const std::pair<float, std::vector<int>> &y) { return x.first < y.first; });
+    if (o.top.size() > 3) o.top.resize(3);
+}
+// A whole sweep without a gain is a local optimum of single moves and swaps - and those lie 0.166 to 0.195 ms apart on H2O/cc-pVTZ,
+// process to process.  The search then starts again (QC_SEARCH_KICKS times) from the best assignment known with two random
+// cross-lane swaps applied - a step no sweep can take - and descends from there; the best three of everything measured go to
+// the finals as before.
+static bool kick(const QcBuild &b) {
+    qc_system::QcOnline &o = b.S->on;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    static const int max_kicks = getenv("QC_SEARCH_KICKS") ? atoi(getenv("QC_SEARCH_KICKS")) : QC_SEARCH_KICKS;
+    if (o.kicks >= max_kicks || o.top.empty()) return false;
+    std::vector<int> act;
+    for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) act.push_back((int)u);
+    if (act.size() < 4) return false;
+    auto rnd = [&]() { o.rng ^= o.rng << 13; o.rng ^= o.rng >> 17; o.rng ^= o.rng << 5; return o.rng; };
+    for (int attempt = 0; attempt < 32; ++attempt) {
+        std::vector<int> t = o.top[0].second;
+        for (int &x : t) x &= 7;
+        for (int rep = 0; rep < 2; ++rep)
+            for (int tries = 0; tries < 16; ++tries) {
+                const int i = act[rnd() % act.size()], j = act[rnd() % act.size()];
+                if (t[i] != t[j]) { std::swap(t[i], t[j]); break; }
             }
-        };
-        auto propose = [&]() -> bool {
-            if (!o.cands.empty()) { o.trial = o.cands.back(); o.cands.pop_back(); return true; }      // (the proposals of the first build)
-            if (o.nb.empty() && o.nb_pos == 0) neighbours();
-            while (o.nb_pos < o.nb.size()) {
-                o.trial = o.nb[o.nb_pos++];
-                bool seen = false;
-                for (const auto &e : o.tried) if (e == o.trial) { seen = true; break; }
-                if (!seen) { o.tried.push_back(o.trial); return true; }
-            }
-            return false;
-        };
-        if (o.best.empty()) o.best = S->unit_stream;
-        if (!o.seeded) { o.seeded = true; if ((rc = seed_proposals()) != QC_OK) return rc; }
-        auto note_top = [&](const std::vector<int> &a, float t) {
-            for (auto &e : o.top) if (e.second == a) { e.first = std::min(e.first, t); return; }
-            o.top.push_back({t, a});
-            std::sort(o.top.begin(), o.top.end(), [](const std::pair<float, std::vector<int>> &x, const std::pair<float, std::vector<int>> &y) { return x.first < y.first; });
-            if (o.top.size() > 3) o.top.resize(3);
-        };
-        float tb = 0.f;
-        if (o.base_ms <= 0.0) { if ((rc = measure(o.best, tb)) != QC_OK) return rc; o.base_ms = tb; note_top(o.best, tb); }
-        // A whole sweep without a gain is a local optimum of single moves and swaps - and those lie 0.166 to 0.195 ms apart on H2O/cc-pVTZ,
-        // process to process.  The search then starts again (QC_SEARCH_KICKS times) from the best assignment known with two random
-        // cross-lane swaps applied - a step no sweep can take - and descends from there; the best three of everything measured go to
-        // the finals as before.
-        auto kick = [&]() -> bool {
-            static const int max_kicks = getenv("QC_SEARCH_KICKS") ? atoi(getenv("QC_SEARCH_KICKS")) : QC_SEARCH_KICKS;
-            if (o.kicks >= max_kicks || o.top.empty()) return false;
-            std::vector<int> act;
-            for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty()) act.push_back((int)u);
-            if (act.size() < 4) return false;
-            auto rnd = [&]() { o.rng ^= o.rng << 13; o.rng ^= o.rng >> 17; o.rng ^= o.rng << 5; return o.rng; };
-            for (int attempt = 0; attempt < 32; ++attempt) {
-                std::vector<int> t = o.top[0].second;
-                for (int &x : t) x &= 7;
-                for (int rep = 0; rep < 2; ++rep)
-                    for (int tries = 0; tries < 16; ++tries) {
-                        const int i = act[rnd() % act.size()], j = act[rnd() % act.size()];
-                        if (t[i] != t[j]) { std::swap(t[i], t[j]); break; }
-                    }
-                bool seen = false;
-                for (const auto &e : o.tried) if (e == t) { seen = true; break; }
-                if (seen) continue;
-                o.tried.push_back(t);
-                o.best = t; o.nb.clear(); o.nb_pos = 0; o.kicks += 1;
-                return true;
-            }
-            return false;
-        };
-        for (int k = 0; k < QC_SEARCH_CHUNK && !o.frozen; ++k) {
-            if (!propose()) {
-                if (!kick()) { o.frozen = true; break; }
-                float tk = 0.f;
-                if ((rc = measure(o.best, tk)) != QC_OK) return rc;
-                o.trials += 1; o.base_ms = tk;
-                note_top(o.best, tk);
-                if (dbg) fprintf(stderr, "[tune] trial %d: restart %d of the search from a perturbed best: %.4f ms (best known %.4f)\n", o.trials, o.kicks, tk, o.top[0].first);
-                if (o.trials >= QC_SEARCH_TRIALS) o.frozen = true;
-                continue;
-            }
-            const bool seeded = !o.cands.empty();
-            float t = 0.f;
-            if ((rc = measure(o.trial, t)) != QC_OK) return rc;
-            o.trials += 1;
-            if (dbg) fprintf(stderr, "[tune] trial %d (build %ld of the handle): %.4f ms against %.4f ms - %s\n", o.trials, (long)o.builds, t, o.base_ms, t < 0.985 * o.base_ms ? "kept" : "dropped");
-            if (t < 0.985 * o.base_ms) { o.best = o.trial; o.base_ms = t; o.rejects = 0; o.nb.clear(); o.nb_pos = 0; }     // (a new neighbourhood)
-            else if (!seeded) o.rejects += 1;
-            note_top(o.trial, t);
+        bool seen = false;
+        for (const auto &e : o.tried) if (e == t) { seen = true; break; }
+        if (seen) continue;
+        o.tried.push_back(t);
+        o.best = t; o.nb.clear(); o.nb_pos = 0; o.kicks += 1;
+        return true;
+    }
+    return false;
+}
+// the search is over: the finals inside SCF passes (qc_fock_feedback) - not for multi-rank handles, whose passes report nothing
+static void search_ended(const QcBuild &b, bool dbg) {
+    qc_system *S = b.S;
+    qc_system::QcOnline &o = S->on;
+    const std::vector<std::vector<int>> &units = b.plan.units;
+    o.fin_sum.assign(o.top.size(), 0.0); o.fin_n.assign(o.top.size(), 0); o.fin_cur = 0;
+    if (S->comm || o.top.size() < 2) o.settled = true;
+    else { S->unit_stream = o.top[0].second; S->cand_skip = true; }
+    qc_assign_cache_store(S);
+    if (!dbg) return;
+    if (!o.top.empty()) { o.best = o.top[0].second; o.base_ms = o.top[0].first; }
+    fprintf(stderr, "[tune] search ends after %d trials, %d restarts (%ld extra builds): %.4f ms; lanes:", o.trials, o.kicks, (long)o.spent, o.base_ms);
+    for (int k = 0; k < QC_NSTREAMS; ++k) {
+        bool any = false;
+        for (int rk = 0; rk < 16; ++rk)
+            for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty() && (o.best[u] & 7) == k && (o.best[u] >> 3) == rk) { fprintf(stderr, "%s u%zu(%.0f)%s", any ? "" : " [", u, S->unit_ms[u] * 1e3, rk ? "'" : ""); any = true; }
+        if (any) fprintf(stderr, " ]");
+    }
+    fprintf(stderr, "\n");
+}
+// an instalment is due: not in the builds of a profiling call (no G0), not before the handle has shown that it lives long
+static bool search_due(const qc_system *S, const QcFockArgs &fa) {
+    return !S->on.frozen && fa.G0 && S->on.builds >= QC_SEARCH_FIRST_BUILD && S->on.spent + 2 * QC_SEARCH_CHUNK <= S->on.builds;
+}
+// one instalment of the search: up to QC_SEARCH_CHUNK trials of two extra builds each
+static int search_instalment(const QcBuild &b) {
+    qc_system *S = b.S;
+    qc_system::QcOnline &o = S->on;
+    EventList evl;
+    if (evl.create(2) != QC_OK) return QC_ERR_HIP;
+    hipEvent_t *ev = evl.ev.data();
+    static const bool dbg = getenv("QC_TUNE_DEBUG") != nullptr;
+    int rc = QC_OK;
+    if (o.best.empty()) o.best = S->unit_stream;
+    if (!o.seeded) { o.seeded = true; if ((rc = seed_proposals(b)) != QC_OK) return rc; }
+    float tb = 0.f;
+    if (o.base_ms <= 0.0) { if ((rc = measure_assignment(b, ev, o.best, tb)) != QC_OK) return rc; o.base_ms = tb; note_top(o, o.best, tb); }
+    for (int k = 0; k < QC_SEARCH_CHUNK && !o.frozen; ++k) {
+        if (!propose(b)) {
+            if (!kick(b)) { o.frozen = true; break; }
+            float tk = 0.f;
+            if ((rc = measure_assignment(b, ev, o.best, tk)) != QC_OK) return rc;
+            o.trials += 1; o.base_ms = tk;
+            note_top(o, o.best, tk);
+            if (dbg) fprintf(stderr, "[tune] trial %d: restart %d of the search from a perturbed best: %.4f ms (best known %.4f)\n", o.trials, o.kicks, tk, o.top[0].first);
             if (o.trials >= QC_SEARCH_TRIALS) o.frozen = true;
+            continue;
         }
-        S->unit_stream = o.top.empty() ? o.best : o.top[0].second;       // (the best known - after a restart `best` is where the search stands)
-        S->assign_gen += 1; S->tune_count += 1;             // (this build carries extra builds: not a timing sample)
-        if (o.frozen) {
-            // finals inside SCF passes (qc_fock_feedback) - not for multi-rank handles, whose passes report nothing
-            o.fin_sum.assign(o.top.size(), 0.0); o.fin_n.assign(o.top.size(), 0); o.fin_cur = 0;
-            if (S->comm || o.top.size() < 2) o.settled = true;
-            else { S->unit_stream = o.top[0].second; S->cand_skip = true; }
-            qc_assign_cache_store(S);
-            if (dbg) {
-                if (!o.top.empty()) { o.best = o.top[0].second; o.base_ms = o.top[0].first; }
-                fprintf(stderr, "[tune] search ends after %d trials, %d restarts (%ld extra builds): %.4f ms; lanes:", o.trials, o.kicks, (long)o.spent, o.base_ms);
-                for (int k = 0; k < QC_NSTREAMS; ++k) {
-                    bool any = false;
-                    for (int rk = 0; rk < 16; ++rk)
-                        for (size_t u = 0; u < units.size(); ++u) if (!units[u].empty() && (o.best[u] & 7) == k && (o.best[u] >> 3) == rk) { fprintf(stderr, "%s u%zu(%.0f)%s", any ? "" : " [", u, S->unit_ms[u] * 1e3, rk ? "'" : ""); any = true; }
-                    if (any) fprintf(stderr, " ]");
-                }
-                fprintf(stderr, "\n");
-            }
-        }
-        QC_HIP_CHECK(hipMemsetAsync(fa.G0, 0, gbytes, S->stream));
+        const bool seeded = !o.cands.empty();
+        float t = 0.f;
+        if ((rc = measure_assignment(b, ev, o.trial, t)) != QC_OK) return rc;
+        o.trials += 1;
+        if (dbg) fprintf(stderr, "[tune] trial %d (build %ld of the handle): %.4f ms against %.4f ms - %s\n", o.trials, (long)o.builds, t, o.base_ms, t < 0.985 * o.base_ms ? "kept" : "dropped");
+        if (t < 0.985 * o.base_ms) { o.best = o.trial; o.base_ms = t; o.rejects = 0; o.nb.clear(); o.nb_pos = 0; }     // (a new neighbourhood)
+        else if (!seeded) o.rejects += 1;
+        note_top(o, o.trial, t);
+        if (o.trials >= QC_SEARCH_TRIALS) o.frozen = true;
+    }
+    S->unit_stream = o.top.empty() ? o.best : o.top[0].second;       // (the best known - after a restart `best` is where the search stands)
+    S->assign_gen += 1; S->tune_count += 1;             // (this build carries extra builds: not a timing sample)
+    if (o.frozen) search_ended(b, dbg);
+    QC_HIP_CHECK(hipMemsetAsync(b.fa.G0, 0, b.accum_bytes(), S->stream));
+    return QC_OK;
+}
+
+// One build: the launch units of the plan on the streams the assignment gives them, joined on the handle's stream.  The first build of
+// a shard times the units and assigns them first; later builds may carry an instalment of the assignment search.
+// Profiling mode (class_ms or unit_ms non-null): serial timed launches only (time_units_serial).
+int qc_launch_fock_classes(qc_system *S, const QcFockArgs &fa, float *class_ms, float *unit_ms, bool nofork) {
+    const QcBuild b{S, fa, base_args(S, fa), launch_plan_of(S)};
+    if (class_ms || unit_ms) return time_units_serial(b, class_ms, unit_ms);
+    int rc;
+    if (S->unit_ms.size() != b.plan.units.size()) {
+        if ((rc = first_build(b)) != QC_OK) return rc;
+        nofork = false;                                  // the side streams must see its memset (and the timing passes) finished
+    }
+    S->on.builds += 1;
+    if (search_due(S, fa)) {
+        if ((rc = search_instalment(b)) != QC_OK) return rc;
         nofork = false;
     }
-    return launch_concurrent(nullptr, false, fa.fork_seq, fa.fold_joins && !fa.fork_seq);
+    return issue_build(b, nullptr, false, nofork);
 }
 
 // ---- Refinement of the stream assignment, paid for by use.  A neighbouring assignment (one launch moved to another lane, two launches
@@ -1471,13 +1332,6 @@ static void qc_assign_cache_store(const qc_system *S) {
     std::lock_guard<std::mutex> lk(C.mu);
     for (auto &kv : C.e) if (kv.first == key) { kv.second = {S->on.best, S->on.settled}; return; }
     if (C.e.size() < 64) C.e.push_back({key, {S->on.best, S->on.settled}});
-}
-// A build may be issued speculatively (device-side fork, scf_iterate) when nothing of it needs the host: the launches have been timed
-// (that first build waits for its serial passes), the side streams are joined on the device, and the accumulation is the fixed-point one
-// whose closing fold leaves the planes clean (the f64 mode starts with a memset the side streams would have to wait for).
-bool qc_fock_can_speculate(const qc_system *S) {
-    return S->device_ready && !S->join_by_events && S->accum_fx && S->launch_plan && !S->unit_ms.empty() &&
-           S->unit_ms.size() == S->launch_plan->units.size();
 }
 // (the SCF passes report their build times: kept as the handle's running mean - the search itself measures its own builds)
 void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen) {

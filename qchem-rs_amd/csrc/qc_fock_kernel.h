@@ -46,8 +46,6 @@ struct QcKernelArgs {
                               // the scale 2^S of this build at fxs[0] (qc_fx_scale_kernel); null = f64 atomics
     size_t fx_lo;             // doubles from an element of the hi plane to the same element of the lo plane
     double *schwarz_out;      // if non-null: no digestion - the slots are (P|P) quartets and sqrt(max |(ab|cd)|) goes to [P]
-    const unsigned *cancel;   // non-null: a speculative build (issued before the host knew that the SCF pass in front of it would not be the
-    unsigned cancel_seq;      // last one) - its kernels return at once when *cancel == cancel_seq (qc_spec_release_kernel, qc_scf_small.hip)
     unsigned long long *tl;   // non-null (QC_DEV_TIMELINE): QC_TL_W clock words of this launch - [0] start of workgroup 0, [1 + (workgroup & 31)] ends
 };
 
@@ -59,11 +57,6 @@ __device__ __forceinline__ void qc_tl_stamp(unsigned long long *tl, int end) {
         if (end) __hip_atomic_store(tl + 1 + (blockIdx.x & 31), t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else __hip_atomic_store(tl, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-// (every class kernel starts with this: one scalar load)
-__device__ __forceinline__ bool qc_build_cancelled(const QcKernelArgs &a) {
-    return a.cancel != nullptr && __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.cancel_seq;
 }
 
 // ---- order-independent, exact accumulation.  The digestion adds ~10^3 contributions from different waves into every
@@ -989,7 +982,6 @@ struct QcTierArgs {
 template <int LAB, int TIER>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(((TIER == 0 && LAB <= 2) || TIER == 2) ? 2 : 1)))
 void qc_fock_tier_kernel(const QcTierArgs a) {
-    if (qc_build_cancelled(a.base)) return;
     qc_tl_stamp(a.base.tl, 0);
     // the high-L tiers are few, long, latency-bound waves: let them win issue arbitration against the many short
     // low-L waves they share a SIMD with
@@ -1025,7 +1017,6 @@ void qc_fock_tier_kernel(const QcTierArgs a) {
 template <int V>     // (every instance lives in its own translation unit: gen/qc_fock_low1.hip, _mid1, _hi1)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC_T1LOW_WAVES(V))))
 void qc_fock_tier1_low_kernel(const QcTierArgs a) {
-    if (qc_build_cancelled(a.base)) return;
     qc_tl_stamp(a.base.tl, 0);
     __builtin_amdgcn_s_setprio(3);
     int s = 0;

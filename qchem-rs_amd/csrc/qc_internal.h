@@ -185,28 +185,14 @@ struct qc_system {
     unsigned long long *d_tl = nullptr, *tl_cur = nullptr;
     int tl_pass = 0;
     unsigned *d_join = nullptr;              // [0] counter of the device-side join of a build's side streams (qc_join_mark / qc_join_wait);
-                                             // [1] fork word: number of the last pass whose densities are final (device-side fork of a speculative build);
-                                             // [2] number of the speculative build that was cancelled on the device (its class kernels return at once)
+                                             // [3] scratch of the lane probe's markers, [4] counter of the spin-parallel Roothaan steps
     int *h_join_timeout = nullptr;           // pinned: set by a device-side wait that gave up (the launches it waited for never finished)
     unsigned join_target = 0;
-    bool fold_join_pending = false;          // the last build left its join to the closing fold (QcFockArgs::fold_joins): join_target is what it waits for
-    unsigned fork_seq = 0;                   // last value promised to the fork word: the speculative build of pass k + 1 waits for fork_seq = k's number
     long long wait_limit = 0;                // device-side waits give up after this many ticks of the 100 MHz clock (qc_wait_limit)
     std::atomic<bool> waits_in_flight{false}; // device-side waits were issued and the host has not seen the handle's stream drained since (qc_gate)
-    // speculative build (scf_iterate): the NEXT pass's Fock build, issued behind this pass's Roothaan step before the host has seen the pass end
-    struct QcSpec {
-        bool pending = false;                // issued and not yet consumed / discarded
-        const void *owner = nullptr;         // the qc_scf_state it belongs to
-        const double *Da = nullptr, *Db = nullptr;   // densities it digests
-        double *Ga = nullptr, *Gb = nullptr; // where its closing kernel leaves G
-        bool f_done = false;                 // ... and F = H + G (the next pass's DIIS slots)
-        unsigned seq = 0;                    // its number (fork word value it waited for; cancel word value that empties it)
-    } spec;
-    int issue_threads = -1;                  // helper threads that issue a build's launches: -1 = by the size of the build (qc_fock.hip)
     bool prep_enqueued = false;              // qc_fock_prepare_device put work on the handle's stream (see scf_iterate)
     bool join_by_events = false;             // dispatches are serialised here (qc_join_probe): the side streams are joined through events
     struct QcLaunchPlan *launch_plan = nullptr; // launch units and their segments of the current work lists (qc_fock.hip)
-    struct QcIssuePool *issue_pool = nullptr; // helper threads that issue a build's launches next to the caller (qc_fock.hip)
     void *comm = nullptr;                    // ncclComm_t
     std::vector<float> unit_ms;              // measured serial time of each launch unit (autotuned once per shard)
     std::vector<int> unit_stream;            // side stream of each launch unit (longest-processing-time assignment)
@@ -284,12 +270,6 @@ struct QcFockArgs {
     const double *fxs;    // non-null: G0 / G1 accumulate 64-bit fixed-point integers (hi plane), scale 2^S at fxs[0], 2^-S at fxs[1] (device)
     size_t fx_lo;         // doubles from the hi plane to the lo plane
     double *schwarz_out;  // non-null: Schwarz pass over the (P|P) quartets, sqrt(max |(ab|cd)|) per pair (device), no digestion
-    // device-side fork (speculative build of the next SCF pass): side streams start with a one-lane kernel that waits for the fork word to
-    // reach fork_seq; the class kernels return at once when the cancel word equals it
-    unsigned fork_seq = 0;   // 0: no device fork
-    // the caller's next kernel on the handle's stream - the closing fold - waits for the join counter itself (qc_system::fold_join_pending
-    // says that it must): no one-lane waiting kernel in front of it, one dependent launch less at the end of the build
-    bool fold_joins = false;
 };
 int qc_launch_eri_full(qc_system *S, double *d_out);
 // MP2 (qc_mp2.hip).  validate: host-side argument and denominator checks of qc_mp2 / qc_scf_mp2 (eps: nspin n-vectors on the host).
@@ -310,9 +290,6 @@ int qc_launch_fock_classes(qc_system *S, const QcFockArgs &a, float *class_ms /*
 // hipEvent time of a build inside an SCF pass that ran under stream assignment `gen` (no-op once the choice is made)
 void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen);
 void qc_assignment_freeze(qc_system *S);
-bool qc_fock_can_speculate(const qc_system *S);            // the next build may be issued with a device-side fork (tuned, device join, fixed point)
-void qc_spec_release(hipStream_t st, unsigned *words, unsigned seq, const double *scal, int n, int nspin, double eps, unsigned *h_cancel,
-                     unsigned *h_seq, unsigned seqval);
 // the beta step of a UHF pass on a side stream (another dispatch pipe than the handle's): fork = that stream, made to wait for what the
 // handle's stream holds so far; join = the handle's stream waits for it (marker + waiting kernel, under the per-device gate)
 hipStream_t qc_spin_fork(qc_system *S);
@@ -328,8 +305,7 @@ void qc_gate_quiet(qc_system *S);                          // the host has seen 
 int qc_fock_prepare_device(qc_system *S, const double *dDa, const double *dDb, bool uhf, const void *owner, bool scale_done = false);
 // (dH with dFa / dFb: the Fock matrices H + G are written by the closing kernel as well; *f_done tells whether both were)
 int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, double *dGa, double *dGb, bool uhf, int *twin_cache = nullptr,
-                         const double *dH = nullptr, double *dFa = nullptr, double *dFb = nullptr, bool *f_done = nullptr, const void *owner = nullptr,
-                         unsigned fork_seq = 0 /* non-zero: speculative build behind the kernel that releases this value of the fork word */);
+                         const double *dH = nullptr, double *dFa = nullptr, double *dFb = nullptr, bool *f_done = nullptr, const void *owner = nullptr);
 
 // dense linear algebra on the handle's stream (all row-major n x n, device pointers)
 void qc_gemm(hipStream_t st, int m, int n, int k, double alpha, const double *A, int lda, bool ta, const double *B,
@@ -369,8 +345,7 @@ void qc_symmetrize_add(hipStream_t st, int n, const double *Gt, size_t lo_off, d
 // fixed-point builds on one rank: replica fold + symmetrisation (+ F = H + G) in one launch
 // (the replicas are zeroed as they are read: the accumulator planes are clean again when it returns)
 void qc_fold_symmetrize(hipStream_t st, int n, int nrep, size_t rep_stride, double *Gt, size_t lo_off, double *G, const double *H, double *F,
-                        const double *fxs, unsigned long long *tl = nullptr, const unsigned *join_cnt = nullptr, unsigned join_target = 0,
-                        int *timeout_flag = nullptr, long long limit = 0);
+                        const double *fxs, unsigned long long *tl = nullptr);
 // out[p * count + x] = sum_r Gt[p * plane_stride + r * stride + x], p < (fx ? 2 : 1)
 void qc_reduce_replicas(hipStream_t st, size_t count, int nrep, size_t stride, const double *Gt, double *out, bool fx, size_t plane_stride);
 void qc_count_diff(hipStream_t st, size_t count, const double *a, const double *b, int *flag);
@@ -441,9 +416,6 @@ struct QcSmallArgs {
     double *fxs_out; double imax;  // non-null (RHF): the fixed-point unit of the build that will digest Dn goes here (qc_fx_scale)
     int *ctl_all, *ctl_out;        // non-null: hand the 16 control words over to ctl_out and clear them
     unsigned *seq_out; unsigned seq; // non-null (pinned host memory): the pass's sequence number, stored after everything else the host reads
-    // non-null: a speculative build of the next pass is queued behind this kernel - release the fork word fork_words[1] = fork_seq at the
-    // end; before that, if the pass meets the reference's stopping rule at eps (> 0), cancel that build (fork_words[2], *h_cancel)
-    unsigned *fork_words; unsigned fork_seq; double eps; unsigned *h_cancel;
     unsigned long long *tl;        // non-null: [start, end] clock of this launch (QC_DEV_TIMELINE)
 };
 int qc_scf_small_launch(hipStream_t st, const QcSmallArgs &a);

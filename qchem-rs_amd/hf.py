@@ -360,7 +360,7 @@ class ScfStepper:
 
     def __init__(self, system: "System", uhf: bool = False, n_alpha: int = 0, n_beta: int = 0, stop_rule: float = 0.0):
         """stop_rule > 0: the caller's loop ends once the reference's test holds at that epsilon (rhf.rs:94 / uhf.rs:139); told to the
-        library so that the Fock build it queues behind a converging pass is emptied on the device (qc_scf_set_stop_rule)."""
+        library (qc_scf_set_stop_rule), which checks the value and otherwise ignores it."""
         self.system = system
         self.uhf = uhf
         self._st = C.c_void_p()
@@ -424,7 +424,7 @@ class ScfStepper:
 
     def counters(self):
         """ms_setup, ms_fock (builds with a tuner run left out), ms_linalg, builds behind ms_fock, host ms of tuner runs, passes,
-        speculative builds consumed / discarded, passes whose eigensolve was repeated."""
+        spec_hits / spec_lost (reserved, always 0), passes whose eigensolve was repeated."""
         v = (C.c_double * 11)()
         _check(lib().qc_scf_counters(self._st, v, 11), "qc_scf_counters")
         k = ("setup", "fock", "linalg", "builds_timed", "tuner", "passes", "spec_hits", "spec_lost", "redos", "assign_trials", "assign_frozen")

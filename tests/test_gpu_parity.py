@@ -476,20 +476,18 @@ def test_fock_build_is_bitwise_reproducible():
 def test_launch_structure_switches_do_not_change_a_bit(monkeypatch):
     """How a build's launches are issued and joined is not allowed to show in the result (integer accumulation): the device-side join
     of the side streams against the event join it replaced (QC_EVENT_JOIN - also what a handle falls back to when dispatches are
-    serialised, e.g. under rocprofv3 --pmc), helper threads issuing the side streams (QC_ISSUE_THREADS), and the end of an SCF pass
-    seen through the pinned sequence word against the stream's event (QC_EVENT_WAIT).  The switches are read per handle / per SCF state."""
+    serialised, e.g. under rocprofv3 --pmc), and the end of an SCF pass seen through the pinned sequence word against the stream's
+    event (QC_EVENT_WAIT).  The switches are read per handle / per SCF state."""
     import qchem_rs_amd as q
     m = load_system("water", "cc-pVTZ")
     D = _rand_sym(58, 43)
     s0 = q.System(m)
     G0 = s0.fock_rhf(D)
     e0 = q.restricted_hartree_fock(s0, q.HartreeFockConfig(100, 1e-10))
-    # (round 4: QC_SPEC - speculative build of the next pass behind the Roothaan step, device-side fork; QC_NO_LANES - launch units drawn
-    # among all seven side streams instead of the four dispatch lanes)
+    # (QC_NO_LANES: launch units drawn among all seven side streams instead of the four dispatch lanes)
     # (QC_NO_BM_MERGE / QC_NO_T1_MERGE: the merged launches of the small builds apart again - 9 and 11 launches instead of 8; QC_NREP_USE: all
     # 32 accumulator replicas instead of 8)
-    for env in ({"QC_EVENT_JOIN": "1"}, {"QC_ISSUE_THREADS": "3"}, {"QC_ISSUE_THREADS": "2", "QC_EVENT_WAIT": "1"}, {"QC_SPEC": "1"},
-                {"QC_SPEC": "1", "QC_EVENT_WAIT": "1"}, {"QC_NO_LANES": "1"}, {"QC_NO_BM_MERGE": "1"}, {"QC_NO_T1_MERGE": "1"},
+    for env in ({"QC_EVENT_JOIN": "1"}, {"QC_EVENT_WAIT": "1"}, {"QC_NO_LANES": "1"}, {"QC_NO_BM_MERGE": "1"}, {"QC_NO_T1_MERGE": "1"},
                 {"QC_NO_BM_MERGE": "1", "QC_NO_T1_MERGE": "1", "QC_NREP_USE": "32"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -508,12 +506,11 @@ def test_launch_structure_switches_do_not_change_a_bit(monkeypatch):
 
 @pytest.mark.parametrize("mol,basis,uhf,na,nb,EPS", [("water", "cc-pVTZ", False, 0, 0, 1e-9), ("water", "cc-pVDZ", True, 0, 0, 1e-9), ("oxygen", "cc-pVDZ", True, 9, 7, 1e-9),
                                                      ("ethylene", "cc-pVDZ", False, 0, 0, 1e-9), ("benzene", "6-31G_st_st", False, 0, 0, 1e-6)])
-def test_speculative_builds_are_used_cancelled_and_never_show(mol, basis, uhf, na, nb, EPS, monkeypatch):
-    """scf_iterate issues the next pass's Fock build behind the pass it is asked for (device-side fork).  Every pass after
-    the first must find its build in flight; the trajectory is bit for bit the one of the host-driven boundary (QC_NO_SPEC); with the
-    stopping rule announced the build behind the converging pass is emptied on the device, and a host that goes on regardless - or one
-    that never announced a rule - still gets correct passes.  All launch paths: one-workgroup RHF (release inside the kernel), closed-shell
-    UHF on that path (release kernel that also ends the pass), open-shell and n > 64 (generic sequence, event wait)."""
+def test_stepper_and_driver_agree_with_and_without_a_stop_rule(mol, basis, uhf, na, nb, EPS):
+    """Announcing the host's stopping rule (qc_scf_set_stop_rule) changes nothing: a stepper without a rule and one with it, both stepped
+    two passes beyond convergence, give the same passes bit for bit; a second run on the same handle (tuned streams) reproduces the first;
+    the whole-run driver on that handle stops at the same pass with the same energy; the reserved counters stay 0.  All launch paths:
+    one-workgroup RHF, closed-shell UHF on that path, open-shell and n > 64 (generic sequence, event wait)."""
     import qchem_rs_amd as q
     m = load_system(mol, basis)
 
@@ -531,28 +528,25 @@ def test_speculative_builds_are_used_cancelled_and_never_show(mol, basis, uhf, n
         st.close()
         return tr, k_conv, c
 
-    s_ref = q.System(m)                                            # (default: host-driven pass boundary)
+    s_ref = q.System(m)
     ref, k_ref, c_ref = run(0.0, 2, s_ref)
-    assert k_ref is not None and c_ref["spec_hits"] == 0
-    monkeypatch.setenv("QC_SPEC", "1")
+    assert k_ref is not None and c_ref["spec_hits"] == 0 and c_ref["spec_lost"] == 0
     s = q.System(m)
-    warm, _, _ = run(0.0, 0, s)                                   # (first run on a handle: its first build tunes the streams)
+    warm, _, c_w = run(0.0, 0, s)                                 # (first run on a handle: its first build tunes the streams)
     assert warm == ref[:len(warm)]
-    a, k_a, c_a = run(0.0, 2, s)                                  # no rule announced: every later pass consumes a speculative build
+    a, k_a, c_a = run(0.0, 2, s)                                  # no rule announced
     assert a == ref and k_a == k_ref
-    # (a pass whose eigensolve had to be repeated discards the build queued behind it)
-    assert c_a["spec_hits"] + c_a["spec_lost"] == len(a) - 1 and c_a["spec_lost"] <= len(a) // 4, c_a
     b, k_b, c_b = run(EPS, 2, s)                                  # rule announced, host goes on for two more passes anyway
     assert b == ref and k_b == k_ref
-    # the build behind the converging pass and behind each later pass that still meets the rule was emptied and rebuilt on request
-    assert c_b["spec_lost"] >= 1 and c_b["spec_hits"] + c_b["spec_lost"] == len(b) - 1, c_b
+    for c in (c_w, c_a, c_b):
+        assert c["spec_hits"] == 0 and c["spec_lost"] == 0, c
     out = (q.unrestricted_hartree_fock if uhf else q.restricted_hartree_fock)(s, q.HartreeFockConfig(100, EPS, na, nb))
     assert out.iterations == k_ref and out.electronic_energy == ref[k_ref][0]
     s.close(); s_ref.close()
 
 
 def test_a_wait_that_gives_up_fails_the_call_that_waited(monkeypatch):
-    """A device-side wait (join of the side streams, fork of a speculative build) that runs into its limit has folded an incomplete
+    """A device-side wait (the join of a build's side streams) that runs into its limit has folded an incomplete
     matrix: the call whose host wait follows it returns QC_ERR_HIP (never a wrong G), and the handle goes on with event joins.  Forced
     here: QC_JOIN_FAULT leaves one side stream's marker out (a join that can never complete, as if a launch had died) and the limit is
     2 ms (QC_WAIT_LIMIT_MS)."""
@@ -583,9 +577,9 @@ def test_a_wait_that_gives_up_fails_the_call_that_waited(monkeypatch):
     s.close(); s2.close()
 
 
-def test_two_handles_from_two_threads(monkeypatch):
+def test_two_handles_from_two_threads():
     """`distinct handles may be used from distinct threads` (include/qchem_hip.h): two SCF runs on one device at the same time - both
-    with device-side waits and speculative builds - end bit-identical to the same runs alone (per-device issue gate, qc_fock.hip)."""
+    with device-side waits - end bit-identical to the same runs alone (per-device issue gate, qc_fock.hip)."""
     import threading
     import qchem_rs_amd as q
     mols = [load_system("water", "cc-pVTZ"), load_system("ethylene", "cc-pVDZ")]
@@ -594,27 +588,24 @@ def test_two_handles_from_two_threads(monkeypatch):
     hs = [q.System(m) for m in mols]
     for h in hs:
         alone.append(q.restricted_hartree_fock(h, cfg))
-    for spec in (False, True):
-        if spec:
-            monkeypatch.setenv("QC_SPEC", "1")
-        res = [[None] * 3, [None] * 3]
+    res = [[None] * 3, [None] * 3]
 
-        def work(i):
-            for r in range(3):
-                res[i][r] = q.restricted_hartree_fock(hs[i], cfg)
+    def work(i):
+        for r in range(3):
+            res[i][r] = q.restricted_hartree_fock(hs[i], cfg)
 
-        th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-        for t in th:
-            t.start()
-        for t in th:
-            t.join(timeout=300)
-        assert not any(t.is_alive() for t in th)
-        for i in range(2):
-            for r in range(3):
-                o = res[i][r]
-                assert o is not None and o.iterations == alone[i].iterations and o.electronic_energy == alone[i].electronic_energy, spec
-                assert o.orbital_energies == alone[i].orbital_energies, spec
-    # one thread stepping two states of two handles alternately (a speculative build of one is in flight while the other issues)
+    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in th)
+    for i in range(2):
+        for r in range(3):
+            o = res[i][r]
+            assert o is not None and o.iterations == alone[i].iterations and o.electronic_energy == alone[i].electronic_energy
+            assert o.orbital_energies == alone[i].orbital_energies
+    # one thread stepping two states of two handles alternately (the waits of one are in flight while the other issues)
     st = [q.ScfStepper(h, stop_rule=1e-10) for h in hs]
     tr = [[], []]
     for k in range(12):
