@@ -521,10 +521,11 @@ __global__ __launch_bounds__(BT_WAVES * 64) void qc_backtransform_kernel(int n, 
 
 size_t qc_eig_tridiag_work_doubles(int n) { return 2 * (size_t)n * n + 8 * (size_t)n + 16; }
 
-// Approximate eigenvectors (columns of dX0, ascending eigenvalues, orthonormal to ~1e-6 for generic matrices) of the symmetric dA,
-// which is left intact.  work: qc_eig_tridiag_work_doubles(n) doubles.  Asynchronous on `st`.
-int qc_eig_tridiag_start(hipStream_t st, int n, const double *dA, double *dX0, double *work) {
+// Approximate eigenvectors (columns of E.x0, ascending eigenvalues, orthonormal to ~1e-6 for generic matrices) of the symmetric dA,
+// which is left intact.  Work array: E.tri.  Asynchronous on `st`.
+int qc_eig_tridiag_start(hipStream_t st, int n, const double *dA, QcEigWork &E) {
     if (!qc_tri_ok(n)) return QC_ERR_UNSUPPORTED;
+    double *const dX0 = E.x0.p, *const work = E.tri.p;
     double *Vr = work, *Zg = work + (size_t)n * n, *tri = Zg + (size_t)n * n, *evn = tri + 4 * (size_t)n;
     static std::atomic<bool> raised{false};
     if (!raised.load(std::memory_order_acquire)) {

@@ -661,7 +661,7 @@ __global__ void qc_spin_join_end_kernel(unsigned *cnt, unsigned target, int *tim
     }
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (threadIdx.x < 16) {
+    if (threadIdx.x < QC_CTL_WORDS) {
         int *p = ctl_all + threadIdx.x;
         ctl_out[threadIdx.x] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

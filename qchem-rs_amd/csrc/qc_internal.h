@@ -1,6 +1,7 @@
 // qc_internal.h - shared declarations of libqchem_hip.so (host model, device buffers, kernel launchers).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
 
 #include <atomic>
 #include <cstdint>
@@ -310,32 +311,58 @@ int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, dou
 // dense linear algebra on the handle's stream (all row-major n x n, device pointers)
 void qc_gemm(hipStream_t st, int m, int n, int k, double alpha, const double *A, int lda, bool ta, const double *B,
              int ldb, bool tb, double beta, double *C, int ldc, const int *skip = nullptr /* device flag: non-zero = no-op */);
-// (`small`: qc_eig_small_doubles(n) doubles - Rayleigh quotients, statistics, partner list, per-workgroup partials)
-inline size_t qc_eig_small_doubles(int n) { return (size_t)3 * n + 32 + 8; }
-int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                        double *t3, double *t4, double *small, int *ctl, int npass);
 void qc_diis_solve(hipStream_t st, int m, int minlen, int maxlen, const int *slots, const double *dots, double *B, double *c, int *flag);
 void qc_lincomb_dev(hipStream_t st, int n, const double *const *Fs, const double *c_dev, int m, double *out);
-// done_tol: the sweeps end after one that met no relative coupling above it (the sweep itself leaves ~done_tol^2 behind)
-// notconv (device int, nullable): set to 1 when the sweeps ran out before the criterion was met
-int qc_eig_device(hipStream_t st, int n, double *dA /*destroyed*/, double *dV, double *dw, double *d_work, int max_sweeps = 40, double done_tol = 1e-9,
-                  int *notconv = nullptr);
-int qc_eig_device_warm(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                       int max_sweeps = 40, double done_tol = 1e-9, int *notconv = nullptr);
-int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                         double *t3, double *t4, double *small, int *notconv = nullptr);
-// Tridiagonalisation-based start vectors (qc_eig_tridiag.hip) + refinement: the cold eigensolve.  ctl[0..3] zero on entry; outcome in
-// ctl[0] (1 done: dV / dw hold the sorted eigenpairs; 2: the start was not good enough - repeat with qc_eig_device).  dX0: n*n scratch,
-// triwork: qc_eig_tridiag_work_doubles(n).  Smaller matrices (n < QC_TRI_MIN_N) are for the single-workgroup Jacobi kernels.
+
+// ---- device control words of an SCF pass: QC_CTL_WORDS ints, cleared by the kernel that hands them to the host at the end of the pass
+//   [QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin + field]  the sync-free eigensolve of that spin
+//   [QC_CTL_DIIS] the DIIS system was singular;  [QC_CTL_NOTCONV] Jacobi sweeps ran out before their criterion was met
+//   [QC_CTL_SETUP + field]  the synchronous cold eigensolves (set-up, repeats): read back and cleared by qc_eig_cold_sync
+// Fields of an eigensolve's four words (zero on entry; every kernel of the refinement returns at once unless STATE is RUNNING):
+//   STATE  QC_EIG_RUNNING / QC_EIG_DONE (dV / dw hold the sorted eigenpairs) / QC_EIG_ROTATE (not perturbative, coupling inside a degenerate
+//   cluster or passes exhausted: repeat with rotations);  LAST  one more update finishes;  CLEAN  no coupling left inside degenerate
+//   pairs;  PASSES  refinement passes used.  The host reads a pass's scalars as QC_SYNC_WORDS 64-bit words: 4 doubles + the ints.
+constexpr int QC_CTL_EIG = 0, QC_CTL_EIG_STRIDE = 4, QC_CTL_DIIS = 8, QC_CTL_NOTCONV = 9, QC_CTL_SETUP = 12, QC_CTL_WORDS = 16;
+constexpr int QC_EIG_STATE = 0, QC_EIG_LAST = 1, QC_EIG_CLEAN = 2, QC_EIG_PASSES = 3;
+constexpr int QC_EIG_RUNNING = 0, QC_EIG_DONE = 1, QC_EIG_ROTATE = 2;
+constexpr int QC_SYNC_WORDS = 4 + QC_CTL_WORDS / 2;
+
+struct DevBuf {
+    double *p = nullptr;
+    int alloc(size_t count) { return hipMalloc(&p, count * sizeof(double)) == hipSuccess ? QC_OK : QC_ERR_HIP; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// ---- eigensolvers (qc_linalg.hip, qc_eig_tridiag.hip).  dA: the symmetric matrix (left intact), dV0: start vectors, dV: sorted
+// eigenvectors, dw: ascending eigenvalues; all on `st`.  QcEigWork: scratch of one eigensolve in flight, allocated once for a given n -
+// work, t1..t4: n*n each (callers may use them between eigensolves); x0 / tri: start vectors and work array of the tridiagonal path;
+// small: Rayleigh quotients, statistics, partner list, per-workgroup partials; ctl: four control words for callers without pass words.
+inline size_t qc_eig_small_doubles(int n) { return (size_t)3 * n + 32 + 8; }
+struct QcEigWork {
+    DevBuf work, t1, t2, t3, t4, x0, tri, small;
+    int *ctl = nullptr;
+    int alloc(int n);
+    ~QcEigWork() { if (ctl) (void)hipFree(ctl); }
+};
+// Jacobi kernels: at most this many sweeps; they end after one that met no relative coupling above the tolerance (the sweep itself
+// leaves ~tolerance^2 behind).  notconv (device int, nullable): set to 1 when the sweeps ran out before the criterion was met.
+constexpr int QC_JACOBI_MAX_SWEEPS = 40;
+constexpr double QC_JACOBI_DONE_TOL = 1e-9;
+bool qc_eig_force_jacobi();              // QC_EIG_JACOBI (A/B switch): no tridiagonal path, the single-workgroup Jacobi kernels only
+int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *notconv = nullptr);
+int qc_eig_device_warm(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *notconv = nullptr);
+int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *notconv = nullptr);
+// sync-free refinement: `npass` passes enqueued, outcome in ctl (four words, zero on entry)
+int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *ctl, int npass);
+// Tridiagonalisation-based start vectors (qc_eig_tridiag.hip, into E.x0) + refinement: the cold eigensolve.  On QC_EIG_ROTATE the start was
+// not good enough - repeat with qc_eig_device.  Smaller matrices (n < QC_TRI_MIN_N) are for the single-workgroup Jacobi kernels.
 constexpr int QC_TRI_MIN_N = 24, QC_TRI_MAX_N = 512;
 inline bool qc_tri_ok(int n) { return n >= QC_TRI_MIN_N && n <= QC_TRI_MAX_N; }
 size_t qc_eig_tridiag_work_doubles(int n);
-int qc_eig_tridiag_start(hipStream_t st, int n, const double *dA, double *dX0, double *work);
-int qc_eig_cold_async(hipStream_t st, int n, double *dA, double *dX0, double *triwork, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                      double *t3, double *t4, double *small, int *ctl, int npass = 3);
-// synchronous: cold_async, then the Jacobi kernels if the control word asks for them (ctl: 4 ints of device scratch)
-int qc_eig_cold_sync(hipStream_t st, int n, double *dA, double *dX0, double *triwork, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                     double *t3, double *t4, double *small, int *ctl, int *notconv = nullptr);
+int qc_eig_tridiag_start(hipStream_t st, int n, const double *dA, QcEigWork &E);
+int qc_eig_cold_async(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *ctl, int npass = 3);
+// synchronous: cold_async, then the Jacobi kernels if the control words ask for them (ctl: four ints of device scratch)
+int qc_eig_cold_sync(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *ctl, int *notconv = nullptr);
 void qc_permute_tensor(hipStream_t st, int n, const double *I, double c_direct, double c_exch, double *T);
 int qc_tensor_gemv(hipStream_t st, int n, const double *T1, const double *D1, const double *T2, const double *D2, double *G);   // QC_OK or QC_ERR_HIP
 void qc_axpby(hipStream_t st, int n, double a, const double *x, double b, const double *y, double *out);
@@ -406,7 +433,7 @@ struct QcSmallArgs {
     // ---- refine
     const double *V0;              // start vectors
     int npass;
-    int *ctl;                      // ctl[0..3] of this spin (0 running / 1 done / 2 rotations needed; last; clean; passes used)
+    int *ctl;                      // this spin's four eigensolve words (QC_EIG_* fields)
     // ---- post
     const double *Cp_in;           // eigenvectors of F' from another eigensolver (post without refine)
     double *Cp_out, *w_out, *C_out, *Dn;
@@ -414,7 +441,7 @@ struct QcSmallArgs {
     int nocc; double dfac;
     double *scal_out;              // [0] 0.5 tr(Dn (2H + G)), [1] sum_i (Dn - Dold)_ii^2
     double *fxs_out; double imax;  // non-null (RHF): the fixed-point unit of the build that will digest Dn goes here (qc_fx_scale)
-    int *ctl_all, *ctl_out;        // non-null: hand the 16 control words over to ctl_out and clear them
+    int *ctl_all, *ctl_out;        // non-null: hand the QC_CTL_WORDS control words over to ctl_out and clear them
     unsigned *seq_out; unsigned seq; // non-null (pinned host memory): the pass's sequence number, stored after everything else the host reads
     unsigned long long *tl;        // non-null: [start, end] clock of this launch (QC_DEV_TIMELINE)
 };
@@ -425,6 +452,20 @@ constexpr int QC_TL_PASSES = 64, QC_TL_SLOTS = QC_NUNITS + 4;       // launch un
 int qc_tl_begin_pass(qc_system *S);                                 // (no-op unless QC_DEV_TIMELINE is set)
 void qc_tl_dump(qc_system *S);
 size_t qc_scf_small_lds_bytes(int n);
+
+// ---- RCCL, bound at run time (qc_rccl.cpp)
+struct QcRccl {
+    void *handle = nullptr;
+    std::string path;
+    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
+    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
+    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*GetVersion)(int *) = nullptr;
+    bool ok = false;
+};
+QcRccl &qc_rccl();
+void qc_system_free(qc_system *S);       // (qc_api.cpp; the last SCF state of a destroyed handle frees it)
 
 #define QC_HIP_CHECK(expr)                                                                  \
     do {                                                                                    \

@@ -412,26 +412,36 @@ __global__ __launch_bounds__(QC_EIG_THREADS) void qc_jacobi1g_kernel(int n, cons
     }
 }
 
-// dA: input (left intact), dV: sorted eigenvectors, dw: eigenvalues, d_work: n*n scratch
-int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, double *d_work, int max_sweeps, double done_tol, int *notconv) {
+int QcEigWork::alloc(int n) {
+    const size_t nn = (size_t)n * n;
+    for (DevBuf *b : {&work, &t1, &t2, &t3, &t4, &x0}) if (b->alloc(nn) != QC_OK) return QC_ERR_HIP;
+    if (tri.alloc(qc_eig_tridiag_work_doubles(n)) != QC_OK || small.alloc(qc_eig_small_doubles(n)) != QC_OK) return QC_ERR_HIP;
+    return hipMalloc(&ctl, QC_CTL_EIG_STRIDE * sizeof(int)) == hipSuccess ? QC_OK : QC_ERR_HIP;
+}
+
+bool qc_eig_force_jacobi() { static const bool force = getenv("QC_EIG_JACOBI") != nullptr; return force; }
+
+// dA: input (left intact), dV: sorted eigenvectors, dw: eigenvalues
+int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *notconv) {
+    double *const d_work = E.work.p;
     const int m = (n + 1) & ~1, ld = m | 1;
     const size_t tail = (2 * (m / 2) + 32) * sizeof(double) + (size_t)m * sizeof(int) + 16;
     const size_t lds2 = 2 * (size_t)m * ld * sizeof(double) + tail, lds1 = (size_t)m * ld * sizeof(double) + tail;
-    const bool v_in_lds = lds2 <= 160 * 1024;
+    const bool v_in_lds = lds2 <= QC_LDS_MAX;
     static const bool force1 = getenv("QC_EIG_ONESIDED") != nullptr;
     if ((!v_in_lds || force1) && n <= QC_EIG1_ROWS * QC_EIG1_TEAM) {   // 100 < n <= 128: one-sided variant, a single matrix in LDS
         const size_t l1 = ((size_t)m * (n | 1) + 32 + m) * sizeof(double) + (size_t)(m + 4) * sizeof(int) + 16;
-        if (l1 <= 160 * 1024) {
+        if (l1 <= QC_LDS_MAX) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(qc_jacobi1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
             if (e != hipSuccess) return QC_ERR_HIP;
-            hipLaunchKernelGGL(qc_jacobi1_kernel, dim3(1), dim3(QC_EIG1_THREADS), l1, st, n, dA, dV, dw, max_sweeps, done_tol, notconv);
+            hipLaunchKernelGGL(qc_jacobi1_kernel, dim3(1), dim3(QC_EIG1_THREADS), l1, st, n, dA, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_DONE_TOL, notconv);
             return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
         }
     }
     const size_t lds = v_in_lds ? lds2 : lds1;
-    if (lds > 160 * 1024 || !v_in_lds) {                // n > 128: the global-memory variant
+    if (lds > QC_LDS_MAX || !v_in_lds) {                // n > 128: the global-memory variant
         if (n > 3000) return QC_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(qc_jacobi1g_kernel, dim3(1), dim3(QC_EIG_THREADS), (size_t)n * 12 + 16, st, n, dA, d_work, dV, dw, max_sweeps, done_tol, notconv);
+        hipLaunchKernelGGL(qc_jacobi1g_kernel, dim3(1), dim3(QC_EIG_THREADS), (size_t)n * 12 + 16, st, n, dA, d_work, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_DONE_TOL, notconv);
         return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
     }
     auto kern = v_in_lds ? qc_jacobi_kernel<true> : qc_jacobi_kernel<false>;
@@ -440,18 +450,18 @@ int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, dou
         if (e != hipSuccess) return QC_ERR_HIP;
     }
     static const int nthreads = getenv("QC_EIG_THREADS") ? atoi(getenv("QC_EIG_THREADS")) : QC_EIG_THREADS;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(nthreads), lds, st, n, dA, d_work, dV, dw, max_sweeps, done_tol, notconv);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(nthreads), lds, st, n, dA, d_work, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_DONE_TOL, notconv);
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
 
 // Warm-started variant for the SCF loop: with V0 the eigenvectors of the previous iteration's matrix,
 // B = V0^T A V0 is nearly diagonal, Jacobi needs 1-3 sweeps instead of ~8, and V = V0 Q.  The three products are
-// f64 MFMA GEMMs.  t1/t2: n*n scratch each.
-int qc_eig_device_warm(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                       int max_sweeps, double done_tol, int *notconv) {
+// f64 MFMA GEMMs.
+int qc_eig_device_warm(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *notconv) {
+    double *const t1 = E.t1.p, *const t2 = E.t2.p;
     qc_gemm(st, n, n, n, 1.0, dA, n, false, dV0, n, false, 0.0, t1, n);        // A V0
     qc_gemm(st, n, n, n, 1.0, dV0, n, true, t1, n, false, 0.0, t2, n);         // V0^T (A V0)
-    int rc = qc_eig_device(st, n, t2, t1, dw, d_work, max_sweeps, done_tol, notconv);   // Q -> t1
+    int rc = qc_eig_device(st, n, t2, t1, dw, E, notconv);   // Q -> t1
     if (rc != QC_OK) return rc;
     qc_gemm(st, n, n, n, 1.0, dV0, n, false, t1, n, false, 0.0, dV, n);        // V = V0 Q
     return QC_OK;
@@ -481,7 +491,7 @@ __device__ __forceinline__ double qc_refine_m(int n, int x, const double *__rest
 __global__ __launch_bounds__(1024) void qc_refine_stats_kernel(int n, const double *__restrict__ S, const double *__restrict__ XtX,
                                                                 double *__restrict__ lam, double *__restrict__ stats, int *__restrict__ partner,
                                                                 int *__restrict__ ctl, double *__restrict__ M) {
-    if (ctl && ctl[0] != 0) return;
+    if (ctl && ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
     __shared__ double red[4 * 16];
     __shared__ double sh_scale;
     __shared__ int sh_multi, sh_nstrong;
@@ -541,16 +551,16 @@ __global__ __launch_bounds__(1024) void qc_refine_stats_kernel(int n, const doub
         stats[3] = 0.5 * sh_nstrong; stats[4] = a; stats[5] = b; stats[6] = multi;
         if (ctl) {   // the decisions qc_eig_device_refine takes on the host, for the sync-free variant
             const double orth = stats[1], scl = fmax(stats[2], 1e-300);
-            if (!(b <= 0.1) || !(orth <= 1e-3) || multi) ctl[0] = 2;             // not perturbative: rotations needed
+            if (!(b <= 0.1) || !(orth <= 1e-3) || multi) ctl[QC_EIG_STATE] = QC_EIG_ROTATE;             // not perturbative: rotations needed
             else {
-                ctl[1] = (b <= 1e-7 && orth <= 1e-7 && sh_nstrong == 0) ? 1 : 0;   // one more update finishes
-                ctl[2] = (a <= 1e-12 * scl) ? 1 : 0;                               // no coupling left inside degenerate pairs
+                ctl[QC_EIG_LAST] = (b <= 1e-7 && orth <= 1e-7 && sh_nstrong == 0) ? 1 : 0;   // one more update finishes
+                ctl[QC_EIG_CLEAN] = (a <= 1e-12 * scl) ? 1 : 0;                               // no coupling left inside degenerate pairs
             }
         }
     }
     if (M) {
         __syncthreads();                                     // partner[], lam[], the decision: written by this workgroup
-        if (ctl[0] != 0) return;
+        if (ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
         const double scl = sh_scale;
         for (int x = tid; x < n * n; x += 1024) M[x] = qc_refine_m(n, x, S, XtX, lam, QC_REF_TINY * scl, QC_REF_GFLOOR * scl, partner);
     }
@@ -569,7 +579,7 @@ constexpr int QC_STATS_ROWS = 8;
 __global__ __launch_bounds__(256) void qc_refine_statsA_kernel(int n, const double *__restrict__ S, const double *__restrict__ XtX,
                                                                 double *__restrict__ lam, int *__restrict__ partner, double *__restrict__ part,
                                                                 const int *__restrict__ ctl) {
-    if (ctl && ctl[0] != 0) return;
+    if (ctl && ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
     extern __shared__ double sh_lam[];                       // n
     __shared__ double red[3][4];
     __shared__ double sh_scale;
@@ -644,7 +654,7 @@ __global__ __launch_bounds__(256) void qc_refine_statsB_kernel(int n, const doub
                                                                 const double *__restrict__ lam, double *__restrict__ stats,
                                                                 const int *__restrict__ partner, const double *__restrict__ part, int nwg,
                                                                 int *__restrict__ ctl, double *__restrict__ M) {
-    if (ctl[0] != 0) return;
+    if (ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
     extern __shared__ double shb[];                          // lam[n], then partner[n] as ints
     double *sh_lam = shb;
     int *sh_partner = reinterpret_cast<int *>(shb + n);
@@ -667,7 +677,7 @@ __global__ __launch_bounds__(256) void qc_refine_statsB_kernel(int n, const doub
         const double scale = part[7], orth = sqrt(rs), scl = fmax(scale, 1e-300);
         sh_scale = scale;
         int c0 = 0, c1 = 0, c2 = 0;
-        if (big || !(orth <= 1e-3) || multi) c0 = 2;                          // not perturbative: rotations needed
+        if (big || !(orth <= 1e-3) || multi) c0 = QC_EIG_ROTATE;                          // not perturbative: rotations needed
         else {
             c1 = (!notlast && orth <= 1e-7 && nstrong == 0.0) ? 1 : 0;        // one more update finishes
             c2 = (cm <= 1e-12 * scl) ? 1 : 0;                                 // no coupling left inside degenerate pairs
@@ -676,7 +686,7 @@ __global__ __launch_bounds__(256) void qc_refine_statsB_kernel(int n, const doub
         if (blockIdx.x == 0) {
             stats[0] = sqrt(off); stats[1] = orth; stats[2] = scale; stats[3] = 0.5 * nstrong; stats[4] = cm;
             stats[5] = big ? 1.0 : (notlast ? 1e-6 : 0.0); stats[6] = multi;
-            if (c0) ctl[0] = c0; else { ctl[1] = c1; ctl[2] = c2; }
+            if (c0) ctl[QC_EIG_STATE] = c0; else { ctl[QC_EIG_LAST] = c1; ctl[QC_EIG_CLEAN] = c2; }
         }
     }
     __syncthreads();
@@ -756,7 +766,7 @@ __device__ __forceinline__ double qc_refine_m(int n, int x, const double *__rest
 __global__ void qc_refine_update_kernel(int n, const double *__restrict__ S, const double *__restrict__ XtX, const double *__restrict__ lam,
                                         const double *__restrict__ stats, const int *__restrict__ partner, double *__restrict__ M,
                                         const int *__restrict__ ctl) {
-    if (ctl && ctl[0] != 0) return;
+    if (ctl && ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
     const double scale = stats[2], tiny = QC_REF_TINY * scale, gfloor = QC_REF_GFLOOR * scale;
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < n * n; x += gridDim.x * blockDim.x) M[x] = qc_refine_m(n, x, S, XtX, lam, tiny, gfloor, partner);
 }
@@ -787,10 +797,9 @@ __global__ __launch_bounds__(1024) void qc_sort_columns_kernel(int n, const doub
 //     * max|E| <= 1e-7: one more update leaves ~1e-14 (quadratic) - unless a cluster still carries coupling, which only
 //       rotations can remove -> Jacobi on S;
 //     * otherwise apply X <- X (I + E) and take another pass.
-// Scratch: t1..t4, d_work (n*n each), small (n + 8 doubles).
-int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                         double *t3, double *t4, double *small, int *notconv) {
+int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *notconv) {
     const size_t nn = (size_t)n * n;
+    double *const d_work = E.work.p, *const t1 = E.t1.p, *const t2 = E.t2.p, *const t3 = E.t3.p, *const t4 = E.t4.p, *const small = E.small.p;
     double *lam = small, *stats = small + n;
     double *X = t4;                                            // current eigenvector estimate
     if (hipMemcpyAsync(X, dV0, nn * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return QC_ERR_HIP;
@@ -815,12 +824,9 @@ int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, d
         const double scale = fmax(hs[2], 1e-300), orth = hs[1], nstrong = hs[3], cmax = hs[4], emax = hs[5], multi = hs[6];
         if (dbg) fprintf(stderr, "[eig n=%d pass %d] off %.2e orth %.2e scale %.1f strong %.0f multi %.0f cmax %.2e emax %.2e\n", n, pass, hs[0], orth, scale, nstrong, multi, cmax, emax);
         if (!(emax <= 0.1) || !(orth <= 1e-3) || multi != 0.0 || pass == MAXPASS - 1) {
-            // not perturbative (or not converging): rotations.  Always from the orthonormal start V0.
-            if (pass > 0) {
-                qc_gemm(st, n, n, n, 1.0, dA, n, false, dV0, n, false, 0.0, t1, n);
-                qc_gemm(st, n, n, n, 1.0, dV0, n, true, t1, n, false, 0.0, t2, n);
-            }
-            int rc = qc_eig_device(st, n, t2, t1, dw, d_work, 40, 1e-9, notconv);      // Q -> t1 (sorted), eigenvalues -> dw
+            // not perturbative (or not converging): rotations.  Always from the orthonormal start V0 (pass 0: t2 holds V0^T A V0 already).
+            if (pass > 0) return qc_eig_device_warm(st, n, dA, dV0, dV, dw, E, notconv);
+            int rc = qc_eig_device(st, n, t2, t1, dw, E, notconv);      // Q -> t1 (sorted), eigenvalues -> dw
             if (rc != QC_OK) return rc;
             qc_gemm(st, n, n, n, 1.0, dV0, n, false, t1, n, false, 0.0, dV, n);    // V = V0 Q
             return QC_OK;
@@ -836,29 +842,24 @@ int qc_eig_device_refine(hipStream_t st, int n, double *dA, const double *dV0, d
         if (last) {
             // converged except for coupling left inside degenerate pairs, which only rotations remove:
             // X is orthonormal to ~1e-14 now, so Jacobi on X^T A X (a handful of non-trivial rotations) finishes the job
-            qc_gemm(st, n, n, n, 1.0, dA, n, false, X, n, false, 0.0, t1, n);
-            qc_gemm(st, n, n, n, 1.0, X, n, true, t1, n, false, 0.0, t2, n);
-            int rc = qc_eig_device(st, n, t2, t1, dw, d_work, 40, 1e-9, notconv);
-            if (rc != QC_OK) return rc;
-            qc_gemm(st, n, n, n, 1.0, X, n, false, t1, n, false, 0.0, dV, n);
-            return QC_OK;
+            return qc_eig_device_warm(st, n, dA, X, dV, dw, E, notconv);
         }
     }
     return QC_ERR_HIP;   // not reached
 }
 
 // Sync-free variant for the SCF loop: a fixed number of passes is enqueued, every kernel looks at the device-side control
-// word ctl[0] (0 running, 1 done, 2 rotations needed) and returns at once when the refinement has ended.  The caller
-// reads ctl[0] together with the iteration's energy; on 2 it repeats the eigensolve with qc_eig_device_refine.
+// word ctl[QC_EIG_STATE] and returns at once when the refinement has ended.  The caller reads it together with the iteration's
+// energy; on QC_EIG_ROTATE it repeats the eigensolve with rotations.
 __global__ __launch_bounds__(1024) void qc_refine_finish_kernel(int n, const double *__restrict__ lam, const double *__restrict__ Xn,
                                                                  double *__restrict__ X, double *__restrict__ w, double *__restrict__ Xs,
                                                                  int *__restrict__ ctl, int final_pass) {
-    if (ctl[0] != 0) return;
+    if (ctl[QC_EIG_STATE] != QC_EIG_RUNNING) return;
     extern __shared__ int rank_s[];
     const int tid = threadIdx.x;
-    const int last = ctl[1], clean = ctl[2];
+    const int last = ctl[QC_EIG_LAST], clean = ctl[QC_EIG_CLEAN];
     __syncthreads();
-    if (tid == 0) ctl[3] += 1;                              // passes used (the host sizes the next step's pipeline with it)
+    if (tid == 0) ctl[QC_EIG_PASSES] += 1;                              // passes used (the host sizes the next step's pipeline with it)
     if (last && clean) {                                    // Xn holds the final vectors: ascending eigenvalues, columns alongside
         double *lam_s = reinterpret_cast<double *>(rank_s + ((n + 1) & ~1));      // (the n quotients once, not n times per thread, from L2)
         for (int i = tid; i < n; i += 1024) lam_s[i] = lam[i];
@@ -885,19 +886,19 @@ __global__ __launch_bounds__(1024) void qc_refine_finish_kernel(int n, const dou
             }
         }
         __syncthreads();
-        if (tid == 0) ctl[0] = 1;
+        if (tid == 0) ctl[QC_EIG_STATE] = QC_EIG_DONE;
     } else if (last || final_pass) {
         __syncthreads();
-        if (tid == 0) ctl[0] = 2;                           // coupling inside a degenerate cluster, or passes exhausted
+        if (tid == 0) ctl[QC_EIG_STATE] = QC_EIG_ROTATE;                           // coupling inside a degenerate cluster, or passes exhausted
     }
     // (otherwise the next pass reads Xn in place: the passes alternate between two buffers, no copy)
 }
 
-int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                        double *t3, double *t4, double *small, int *ctl, int npass) {
+int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *ctl, int npass) {
+    double *const d_work = E.work.p, *const t1 = E.t1.p, *const t2 = E.t2.p, *const t3 = E.t3.p, *const t4 = E.t4.p, *const small = E.small.p;
     double *lam = small, *stats = small + n;
     int *partner = reinterpret_cast<int *>(small + n + 8);
-    // ctl[0..3] must be zero on entry (the SCF step clears all control words with one memset)
+    // the four words of ctl must be zero on entry (the SCF step clears all control words with one memset)
     const double *X = dV0;                                    // pass 0 reads the start vectors in place
     for (int pass = 0; pass < npass; ++pass) {
         qc_gemm_pair(st, n, dA, false, X, t1, X, true, X, t3, ctl);                     // A X  and  X^T X in one launch
@@ -907,7 +908,7 @@ int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, do
             if (one_wg) hipLaunchKernelGGL(qc_refine_stats_kernel, dim3(1), dim3(1024), 0, st, n, t2, t3, lam, stats, partner, ctl, t1);
             else {
                 const int nwg = (n + QC_STATS_ROWS - 1) / QC_STATS_ROWS;
-                double *part = small + 2 * n + 16;            // (behind lam[n], stats[8], partner[n]: callers allocate qc_eig_small_doubles(n))
+                double *part = small + 2 * n + 16;            // (behind lam[n], stats[8], partner[n]: qc_eig_small_doubles(n))
                 hipLaunchKernelGGL(qc_refine_statsA_kernel, dim3(nwg), dim3(256), n * sizeof(double), st, n, t2, t3, lam, partner, part, ctl);
                 hipLaunchKernelGGL(qc_refine_statsB_kernel, dim3(nwg), dim3(256), n * sizeof(double) + n * sizeof(int) + 8, st, n, t2, t3, lam, stats, partner,
                                    part, nwg, ctl, t1);
@@ -921,27 +922,24 @@ int qc_eig_refine_async(hipStream_t st, int n, double *dA, const double *dV0, do
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
 
-int qc_eig_cold_async(hipStream_t st, int n, double *dA, double *dX0, double *triwork, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                      double *t3, double *t4, double *small, int *ctl, int npass) {
-    int rc = qc_eig_tridiag_start(st, n, dA, dX0, triwork);
+int qc_eig_cold_async(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *ctl, int npass) {
+    int rc = qc_eig_tridiag_start(st, n, dA, E);
     if (rc != QC_OK) return rc;
-    return qc_eig_refine_async(st, n, dA, dX0, dV, dw, d_work, t1, t2, t3, t4, small, ctl, npass);
+    return qc_eig_refine_async(st, n, dA, E.x0.p, dV, dw, E, ctl, npass);
 }
 
-int qc_eig_cold_sync(hipStream_t st, int n, double *dA, double *dX0, double *triwork, double *dV, double *dw, double *d_work, double *t1, double *t2,
-                     double *t3, double *t4, double *small, int *ctl, int *notconv) {
-    static const bool force_jacobi = getenv("QC_EIG_JACOBI") != nullptr;      // A/B switch: the single-workgroup Jacobi kernels only
-    if (!qc_tri_ok(n) || force_jacobi) return qc_eig_device(st, n, dA, dV, dw, d_work, 40, 1e-9, notconv);
-    if (hipMemsetAsync(ctl, 0, 4 * sizeof(int), st) != hipSuccess) return QC_ERR_HIP;
-    int rc = qc_eig_cold_async(st, n, dA, dX0, triwork, dV, dw, d_work, t1, t2, t3, t4, small, ctl, 4);
+int qc_eig_cold_sync(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *ctl, int *notconv) {
+    if (!qc_tri_ok(n) || qc_eig_force_jacobi()) return qc_eig_device(st, n, dA, dV, dw, E, notconv);
+    if (hipMemsetAsync(ctl, 0, QC_CTL_EIG_STRIDE * sizeof(int), st) != hipSuccess) return QC_ERR_HIP;
+    int rc = qc_eig_cold_async(st, n, dA, dV, dw, E, ctl, 4);
     if (rc != QC_OK) return rc;
-    int h[4] = {0, 0, 0, 0};
-    if (hipMemcpyAsync(h, ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return QC_ERR_HIP;
+    int h[QC_CTL_EIG_STRIDE] = {0, 0, 0, 0};
+    if (hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return QC_ERR_HIP;
     static const bool dbg = getenv("QC_EIG_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[eig cold n=%d] ctl %d %d %d passes %d\n", n, h[0], h[1], h[2], h[3]);
-    if (h[0] == 1) return QC_OK;
-    if (hipMemsetAsync(ctl, 0, 4 * sizeof(int), st) != hipSuccess) return QC_ERR_HIP;
-    return qc_eig_device(st, n, dA, dV, dw, d_work, 40, 1e-9, notconv);      // rotations: the start was not good enough
+    if (dbg) fprintf(stderr, "[eig cold n=%d] ctl %d %d %d passes %d\n", n, h[QC_EIG_STATE], h[QC_EIG_LAST], h[QC_EIG_CLEAN], h[QC_EIG_PASSES]);
+    if (h[QC_EIG_STATE] == QC_EIG_DONE) return QC_OK;
+    if (hipMemsetAsync(ctl, 0, QC_CTL_EIG_STRIDE * sizeof(int), st) != hipSuccess) return QC_ERR_HIP;
+    return qc_eig_device(st, n, dA, dV, dw, E, notconv);      // rotations: the start was not good enough
 }
 
 // DIIS coefficients on the device (diis.rs:40-51): B is kept slot-indexed in HBM, the new row <e_0, e_j> arrives in
@@ -1346,7 +1344,7 @@ __global__ __launch_bounds__(1024) void qc_energy_rms_kernel(int n, const double
         for (int k = 0; k < 16; ++k) { e += sh[0][k]; r += sh[1][k]; }
         out2[0] = 0.5 * e; out2[1] = r;
     }
-    if (ctl && threadIdx.x < 16) { ctl_out[threadIdx.x] = ctl[threadIdx.x]; ctl[threadIdx.x] = 0; }
+    if (ctl && threadIdx.x < QC_CTL_WORDS) { ctl_out[threadIdx.x] = ctl[threadIdx.x]; ctl[threadIdx.x] = 0; }
     __threadfence_system();
 }
 void qc_energy_rms(hipStream_t st, int n, const double *Dnew, const double *Dold, const double *H, const double *G, double *out2, int *ctl,

@@ -1,0 +1,831 @@
+// qc_scf.cpp - the host-side SCF drivers and the step API (qc_scf_* of include/qchem_hip.h).
+//
+// qc_scf_rhf / qc_scf_uhf restate the control flow of restricted_hartree_fock (core/src/hf/rhf.rs:32-108) and
+// unrestricted_hartree_fock (uhf.rs:36-167) - guess, DIIS windows, update order, energy expression, diagonal-only
+// convergence test - with every matrix resident in HBM and every step a HIP kernel, the DIIS (<= 9 x 9) QR solve
+// included; the host takes the convergence decision from two scalars it reads back once per pass.
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <new>
+
+#include "qc_internal.h"
+
+namespace {
+
+double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// Diis (diis.rs:6-60) with the sample window, the B matrix and the QR solve in HBM / on the device: nothing of it
+// synchronises with the host.  Samples live in ring slots; `slots` lists them newest first.  A singular system
+// ("DIIS failed", rhf.rs:73) raises *d_flag, which the SCF step reads back together with the energy.
+struct DeviceDiis {
+    int minlen, maxlen, n;
+    std::deque<int> slots;
+    std::vector<double *> pool;            // err of slot s = pool[2s], fock = pool[2s + 1]
+    double *d_dots = nullptr, *d_B = nullptr, *d_c = nullptr;
+    DeviceDiis(int mn, int mx, int n_) : minlen(mn), maxlen(mx), n(n_) {}
+    ~DeviceDiis() {
+        for (auto p : pool) (void)hipFree(p);
+        if (d_dots) (void)hipFree(d_dots);
+        if (d_B) (void)hipFree(d_B);
+        if (d_c) (void)hipFree(d_c);
+    }
+    int init() {
+        if (maxlen > 11) return QC_ERR_INVALID;
+        for (int i = 0; i < 2 * maxlen; ++i) { double *p; if (hipMalloc(&p, sizeof(double) * n * n) != hipSuccess) return QC_ERR_HIP; pool.push_back(p); }
+        if (hipMalloc(&d_dots, 16 * sizeof(double)) != hipSuccess || hipMalloc(&d_c, 16 * sizeof(double)) != hipSuccess ||
+            hipMalloc(&d_B, sizeof(double) * maxlen * maxlen) != hipSuccess) return QC_ERR_HIP;
+        return hipMemset(d_B, 0, sizeof(double) * maxlen * maxlen) == hipSuccess ? QC_OK : QC_ERR_HIP;
+    }
+    // claim the slot of the next sample (push_front + truncate, diis.rs:29-30: the oldest slot is recycled); the caller
+    // writes the error and Fock matrices straight into the returned buffers
+    void next_sample(double **d_err, double **d_fock) {
+        int s;
+        if ((int)slots.size() == maxlen) { s = slots.back(); slots.pop_back(); } else s = (int)slots.size();
+        slots.push_front(s);
+        *d_err = pool[2 * s]; *d_fock = pool[2 * s + 1];
+    }
+    // enqueues: new row of B, coefficient solve, extrapolated Fock matrix into d_out
+    int extrapolate(hipStream_t st, double *d_out, int *d_flag) {
+        const int m = (int)slots.size();
+        const double *ys[12], *fs[12];
+        int sl[12];
+        for (int j = 0; j < m; ++j) { sl[j] = slots[j]; ys[j] = pool[2 * slots[j]]; fs[j] = pool[2 * slots[j] + 1]; }
+        qc_dots(st, n, ys[0], ys, m, d_dots);                                         // <e_0, e_j>, diis.rs:43-45
+        // (sensitivity probe, QC_DIIS_PERTURB: one dot product moved by one unit in the last place - what a different summation
+        // order does - to see how far a run's trajectory depends on such bits)
+        static const bool perturb = getenv("QC_DIIS_PERTURB") != nullptr;
+        if (perturb && m > 1) qc_axpby(st, 1, 1.0 + 0x1p-52, d_dots + 1, 0.0, nullptr, d_dots + 1);
+        qc_diis_solve(st, m, minlen, maxlen, sl, d_dots, d_B, d_c, d_flag);           // (1, 0, ...) while m < minlen
+        qc_lincomb_dev(st, n, fs, d_c, m, d_out);                                     // diis.rs:52-58
+        return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
+    }
+};
+
+struct ScfWork {
+    int n;
+    // (work buffers of a Roothaan step come in two sets: the two spins of a UHF pass run at the same time on two streams, set b = spin;
+    // eig[b].t1 .. t4 double as the step's GEMM scratch)
+    DevBuf H, S, X, Fp[2], Cp, C, w, Fd[2], scal, CpPrev[2], CpNew[2], Fps[2];
+    QcEigWork eig[2];
+    bool have_prev[2] = {false, false};
+    // Open-shell runs (n_alpha != n_beta) use the rotation-based eigensolvers only.  Their SCF solutions of interest include
+    // saddles of the UHF functional that are kept by spatial symmetry alone (O2 triplet, BASELINE config 4): Jacobi rotations
+    // never mix functions that are not coupled, so symmetry-equivalent blocks of F' get bit-identical treatment and the
+    // iteration stays on the symmetric determinant exactly like the reference's fixed sequence of operations; Householder
+    // reflectors mix everything and seed the unstable direction with rounding noise (measured: the run then leaves the saddle
+    // for the 0.024 Eh lower broken-symmetry determinant after ~60 passes).
+    bool rotations_only = false;
+    bool small_fused = false;              // n <= QC_SMALL_MAXN: the Roothaan step runs as one workgroup with its matrices in LDS (qc_scf_small.hip)
+    bool cold[2] = {false, false};         // this pass's eigensolve of the spin started from the tridiagonal path (no previous vectors involved)
+    int npass[2] = {3, 3};                 // refinement passes enqueued per eigensolve (follows what the last one needed)
+    int mode[2] = {2, 2};                  // eigensolve of the next pass: 0 refinement, 1 two Jacobi sweeps + refinement, 2 Jacobi
+    int *ctl = nullptr;                    // the pass's QC_CTL_WORDS device control words
+    double *h_scal = nullptr;              // pinned read-back: the QC_SYNC_WORDS words of pass scalars, then (multi-rank) their complements
+    unsigned long long *d_sync = nullptr;  // multi-rank runs: the same words + their bitwise complements, all-reduced (max) across the ranks
+    ~ScfWork() {
+        if (ctl) (void)hipFree(ctl);
+        if (h_scal) (void)hipHostFree(h_scal);
+        if (d_sync) (void)hipFree(d_sync);
+    }
+    int init(int n_, int nsets) {
+        n = n_;
+        const size_t nn = (size_t)n * n;
+        DevBuf *all[] = {&H, &S, &X, &Cp, &C, &CpPrev[0], &CpPrev[1], &CpNew[0], &CpNew[1], &Fps[0], &Fps[1]};
+        for (auto b : all) if (b->alloc(nn) != QC_OK) return QC_ERR_HIP;
+        for (int b = 0; b < nsets; ++b)
+            if (eig[b].alloc(n) != QC_OK || Fp[b].alloc(nn) != QC_OK || Fd[b].alloc(nn) != QC_OK) return QC_ERR_HIP;
+        if (w.alloc(n) != QC_OK || scal.alloc(16) != QC_OK) return QC_ERR_HIP;
+        if (hipMalloc(&ctl, QC_CTL_WORDS * sizeof(int)) != hipSuccess || hipMemset(ctl, 0, QC_CTL_WORDS * sizeof(int)) != hipSuccess) return QC_ERR_HIP;
+        if (hipHostMalloc(&h_scal, (2 * QC_SYNC_WORDS + 1) * sizeof(double)) != hipSuccess) return QC_ERR_HIP;
+        std::memset(h_scal, 0, (2 * QC_SYNC_WORDS + 1) * sizeof(double));     // (the last word: sequence number of the pass, see scf_iterate)
+        if (hipMalloc(&d_sync, 2 * QC_SYNC_WORDS * sizeof(unsigned long long)) != hipSuccess) return QC_ERR_HIP;
+        return QC_OK;
+    }
+};
+
+// sorted_eigs on device (utils.rs:20-36): Fp -> (Cp, w)
+int device_sorted_eigs(qc_system *S, ScfWork &W, double *dA, double *dV, double *dw) {
+    // (set-up eigensolves: synchronous)
+    if (W.rotations_only) return qc_eig_device(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl + QC_CTL_NOTCONV);
+    return qc_eig_cold_sync(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl + QC_CTL_SETUP, W.ctl + QC_CTL_NOTCONV);
+}
+
+// start-up shared by both drivers: H = T + V, X = S^-1/2 (rhf.rs:124-131), Hückel matrix (rhf.rs:141-143)
+int scf_setup(qc_system *S, ScfWork &W, std::vector<double> &h_eht) {
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    // S, T, V on the device (molint::overlap / kinetic / nuclear, rhf.rs:41-43); H = T + V (rhf.rs:48)
+    hipStream_t st = S->stream;
+    int rc1 = qc_one_electron_device(S, 0, W.S.p);
+    if (rc1 == QC_OK) rc1 = qc_one_electron_device(S, 1, W.eig[0].t1.p);
+    if (rc1 == QC_OK) rc1 = qc_one_electron_device(S, 2, W.eig[0].t2.p);
+    if (rc1 != QC_OK) return rc1;
+    qc_axpby(st, n, 1.0, W.eig[0].t1.p, 1.0, W.eig[0].t2.p, W.H.p);
+    std::vector<double> s(nn), h(nn);
+    QC_HIP_CHECK(hipMemcpyAsync(s.data(), W.S.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    QC_HIP_CHECK(hipMemcpyAsync(h.data(), W.H.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    QC_HIP_CHECK(hipStreamSynchronize(st));
+    h_eht.assign(nn, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j)
+            h_eht[(size_t)i * n + j] = h_eht[(size_t)j * n + i] = 1.75 * s[(size_t)i * n + j] * (h[(size_t)i * n + i] + h[(size_t)j * n + j]) / 2.0;
+    // X = U (diag((U^T S U)_ii^-1/2) U^T): note the diagonal of the product, not the returned eigenvalues
+    int rc = device_sorted_eigs(S, W, W.S.p, W.Cp.p, W.w.p);          // U (column order is immaterial for X)
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.S.p, n, false, W.Cp.p, n, false, 0.0, W.eig[0].t1.p, n);      // S U
+    qc_gemm(st, n, n, n, 1.0, W.Cp.p, n, true, W.eig[0].t1.p, n, false, 0.0, W.eig[0].t2.p, n);      // U^T (S U)
+    qc_scale_cols_invsqrt(st, n, W.Cp.p, W.eig[0].t2.p, W.eig[0].t1.p);                               // U diag^-1/2
+    qc_gemm(st, n, n, n, 1.0, W.eig[0].t1.p, n, false, W.Cp.p, n, true, 0.0, W.X.p, n);       // (.) U^T
+    return QC_OK;
+}
+
+// compute_hückel_density (rhf.rs:133-150): D = factor * C_occ C_occ^T with C = X eigvecs(X^T H_eht X)
+int huckel_density(qc_system *S, ScfWork &W, const std::vector<double> &h_eht, int nocc, double factor, double *dD) {
+    const int n = S->nbasis;
+    hipStream_t st = S->stream;
+    QC_HIP_CHECK(hipMemcpyAsync(W.Fd[0].p, h_eht.data(), h_eht.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    qc_gemm(st, n, n, n, 1.0, W.Fd[0].p, n, false, W.X.p, n, false, 0.0, W.eig[0].t1.p, n);
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, true, W.eig[0].t1.p, n, false, 0.0, W.Fp[0].p, n);
+    int rc = device_sorted_eigs(S, W, W.Fp[0].p, W.Cp.p, W.w.p);
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, W.Cp.p, n, false, 0.0, W.C.p, n);
+    if (nocc > 0) qc_gemm(st, n, n, nocc, factor, W.C.p, n, false, W.C.p, n, true, 0.0, dD, n);
+    else QC_HIP_CHECK(hipMemsetAsync(dD, 0, sizeof(double) * n * n, st));
+    return QC_OK;
+}
+
+// The eigensolve of a spin's Roothaan step.  Near convergence (mode 0): GEMM refinement from this spin's previous vectors.  Otherwise -
+// first pass, or the density still moves by more than the warm threshold per element - the tridiagonal path (start vectors from
+// qc_eig_tridiag.hip + the same refinement); matrices below QC_TRI_MIN_N, open-shell runs and QC_EIG_JACOBI go to the single-workgroup
+// Jacobi kernels, in the basis of the previous vectors once they exist.  Refine and Tridiag report through the spin's control words.
+enum class EigRoute { Refine, Tridiag, JacobiWarm, JacobiCold };
+EigRoute eig_route(const ScfWork &W, int spin, int n) {
+    if (W.have_prev[spin] && W.mode[spin] == 0) return EigRoute::Refine;
+    if (qc_tri_ok(n) && !qc_eig_force_jacobi() && !W.rotations_only) return EigRoute::Tridiag;
+    return W.have_prev[spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold;
+}
+
+// One spin's Roothaan step, enqueued without any host synchronisation: F = H + G; e = FDS - SDF; DIIS; F' = X^T F X;
+// eigenvectors (eig_route); C = X C'   (rhf.rs:70-76).  New vectors go to CpNew[spin], C to dC.
+// (`st`, `b`: the stream the step is enqueued on and its set of work buffers - the two spins of a UHF pass are independent until their
+// scalars meet and run side by side, scf_iterate)
+int roothaan_enqueue(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG, const double *dD, double *dw_out, double *dC, int spin,
+                     double *dE, double *dF, bool have_F, hipStream_t st, int b) {
+    const int n = S->nbasis;
+    QcEigWork &E = W.eig[b];
+    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
+    int *const ctl = W.ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin, *const notconv = W.ctl + QC_CTL_NOTCONV;
+    if (!have_F) qc_axpby(st, n, 1.0, W.H.p, 1.0, dG, dF);                               // F (else written by the build's closing kernel)
+    qc_gemm(st, n, n, n, 1.0, dF, n, false, dD, n, false, 0.0, E.t2.p, n);                  // F D
+    qc_gemm(st, n, n, n, 1.0, E.t2.p, n, false, W.S.p, n, false, 0.0, W.Fp[b].p, n);        // F D S
+    qc_sub_transpose(st, n, W.Fp[b].p, dE);                                                 // e = FDS - (FDS)^T = FDS - SDF
+    int rc = diis.extrapolate(st, W.Fd[b].p, W.ctl + QC_CTL_DIIS);
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.Fd[b].p, n, false, W.X.p, n, false, 0.0, E.t1.p, n);        // F X
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, true, E.t1.p, n, false, 0.0, Fps, n);               // X^T (F X)
+    const EigRoute route = eig_route(W, spin, n);
+    W.cold[spin] = route == EigRoute::Tridiag;
+    switch (route) {
+    case EigRoute::Refine: rc = qc_eig_refine_async(st, n, Fps, CpPrev, CpNew, dw_out, E, ctl, W.npass[spin]); break;
+    // (three refinement passes are enqueued: two finish most starts - the third is then five empty launches - but near-degenerate
+    // clusters of a nearly converged benzene need it, and running out of passes costs a Jacobi eigensolve)
+    case EigRoute::Tridiag: rc = qc_eig_cold_async(st, n, Fps, CpNew, dw_out, E, ctl, 3); break;
+    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
+    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); break;     // sorted_eigs (rhf.rs:75)
+    }
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, CpNew, n, false, 0.0, dC, n);   // C = X C'
+    return QC_OK;
+}
+
+// The same step for n <= QC_SMALL_MAXN, density / energy / rms of rhf.rs:78-88 included: one launch when the eigensolve is a refinement from
+// the previous vectors, pre | tridiagonal start | refine + post when it starts cold, pre | Jacobi kernel | post for the rotation-only runs.
+struct SmallTail { int nocc; double dfac; double *Dn; const double *Dold; double *scal_out; int *ctl_all, *ctl_out; double *fxs_out; unsigned *seq_out = nullptr; unsigned seq = 0; };
+int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG, const double *dD, double *dw_out, double *dC, int spin,
+                   double *dE, double *dF, bool have_F, const SmallTail &tl, hipStream_t st_in = nullptr, int b = 0) {
+    const int n = S->nbasis;
+    hipStream_t st = st_in ? st_in : S->stream;               // (`st_in`, `b`: the beta step of a spin-parallel pass - side stream, second set of work buffers)
+    QcSmallArgs a{};
+    a.n = n;
+    a.F = have_F ? dF : nullptr; a.F_out = dF;
+    a.D = dD; a.S = W.S.p; a.X = W.X.p; a.H = W.H.p; a.G = dG;
+    a.E_out = dE;
+    a.m = (int)diis.slots.size(); a.minlen = diis.minlen; a.maxlen = diis.maxlen;
+    a.dots_generic = W.rotations_only ? 1 : 0;
+    for (int j = 0; j < a.m; ++j) { a.slot[j] = diis.slots[j]; a.errs[j] = diis.pool[2 * diis.slots[j]]; a.focks[j] = diis.pool[2 * diis.slots[j] + 1]; }
+    a.Bmat = diis.d_B; a.c_out = diis.d_c; a.diis_flag = W.ctl + QC_CTL_DIIS;
+    a.Fp = W.Fps[spin].p;
+    a.ctl = W.ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin;
+    a.Cp_out = W.CpNew[spin].p; a.w_out = dw_out; a.C_out = dC; a.Dn = tl.Dn; a.Dold = tl.Dold; a.nocc = tl.nocc; a.dfac = tl.dfac;
+    a.scal_out = tl.scal_out; a.ctl_all = tl.ctl_all; a.ctl_out = tl.ctl_out; a.fxs_out = tl.fxs_out; a.imax = S->imax;
+    a.seq_out = tl.seq_out; a.seq = tl.seq;
+    a.tl = S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
+    QcEigWork &E = W.eig[b];
+    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
+    int *const notconv = W.ctl + QC_CTL_NOTCONV;
+    const EigRoute route = eig_route(W, spin, n);
+    W.cold[spin] = route == EigRoute::Tridiag;
+    int rc = QC_OK;
+    if (route != EigRoute::Refine) {
+        QcSmallArgs pre = a;
+        pre.phases = 1; pre.ctl_all = nullptr; pre.seq_out = nullptr;
+        if (a.tl) a.tl += QC_TL_W;                              // (the second launch of the pass has its own slot)
+        if ((rc = qc_scf_small_launch(st, pre)) != QC_OK) return rc;
+    }
+    switch (route) {
+    case EigRoute::Refine: a.phases = 7; a.V0 = CpPrev; a.npass = W.npass[spin]; break;
+    case EigRoute::Tridiag: rc = qc_eig_tridiag_start(st, n, Fps, E); a.phases = 6; a.V0 = E.x0.p; a.npass = 3; break;
+    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); a.phases = 4; a.Cp_in = CpNew; break;
+    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); a.phases = 4; a.Cp_in = CpNew; break;
+    }
+    if (rc != QC_OK) return rc;
+    return qc_scf_small_launch(st, a);
+}
+
+// The rare repeat of a spin's eigensolve when the route that reports through the control words asked for rotations (QC_EIG_ROTATE).
+// After Tridiag (the start was not good enough): the Jacobi routes.  After Refine (not perturbative after all): the synchronous forms
+// of Tridiag (its own fallback: the Jacobi kernels) or, for the rotation-only runs, of Refine (rotations in the basis of the previous vectors).
+int roothaan_redo_eig(qc_system *S, ScfWork &W, double *dw_out, double *dC, int spin) {
+    const int n = S->nbasis;
+    hipStream_t st = S->stream;
+    QcEigWork &E = W.eig[0];
+    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
+    int *const notconv = W.ctl + QC_CTL_NOTCONV;
+    const EigRoute again = W.cold[spin] ? (W.have_prev[spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold)
+                                        : (W.rotations_only ? EigRoute::Refine : EigRoute::Tridiag);
+    int rc = QC_OK;
+    switch (again) {
+    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
+    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); break;
+    case EigRoute::Refine: rc = qc_eig_device_refine(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
+    case EigRoute::Tridiag: rc = qc_eig_cold_sync(st, n, Fps, CpNew, dw_out, E, W.ctl + QC_CTL_SETUP, notconv); break;
+    }
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, CpNew, n, false, 0.0, dC, n);
+    return QC_OK;
+}
+
+}  // namespace
+
+// ---- step-wise drivers: the host (the Rust `core` crate in the north-star design) owns the convergence loop and
+// calls one FFI entry per loop-body pass; qc_scf_rhf / qc_scf_uhf below are that loop written in C++.
+struct qc_scf_state {
+    qc_system *S = nullptr;
+    bool uhf = false;
+    int nocc[2] = {0, 0};
+    ScfWork W;
+    DevBuf D[2], Dn[2], G, Cs, ws;             // densities are double-buffered per spin: D <-> Dn swap when a pass is accepted
+    int64_t builds_timed = 0, passes = 0, redos = 0;
+    bool spin_parallel = getenv("QC_NO_SPIN_PARALLEL") == nullptr;      // (A/B switch, read per SCF state)
+    double warm_rms_env = getenv("QC_EIG_WARM_RMS") ? atof(getenv("QC_EIG_WARM_RMS")) : 0.0;   // (read per SCF state: tests reach the repeat branch with it)
+    double ms_tuner = 0;
+    bool cur_build_tuned = false, pend_build_tuned = false;   // the build of the current / the pending timing set contained a tuner run
+    unsigned cur_build_gen = 0, pend_build_gen = 0;           // ... and ran under this stream assignment (qc_system::assign_gen)
+    DevBuf T4, TK, Dtot;                       // stored mode: RHF T = I - I^x / 2; UHF I and its exchange-permuted copy
+    bool stored = false;
+    int twin = -1;                             // UHF spin-twin decision, taken at the first build
+    double ms_tensor = 0;
+    DeviceDiis *diis[2] = {nullptr, nullptr};
+    // timing events of a pass (start | build done | pass done), two sets used alternately: a pass whose end the host saw through the pinned
+    // sequence word reads none of them before it returns - the next pass does, after its own build has been issued
+    hipEvent_t evs[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    int ev_cur = 0, pending_set = 0;
+    double ms_fock = 0, ms_linalg = 0, ms_setup = 0;
+    unsigned pass_seq = 0;                     // sequence number of the last pass whose end the host saw through the pinned word
+    bool event_wait = getenv("QC_EVENT_WAIT") != nullptr;      // (A/B switch, read per SCF state: the stream's event instead)
+    bool timing_pending = false;               // ... and whose event times (set `pending_set`) have not been read yet
+    ~qc_scf_state() {
+        if (S && S->prep_owner == this) { S->prepared = false; S->prep_owner = nullptr; }
+        delete diis[0]; delete diis[1];
+        if (S && S->stream) { (void)hipStreamSynchronize(S->stream); qc_gate_quiet(S); qc_tl_dump(S); }
+        for (auto &set : evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
+    }
+};
+static void scf_state_delete(qc_scf_state *st) {
+    if (!st) return;
+    qc_system *S = st->S;
+    delete st;
+    if (S && --S->live_states == 0 && S->zombie) qc_system_free(S);
+}
+
+static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out) {
+    if (!S || !out) return QC_ERR_INVALID;
+    const double t0 = now_ms();
+    static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
+    double tt = t0;
+    auto lap = [&](const char *what) { if (sdbg) { const double t = now_ms(); fprintf(stderr, "[setup] %-28s %.3f ms\n", what, t - tt); tt = t; } };
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    lap("qc_device_init (total)");
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    qc_scf_state *st = new (std::nothrow) qc_scf_state();
+    if (!st) return QC_ERR_INVALID;
+    struct Del { void operator()(qc_scf_state *p) const { scf_state_delete(p); } };
+    std::unique_ptr<qc_scf_state, Del> guard(st);
+    st->S = S; st->uhf = uhf;
+    ++S->live_states;
+    st->nocc[0] = st->nocc[1] = S->nelec / 2;                             // rhf.rs:176 / uhf.rs:43-45
+    if (uhf && (n_alpha > 0 || n_beta > 0)) { st->nocc[0] = n_alpha; st->nocc[1] = n_beta; }
+    if (st->nocc[0] < 0 || st->nocc[1] < 0 || st->nocc[0] > n || st->nocc[1] > n) return QC_ERR_INVALID;
+    const int nspin = uhf ? 2 : 1;
+    st->W.rotations_only = uhf && st->nocc[0] != st->nocc[1];
+    // (QC_NO_SMALL_FUSED: A/B switch, the generic launch sequence.  Open-shell runs take the one-workgroup kernels too since the two spins'
+    // kernels run side by side - pre | Jacobi kernel | post per spin, O2 triplet/cc-pVDZ 0.130 ms of linear algebra per pass against 0.148
+    // for the generic sequence, 0.198 with the spins one after the other - with the DIIS dot products in the generic sequence's summation
+    // order, QcSmallArgs::dots_generic.  Their saddle-point trajectories depend on every last bit - DESIGN.md 1 - and the two paths differ
+    // in the last bit of the first pass's energy: O2 triplet reaches 1e-10 in 118 passes on this path and in 450 on the generic one, 15
+    // and 15 at the CLI's 1e-6, energies 8e-6 Eh apart there.  QC_NO_OPEN_SHELL_FUSED: A/B switch.)
+    static const bool open_fused = getenv("QC_NO_OPEN_SHELL_FUSED") == nullptr;
+    st->W.small_fused = n <= QC_SMALL_MAXN && (!st->W.rotations_only || open_fused) && getenv("QC_NO_SMALL_FUSED") == nullptr;
+    if ((rc = st->W.init(n, uhf ? 2 : 1)) != QC_OK) return rc;
+    for (int s = 0; s < nspin; ++s) if (st->D[s].alloc(nn) != QC_OK || st->Dn[s].alloc(nn) != QC_OK) return QC_ERR_HIP;
+    if (st->G.alloc(nspin * nn) != QC_OK || st->Cs.alloc(nspin * nn) != QC_OK || st->ws.alloc(nspin * n) != QC_OK) return QC_ERR_HIP;
+    std::vector<double> h_eht;
+    lap("state buffers");
+    if ((rc = scf_setup(S, st->W, h_eht)) != QC_OK) return rc;           // rhf.rs:41-49
+    lap("S, T, V, X = S^-1/2");
+    for (int s = 0; s < nspin; ++s)                                       // rhf.rs:50 / uhf.rs:60-63
+        if ((rc = huckel_density(S, st->W, h_eht, st->nocc[s], uhf ? 1.0 : 2.0, st->D[s].p)) != QC_OK) return rc;
+    lap("Hueckel guess");
+    if (S->fock_mode == 1) {
+        // the reference's conventional SCF: ERI tensor once (rhf.rs:45), antisymmetrised copy (rhf.rs:58-62), dense
+        // contraction per pass.  8 n^4 bytes per tensor; two of them live during the build.
+        if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;        // sharded builds are direct-mode only
+        const size_t n4 = nn * nn;
+        size_t free_b = 0, total_b = 0;
+        QC_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if ((double)n4 * 8.0 * 2.2 > (double)free_b) return QC_ERR_UNSUPPORTED;
+        const double tt0 = now_ms();
+        DevBuf I;
+        if (I.alloc(n4) != QC_OK || st->T4.alloc(n4) != QC_OK) return QC_ERR_HIP;
+        QC_HIP_CHECK(hipMemsetAsync(I.p, 0, n4 * sizeof(double), S->stream));
+        if ((rc = qc_launch_eri_full(S, I.p)) != QC_OK) return rc;
+        if (uhf) {
+            qc_permute_tensor(S->stream, n, I.p, 0.0, 1.0, st->T4.p);      // TK[i,j,k,l] = I[i,k,j,l]
+            st->TK.p = st->T4.p; st->T4.p = I.p; I.p = nullptr;            // keep I (as T4) and TK
+            if (st->Dtot.alloc(nn) != QC_OK) return QC_ERR_HIP;
+        } else {
+            qc_permute_tensor(S->stream, n, I.p, 1.0, -0.5, st->T4.p);     // electron_terms, rhf.rs:58-62
+        }
+        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+        st->stored = true;
+        st->ms_tensor = now_ms() - tt0;
+    }
+    for (int s = 0; s < nspin; ++s) {                                     // Diis::new(4,6) rhf.rs:65 / (2,8) uhf.rs:76-78
+        st->diis[s] = uhf ? new DeviceDiis(2, 8, n) : new DeviceDiis(4, 6, n);
+        if ((rc = st->diis[s]->init()) != QC_OK) return rc;
+    }
+    for (auto &set : st->evs) for (hipEvent_t &e : set) QC_HIP_CHECK(hipEventCreate(&e));
+    int eig_flag = 0;                                                     // the eigensolves of X and of the Hueckel guess
+    QC_HIP_CHECK(hipMemcpyAsync(&eig_flag, st->W.ctl + QC_CTL_NOTCONV, sizeof(int), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    if (eig_flag) return QC_EIG_NOT_CONVERGED;
+    st->ms_setup = now_ms() - t0;
+    *out = guard.release();
+    return QC_OK;
+}
+
+// (a pass whose end the host saw through the pinned sequence word has not read its event times yet: the last event may still have been
+// in flight, and asking costs host time between two passes.  The next pass asks once its own build is out.)
+static void scf_flush_timing(qc_scf_state *st) {
+    if (!st->timing_pending) return;
+    st->timing_pending = false;
+    hipEvent_t *e = st->evs[st->pending_set];
+    float ms_f = 0, ms_l = 0;
+    if (hipEventSynchronize(e[2]) != hipSuccess) return;
+    const bool have_f = hipEventElapsedTime(&ms_f, e[0], e[1]) == hipSuccess;
+    if (hipEventElapsedTime(&ms_l, e[1], e[2]) == hipSuccess) st->ms_linalg += ms_l;
+    if (!have_f) return;
+    // (a build that contained a tuner run is not a sample of the build time: neither for the totals nor for the tuner's online choice)
+    if (st->pend_build_tuned) return;
+    st->ms_fock += ms_f; st->builds_timed += 1;
+    if (!st->stored && !st->S->comm) qc_fock_feedback(st->S, ms_f, st->pend_build_gen);
+}
+
+// Wait for an event by polling (what hipStreamSynchronize does too): a parked thread's wake-up latency is longer
+// than a whole SCF pass of a small molecule.  Not for ever: a kernel that never finishes is an error of the call, not a host core
+// pinned for good (QC_HOST_WAIT_LIMIT_S, default 120 s; the device-side waits give up earlier and say why).
+static double host_wait_limit_ms() {
+    static const double lim = getenv("QC_HOST_WAIT_LIMIT_S") ? atof(getenv("QC_HOST_WAIT_LIMIT_S")) * 1e3 : 120e3;
+    return lim;
+}
+static hipError_t wait_event(hipEvent_t ev) {
+    hipError_t e;
+    unsigned spins = 0;
+    double t0 = 0.0;
+    while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
+        if ((++spins & 0x3fff) == 0) {
+            const double t = now_ms();
+            if (t0 == 0.0) t0 = t;
+            else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return hipErrorLaunchTimeOut; }
+        }
+    }
+    return e;
+}
+
+// one pass of the loop body.  RHF: rhf.rs:67-88.  UHF: uhf.rs:81-137 (returns the reference's `density_rms`,
+// i.e. (rms_a + rms_b) / 2, and the energy expression of uhf.rs:145-153 evaluated every pass).
+// The whole pass is enqueued without looking at the device; one synchronisation at its end returns the energy, the rms
+// and the control words (DIIS failure, eigen-refinement outcome).  Launch latency of ~50 small kernels then overlaps with
+// their execution instead of adding to it.
+static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
+    qc_system *S = st->S;
+    ScfWork &W = st->W;
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    hipStream_t sm = S->stream;
+    const int nspin = st->uhf ? 2 : 1;
+    int rc;
+    const double th0 = now_ms();
+    qc_stamp("enter pass");
+    if ((rc = qc_tl_begin_pass(S)) != QC_OK) return rc;
+    st->ev_cur ^= 1;
+    hipEvent_t *const ev = st->evs[st->ev_cur];
+    hipEvent_t const ev0 = ev[0], ev1 = ev[1], ev2 = ev[2];
+    double *const dG = st->G.p;
+    double *dE[2] = {nullptr, nullptr}, *dF[2] = {nullptr, nullptr};       // this pass's DIIS sample buffers (error, Fock matrix) per spin
+    for (int s = 0; s < nspin; ++s) st->diis[s]->next_sample(&dE[s], &dF[s]);
+    bool have_F = false;
+    // G of every spin from the *old* densities
+    if (st->stored) {
+        QC_HIP_CHECK(hipEventRecord(ev0, sm));
+        if (st->uhf) {   // uhf.rs:216-226: G_s = <I, D_s + D_s'> - <I^x, D_s>
+            qc_axpby(sm, n, 1.0, st->D[0].p, 1.0, st->D[1].p, st->Dtot.p);
+            qc_axpby(sm, n, -1.0, st->D[0].p, 0.0, nullptr, W.eig[0].t1.p);
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.eig[0].t1.p, dG)) != QC_OK) return rc;
+            qc_axpby(sm, n, -1.0, st->D[1].p, 0.0, nullptr, W.eig[0].t1.p);
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.eig[0].t1.p, dG + nn)) != QC_OK) return rc;
+        } else {
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, dG)) != QC_OK) return rc;   // rhf.rs:152-167
+        }
+        st->cur_build_tuned = false; st->cur_build_gen = S->assign_gen;
+    } else {
+        QC_HIP_CHECK(hipEventRecord(ev0, sm));
+        qc_stamp("ev0");
+        const int tunes0 = S->tune_count;
+        const double tt0 = now_ms();
+        if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dG + nn : nullptr, st->uhf,
+                                       &st->twin, W.H.p, dF[0], dF[1], &have_F, st)) != QC_OK) return rc;
+        st->cur_build_tuned = S->tune_count != tunes0;
+        if (st->cur_build_tuned) st->ms_tuner += now_ms() - tt0;
+        st->cur_build_gen = S->assign_gen;
+    }
+    qc_stamp("build out");
+    scf_flush_timing(st);                                                 // (the previous pass's times, now that this pass's build is out)
+    QC_HIP_CHECK(hipEventRecord(ev1, sm));
+    qc_stamp("flush timing, ev1");
+    // UHF: the two spins' steps are independent (uhf.rs:84-135 runs them one after the other) - the beta step goes to a side stream on
+    // another dispatch pipe, behind an event of the build's closing kernel, and meets the handle's stream again before the scalars
+    // (device-side join).  Same kernels, same arithmetic, per spin: results are bit for bit those of the serial order (QC_NO_SPIN_PARALLEL).
+    const bool spin_par = st->uhf && !W.small_fused && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events;
+    if (!W.small_fused) {
+        hipStream_t side = spin_par ? qc_spin_fork(S) : nullptr;
+        if (spin_par && !side) return QC_ERR_HIP;
+        for (int s = 0; s < nspin; ++s) {                                 // (the control words were cleared by the previous pass)
+            const bool on_side = spin_par && s == 1;
+            if ((rc = roothaan_enqueue(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F,
+                                       on_side ? side : sm, on_side ? 1 : 0)) != QC_OK) return rc;
+            if (on_side) {    // the beta density on the side stream as well; then the streams meet
+                if (st->nocc[s] > 0) qc_gemm(side, n, n, st->nocc[s], 1.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
+                else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), side));
+            }
+        }
+        if (spin_par && (rc = qc_spin_join(S)) != QC_OK) return rc;
+    }
+    int *h_ctl = reinterpret_cast<int *>(W.h_scal + 4);
+    // Multi-rank runs take every decision (convergence, DIIS failure, eigensolve mode, repeat) from the SAME numbers on every
+    // rank: the pass scalars go to device memory, are all-reduced as bit patterns (max) together with their complements - so a
+    // rank whose copy differs is noticed (max(x) != ~max(~x)) - and only then reach the host.  The replicated linear algebra is
+    // deterministic and starts from bit-identical G (integer all-reduce), so the copies agree; this makes a divergence an
+    // error on all ranks in the same pass instead of a hang in the next all-reduce.
+    const bool multi = S->comm != nullptr;
+    double *scal_out = multi ? reinterpret_cast<double *>(W.d_sync) : W.h_scal;
+    int *ctl_out = multi ? reinterpret_cast<int *>(W.d_sync + 4) : h_ctl;
+    bool dens_done[2] = {false, spin_par};                               // (the beta density of a spin-parallel pass was formed on the side stream)
+    auto density_and_scalars = [&](int s, bool hand_over) -> int {
+        if (dens_done[s]) dens_done[s] = false;                          // (once: a repeat of the eigensolve forms it again, here)
+        else if (st->nocc[s] > 0) qc_gemm(sm, n, n, st->nocc[s], st->uhf ? 1.0 : 2.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
+        else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), sm));
+        // energy and rms straight into pinned host memory; the last spin's kernel also hands over and clears the control words
+        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, dG + s * nn, scal_out + 2 * s, hand_over ? W.ctl : nullptr, ctl_out);
+        return QC_OK;
+    };
+    auto publish_scalars = [&]() -> int {
+        if (!multi) return QC_OK;
+        qc_sync_pack(sm, W.d_sync, QC_SYNC_WORDS);
+        if (qc_rccl().AllReduce(W.d_sync, W.d_sync, 2 * QC_SYNC_WORDS, ncclUint64, ncclMax, (ncclComm_t)S->comm, sm) != ncclSuccess) return QC_ERR_RCCL;
+        QC_HIP_CHECK(hipMemcpyAsync(W.h_scal, W.d_sync, 2 * QC_SYNC_WORDS * sizeof(double), hipMemcpyDeviceToHost, sm));
+        return QC_OK;
+    };
+    auto ranks_agree = [&]() -> bool {
+        if (!multi) return true;
+        const unsigned long long *w = reinterpret_cast<const unsigned long long *>(W.h_scal);
+        for (int i = 0; i < QC_SYNC_WORDS; ++i) if (w[QC_SYNC_WORDS + i] != ~w[i]) return false;
+        return true;
+    };
+    if (multi && nspin == 1) QC_HIP_CHECK(hipMemsetAsync(W.d_sync + 2, 0, 2 * sizeof(double), sm));       // unused spin slot
+    bool scale_in_kernel = false;
+    // Single-rank runs on the one-workgroup path: the kernel that ends the pass stores the pass's sequence number into pinned memory
+    // after the scalars and control words, and the host polls THAT instead of the event behind it (a few microseconds earlier per pass).
+    unsigned *h_seq = reinterpret_cast<unsigned *>(W.h_scal + 2 * QC_SYNC_WORDS);
+    const bool seq_wait = W.small_fused && !multi && !st->event_wait;
+    // UHF on the one-workgroup path: the two spins' kernels side by side as well - beta on a side stream of another dispatch pipe behind an
+    // event of the build's closing kernel, with the second set of work buffers; the kernel that joins the streams on the device also hands
+    // the control words over and stores the sequence word (qc_spin_join_end).  Same kernels per spin: bit for bit the serial order.
+    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events && !multi;
+    if (small_par) {
+        hipStream_t side = qc_spin_fork(S);
+        if (!side) return QC_ERR_HIP;
+        for (int s = 0; s < nspin; ++s) {
+            SmallTail tl{st->nocc[s], 1.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, nullptr, ctl_out, nullptr};
+            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl,
+                                     s == 1 ? side : nullptr, s)) != QC_OK) return rc;
+        }
+        if ((rc = qc_spin_join_end(S, W.ctl, ctl_out, seq_wait ? h_seq : nullptr, st->pass_seq + 1)) != QC_OK) return rc;
+    } else if (W.small_fused) {
+        for (int s = 0; s < nspin; ++s) {
+            // (RHF, direct fixed-point builds: the kernel that forms the new density also leaves the next build's fixed-point unit)
+            const bool scale_here = !st->uhf && !st->stored && S->accum_fx;
+            scale_in_kernel = scale_here;
+            SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl : nullptr, ctl_out,
+                         scale_here ? S->d_fxs : nullptr};
+            if (seq_wait && s == nspin - 1) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
+            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
+        }
+    } else
+        for (int s = 0; s < nspin; ++s) if ((rc = density_and_scalars(s, s == nspin - 1)) != QC_OK) return rc;
+    if ((rc = publish_scalars()) != QC_OK) return rc;
+    // the next pass's build starts from Dn: its density-only preliminaries run while the host turns around
+    auto prepare_next = [&]() -> int { return st->stored ? QC_OK : qc_fock_prepare_device(S, st->Dn[0].p, st->uhf ? st->Dn[1].p : nullptr, st->uhf, st, scale_in_kernel); };
+    if ((rc = prepare_next()) != QC_OK) return rc;
+    qc_stamp("roothaan out");
+    QC_HIP_CHECK(hipEventRecord(ev2, sm));
+    qc_stamp("ev2");
+    const double th1 = now_ms();
+    if (seq_wait) {
+        const unsigned want = st->pass_seq + 1;
+        unsigned spins = 0;
+        double t0 = 0.0;
+        while (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != want) {
+            if ((++spins & 0xfff) == 0) {                   // (a failed launch or a fault never stores the word: the event knows)
+                const hipError_t e = hipEventQuery(ev2);
+                if (e == hipErrorNotReady) {
+                    const double t = now_ms();
+                    if (t0 == 0.0) t0 = t;
+                    else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return QC_ERR_HIP; }
+                    continue;
+                }
+                if (e != hipSuccess || __atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != want) { fprintf(stderr, "qchem_hip: the pass ended without its sequence word (%s)\n", hipGetErrorString(e)); return QC_ERR_HIP; }
+            }
+        }
+        st->pass_seq = want;
+        // The word says that the pass's last kernel is through.  If the preliminaries of the next build were put behind it (UHF: density
+        // sum and fixed-point unit; a memset after a mode change), the next build's side streams - which start without a fork event -
+        // must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there: the kernel
+        // leaves the fixed-point unit itself and the fold left the planes clean.)
+        if (!st->stored && S->prep_enqueued) QC_HIP_CHECK(wait_event(ev2));
+    } else QC_HIP_CHECK(wait_event(ev2));
+    const double th2 = now_ms();
+    qc_stamp("pass seen");
+    if ((rc = qc_join_check(S)) != QC_OK) return rc;                     // (the join of this pass's build is in front of everything waited for)
+    qc_gate_quiet(S);                                                    // (nothing of this handle waits on the device any more)
+    if (!ranks_agree()) { fprintf(stderr, "qchem_hip: rank %d: the ranks' SCF scalars differ - replicated state diverged\n", S->rank); return QC_ERR_RCCL; }
+    if (h_ctl[QC_CTL_DIIS] != 0) return QC_DIIS_SINGULAR;                          // "DIIS failed", rhf.rs:73
+    if (h_ctl[QC_CTL_NOTCONV] != 0) return QC_EIG_NOT_CONVERGED;
+    static const bool dbg = getenv("QC_SCF_DEBUG") != nullptr;
+    const int *const ea = h_ctl + QC_CTL_EIG, *const eb = ea + QC_CTL_EIG_STRIDE;
+    if (dbg) fprintf(stderr, "[scf] ctl a: %d %d %d %d  b: %d %d %d %d  npass %d %d have_prev %d mode %d cold %d | host enqueue %.0f us, then waited %.0f us\n", ea[QC_EIG_STATE], ea[QC_EIG_LAST], ea[QC_EIG_CLEAN], ea[QC_EIG_PASSES], eb[QC_EIG_STATE], eb[QC_EIG_LAST], eb[QC_EIG_CLEAN], eb[QC_EIG_PASSES], W.npass[0], W.npass[1], (int)W.have_prev[0], W.mode[0], (int)W.cold[0], (th1 - th0) * 1e3, (th2 - th1) * 1e3);
+    if (dbg) {   // the pass's DIIS coefficients (diis.rs:50-51), newest sample first
+        double c[12] = {0};
+        const int m = (int)st->diis[0]->slots.size();
+        (void)hipMemcpy(c, st->diis[0]->d_c, m * sizeof(double), hipMemcpyDeviceToHost);
+        fprintf(stderr, "[scf] diis c:");
+        for (int j = 0; j < m; ++j) fprintf(stderr, " %.3e", c[j]);
+        fprintf(stderr, "\n");
+    }
+    // the pass's event times are read by the next pass (scf_flush_timing): the last event may still be in flight when the host has seen
+    // the sequence word
+    st->timing_pending = true; st->pending_set = st->ev_cur;
+    st->pend_build_tuned = st->cur_build_tuned; st->pend_build_gen = st->cur_build_gen;
+    bool redo = false;
+    for (int s = 0; s < nspin; ++s) {
+        const bool refined = W.cold[s] || (W.have_prev[s] && W.mode[s] == 0);       // the eigensolve reported through the control word
+        if (!refined) continue;
+        const int *const eig = h_ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * s;
+        if (eig[QC_EIG_STATE] == QC_EIG_DONE) { W.npass[s] = W.cold[s] ? 3 : std::max(1, std::min(3, eig[QC_EIG_PASSES])); continue; }
+        W.npass[s] = 3;
+        // the refinement wanted rotations (large step, or a degenerate cluster): repeat this spin's eigensolve the careful way
+        if (!redo) { scf_flush_timing(st); QC_HIP_CHECK(hipEventRecord(ev1, sm)); }
+        if ((rc = roothaan_redo_eig(S, W, st->ws.p + s * n, st->Cs.p + s * nn, s)) != QC_OK) return rc;
+        if ((rc = density_and_scalars(s, false)) != QC_OK) return rc;
+        redo = true;
+    }
+    if (redo) {
+        st->redos += 1;
+        // the repeated eigensolves report through the same control words (Jacobi sweeps exhausted: QC_CTL_NOTCONV): hand them over again,
+        // whichever spin was repeated, and clear them for the next pass
+        QC_HIP_CHECK(hipMemcpyAsync(ctl_out, W.ctl, QC_CTL_WORDS * sizeof(int), hipMemcpyDefault, sm));
+        QC_HIP_CHECK(hipMemsetAsync(W.ctl, 0, QC_CTL_WORDS * sizeof(int), sm));
+        if ((rc = publish_scalars()) != QC_OK) return rc;
+        scale_in_kernel = false;
+        if ((rc = prepare_next()) != QC_OK) return rc;                    // (the density changed)
+        QC_HIP_CHECK(hipEventRecord(ev2, sm));
+        QC_HIP_CHECK(wait_event(ev2));
+        if ((rc = qc_join_check(S)) != QC_OK) return rc;
+        qc_gate_quiet(S);
+        if (!ranks_agree()) return QC_ERR_RCCL;
+        if (h_ctl[QC_CTL_NOTCONV] != 0) return QC_EIG_NOT_CONVERGED;     // the repeat ran out of sweeps: no vectors to go on with
+        float ms_r = 0;
+        (void)hipEventElapsedTime(&ms_r, ev1, ev2);
+        st->ms_linalg += ms_r;
+    }
+    double rms_sum = 0.0, e_sum = 0.0;
+    for (int s = 0; s < nspin; ++s) {
+        const double rms_s = std::sqrt(W.h_scal[2 * s + 1] / n);
+        e_sum += W.h_scal[2 * s]; rms_sum += rms_s;
+        // the refinement is perturbative: on its own once the density has nearly stopped moving, behind two Jacobi sweeps
+        // while it still moves, not at all in the first wild passes
+        // (the one-workgroup path of small matrices pays 150 us for a cold start and nothing extra for a refinement pass that turns out to
+        // be needed: it refines from the previous vectors one decade earlier - H2O/cc-pVTZ: one cold pass less per run, no repeats;
+        // benzene at 1e-2: two repeated eigensolves per run, slower than 1e-3)
+        const double warm_rms = st->warm_rms_env > 0.0 ? st->warm_rms_env : (W.small_fused ? 1e-2 : 1e-3);
+        W.mode[s] = rms_s >= 1.0 ? 2 : (rms_s >= warm_rms || redo) ? 1 : 0;
+        std::swap(st->D[s].p, st->Dn[s].p);                              // D += 1.0 * dD
+        std::swap(W.CpPrev[s].p, W.CpNew[s].p);
+        W.have_prev[s] = true;
+    }
+    st->passes += 1;
+    qc_stamp("pass end");
+    qc_stamp_flush();
+    if (energy) *energy = e_sum;
+    if (rms_out) *rms_out = st->uhf ? rms_sum / 2.0 : rms_sum;
+    return QC_OK;
+}
+
+static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, bool uhf) {
+    if (!S || !cfg || !out || !out->orbital_energies || (uhf && !out->orbital_energies_beta)) return QC_ERR_INVALID;
+    const double t_begin = now_ms();
+    qc_scf_state *st = nullptr;
+    int rc = scf_begin(S, uhf, cfg->n_alpha, cfg->n_beta, &st);
+    if (rc != QC_OK) return rc;
+    struct Del { void operator()(qc_scf_state *p) const { scf_state_delete(p); } };
+    std::unique_ptr<qc_scf_state, Del> guard(st);
+    const int n = S->nbasis;
+    out->nuclear_repulsion = qc_nuclear_repulsion(S);                    // rhf.rs:39
+    out->electronic_energy = 0.0; out->iterations = 0;
+    int status = QC_NOT_CONVERGED;
+    for (size_t it = 0; it <= cfg->max_iterations; ++it) {               // inclusive range, rhf.rs:66 / uhf.rs:80
+        double e = 0.0, rms = 0.0;
+        rc = scf_iterate(st, &e, &rms);
+        if (rc != QC_OK) { status = rc; break; }
+        // the reference's per-iteration log line (rhf.rs:90-92, uhf.rs:138; `log::info!`, silent unless a logger is installed): QC_LOG=1
+        static const bool log_info = getenv("QC_LOG") != nullptr;
+        if (log_info) fprintf(stderr, "iteration %-4zu - electronic energy %1.4f. density rms %1.4e\n", it, e, rms);
+        const bool conv = uhf ? (rms / 2.0 < cfg->epsilon) : (rms < cfg->epsilon);   // uhf.rs:139 / rhf.rs:94
+        if (conv) {
+            out->electronic_energy = e; out->iterations = it;
+            QC_HIP_CHECK(hipMemcpy(out->orbital_energies, st->ws.p, n * sizeof(double), hipMemcpyDeviceToHost));
+            if (uhf) QC_HIP_CHECK(hipMemcpy(out->orbital_energies_beta, st->ws.p + n, n * sizeof(double), hipMemcpyDeviceToHost));
+            status = QC_OK;
+            break;
+        }
+    }
+    scf_flush_timing(st);
+    out->ms_setup = st->ms_setup; out->ms_fock_total = st->ms_fock; out->ms_linalg_total = st->ms_linalg;
+    out->ms_total = now_ms() - t_begin;
+    out->ms_tuner = st->ms_tuner;
+    return status;
+}
+
+extern "C" {
+
+int qc_scf_begin_rhf(qc_system *S, qc_scf_state **out) { return scf_begin(S, false, 0, 0, out); }
+int qc_scf_begin_uhf(qc_system *S, int n_alpha, int n_beta, qc_scf_state **out) { return scf_begin(S, true, n_alpha, n_beta, out); }
+int qc_scf_iterate(qc_scf_state *st, double *electronic_energy, double *density_rms) {
+    if (!st) return QC_ERR_INVALID;
+    return scf_iterate(st, electronic_energy, density_rms);
+}
+int qc_scf_orbital_energies(qc_scf_state *st, int spin, double *out) {
+    if (!st || !out || spin < 0 || spin > (st->uhf ? 1 : 0)) return QC_ERR_INVALID;
+    QC_HIP_CHECK(hipMemcpy(out, st->ws.p + (size_t)spin * st->S->nbasis, st->S->nbasis * sizeof(double), hipMemcpyDeviceToHost));
+    return QC_OK;
+}
+int qc_scf_density(qc_scf_state *st, int spin, double *out) {
+    if (!st || !out || spin < 0 || spin > (st->uhf ? 1 : 0)) return QC_ERR_INVALID;
+    const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;
+    QC_HIP_CHECK(hipMemcpy(out, st->D[spin].p, nn * sizeof(double), hipMemcpyDeviceToHost));
+    return QC_OK;
+}
+int qc_scf_coefficients(qc_scf_state *st, int spin, double *out) {
+    if (!st || !out || spin < 0 || spin > (st->uhf ? 1 : 0) || st->passes == 0) return QC_ERR_INVALID;
+    const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;
+    QC_HIP_CHECK(hipStreamSynchronize(st->S->stream));
+    QC_HIP_CHECK(hipMemcpy(out, st->Cs.p + spin * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
+    return QC_OK;
+}
+int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out) {
+    if (!st || !out || st->passes == 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    const int n = S->nbasis, nspin = st->uhf ? 2 : 1;
+    std::vector<double> eps((size_t)nspin * n);
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    QC_HIP_CHECK(hipMemcpy(eps.data(), st->ws.p, eps.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int32_t nocc[2] = {st->nocc[0], st->nocc[1]};
+    int rc = qc_mp2_validate(n, nspin, eps.data(), nocc, n_frozen);
+    if (rc != QC_OK) return rc;
+    return qc_mp2_device(S, nspin, st->Cs.p, st->ws.p, nocc, n_frozen, out);   // (reads Cs / ws, writes nothing of the state)
+}
+int qc_scf_gradient(qc_scf_state *st, double *grad) {
+    if (!st || !grad || st->passes == 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const int n = S->nbasis, nspin = st->uhf ? 2 : 1, na3 = 3 * S->natoms;
+    const size_t nn = (size_t)n * n;
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    DevBuf dP, dW;
+    if (dP.alloc(nspin * nn) != QC_OK || dW.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    hipEvent_t ev[2];
+    for (auto &e : ev) QC_HIP_CHECK(hipEventCreate(&e));
+    struct EvDel { hipEvent_t *e; ~EvDel() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } evdel{ev};
+    // P: the state's own density, exactly what qc_scf_density returns; W from the C and orbital energies the state reports
+    QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
+    for (int s = 0; s < nspin; ++s) QC_HIP_CHECK(hipMemcpyAsync(dP.p + s * nn, st->D[s].p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+    const int nocc[2] = {st->nocc[0], st->nocc[1]};
+    int rc = qc_gradient_w_device(S, nspin, st->Cs.p, st->ws.p, nocc, dW.p);   // (reads Cs / ws, writes nothing of the state)
+    if (rc != QC_OK) return rc;
+    QC_HIP_CHECK(hipEventRecord(ev[1], S->stream));
+    std::vector<double> t((size_t)4 * na3);
+    qc_nuclear_gradient(S, t.data());
+    if ((rc = qc_gradient_device(S, nspin, dP.p, dW.p, t.data() + na3, S->grad_ms)) != QC_OK) return rc;
+    float pw = 0.f;
+    QC_HIP_CHECK(hipEventElapsedTime(&pw, ev[0], ev[1]));
+    S->grad_ms[0] += pw;                                                    // (phase 0: P/W build + Cartesian transform)
+    for (int k = 0; k < na3; ++k) grad[k] = ((t[k] + t[na3 + k]) + t[2 * na3 + k]) + t[3 * na3 + k];
+    return QC_OK;
+}
+int qc_scf_matrix(qc_scf_state *st, int which, double *out) {
+    if (!st || !out || which < 0 || which > 2) return QC_ERR_INVALID;
+    const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;
+    const double *src = which == 0 ? st->W.S.p : which == 1 ? st->W.H.p : st->W.X.p;
+    QC_HIP_CHECK(hipMemcpy(out, src, nn * sizeof(double), hipMemcpyDeviceToHost));
+    return QC_OK;
+}
+int qc_scf_spin_square(qc_scf_state *st, double *s2) {
+    if (!st || !s2) return QC_ERR_INVALID;
+    *s2 = 0.0;
+    if (!st->uhf) return QC_OK;
+    qc_system *S = st->S;
+    ScfWork &W = st->W;
+    const int n = S->nbasis;
+    hipStream_t sm = S->stream;
+    qc_gemm(sm, n, n, n, 1.0, st->D[0].p, n, false, W.S.p, n, false, 0.0, W.eig[0].t1.p, n);      // D_alpha S
+    qc_gemm(sm, n, n, n, 1.0, st->D[1].p, n, false, W.S.p, n, false, 0.0, W.eig[0].t2.p, n);      // D_beta S
+    // tr(A B) = sum_ij A_ij B_ji: one dot product of A with B^T - reuse the DIIS dot kernel on (A, B^T)
+    qc_sub_transpose(sm, n, W.eig[0].t2.p, W.eig[0].t3.p);                                                // t3 = B - B^T
+    qc_axpby(sm, n, 1.0, W.eig[0].t2.p, -1.0, W.eig[0].t3.p, W.eig[0].t4.p);                                    // t4 = B^T
+    const double *ys[1] = {W.eig[0].t4.p};
+    qc_dots(sm, n, W.eig[0].t1.p, ys, 1, W.scal.p);
+    double tr = 0.0;
+    QC_HIP_CHECK(hipMemcpyAsync(&tr, W.scal.p, sizeof(double), hipMemcpyDeviceToHost, sm));
+    QC_HIP_CHECK(hipStreamSynchronize(sm));
+    const double sz = 0.5 * (st->nocc[0] - st->nocc[1]);
+    *s2 = sz * (sz + 1.0) + st->nocc[1] - tr;
+    return QC_OK;
+}
+double qc_scf_tensor_ms(qc_scf_state *st) { return st ? st->ms_tensor : 0.0; }
+int qc_scf_timings(qc_scf_state *st, double *ms_setup, double *ms_fock, double *ms_linalg) {
+    if (!st) return QC_ERR_INVALID;
+    scf_flush_timing(st);
+    if (ms_setup) *ms_setup = st->ms_setup;
+    if (ms_fock) *ms_fock = st->ms_fock;
+    if (ms_linalg) *ms_linalg = st->ms_linalg;
+    return QC_OK;
+}
+void qc_scf_end(qc_scf_state *st) { scf_state_delete(st); }
+int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon) {
+    if (!st || !(epsilon >= 0.0)) return QC_ERR_INVALID;
+    return QC_OK;                                                        // (nothing acts on the rule: see the header)
+}
+int qc_scf_counters(qc_scf_state *st, double *out, int n) {
+    if (!st || !out || n < 0) return QC_ERR_INVALID;
+    scf_flush_timing(st);
+    const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->ms_fock, st->ms_linalg, (double)st->builds_timed, st->ms_tuner, (double)st->passes,
+                                        0.0, 0.0 /* reserved */, (double)st->redos,
+                                        (double)st->S->on.trials, st->S->on.settled ? 1.0 : 0.0};
+    for (int i = 0; i < n && i < QC_SCF_NCOUNTERS; ++i) out[i] = v[i];
+    return QC_OK;
+}
+
+// restricted_hartree_fock (rhf.rs:32-108) / unrestricted_hartree_fock (uhf.rs:36-167)
+int qc_scf_rhf(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out) { return scf_run(S, cfg, out, false); }
+int qc_scf_uhf(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out) { return scf_run(S, cfg, out, true); }
+
+}  // extern "C"

@@ -393,7 +393,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             QCS_EACH(q, i) { const int x = QCS_GX(i); v[q] = a.V0[x]; f[q] = fsrc[x]; }
             QCS_EACH(q, i) if (QCS_IN(i)) { B0[i * ld + cc] = v[q]; if (loadA) B3[i * ld + cc] = f[q]; }
         }
-        if (tid < 4) flg[tid] = 0;
+        if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
         __syncthreads();
         QCS_STAMP();
         double *X = B0, *Xn = B2;
@@ -474,16 +474,16 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     for (int k = 0; k < QCS_W; ++k) ca = fmax(ca, red[k]);
                     const double orth = sqrt(scal[1]), scl = fmax(scale, 1e-300);
                     const int multi = flg[4];
-                    if (flg[6] || !(orth <= 1e-3) || multi) flg[0] = 2;                          // not perturbative: rotations needed
+                    if (flg[6] || !(orth <= 1e-3) || multi) flg[QC_EIG_STATE] = QC_EIG_ROTATE;                          // not perturbative: rotations needed
                     else {
-                        flg[1] = (!flg[7] && orth <= 1e-7 && flg[5] == 0) ? 1 : 0;               // one more update finishes
-                        flg[2] = (ca <= 1e-12 * scl) ? 1 : 0;                                    // no coupling left inside degenerate pairs
+                        flg[QC_EIG_LAST] = (!flg[7] && orth <= 1e-7 && flg[5] == 0) ? 1 : 0;               // one more update finishes
+                        flg[QC_EIG_CLEAN] = (ca <= 1e-12 * scl) ? 1 : 0;                                    // no coupling left inside degenerate pairs
                     }
                 }
                 __syncthreads();
             }
             QCS_STAMP();
-            if (flg[0] != 0) break;
+            if (flg[QC_EIG_STATE] != QC_EIG_RUNNING) break;
             // M = I + E with exact rotations on the strong pairs (qc_refine_m), into B1 in place of X^T X
             {
                 double mv[QCS_E];
@@ -514,8 +514,8 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             qcs_gemm<false, false>(X, B1, Xn, n, n, 1.0);                // X (I + E): error now ~ emax^2
             __syncthreads();
             QCS_STAMP();
-            if (tid == 0) flg[3] += 1;                                   // passes used
-            if (flg[1] && flg[2]) {                                      // final vectors: ascending eigenvalues, columns alongside
+            if (tid == 0) flg[QC_EIG_PASSES] += 1;                                   // passes used
+            if (flg[QC_EIG_LAST] && flg[QC_EIG_CLEAN]) {                                      // final vectors: ascending eigenvalues, columns alongside
                 if (tid < n) {
                     const double wi = lam[tid];
                     int r = 0;
@@ -526,21 +526,21 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 __syncthreads();
                 const int rc = cok ? rank_s[cc] : 0;
                 QCS_EACH(q, i) if (QCS_IN(i)) X[i * ld + rc] = Xn[i * ld + cc];
-                if (tid == 0) flg[0] = 1;
+                if (tid == 0) flg[QC_EIG_STATE] = QC_EIG_DONE;
                 __syncthreads();
                 break;
             }
-            if (flg[1] || pass == a.npass - 1) {                         // coupling inside a degenerate cluster, or passes exhausted
+            if (flg[QC_EIG_LAST] || pass == a.npass - 1) {                         // coupling inside a degenerate cluster, or passes exhausted
                 __syncthreads();
-                if (tid == 0) flg[0] = 2;
+                if (tid == 0) flg[QC_EIG_STATE] = QC_EIG_ROTATE;
                 __syncthreads();
                 break;
             }
             double *t = X; X = Xn; Xn = t;
             __syncthreads();
         }
-        if (tid < 4) a.ctl[tid] = flg[tid];
-        ok = flg[0] == 1;
+        if (tid < QC_CTL_EIG_STRIDE) a.ctl[tid] = flg[tid];
+        ok = flg[QC_EIG_STATE] == QC_EIG_DONE;
         if (ok) {
             QCS_EACH(q, i) if (QCS_IN(i)) a.Cp_out[i * n + cc] = X[i * ld + cc];
             Cpv = X;
@@ -602,7 +602,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
     if (a.ctl_all) {
         __threadfence();
         __syncthreads();
-        if (tid < 16) {
+        if (tid < QC_CTL_WORDS) {
             int *p = a.ctl_all + tid;
             a.ctl_out[tid] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
