@@ -6,33 +6,15 @@ import numpy as np
 import pytest
 
 from conftest import data
+from synthetic_systems import H, check_terms as _check_terms, displaced as _displaced, rand_sym as _rand_sym
 
 pytestmark = pytest.mark.gpu
-
-H = 1e-3
-
-
-def _displaced(mol, atom, axis, d):
-    import qchem_rs_amd as q
-    atoms = [q.Atom(a.ordinal, list(a.position)) for a in mol.atoms]
-    atoms[atom].position[axis] += d
-    m = q.MolecularSystem.from_atoms(atoms, _basis_of(mol))
-    return m
-
-
-_BASES = {}
-
-
-def _basis_of(mol):
-    return _BASES[id(mol)]
 
 
 def _load(mol, basis, basis_path=None):
     import qchem_rs_amd as q
     b = q.BasisSet.load(basis_path or data("basis", basis + ".json"))
-    m = q.MolecularSystem.load(data("mol", mol + ".json"), b)
-    _BASES[id(m)] = b
-    return m
+    return q.MolecularSystem.load(data("mol", mol + ".json"), b)
 
 
 def _cart_basis(tmp_path):
@@ -44,28 +26,6 @@ def _cart_basis(tmp_path):
     f = tmp_path / "cc-pVTZ-cart.json"
     f.write_text(json.dumps(b))
     return str(f)
-
-
-def _term_energies(m, Pt, Pa, Pb, W):
-    """[Vnn, core, overlap, two-electron] of fixed AO densities, from the oracle's integrals at geometry m"""
-    from oracle.oracle import Oracle
-    o = Oracle(m)
-    I = o.eri()
-    e2 = 0.5 * (np.einsum("mnls,mn,ls->", I, Pt, Pt, optimize=True) - np.einsum("mnls,ml,ns->", I, Pa, Pa, optimize=True)
-                - np.einsum("mnls,ml,ns->", I, Pb, Pb, optimize=True))
-    return np.array([o.nuclear_repulsion(), np.sum(Pt * (o.kinetic() + o.nuclear())), -np.sum(W * o.overlap()), e2])
-
-
-def _fd_terms(m, coord, Pt, Pa, Pb, W):
-    atom, axis = coord
-    f = {k: _term_energies(_displaced(m, atom, axis, k * H), Pt, Pa, Pb, W) for k in (-2, -1, 1, 2)}
-    return (f[-2] - 8 * f[-1] + 8 * f[1] - f[2]) / (12 * H)
-
-
-def _rand_sym(n, seed, scale=0.1):
-    rng = np.random.default_rng(seed)
-    A = rng.standard_normal((n, n)) * scale
-    return 0.5 * (A + A.T)
 
 
 def _converged(s, uhf=False, na=0, nb=0, eps=1e-10, maxit=1000):
@@ -86,18 +46,6 @@ def _rhf_pw(st):
     Cm, e = st.coefficients(0), st.orbital_energies(0)
     Co = Cm[:, :nocc]
     return st.density(0), 2.0 * (Co * e[:nocc]) @ Co.T
-
-
-def _check_terms(s, m, coords, Pt, Pa, Pb, W, nspin):
-    if nspin == 1:
-        t = np.array(s.gradient(Pt, W))
-    else:
-        t = np.array(s.gradient(Pa, W, Db=Pb))
-    for c in coords:
-        fd = _fd_terms(m, c, Pt, Pa, Pb, W)
-        for k in range(4):
-            an = t[k][c[0], c[1]]
-            assert abs(an - fd[k]) <= 1e-9 * max(1.0, abs(fd[k])), (c, k, an, fd[k])
 
 
 SYSTEMS = [("STO-3G", None, "all"), ("6-31G_st_st", None, "all"), ("cc-pVDZ", None, "all"), ("cc-pVTZ", None, "few"), ("cc-pVTZ", "cart", "few")]

@@ -8,7 +8,8 @@ different restatement of the published formulas, used to pin the C oracle:
   * real solid harmonics for d/f/g from explicit textbook polynomials (the oracle uses the general closed formula),
   * per-function normalisation by numerical self-overlap,
   * a numpy SCF loop following SURVEY.md App. A with numpy.linalg.eigh.
-Run:  python tools/gen_golden.py      (about a minute; pure Python)
+Run:  python tools/gen_golden.py      (about a minute; pure Python.  `python tools/gen_golden.py skew` writes
+      skew_quartets_golden.json alone)
 """
 import functools
 import itertools
@@ -192,7 +193,10 @@ def eri_block(sa, sb, sc, sd):
 
 def build(mol, basis):
     b = BasisSet.load(os.path.join(ROOT, "data/basis", basis + ".json"))
-    s = MolecularSystem.load(os.path.join(ROOT, "data/mol", mol + ".json"), b)
+    return build_system(MolecularSystem.load(os.path.join(ROOT, "data/mol", mol + ".json"), b))
+
+
+def build_system(s):
     shells, off, pos = [], [], 0
     k = 0
     for ia, L, pure, npr in zip(s.shell_atom, s.shell_L, s.shell_pure, s.shell_nprim):
@@ -272,9 +276,71 @@ def rhf(s, S, T, V, I, eps, max_it=100):
     return None
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/golden/skew_quartets_golden.json: quartets and pairs in general position (tests/synthetic_systems.py) - shells on four
+# distinct centres that share no coordinate, so that no component of P - Q vanishes and every R_tuv of orders 9..12 carries weight -
+# and f quartets at a Boys argument beyond the tabulated range.  A Cartesian (ff|ff) block alone has 10^4 elements, so an ERI block is
+# stored as a strided sample of at most SKEW_SAMPLE elements (stride coprime to every dimension of the block: the sample walks
+# through all index residues) plus SKEW_SIGNS sums of the WHOLE block under seeded +-1 signs: a single wrong element moves every sum by
+# its full error, an error pattern e moves a sum by |e|_2 in the mean.  One-electron blocks are stored whole.
+SKEW_SAMPLE = 192
+SKEW_SIGNS = 4
+SKEW_T = 59.0          # the Boys argument of the far() quartets: beyond the tabulated range
+
+
+def skew_stride(shape):
+    n = int(np.prod(shape))
+    k = max(1, -(-n // SKEW_SAMPLE))
+    while any(math.gcd(k, d) != 1 for d in shape if d > 1) and k > 1:
+        k += 1
+    return k
+
+
+def skew_block(shells, quartet):
+    from synthetic_systems import skew_signs
+    blk = eri_block(*(shells[i] for i in quartet))
+    flat = blk.reshape(-1)
+    stride = skew_stride(blk.shape)
+    return dict(shells=list(map(int, quartet)), L=[shells[i].L for i in quartet], shape=list(blk.shape), stride=stride,
+                values=flat[::stride].tolist(), signed_sums=[float(np.dot(skew_signs(flat.size, k), flat)) for k in range(SKEW_SIGNS)])
+
+
+def main_skew(out_dir):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import synthetic_systems as syn
+    gold = {"_generator": "tools/gen_golden.py (independent numpy/scipy implementation; NOT reference output)",
+            "sample": SKEW_SAMPLE, "signs": SKEW_SIGNS}
+    sh = lambda atom, L: 4 * atom + L           # tetra() and far(): one s, p, d, f shell per atom, in that order
+    for name, pure in (("tetra-pure", True), ("tetra-cart", False)):
+        s, shells, off, n, atoms = build_system(syn.tetra(pure, 1)[0])
+        quartets = [(sh(0, 3), sh(1, 3), sh(2, 3), sh(3, 3)), (sh(0, 3), sh(1, 2), sh(2, 3), sh(3, 3)),
+                    (sh(0, 3), sh(1, 1), sh(2, 2), sh(3, 3)), (sh(0, 2), sh(1, 2), sh(2, 2), sh(3, 2)),
+                    (sh(0, 3), sh(1, 0), sh(2, 1), sh(3, 0)), (sh(0, 1), sh(1, 1), sh(2, 1), sh(3, 1))]
+        blocks = []
+        for qt in quartets:
+            blocks.append(skew_block(shells, qt))
+            print(name, "quartet", qt, blocks[-1]["L"], "stride", blocks[-1]["stride"], flush=True)
+        oneel = []
+        for a, b in ((sh(0, 3), sh(1, 3)), (sh(0, 3), sh(2, 2)), (sh(1, 2), sh(3, 1))):
+            ss, tt, vv = one_electron_block(shells[a], shells[b], atoms)
+            oneel.append(dict(shells=[int(a), int(b)], S=ss.tolist(), T=tt.tolist(), V=vv.tolist()))
+        gold[name] = dict(n=n, eri_blocks=blocks, one_electron_blocks=oneel)
+    m = syn.far(syn.far_distance(SKEW_T))[0]
+    s, shells, off, n, atoms = build_system(m)
+    blocks = [skew_block(shells, qt) for qt in ((sh(0, 3), sh(0, 3), sh(1, 3), sh(1, 3)), (sh(0, 2), sh(0, 3), sh(1, 3), sh(1, 2)))]
+    gold["far"] = dict(n=n, boys_argument=syn.far_boys_argument(m), eri_blocks=blocks)
+    path = os.path.join(out_dir, "skew_quartets_golden.json")
+    with open(path, "w") as f:
+        json.dump(gold, f)
+    print("written", path)
+
+
 def main():
     out_dir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
+    main_skew(out_dir)
+    if sys.argv[1:] == ["skew"]:                 # (the skew file alone: seconds instead of a minute)
+        return
     gold = {"_generator": "tools/gen_golden.py (independent numpy/scipy implementation; NOT reference output)"}
     # Boys
     xs = [0.0, 1e-7, 0.003, 0.5, 1.0, 2.7, 9.9, 17.0, 25.0, 34.9, 35.1, 50.0, 120.0, 1000.0]
