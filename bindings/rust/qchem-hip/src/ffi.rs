@@ -42,6 +42,24 @@ pub struct QcMp2Output {
     pub reserved: [i32; 7],
 }
 
+/// In / out block of `qc_scf_stability`: set kind, nroots (1..8), tol (0: 1e-6), max_iterations (0: 100), zero the rest.
+#[repr(C)]
+pub struct QcStability {
+    pub kind: i32,
+    pub nroots: i32,
+    pub max_iterations: i32,
+    pub reserved0: i32,
+    pub tol: f64,
+    pub eigenvalues: [f64; 8],
+    pub residuals: [f64; 8],
+    pub nconverged: i32,
+    pub iterations: i32,
+    pub builds: i32,
+    pub reserved1: i32,
+    pub ms_total: f64,
+    pub ms_builds: f64,
+}
+
 pub const QC_OK: c_int = 0;
 pub const QC_NOT_CONVERGED: c_int = 1;
 pub const QC_DIIS_SINGULAR: c_int = 2;
@@ -89,6 +107,17 @@ extern "C" {
     pub fn qc_scf_gradient(st: *mut QcScfState, grad: *mut f64) -> c_int;
     /// Phase times (ms) of the handle's last gradient: transform, one-electron, two-electron, sum.
     pub fn qc_gradient_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
+    /// Length of a stability vector: RHF o*v (kinds 0 singlet, 1 triplet); UHF o_a*v_a + o_b*v_b (kind 0), alpha block first, x[i*v + a].
+    pub fn qc_scf_stability_dim(st: *mut QcScfState, kind: c_int) -> c_int;
+    /// Lowest eigenpairs of the orbital Hessian (A+B) at the state's last orbitals; vectors: null or nroots x dim.  The state is left as it was.
+    pub fn qc_scf_stability(st: *mut QcScfState, io: *mut QcStability, vectors: *mut f64) -> c_int;
+    /// Densities (n*n per spin) and electronic energy of the determinant rotated along x; angle <= 0: the library's ladder of angles.
+    pub fn qc_scf_rotated_density(st: *mut QcScfState, kind: c_int, x: *const f64, angle: f64, da: *mut f64, db: *mut f64,
+                                  energy: *mut f64) -> c_int;
+    /// qc_scf_begin_rhf / qc_scf_begin_uhf from the caller's densities (the convention of qc_scf_density) instead of the Hueckel guess.
+    pub fn qc_scf_begin_rhf_from(sys: *mut QcSystem, d: *const f64, out: *mut *mut QcScfState) -> c_int;
+    pub fn qc_scf_begin_uhf_from(sys: *mut QcSystem, n_alpha: c_int, n_beta: c_int, da: *const f64, db: *const f64,
+                                 out: *mut *mut QcScfState) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

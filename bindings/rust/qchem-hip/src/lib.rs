@@ -112,3 +112,15 @@ pub fn restricted_hartree_fock_stepwise(system: &FlatSystem, config: &HartreeFoc
     unsafe { ffi::qc_scf_end(st) };
     result
 }
+
+/// Lowest eigenvalue of the real orbital Hessian (A+B) of a state that has done at least one pass (`qc_scf_stability`): kind 0 = RHF
+/// singlet / UHF internal, 1 = RHF -> UHF.  Negative: the determinant is a saddle of the HF functional.  None on any error or when the
+/// Davidson iteration runs out.  The state is left as it was.
+pub fn lowest_hessian_eigenvalue(st: *mut ffi::QcScfState, kind: i32) -> Option<f64> {
+    let mut io = ffi::QcStability { kind, nroots: 1, max_iterations: 0, reserved0: 0, tol: 0.0, eigenvalues: [0.0; 8], residuals: [0.0; 8],
+                                    nconverged: 0, iterations: 0, builds: 0, reserved1: 0, ms_total: 0.0, ms_builds: 0.0 };
+    match unsafe { ffi::qc_scf_stability(st, &mut io, null_mut()) } {
+        ffi::QC_OK => Some(io.eigenvalues[0]),
+        _ => None,
+    }
+}

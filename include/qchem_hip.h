@@ -206,6 +206,44 @@ int qc_scf_gradient(qc_scf_state *st, double *grad);
  * densities) + Cartesian transform, one-electron terms, two-electron term, sum. */
 int qc_gradient_timings(const qc_system *sys, double *ms4);
 
+/* ---- wave-function stability (after SCF, not in the reference).  The lowest eigenvalues of the real orbital Hessian (A + B) at the state's
+ * last C and orbital energies (what qc_scf_coefficients / qc_scf_orbital_energies report), by a Davidson iteration on the device whose
+ * Hessian-vector product is one direct Fock build per trial vector (always the direct build, whatever qc_set_fock_mode says; no n^4
+ * storage).  A negative eigenvalue: the state is a saddle of the HF functional, the eigenvector points downhill.  The diagonal uses the
+ * canonical-orbital formula e_a - e_i: at an unconverged state the result is that formula at the current orbitals, as for the gradient.
+ *   kind 0  RHF state: singlet (real RHF -> real RHF) instabilities;  UHF state: internal (real UHF -> real UHF) instabilities
+ *   kind 1  RHF state only: triplet (RHF -> UHF) instabilities
+ * A vector has qc_scf_stability_dim entries: RHF o*v; UHF o_a*v_a + o_b*v_b, alpha block first; each block laid out x[i*v + a] (i occupied,
+ * a virtual, both counted from 0 in the order of the orbital energies); |x| = 1 over the whole vector.
+ * In:  kind; nroots 1..8 (and <= dim); tol: residual 2-norm every root must reach (0: 1e-6); max_iterations (0: 100).
+ * Out: eigenvalues ascending, residual norms, roots converged, iterations, Fock builds, wall time of the call and of its builds (ms).
+ * QC_NOT_CONVERGED when the iterations run out (the outputs are filled with the best estimates).  QC_ERR_INVALID: null pointers, bad
+ * nroots / kind, kind 1 on a UHF state, a state before its first qc_scf_iterate, dim = 0 - all checked before the device is touched.
+ * QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator.  Bitwise reproducible from call to call and across fresh handles.
+ * The state is left exactly as it was: qc_scf_iterate may be called again and gives what it would have given. */
+typedef struct {
+    int32_t kind, nroots, max_iterations, reserved0;
+    double tol;
+    double eigenvalues[8], residuals[8];
+    int32_t nconverged, iterations, builds, reserved1;
+    double ms_total, ms_builds;
+} qc_stability;
+int qc_scf_stability_dim(qc_scf_state *st, int kind);                   /* length of a vector; QC_ERR_INVALID for a bad kind */
+int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors /* nullable: nroots x dim doubles on the host */);
+
+/* The determinant rotated along x (a vector of qc_scf_stability): C' = C exp(theta kappa), kappa_ai = x_ia = -kappa_ia in the MO basis - an
+ * exact orthogonal rotation for any theta.  Da, Db: n*n each on the host, C_occ' C_occ'^T per spin (no factor 2; an RHF state fills both).
+ * RHF kind 0 rotates both spins by theta, RHF kind 1 alpha by +theta and beta by -theta.  angle > 0: theta in radians; angle <= 0: the
+ * library evaluates the energy at theta = +-0.1 * 2^k, k = 0..4 (at most ten Fock builds) and returns the lowest.  energy (nullable): the
+ * electronic energy of the returned determinant.  Errors as qc_scf_stability; the state is left exactly as it was. */
+int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double angle, double *Da, double *Db, double *energy);
+
+/* qc_scf_begin_rhf / qc_scf_begin_uhf with the caller's densities (host, n*n, in the convention of qc_scf_density: the RHF density carries
+ * the factor 2) in place of the Hueckel guess: DIIS windows empty, first eigensolve cold.  Null densities are QC_ERR_INVALID (checked
+ * before the device is touched). */
+int qc_scf_begin_rhf_from(qc_system *sys, const double *D, qc_scf_state **out);
+int qc_scf_begin_uhf_from(qc_system *sys, int n_alpha, int n_beta, const double *Da, const double *Db, qc_scf_state **out);
+
 /* ---- Fock mode of the SCF drivers on this handle.  0 (default): direct - quartets are evaluated and digested every pass.
  * 1: stored - the reference's own conventional algorithm with the tensor resident in HBM: molint::eri once (rhf.rs:45),
  * electron_terms (rhf.rs:58-62), then one streaming GEMV per pass (rhf.rs:152-167 / uhf.rs:216-226).  Needs ~18 n^4 bytes

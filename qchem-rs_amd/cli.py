@@ -10,7 +10,11 @@ Three additions, all opt-in:
   * `--mp2 [--frozen-core N]` adds the MP2 correlation energy of the converged determinant after the reference's lines (the SCF
     then runs pass by pass through hf.ScfStepper; its lines are those of the run without the flag);
   * `--gradient` adds the analytic nuclear gradient of the converged determinant (Eh/bohr), one line per atom - index, Z, gx, gy,
-    gz - after the reference's lines and any MP2 lines; `--json` then carries a "gradient" array.
+    gz - after the reference's lines and any MP2 lines; `--json` then carries a "gradient" array;
+  * `--stability` adds the lowest eigenvalue of the orbital Hessian of the converged determinant (rhf: triplet and singlet kind; uhf:
+    internal) and a `wave function: stable` / `unstable` line; `--json` then carries a "stability" object;
+  * `--follow` runs hf.stabilize instead: converge, follow the lowest negative eigenvalue, converge again - one `cycle` line each - and
+    prints the final determinant's lines (those of uhf once an rhf run has followed a triplet instability); `--json` carries "follow".
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -75,6 +79,8 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--frozen-core", type=int, default=None, metavar="N",
                        help="leave the lowest N orbitals of each spin out of the MP2 sums (requires --mp2)")
         s.add_argument("--gradient", action="store_true", help="also print the analytic nuclear gradient (Eh/bohr) of the converged determinant")
+        s.add_argument("--stability", action="store_true", help="also print the lowest eigenvalue(s) of the orbital Hessian and whether the determinant is a minimum")
+        s.add_argument("--follow", action="store_true", help="follow instabilities downhill until the determinant is stable (at most 8 cycles)")
     return p
 
 
@@ -85,6 +91,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--frozen-core requires --mp2")
     if args.frozen_core is not None and args.frozen_core < 0:
         p.error("--frozen-core must not be negative")
+    if args.follow and (args.mp2 or args.gradient):
+        p.error("--follow cannot be combined with --mp2 or --gradient")
     return args
 
 
@@ -101,6 +109,57 @@ def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
 def _print_gradient(system: MolecularSystem, g) -> None:
     for i, (atom, row) in enumerate(zip(system.atoms, g)):
         print("%d %d %.10f %.10f %.10f" % (i, atom.ordinal, row[0], row[1], row[2]))
+
+
+STABILITY_THRESHOLD = 1e-5        # eigenvalues above -threshold count as stable (exact zero modes come out as +-1e-9)
+KIND_NAME = {(False, 0): "singlet", (False, 1): "triplet", (True, 0): "internal"}
+
+
+def _stability(st, uhf: bool) -> dict:
+    """The lowest eigenvalue of every kind the state has (hf.ScfStepper.stability)."""
+    ev = {}
+    for kind in ((0,) if uhf else (1, 0)):
+        if st.stability_dim(kind) > 0:
+            ev[KIND_NAME[(uhf, kind)]] = float(st.stability(kind=kind, nroots=1).eigenvalues[0])
+    return {"eigenvalues": ev, "stable": all(v >= -STABILITY_THRESHOLD for v in ev.values()), "threshold": STABILITY_THRESHOLD}
+
+
+def _print_stability(stab: dict) -> None:
+    for name, v in stab["eigenvalues"].items():
+        print("stability %s: lowest eigenvalue %.8f" % (name, v))
+    print("wave function: " + ("stable" if stab["stable"] else "unstable"))
+
+
+def run_follow(args, uhf: bool, n_alpha: int = 0, n_beta: int = 0) -> int:
+    basis = BasisSet.load(args.basis_set)
+    system = MolecularSystem.load(args.molecule, basis)
+    start = time.perf_counter()
+    res = hf.stabilize(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon), n_alpha, n_beta, threshold=STABILITY_THRESHOLD, uhf=uhf)
+    elapsed = time.perf_counter() - start
+    if res is None:
+        return _not_converged()
+    for k, (e, ev, kind) in enumerate(res.history):
+        print("cycle %d: electronic energy %.9f, lowest eigenvalue %.8f" % (k, e, ev))
+    out = res.output
+    now_uhf = isinstance(out, hf.UnrestrictedHartreeFockOutput)
+    print("hartree fock converged after %d iterations and %s" % (out.iterations, fmt_duration(elapsed, None if now_uhf else 2)))
+    print("electronic energy: " + fmt_f(out.electronic_energy))
+    print("nuclear repulsion energy: " + fmt_f(out.nuclear_repulsion))
+    print("hartree fock energy: " + fmt_f(out.total_energy()))
+    if now_uhf:
+        print("orbital energies alpha spin:   " + fmt_vec(out.orbital_energies_alpha))
+        print("orbital energies beta spin: " + fmt_vec(out.orbital_energies_beta))
+        print("<S^2>: " + fmt_f(res.spin_square))
+    else:
+        print("orbital energies: " + fmt_vec(out.orbital_energies))
+    print("wave function: " + ("stable" if res.stable else "unstable"))
+    if args.json:
+        doc = {"method": "uhf" if now_uhf else "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
+               "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(), "seconds": elapsed,
+               "follow": {"history": [{"electronic_energy": e, "lowest_eigenvalue": ev, "kind": kind} for e, ev, kind in res.history],
+                          "stable": res.stable, "spin_square": res.spin_square, "threshold": STABILITY_THRESHOLD}}
+        print(json.dumps(doc))
+    return 0
 
 
 def occupations(n_electrons_neutral: int, charge: int, multiplicity: int) -> Tuple[int, int]:
@@ -123,12 +182,18 @@ def _not_converged() -> int:
 
 
 def run_rhf(args) -> int:
+    if args.follow:
+        return run_follow(args, False)
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = grad = None
+    mp2 = grad = stab = None
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.gradient:
+    if args.stability:
+        res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
+                                                             st.gradient() if args.gradient else None, _stability(st, False)))
+        out, (mp2, grad, stab) = res if res is not None else (None, (None, None, None))
+    elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
     elif args.mp2:
@@ -148,6 +213,8 @@ def run_rhf(args) -> int:
         _print_mp2(mp2, out.total_energy())
     if grad is not None:
         _print_gradient(system, grad)
+    if stab is not None:
+        _print_stability(stab)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -156,6 +223,8 @@ def run_rhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if stab is not None:
+            doc["stability"] = stab
         print(json.dumps(doc))
     return 0
 
@@ -167,9 +236,11 @@ def run_uhf(args) -> int:
     n_alpha = n_beta = 0
     if extension:
         n_alpha, n_beta = occupations(system.n_electrons, args.charge, args.spin_multiplicity)
+    if args.follow:
+        return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
-    s2 = mp2 = grad = None
-    if not extension and not args.mp2 and not args.gradient:
+    s2 = mp2 = grad = stab = None
+    if not extension and not args.mp2 and not args.gradient and not args.stability:
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
@@ -188,6 +259,8 @@ def run_uhf(args) -> int:
                         mp2 = st.mp2(args.frozen_core or 0)
                     if args.gradient:
                         grad = st.gradient()
+                    if args.stability:
+                        stab = _stability(st, True)
                     break
         finally:
             st.close()
@@ -207,6 +280,8 @@ def run_uhf(args) -> int:
         _print_mp2(mp2, out.total_energy())
     if grad is not None:
         _print_gradient(system, grad)
+    if stab is not None:
+        _print_stability(stab)
     if args.json:
         doc = {"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -217,6 +292,8 @@ def run_uhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if stab is not None:
+            doc["stability"] = stab
         print(json.dumps(doc))
     return 0
 

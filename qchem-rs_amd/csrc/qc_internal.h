@@ -283,6 +283,14 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
 int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *dW, double *terms3, double *ms);
 int qc_gradient_w_device(qc_system *S, int nspin, const double *dC, const double *dEps, const int *nocc, double *dW);
 void qc_nuclear_gradient(const qc_system *S, double *g);
+// stability analysis (qc_stability.hip).  dim: length of a vector.  device: the Davidson iteration for the lowest eigenpairs of (A + B) at the
+// orbitals dC / energies dEps (nspin blocks, device); io's inputs are checked by the caller.  rotated_density: the determinant rotated along
+// x (host) and its energy (dH: core Hamiltonian, device).  Both run direct Fock builds on the handle: the caller saves and restores what a
+// prepared build of an SCF state left there (qc_scf.cpp, FockPrepSave).
+int qc_stability_dim(int n, bool uhf, const int *nocc);
+int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_stability *io, double *vectors);
+int qc_rotated_density_device(qc_system *S, bool uhf, int kind, const int *nocc, const double *dC, const double *dH, const double *x, double angle,
+                              double *hDa, double *hDb, double *energy);
 int qc_schwarz_device(qc_system *S);     // fills pairQ / imax from the (P|P) quartets, then screens the work lists
 // fixed-point scale of a build from its densities: out[0] = 2^S, out[1] = 2^-S, S = min(QC_FX_MAXBITS, 60 - ceil(log2(4 imax sum|D|)))
 void qc_fx_scale(hipStream_t st, int n, const double *Da, const double *Db /*nullable*/, double imax, double *out);

@@ -315,7 +315,8 @@ static void scf_state_delete(qc_scf_state *st) {
     if (S && --S->live_states == 0 && S->zombie) qc_system_free(S);
 }
 
-static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out) {
+// (hDa / hDb non-null: the caller's densities, host, in place of the Hueckel guess - qc_scf_begin_*_from)
+static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out, const double *hDa = nullptr, const double *hDb = nullptr) {
     if (!S || !out) return QC_ERR_INVALID;
     const double t0 = now_ms();
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
@@ -352,8 +353,11 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     lap("state buffers");
     if ((rc = scf_setup(S, st->W, h_eht)) != QC_OK) return rc;           // rhf.rs:41-49
     lap("S, T, V, X = S^-1/2");
-    for (int s = 0; s < nspin; ++s)                                       // rhf.rs:50 / uhf.rs:60-63
-        if ((rc = huckel_density(S, st->W, h_eht, st->nocc[s], uhf ? 1.0 : 2.0, st->D[s].p)) != QC_OK) return rc;
+    for (int s = 0; s < nspin; ++s) {                                     // rhf.rs:50 / uhf.rs:60-63
+        const double *given = s == 0 ? hDa : hDb;
+        if (given) QC_HIP_CHECK(hipMemcpyAsync(st->D[s].p, given, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+        else if ((rc = huckel_density(S, st->W, h_eht, st->nocc[s], uhf ? 1.0 : 2.0, st->D[s].p)) != QC_OK) return rc;
+    }
     lap("Hueckel guess");
     if (S->fock_mode == 1) {
         // the reference's conventional SCF: ERI tensor once (rhf.rs:45), antisymmetrised copy (rhf.rs:58-62), dense
@@ -770,6 +774,79 @@ int qc_scf_gradient(qc_scf_state *st, double *grad) {
     S->grad_ms[0] += pw;                                                    // (phase 0: P/W build + Cartesian transform)
     for (int k = 0; k < na3; ++k) grad[k] = ((t[k] + t[na3 + k]) + t[2 * na3 + k]) + t[3 * na3 + k];
     return QC_OK;
+}
+// What a direct Fock build outside the SCF loop overwrites on the handle, saved and put back around it: the fixed-point unit (the
+// one-workgroup Roothaan path leaves the unit of the NEXT pass's build there, SmallTail::fxs_out), the UHF density sum of a prepared
+// build, and the flags that let the next pass's build skip its preliminaries.  (The accumulator planes need nothing: every build's
+// closing fold leaves them zero, whatever its layout.)  With this a later qc_scf_iterate is bit for bit what it would have been.
+namespace {
+struct FockPrepSave {
+    qc_system *S;
+    DevBuf fxs, Dj;
+    bool prepared, gt_clean, prep_enqueued;
+    int gt_clean_nspin;
+    const double *prep_Da, *prep_Db;
+    const void *prep_owner;
+    explicit FockPrepSave(qc_system *S_) : S(S_), prepared(S_->prepared), gt_clean(S_->gt_clean), prep_enqueued(S_->prep_enqueued),
+        gt_clean_nspin(S_->gt_clean_nspin), prep_Da(S_->prep_Da), prep_Db(S_->prep_Db), prep_owner(S_->prep_owner) {}
+    int save() {
+        const size_t nn = (size_t)S->nbasis * S->nbasis;
+        if (fxs.alloc(2) != QC_OK || Dj.alloc(nn) != QC_OK) return QC_ERR_HIP;
+        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(fxs.p, S->d_fxs, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(Dj.p, S->d_Dj, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        return QC_OK;
+    }
+    int restore() {
+        const size_t nn = (size_t)S->nbasis * S->nbasis;
+        QC_HIP_CHECK(hipMemcpyAsync(S->d_fxs, fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(S->d_Dj, Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+        // (a build that ran in between left the planes clean for ITS layout; the saved flags speak of the state's layout, which is zero too)
+        S->prepared = prepared; S->gt_clean = gt_clean && S->gt_clean; S->gt_clean_nspin = gt_clean_nspin; S->prep_enqueued = prep_enqueued;
+        S->prep_Da = prep_Da; S->prep_Db = prep_Db; S->prep_owner = prep_owner;
+        return QC_OK;
+    }
+};
+}  // namespace
+
+int qc_scf_stability_dim(qc_scf_state *st, int kind) {
+    if (!st || kind < 0 || kind > (st->uhf ? 0 : 1)) return QC_ERR_INVALID;
+    return qc_stability_dim(st->S->nbasis, st->uhf, st->nocc);
+}
+int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors) {
+    if (!st || !io || st->passes == 0) return QC_ERR_INVALID;
+    if (io->kind < 0 || io->kind > (st->uhf ? 0 : 1) || io->nroots < 1 || io->nroots > 8 || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    const int dim = qc_stability_dim(S->nbasis, st->uhf, st->nocc);
+    if (dim <= 0 || io->nroots > dim) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    FockPrepSave keep(S);
+    int rc = keep.save();
+    if (rc != QC_OK) return rc;
+    rc = qc_stability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, vectors);   // (reads Cs / ws, writes nothing of the state)
+    const int rc2 = keep.restore();
+    return rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc);
+}
+int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double angle, double *Da, double *Db, double *energy) {
+    if (!st || !x || !Da || !Db || st->passes == 0 || kind < 0 || kind > (st->uhf ? 0 : 1) || angle != angle) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (qc_stability_dim(S->nbasis, st->uhf, st->nocc) <= 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    FockPrepSave keep(S);
+    int rc = keep.save();
+    if (rc != QC_OK) return rc;
+    rc = qc_rotated_density_device(S, st->uhf, kind, st->nocc, st->Cs.p, st->W.H.p, x, angle, Da, Db, energy);
+    const int rc2 = keep.restore();
+    return rc != QC_OK ? rc : rc2;
+}
+int qc_scf_begin_rhf_from(qc_system *S, const double *D, qc_scf_state **out) {
+    if (!S || !D || !out) return QC_ERR_INVALID;
+    return scf_begin(S, false, 0, 0, out, D, nullptr);
+}
+int qc_scf_begin_uhf_from(qc_system *S, int n_alpha, int n_beta, const double *Da, const double *Db, qc_scf_state **out) {
+    if (!S || !Da || !Db || !out) return QC_ERR_INVALID;
+    return scf_begin(S, true, n_alpha, n_beta, out, Da, Db);
 }
 int qc_scf_matrix(qc_scf_state *st, int which, double *out) {
     if (!st || !out || which < 0 || which > 2) return QC_ERR_INVALID;

@@ -1,0 +1,483 @@
+// qc_stability.hip - SCF wave-function stability analysis: the lowest eigenpairs of the real orbital Hessian (A + B) by a block
+// Davidson iteration whose Hessian-vector product is the direct Fock build, and the orbital rotation that follows an eigenvector.
+//
+// For real orbitals and a trial vector x^s_ia (s = spin, i occupied, a virtual, laid out x[i * v + a]) the symmetric pseudo-density
+//   D1^s = C_occ^s x^s C_virt^s^T + transpose
+// turns the two-electron part of (A + B) x into one Fock build:
+//   UHF internal      sigma^s = (e_a - e_i) x^s + [C_virt^s^T (J[D1^a + D1^b] - K[D1^s]) C_occ^s]_ai      one UHF build of (D1^a, D1^b)
+//   RHF singlet       the bracket is 2 J[D1] - K[D1]: one RHF build of 2 D1
+//   RHF -> UHF        the bracket is -K[D1]: the alpha output of one UHF build of (D1, -D1)
+// Trial vectors, sigma vectors and the correction vector live in HBM (msub + 1 rows of `dim` doubles each); the subspace matrix
+// (at most QC_STAB_MAXSUB rows) is diagonalised on the host.  Every dot product is a fixed-order reduction (a thread's elements in
+// index order, the 64 lanes of a wave by a shuffle tree, the waves in order) and the Fock build accumulates integers: a call is bitwise
+// reproducible.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "qc_internal.h"
+
+namespace {
+
+constexpr int QC_STAB_MAXROOTS = 8;
+constexpr int QC_STAB_MAXSUB = 40;            // rows of the subspace: full -> collapse onto the Ritz vectors of the requested roots
+constexpr double QC_STAB_DENOM_FLOOR = 1e-4;  // |e_a - e_i - theta| of the diagonal preconditioner is not allowed below this
+constexpr double QC_STAB_KEEP = 1e-4;         // a correction vector that loses more than this factor to the orthogonalisation is dropped
+
+double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// sum of `s` over the workgroup, the same bits in every thread: lanes by a shuffle tree, waves in index order (sh: 16 doubles)
+__device__ __forceinline__ double qc_stab_block_sum(double s, double *sh) {
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    __syncthreads();                                    // (the previous sum has been read by everybody)
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    double t = 0.0;
+    const int nw = (int)(blockDim.x >> 6);
+    for (int k = 0; k < nw; ++k) t += sh[k];
+    return t;
+}
+
+// de[i * v + a] = eps[o + a] - eps[i]
+__global__ void qc_stab_delta_kernel(int o, int v, const double *__restrict__ eps, double *__restrict__ de) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < o * v) de[e] = eps[o + e % v] - eps[e / v];
+}
+
+// pseudo-density: D = s (Q + Q^T) with Q = C_occ x C_virt^T; Dneg (nullable) = -D
+__global__ void qc_stab_symmetrize_kernel(int n, double s, const double *__restrict__ Q, double *__restrict__ D, double *__restrict__ Dneg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n) return;
+    const int r = e / n, c = e % n;
+    const double d = s * (Q[e] + Q[(size_t)c * n + r]);
+    D[e] = d;
+    if (Dneg) Dneg[e] = -d;
+}
+
+// sigma = de * x + R, R = the occupied-virtual block of the two-electron matrix
+__global__ void qc_stab_sigma_kernel(int dim, const double *__restrict__ de, const double *__restrict__ x, const double *__restrict__ R,
+                                     double *__restrict__ sg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < dim) sg[e] = fma(de[e], x[e], R[e]);
+}
+
+// M[(k0 + k) * ldm + j] = <V_j, Sg_(k0 + k)>: workgroup (j, k), 256 threads
+__global__ __launch_bounds__(256) void qc_stab_dots_kernel(int dim, const double *__restrict__ V, const double *__restrict__ Sg, int k0, int ldm,
+                                                           double *__restrict__ M) {
+    __shared__ double sh[16];
+    const int j = blockIdx.x, k = k0 + blockIdx.y;
+    const double *a = V + (size_t)j * dim, *b = Sg + (size_t)k * dim;
+    double s = 0.0;
+    for (int e = threadIdx.x; e < dim; e += 256) s = fma(a[e], b[e], s);
+    s = qc_stab_block_sum(s, sh);
+    if (threadIdx.x == 0) M[(size_t)k * ldm + j] = s;
+}
+
+// out[r * dim + e] = sum_j Y[r * ldy + j] In[j * dim + e], j < m (Ritz vectors and their sigma vectors)
+__global__ void qc_stab_lincomb_kernel(int dim, int m, int ldy, const double *__restrict__ Y, const double *__restrict__ In, double *__restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (e >= dim) return;
+    double s = 0.0;
+    for (int j = 0; j < m; ++j) s = fma(Y[(size_t)r * ldy + j], In[(size_t)j * dim + e], s);
+    out[(size_t)r * dim + e] = s;
+}
+
+// One new basis vector, one workgroup.  With m = m0 + *cnt vectors in V (m0 spanned by the Ritz coefficients y, *cnt added by earlier
+// launches of this round):
+//   src == null:  r = sum_j y_j (Sg_j - theta V_j), info[0] = |r|^2; if |r| > tol: t = r / (de - theta) with the floor on the denominator
+//   src != null:  t = src (start vectors), info[0] = |t|^2
+// then t is orthogonalised against V_0 .. V_(m-1) twice (modified Gram-Schmidt), and if it keeps more than QC_STAB_KEEP of its length and
+// the subspace has room it is normalised into row m and *cnt goes up.  info[1] = its length after the orthogonalisation (0: not added).
+// Row m of V is the work array (V has msub + 1 rows).
+__global__ __launch_bounds__(1024) void qc_stab_expand_kernel(int dim, int m0, int msub, double *__restrict__ V, const double *__restrict__ Sg,
+                                                              const double *__restrict__ y, const double *__restrict__ theta_p,
+                                                              const double *__restrict__ de, const double *__restrict__ src, double tol,
+                                                              int *cnt, double *__restrict__ info) {
+    __shared__ double sh[16];
+    const int m = m0 + *cnt;
+    double *t = V + (size_t)m * dim;
+    const double theta = theta_p ? *theta_p : 0.0;
+    double s = 0.0;
+    for (int e = threadIdx.x; e < dim; e += 1024) {
+        double r;
+        if (src) r = src[e];
+        else {
+            r = 0.0;
+            for (int j = 0; j < m0; ++j) r = fma(y[j], Sg[(size_t)j * dim + e] - theta * V[(size_t)j * dim + e], r);
+        }
+        s = fma(r, r, s);
+        t[e] = r;
+    }
+    const double rn2 = qc_stab_block_sum(s, sh);
+    if (threadIdx.x == 0) { info[0] = rn2; info[1] = 0.0; }
+    if (m >= msub || !(rn2 > 0.0) || (!src && sqrt(rn2) <= tol)) return;            // (uniform: every thread holds the same sum)
+    s = 0.0;
+    if (!src)
+        for (int e = threadIdx.x; e < dim; e += 1024) {
+            double d = de[e] - theta;
+            if (fabs(d) < QC_STAB_DENOM_FLOOR) d = d < 0.0 ? -QC_STAB_DENOM_FLOOR : QC_STAB_DENOM_FLOOR;
+            const double x = t[e] / d;
+            t[e] = x;
+            s = fma(x, x, s);
+        }
+    const double before = src ? rn2 : qc_stab_block_sum(s, sh);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j < m; ++j) {
+            const double *vj = V + (size_t)j * dim;
+            s = 0.0;
+            for (int e = threadIdx.x; e < dim; e += 1024) s = fma(t[e], vj[e], s);
+            const double c = qc_stab_block_sum(s, sh);
+            for (int e = threadIdx.x; e < dim; e += 1024) t[e] = fma(-c, vj[e], t[e]);
+        }
+    s = 0.0;
+    for (int e = threadIdx.x; e < dim; e += 1024) s = fma(t[e], t[e], s);
+    const double after = qc_stab_block_sum(s, sh);
+    if (!(after > QC_STAB_KEEP * QC_STAB_KEEP * before)) return;
+    const double inv = 1.0 / sqrt(after);
+    for (int e = threadIdx.x; e < dim; e += 1024) t[e] *= inv;
+    if (threadIdx.x == 0) { info[1] = sqrt(after); *cnt = m - m0 + 1; }
+}
+
+// eigenpairs of a small symmetric matrix on the host: cyclic Jacobi, ascending eigenvalues, vectors as the ROWS of Vr (Vr[k * m + i])
+void host_sym_eig(int m, std::vector<double> A, std::vector<double> &w, std::vector<double> &Vr) {
+    std::vector<double> V((size_t)m * m, 0.0);
+    for (int i = 0; i < m; ++i) V[(size_t)i * m + i] = 1.0;
+    for (int i = 0; i < m; ++i) for (int j = 0; j < i; ++j) A[(size_t)j * m + i] = A[(size_t)i * m + j];      // (the lower triangle counts)
+    for (int sweep = 0; sweep < 100; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) (i == j ? diag : off) += A[(size_t)i * m + j] * A[(size_t)i * m + j];
+        if (off <= 1e-32 * diag || off == 0.0) break;
+        for (int p = 0; p < m - 1; ++p)
+            for (int q = p + 1; q < m; ++q) {
+                const double apq = A[(size_t)p * m + q];
+                if (apq == 0.0) continue;
+                const double tau = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2.0 * apq);
+                const double tn = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double c = 1.0 / std::sqrt(1.0 + tn * tn), sn = tn * c;
+                for (int k = 0; k < m; ++k) {
+                    const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
+                    A[(size_t)k * m + p] = c * akp - sn * akq; A[(size_t)k * m + q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < m; ++k) {
+                    const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
+                    A[(size_t)p * m + k] = c * apk - sn * aqk; A[(size_t)q * m + k] = sn * apk + c * aqk;
+                }
+                for (int k = 0; k < m; ++k) {
+                    const double vkp = V[(size_t)k * m + p], vkq = V[(size_t)k * m + q];
+                    V[(size_t)k * m + p] = c * vkp - sn * vkq; V[(size_t)k * m + q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    std::vector<int> idx(m);
+    std::iota(idx.begin(), idx.end(), 0);
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return A[(size_t)a * m + a] < A[(size_t)b * m + b]; });
+    w.resize(m); Vr.assign((size_t)m * m, 0.0);
+    for (int k = 0; k < m; ++k) {
+        w[k] = A[(size_t)idx[k] * m + idx[k]];
+        for (int i = 0; i < m; ++i) Vr[(size_t)k * m + i] = V[(size_t)i * m + idx[k]];
+    }
+}
+
+// blocks of a vector: one per spin of a UHF state, one for an RHF state
+struct StabLayout {
+    int nblk = 1, o[2] = {0, 0}, v[2] = {0, 0}, off[2] = {0, 0}, dim = 0;
+    StabLayout(int n, bool uhf, const int *nocc) {
+        nblk = uhf ? 2 : 1;
+        for (int b = 0; b < nblk; ++b) { o[b] = nocc[b]; v[b] = n - nocc[b]; off[b] = dim; dim += o[b] * v[b]; }
+    }
+};
+
+// the Hessian-vector product: sigma = (A + B) x, one direct Fock build
+struct StabSigma {
+    qc_system *S;
+    StabLayout L;
+    bool uhf;
+    int kind;
+    const double *dC;          // nblk blocks of n x n, columns = MOs
+    const double *dDe;         // e_a - e_i, `dim` doubles
+    DevBuf P, Q, D1, G, R;
+    double ms_builds = 0.0;
+    int builds = 0;
+    StabSigma(qc_system *S_, const StabLayout &L_, bool uhf_, int kind_, const double *dC_, const double *dDe_) : S(S_), L(L_), uhf(uhf_), kind(kind_), dC(dC_), dDe(dDe_) {}
+    int alloc() {
+        const size_t n = S->nbasis, nn = n * n;
+        if (P.alloc(nn) != QC_OK || Q.alloc(nn) != QC_OK || D1.alloc(2 * nn) != QC_OK || G.alloc(2 * nn) != QC_OK || R.alloc(std::max<size_t>(L.dim, 1)) != QC_OK) return QC_ERR_HIP;
+        return QC_OK;
+    }
+    int apply(const double *dx, double *dsg) {
+        const int n = S->nbasis;
+        const size_t nn = (size_t)n * n;
+        hipStream_t st = S->stream;
+        const bool triplet = !uhf && kind == 1, rhf_build = !uhf && kind == 0;
+        for (int b = 0; b < L.nblk; ++b) {
+            const double *Cb = dC + b * nn;
+            double *Db = D1.p + b * nn;
+            if (L.o[b] == 0 || L.v[b] == 0) { QC_HIP_CHECK(hipMemsetAsync(Db, 0, nn * sizeof(double), st)); continue; }
+            qc_gemm(st, n, L.v[b], L.o[b], 1.0, Cb, n, false, dx + L.off[b], L.v[b], false, 0.0, P.p, L.v[b]);          // C_occ x
+            qc_gemm(st, n, n, L.v[b], 1.0, P.p, L.v[b], false, Cb + L.o[b], n, true, 0.0, Q.p, n);                       // (.) C_virt^T
+            hipLaunchKernelGGL(qc_stab_symmetrize_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, n, rhf_build ? 2.0 : 1.0, Q.p, Db,
+                               triplet ? D1.p + nn : nullptr);
+        }
+        const double t0 = now_ms();
+        int rc = rhf_build ? qc_fock_build_device(S, D1.p, nullptr, G.p, nullptr, false)
+                           : qc_fock_build_device(S, D1.p, D1.p + nn, G.p, G.p + nn, true);
+        if (rc != QC_OK) return rc;
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        if ((rc = qc_join_check(S)) != QC_OK) return rc;
+        qc_gate_quiet(S);
+        ms_builds += now_ms() - t0; builds += 1;
+        for (int b = 0; b < L.nblk; ++b) {
+            if (L.o[b] == 0 || L.v[b] == 0) continue;
+            const double *Cb = dC + b * nn;
+            const int ov = L.o[b] * L.v[b];
+            qc_gemm(st, n, L.v[b], n, 1.0, G.p + b * nn, n, false, Cb + L.o[b], n, false, 0.0, P.p, L.v[b]);             // G C_virt
+            qc_gemm(st, L.o[b], L.v[b], n, 1.0, Cb, n, true, P.p, L.v[b], false, 0.0, R.p + L.off[b], L.v[b]);            // C_occ^T (.)
+            hipLaunchKernelGGL(qc_stab_sigma_kernel, dim3((ov + 255) / 256), dim3(256), 0, st, ov, dDe + L.off[b], dx + L.off[b], R.p + L.off[b],
+                               dsg + L.off[b]);
+        }
+        QC_HIP_CHECK(hipGetLastError());
+        return QC_OK;
+    }
+};
+
+struct DevInts {
+    int *p = nullptr;
+    ~DevInts() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+
+int qc_stability_dim(int n, bool uhf, const int *nocc) { return StabLayout(n, uhf, nocc).dim; }
+
+// Lowest `nroots` eigenpairs of (A + B) at the orbitals dC / energies dEps (device; nblk blocks).  io: kind, nroots, tol, max_iterations
+// checked by the caller.  vectors (host, nullable): nroots x dim.
+int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_stability *io, double *vectors) {
+    const double t_begin = now_ms();
+    const int n = S->nbasis, nroots = io->nroots;
+    const StabLayout L(n, uhf, nocc);
+    const int dim = L.dim;
+    const double tol = io->tol > 0.0 ? io->tol : 1e-6;
+    const int maxit = io->max_iterations > 0 ? io->max_iterations : 100;
+    hipStream_t st = S->stream;
+    const int msub = std::min(dim, QC_STAB_MAXSUB);
+
+    // diagonal e_a - e_i, on the device and on the host (start vectors)
+    DevBuf dDe;
+    if (dDe.alloc(dim) != QC_OK) return QC_ERR_HIP;
+    for (int b = 0; b < L.nblk; ++b) {
+        const int ov = L.o[b] * L.v[b];
+        if (ov > 0) hipLaunchKernelGGL(qc_stab_delta_kernel, dim3((ov + 255) / 256), dim3(256), 0, st, L.o[b], L.v[b], dEps + (size_t)b * n, dDe.p + L.off[b]);
+    }
+    std::vector<double> de(dim);
+    QC_HIP_CHECK(hipMemcpyAsync(de.data(), dDe.p, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, st));
+    QC_HIP_CHECK(hipStreamSynchronize(st));
+
+    StabSigma sigma(S, L, uhf, io->kind, dC, dDe.p);
+    DevBuf V, Sg, Wk, dM, dY, dTheta, dInfo;
+    DevInts dCnt;
+    const size_t rows = (size_t)msub + 1;
+    if (sigma.alloc() != QC_OK || V.alloc(rows * dim) != QC_OK || Sg.alloc(rows * dim) != QC_OK || Wk.alloc(2 * (size_t)QC_STAB_MAXROOTS * dim) != QC_OK ||
+        dM.alloc((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB) != QC_OK || dY.alloc((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB) != QC_OK ||
+        dTheta.alloc(QC_STAB_MAXROOTS) != QC_OK || dInfo.alloc(2 * (QC_STAB_MAXSUB + 1)) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMalloc(&dCnt.p, sizeof(int)));
+
+    // Start vectors: unit vectors on the smallest e_a - e_i (ties: lower index first); a subspace that can hold the whole space starts as
+    // the whole space.  Unit vectors carry the symmetry of one orbital pair, and a Krylov space never leaves the symmetries it starts
+    // with - so one more start vector has a fixed pseudo-random component on every orbital pair.
+    std::vector<int> order(dim);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return de[a] < de[b]; });
+    const bool whole = dim <= QC_STAB_MAXSUB;
+    const int nunit = whole ? dim : std::min(dim, 2 * nroots);
+    const int nstart = whole ? dim : nunit + 1;
+    {
+        std::vector<double> start((size_t)nstart * dim, 0.0);
+        for (int k = 0; k < nunit; ++k) start[(size_t)k * dim + order[k]] = 1.0;
+        if (!whole) {
+            uint32_t lcg = 12345u;
+            for (int e = 0; e < dim; ++e) { lcg = lcg * 1664525u + 1013904223u; start[(size_t)nunit * dim + e] = (double)(lcg >> 8) / 8388608.0 - 1.0; }
+        }
+        // (staged behind the subspace rows: Sg is not in use yet)
+        if (nstart > (int)rows) return QC_ERR_INVALID;
+        QC_HIP_CHECK(hipMemcpyAsync(Sg.p, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
+        for (int k = 0; k < nstart; ++k)
+            hipLaunchKernelGGL(qc_stab_expand_kernel, dim3(1), dim3(1024), 0, st, dim, 0, msub, V.p, (const double *)nullptr, (const double *)nullptr,
+                               (const double *)nullptr, (const double *)nullptr, (const double *)(Sg.p + (size_t)k * dim), 0.0, dCnt.p, dInfo.p + 2 * k);
+        QC_HIP_CHECK(hipStreamSynchronize(st));      // (the staged vectors have been read before the first sigma vector overwrites them)
+    }
+    int m = 0;
+    QC_HIP_CHECK(hipMemcpy(&m, dCnt.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (m < nroots) return QC_ERR_INVALID;
+
+    std::vector<double> M((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB, 0.0), w, Y, theta(nroots, 0.0), rnorm(nroots, 0.0), info(2 * QC_STAB_MAXROOTS);
+    std::vector<double> Ysel((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB, 0.0);
+    int m_done = 0, it = 0, nconv = 0, rc = QC_OK;
+    bool converged = false;
+    for (it = 1; it <= maxit; ++it) {
+        for (int k = m_done; k < m; ++k)
+            if ((rc = sigma.apply(V.p + (size_t)k * dim, Sg.p + (size_t)k * dim)) != QC_OK) return rc;
+        // new rows of the subspace matrix: M[k][j] = <V_j, Sg_k>, j <= k
+        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sg.p, m_done, QC_STAB_MAXSUB, dM.p);
+        QC_HIP_CHECK(hipMemcpyAsync(M.data() + (size_t)m_done * QC_STAB_MAXSUB, dM.p + (size_t)m_done * QC_STAB_MAXSUB,
+                                    (size_t)(m - m_done) * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        m_done = m;
+        std::vector<double> A((size_t)m * m);
+        for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = M[(size_t)i * QC_STAB_MAXSUB + j];
+        host_sym_eig(m, A, w, Y);
+        for (int r = 0; r < nroots; ++r) {
+            theta[r] = w[r];
+            for (int j = 0; j < QC_STAB_MAXSUB; ++j) Ysel[(size_t)r * QC_STAB_MAXSUB + j] = j < m ? Y[(size_t)r * m + j] : 0.0;
+        }
+        QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemcpyAsync(dTheta.p, theta.data(), nroots * sizeof(double), hipMemcpyHostToDevice, st));
+        // the subspace is full: collapse onto the Ritz vectors of the requested roots (their sigma vectors follow by linearity)
+        if (m + nroots > msub && m > nroots && m < dim) {
+            dim3 grid((dim + 255) / 256, nroots);
+            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
+            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim);
+            QC_HIP_CHECK(hipMemcpyAsync(V.p, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+            QC_HIP_CHECK(hipMemcpyAsync(Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+            m = m_done = nroots;
+            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sg.p, 0, QC_STAB_MAXSUB, dM.p);
+            QC_HIP_CHECK(hipMemcpyAsync(M.data(), dM.p, (size_t)m * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
+            std::fill(Ysel.begin(), Ysel.end(), 0.0);
+            for (int r = 0; r < nroots; ++r) Ysel[(size_t)r * QC_STAB_MAXSUB + r] = 1.0;
+            QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        // residual | preconditioner | orthogonalisation of every requested root, one launch each; the device counts the vectors it added
+        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
+        for (int r = 0; r < nroots; ++r)
+            hipLaunchKernelGGL(qc_stab_expand_kernel, dim3(1), dim3(1024), 0, st, dim, m, msub, V.p, (const double *)Sg.p,
+                               (const double *)(dY.p + (size_t)r * QC_STAB_MAXSUB), (const double *)(dTheta.p + r), (const double *)dDe.p,
+                               (const double *)nullptr, tol, dCnt.p, dInfo.p + 2 * r);
+        int added = 0;
+        QC_HIP_CHECK(hipMemcpyAsync(info.data(), dInfo.p, 2 * nroots * sizeof(double), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipMemcpyAsync(&added, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        nconv = 0;
+        for (int r = 0; r < nroots; ++r) { rnorm[r] = std::sqrt(info[2 * r]); if (rnorm[r] <= tol) ++nconv; }
+        if (nconv == nroots) { converged = true; break; }
+        if (added == 0) break;                           // (nothing left to add: the residuals are as small as this arithmetic makes them)
+        m += added;
+    }
+    if (it > maxit) it = maxit;
+    for (int r = 0; r < QC_STAB_MAXROOTS; ++r) { io->eigenvalues[r] = r < nroots ? theta[r] : 0.0; io->residuals[r] = r < nroots ? rnorm[r] : 0.0; }
+    io->nconverged = nconv; io->iterations = it; io->builds = sigma.builds;
+    if (vectors) {
+        dim3 grid((dim + 255) / 256, nroots);
+        hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m_done, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
+        QC_HIP_CHECK(hipMemcpyAsync(vectors, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    QC_HIP_CHECK(hipGetLastError());
+    io->ms_builds = sigma.ms_builds;
+    io->ms_total = now_ms() - t_begin;
+    return converged ? QC_OK : QC_NOT_CONVERGED;
+}
+
+// ---- rotation along a vector.  In the MO basis (occupied first) kappa = [[0, -x], [x^T, 0]] with x the o x v block, so kappa_ai = x_ia.
+// exp(theta kappa) applied to the occupied columns, with x x^T = U diag(s^2) U^T:
+//   C_occ' = C_occ U cos(theta s) U^T + C_virt x^T U (sin(theta s) / s) U^T
+// - an exact orthogonal rotation for any theta.  Host arithmetic (n x o matrices); hD = C_occ' C_occ'^T.
+static void rotate_block(int n, int o, const double *C, const double *x, double theta, double *hD) {
+    const int v = n - o;
+    std::fill(hD, hD + (size_t)n * n, 0.0);
+    if (o == 0) return;
+    std::vector<double> Co((size_t)n * o);
+    for (int mu = 0; mu < n; ++mu) for (int i = 0; i < o; ++i) Co[(size_t)mu * o + i] = C[(size_t)mu * n + i];
+    if (v > 0) {
+        std::vector<double> XX((size_t)o * o, 0.0), s2, U;
+        for (int i = 0; i < o; ++i) for (int j = 0; j <= i; ++j) {
+            double t = 0.0;
+            for (int a = 0; a < v; ++a) t += x[(size_t)i * v + a] * x[(size_t)j * v + a];
+            XX[(size_t)i * o + j] = XX[(size_t)j * o + i] = t;
+        }
+        host_sym_eig(o, XX, s2, U);                          // rows of U: eigenvectors
+        // Fc = U cos U^T, Fs = U (sin / s) U^T (o x o)
+        std::vector<double> Fc((size_t)o * o, 0.0), Fs((size_t)o * o, 0.0);
+        for (int k = 0; k < o; ++k) {
+            const double sk = std::sqrt(std::max(s2[k], 0.0)), ck = std::cos(theta * sk), sn = sk > 1e-8 ? std::sin(theta * sk) / sk : theta;
+            for (int i = 0; i < o; ++i) for (int j = 0; j < o; ++j) {
+                const double uu = U[(size_t)k * o + i] * U[(size_t)k * o + j];
+                Fc[(size_t)i * o + j] += ck * uu; Fs[(size_t)i * o + j] += sn * uu;
+            }
+        }
+        // xf = x^T Fs (v x o); Co' = Co Fc + C_virt xf
+        std::vector<double> xf((size_t)v * o, 0.0), Cn((size_t)n * o, 0.0);
+        for (int a = 0; a < v; ++a) for (int i = 0; i < o; ++i) { const double xa = x[(size_t)i * v + a]; if (xa != 0.0) for (int j = 0; j < o; ++j) xf[(size_t)a * o + j] += xa * Fs[(size_t)i * o + j]; }
+        for (int mu = 0; mu < n; ++mu) {
+            double *row = &Cn[(size_t)mu * o];
+            for (int i = 0; i < o; ++i) { const double c = Co[(size_t)mu * o + i]; for (int j = 0; j < o; ++j) row[j] += c * Fc[(size_t)i * o + j]; }
+            for (int a = 0; a < v; ++a) { const double c = C[(size_t)mu * n + o + a]; for (int j = 0; j < o; ++j) row[j] += c * xf[(size_t)a * o + j]; }
+        }
+        Co.swap(Cn);
+    }
+    for (int mu = 0; mu < n; ++mu) for (int nu = 0; nu <= mu; ++nu) {
+        double t = 0.0;
+        for (int i = 0; i < o; ++i) t += Co[(size_t)mu * o + i] * Co[(size_t)nu * o + i];
+        hD[(size_t)mu * n + nu] = hD[(size_t)nu * n + mu] = t;
+    }
+}
+
+// Densities (host, per spin, n x n) of the determinant rotated along x, and its electronic energy 1/2 sum_s tr(D_s (2 H + G_s)) from one UHF
+// build.  angle <= 0: the lowest of theta = +-0.1 * 2^k, k = 0..4.
+int qc_rotated_density_device(qc_system *S, bool uhf, int kind, const int *nocc, const double *dC, const double *dH, const double *x, double angle,
+                              double *hDa, double *hDb, double *energy) {
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    const StabLayout L(n, uhf, nocc);
+    hipStream_t st = S->stream;
+    std::vector<double> C((uhf ? 2 : 1) * nn);
+    QC_HIP_CHECK(hipMemcpyAsync(C.data(), dC, C.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    QC_HIP_CHECK(hipStreamSynchronize(st));
+    DevBuf dD, dG, dE;
+    if (dD.alloc(2 * nn) != QC_OK || dG.alloc(2 * nn) != QC_OK || dE.alloc(4) != QC_OK) return QC_ERR_HIP;
+    std::vector<double> Da(nn), Db(nn);
+    auto eval = [&](double theta, double *e) -> int {
+        rotate_block(n, L.o[0], C.data(), x, theta, Da.data());
+        if (uhf) rotate_block(n, L.o[1], C.data() + nn, x + L.off[1], theta, Db.data());
+        else if (kind == 1) rotate_block(n, L.o[0], C.data(), x, -theta, Db.data());
+        else Db = Da;
+        QC_HIP_CHECK(hipMemcpyAsync(dD.p, Da.data(), nn * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemcpyAsync(dD.p + nn, Db.data(), nn * sizeof(double), hipMemcpyHostToDevice, st));
+        int rc = qc_fock_build_device(S, dD.p, dD.p + nn, dG.p, dG.p + nn, true);
+        if (rc != QC_OK) return rc;
+        for (int s = 0; s < 2; ++s) qc_energy_rms(st, n, dD.p + s * nn, dD.p + s * nn, dH, dG.p + s * nn, dE.p + 2 * s);
+        double h[4];
+        QC_HIP_CHECK(hipMemcpyAsync(h, dE.p, sizeof(h), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        if ((rc = qc_join_check(S)) != QC_OK) return rc;
+        qc_gate_quiet(S);
+        *e = h[0] + h[2];
+        return QC_OK;
+    };
+    double best_e = 0.0, best_theta = angle;
+    int rc;
+    if (angle > 0.0) { if ((rc = eval(angle, &best_e)) != QC_OK) return rc; }
+    else {
+        bool first = true;
+        const bool mirror = !uhf && kind == 1;           // (alpha by +theta and beta by -theta: the sign of theta only swaps the spins)
+        std::vector<double> keep_a, keep_b;
+        for (int k = 0; k < 5; ++k)
+            for (int sgn = 0; sgn < (mirror ? 1 : 2); ++sgn) {
+                const double theta = (sgn ? -0.1 : 0.1) * (double)(1 << k);
+                double e = 0.0;
+                if ((rc = eval(theta, &e)) != QC_OK) return rc;
+                if (first || e < best_e) { best_e = e; best_theta = theta; first = false; keep_a = Da; keep_b = Db; }
+            }
+        Da.swap(keep_a); Db.swap(keep_b);
+    }
+    (void)best_theta;
+    std::memcpy(hDa, Da.data(), nn * sizeof(double));
+    std::memcpy(hDb, Db.data(), nn * sizeof(double));
+    if (energy) *energy = best_e;
+    return QC_OK;
+}

@@ -44,7 +44,8 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_fock_profile", "qc_plan_shard_quartets", "qc_scf_begin_rhf", "qc_scf_begin_uhf", "qc_scf_iterate",
            "qc_scf_orbital_energies", "qc_scf_density", "qc_scf_spin_square", "qc_scf_timings", "qc_scf_end", "qc_fock_profile_tiers", "qc_unit_quartets", "qc_sym_eig_warm", "qc_set_fock_mode", "qc_scf_tensor_ms", "qc_set_accumulation", "qc_set_schwarz", "qc_scf_matrix", "qc_rccl_info", "qc_measure_peaks",
            "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment",
-           "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings"]
+           "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
+           "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from"]
 
 
 class QcError(RuntimeError):
@@ -82,6 +83,27 @@ class Mp2Output:
     @classmethod
     def _from(cls, o: "_Mp2Output") -> "Mp2Output":
         return cls(o.e_os, o.e_ss, o.e_corr, o.ms_tensor, o.ms_transform, o.ms_energy, int(o.n_frozen))
+
+
+class _Stability(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nroots", C.c_int32), ("max_iterations", C.c_int32), ("reserved0", C.c_int32), ("tol", C.c_double),
+                ("eigenvalues", C.c_double * 8), ("residuals", C.c_double * 8), ("nconverged", C.c_int32), ("iterations", C.c_int32),
+                ("builds", C.c_int32), ("reserved1", C.c_int32), ("ms_total", C.c_double), ("ms_builds", C.c_double)]
+
+
+@dataclass
+class StabilityOutput:
+    """qc_stability: the lowest eigenvalues of the real orbital Hessian (A + B), ascending, with their residual norms; `vectors`
+    (nroots, dim) when asked for.  converged: every root reached the tolerance."""
+    kind: int
+    eigenvalues: np.ndarray
+    residuals: np.ndarray
+    converged: bool
+    iterations: int
+    builds: int
+    ms_total: float
+    ms_builds: float
+    vectors: Optional[np.ndarray] = None
 
 
 class WorkStats(C.Structure):
@@ -162,6 +184,11 @@ def lib():
         L.qc_gradient.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.qc_scf_gradient.argtypes = [vp, _dp]
         L.qc_gradient_timings.argtypes = [vp, _dp]
+        L.qc_scf_stability_dim.argtypes = [vp, C.c_int]
+        L.qc_scf_stability.argtypes = [vp, C.POINTER(_Stability), vp]
+        L.qc_scf_rotated_density.argtypes = [vp, C.c_int, vp, C.c_double, vp, vp, C.POINTER(C.c_double)]
+        L.qc_scf_begin_rhf_from.argtypes = [vp, vp, C.POINTER(vp)]
+        L.qc_scf_begin_uhf_from.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
         _lib = L
     return _lib
 
@@ -358,13 +385,25 @@ class ScfStepper:
     """One loop-body pass per call (`qc_scf_begin_* / qc_scf_iterate / qc_scf_end`): what a host that owns the
     convergence loop binds, and what bench.py times."""
 
-    def __init__(self, system: "System", uhf: bool = False, n_alpha: int = 0, n_beta: int = 0, stop_rule: float = 0.0):
+    def __init__(self, system: "System", uhf: bool = False, n_alpha: int = 0, n_beta: int = 0, stop_rule: float = 0.0, density=None):
         """stop_rule > 0: the caller's loop ends once the reference's test holds at that epsilon (rhf.rs:94 / uhf.rs:139); told to the
-        library (qc_scf_set_stop_rule), which checks the value and otherwise ignores it."""
+        library (qc_scf_set_stop_rule), which checks the value and otherwise ignores it.
+        density: start from it instead of the Hueckel guess (qc_scf_begin_*_from) - RHF: D (n, n) in the convention of density(), the
+        factor 2 included; UHF: (D_alpha, D_beta)."""
         self.system = system
         self.uhf = uhf
         self._st = C.c_void_p()
-        if uhf:
+        if density is not None:
+            n = system.n
+            Ds = [np.ascontiguousarray(d, np.float64) for d in (density if uhf else [density])]
+            if len(Ds) != (2 if uhf else 1) or any(d.shape != (n, n) for d in Ds):
+                raise QcError("ScfStepper: density must be %s of shape (%d, %d)" % ("(D_alpha, D_beta)" if uhf else "one matrix", n, n))
+            ptr = [d.ctypes.data_as(C.c_void_p) for d in Ds]
+            if uhf:
+                _check(lib().qc_scf_begin_uhf_from(system.handle, n_alpha, n_beta, ptr[0], ptr[1], C.byref(self._st)), "qc_scf_begin_uhf_from")
+            else:
+                _check(lib().qc_scf_begin_rhf_from(system.handle, ptr[0], C.byref(self._st)), "qc_scf_begin_rhf_from")
+        elif uhf:
             _check(lib().qc_scf_begin_uhf(system.handle, n_alpha, n_beta, C.byref(self._st)), "qc_scf_begin_uhf")
         else:
             _check(lib().qc_scf_begin_rhf(system.handle, C.byref(self._st)), "qc_scf_begin_rhf")
@@ -404,6 +443,33 @@ class ScfStepper:
         """Total nuclear gradient (natoms, 3), Eh/bohr, at the state's last Roothaan step (qc_scf_gradient); the state is left as it was."""
         g = np.zeros((len(self.system.mol.atoms), 3))
         _check(lib().qc_scf_gradient(self._st, g), "qc_scf_gradient"); return g
+
+    def stability_dim(self, kind: int = 0) -> int:
+        dim = lib().qc_scf_stability_dim(self._st, int(kind))           # (a length, not a status: 3 is a valid answer)
+        if dim < 0:
+            _check(dim, "qc_scf_stability_dim")
+        return dim
+
+    def stability(self, kind: int = 0, nroots: int = 1, tol: float = 0.0, max_iterations: int = 0, vectors: bool = False) -> "StabilityOutput":
+        """Lowest eigenvalues of the orbital Hessian (A + B) at the state's last orbitals (qc_scf_stability); the state is left as it was.
+        kind 0: RHF singlet / UHF internal; kind 1: RHF -> UHF (triplet).  tol 0: 1e-6; max_iterations 0: 100."""
+        io = _Stability(kind=int(kind), nroots=int(nroots), max_iterations=int(max_iterations), tol=float(tol))
+        X = np.zeros((int(nroots), self.stability_dim(kind))) if vectors else None
+        rc = _check(lib().qc_scf_stability(self._st, C.byref(io), None if X is None else X.ctypes.data_as(C.c_void_p)), "qc_scf_stability")
+        return StabilityOutput(int(kind), np.array(io.eigenvalues[:nroots]), np.array(io.residuals[:nroots]), rc == QC_OK, int(io.iterations),
+                               int(io.builds), io.ms_total, io.ms_builds, X)
+
+    def rotated_density(self, x, angle: float = 0.0, kind: int = 0):
+        """(D_alpha, D_beta, electronic energy) of the determinant rotated along x by `angle` radians (qc_scf_rotated_density);
+        angle <= 0: the library picks the lowest energy among +-0.1 * 2^k, k = 0..4.  The state is left as it was."""
+        n = self.system.n
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        if x.size != self.stability_dim(kind):
+            raise QcError("rotated_density: x needs %d entries" % self.stability_dim(kind))
+        Da, Db, e = np.zeros((n, n)), np.zeros((n, n)), C.c_double()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(lib().qc_scf_rotated_density(self._st, int(kind), p(x), float(angle), p(Da), p(Db), C.byref(e)), "qc_scf_rotated_density")
+        return Da, Db, e.value
 
     def matrix(self, which: str):
         """Set-up matrix of the state: 'S' (overlap), 'H' (core Hamiltonian) or 'X' (S^-1/2, rhf.rs:124-131)."""
@@ -573,3 +639,69 @@ def unrestricted_gradient(system, config: HartreeFockConfig, n_alpha: int, n_bet
     """(UnrestrictedHartreeFockOutput, gradient (natoms, 3) in Eh/bohr), or None when the SCF does not converge."""
     cfg = HartreeFockConfig(config.max_iterations, config.epsilon, int(n_alpha), int(n_beta))
     return _stepped(system, cfg, True, lambda st: st.gradient())
+
+
+@dataclass
+class StabilizeOutput:
+    """Result of stabilize(): the last converged output (Restricted... while the state stayed RHF, Unrestricted... after an RHF -> UHF
+    instability was followed or for a UHF start), per cycle (electronic energy, lowest eigenvalue, kind of that eigenvalue), whether the
+    last state is stable, and its <S^2>."""
+    output: object
+    history: list
+    stable: bool
+    spin_square: float = 0.0
+
+
+def stabilize(system, config: HartreeFockConfig, n_alpha: int = 0, n_beta: int = 0, max_cycles: int = 8, threshold: float = 1e-5,
+              uhf: Optional[bool] = None, tol: float = 0.0) -> Optional[StabilizeOutput]:
+    """Converge; ask for the lowest eigenvalue of the orbital Hessian; if it is below -threshold, rotate along its eigenvector
+    (rotated_density with the library's angle ladder), start again from that determinant and repeat, at most max_cycles times.
+    An RHF state (uhf None: n_alpha == n_beta; or uhf False) is checked for RHF -> UHF instabilities first (the followed state is UHF),
+    then for singlet ones.  threshold absorbs exact zero modes, which come out as +-1e-9.  None when an SCF does not converge."""
+    sysh = _as_system(system)
+    if n_alpha <= 0 and n_beta <= 0:
+        n_alpha = n_beta = sysh.n_electrons() // 2
+    is_uhf = (n_alpha != n_beta) if uhf is None else bool(uhf)
+    density, history = None, []
+    for cycle in range(int(max_cycles) + 1):
+        st = ScfStepper(sysh, uhf=is_uhf, n_alpha=n_alpha, n_beta=n_beta, stop_rule=float(config.epsilon), density=density)
+        try:
+            e = None
+            for it in range(int(config.max_iterations) + 1):
+                e, rms = st.iterate()
+                if (rms / 2.0 if is_uhf else rms) < config.epsilon:
+                    break
+            else:
+                return None
+            if is_uhf:
+                out = UnrestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), st.orbital_energies(1).tolist(), e,
+                                                    sysh.nuclear_repulsion(), it, st.timings())
+            else:
+                out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, st.timings())
+            s2 = st.spin_square()
+            follow, lowest = None, None
+            for kind in ((0,) if is_uhf else (1, 0)):
+                if st.stability_dim(kind) == 0:
+                    continue
+                r = st.stability(kind=kind, nroots=1, tol=tol, vectors=True)
+                ev = float(r.eigenvalues[0])
+                if lowest is None or ev < lowest[0]:
+                    lowest = (ev, kind)
+                if ev < -threshold:
+                    follow = (kind, r.vectors[0])
+                    break
+            if lowest is None:
+                lowest = (0.0, 0)
+            history.append((e, lowest[0], lowest[1]))
+            if follow is None or cycle == max_cycles:
+                return StabilizeOutput(out, history, follow is None, s2)
+            Da, Db, _ = st.rotated_density(follow[1], 0.0, kind=follow[0])
+            if is_uhf:
+                density = (Da, Db)
+            elif follow[0] == 1:
+                is_uhf, density = True, (Da, Db)
+            else:
+                density = 2.0 * Da
+        finally:
+            st.close()
+    return None
