@@ -59,7 +59,7 @@ int sym_eig_host(qc_system *S, int n, const double *A, const double *V0, double 
     if (V0) QC_HIP_CHECK(hipMemcpyAsync(dV0.p, V0, nn * sizeof(double), hipMemcpyHostToDevice, st));
     int flag = 0;
     QC_HIP_CHECK(hipMemsetAsync(S->d_flag, 0, (V0 ? 1 : 4) * sizeof(int), st));
-    rc = V0 ? qc_eig_device_refine(st, n, dA.p, dV0.p, dV.p, dw.p, E, S->d_flag) : qc_eig_cold_sync(st, n, dA.p, dV.p, dw.p, E, E.ctl, S->d_flag);
+    rc = V0 ? qc_eig_device_refine(st, n, dA.p, dV0.p, dV.p, dw.p, E, S->d_flag) : qc_eig_cold_sync(st, n, dA.p, dV.p, dw.p, E, E.ctl.p, S->d_flag);
     if (rc != QC_OK) return rc;
     QC_HIP_CHECK(hipMemcpyAsync(V, dV.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipMemcpyAsync(w, dw.p, n * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -321,13 +321,14 @@ void qc_device_free(qc_system *S) {
     if (S->stream) (void)hipStreamSynchronize(S->stream);
     qc_gate_forget(S);
     drop_lists(S);
-    void *ptrs[] = {S->d_rplan, S->d_gidx, S->d_shells, S->d_pairdata, S->d_pairdataT, S->d_pspack, S->d_pairs, S->d_boys, S->d_D, S->d_G, S->d_Gtmp, S->d_Gred, S->d_Dj, S->d_flag, S->d_fxs};
+    void *ptrs[] = {S->d_rplan, S->d_gidx, S->d_pairdata, S->d_pairdataT, S->d_pspack, S->d_pairs, S->d_boys, S->d_D, S->d_G, S->d_Gtmp, S->d_Gred, S->d_Dj, S->d_flag, S->d_fxs};
     S->d_flag = nullptr; S->d_fxs = nullptr;
     drop_launch_plan(S);
     if (S->d_join) { (void)hipFree(S->d_join); S->d_join = nullptr; }
     if (S->h_join_timeout) { (void)hipHostFree(S->h_join_timeout); S->h_join_timeout = nullptr; }
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    S->d_shells = nullptr; S->d_pairdata = S->d_pairdataT = S->d_pspack = nullptr; S->d_pairs = nullptr; S->d_rplan = nullptr; S->d_gidx = nullptr; S->d_boys = S->d_D = S->d_G = S->d_Gtmp = S->d_Gred = S->d_Dj = nullptr;
+    delete S->shell_blob; S->shell_blob = nullptr;
+    S->d_pairdata = S->d_pairdataT = S->d_pspack = nullptr; S->d_pairs = nullptr; S->d_rplan = nullptr; S->d_gidx = nullptr; S->d_boys = S->d_D = S->d_G = S->d_Gtmp = S->d_Gred = S->d_Dj = nullptr;
     if (!qc_stream_pool_give(S)) {
         for (int i = 0; i < QC_NSTREAMS; ++i) {
             if (S->side[i]) (void)hipStreamDestroy(S->side[i]);
@@ -1355,13 +1356,6 @@ void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen) {
     qc_assign_cache_store(S);
 }
 
-// temporary device buffer of the two set-up passes below: released on every return path
-template <class T> struct QcTmpDev {
-    T *p = nullptr;
-    ~QcTmpDev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
-};
-
 // Schwarz pass (the reference's own TODO at uhf.rs:49-50): the (P|P) quartet of every stored pair through the
 // class kernels in their `schwarz_out` mode - unsplit slots / one-ket bundles, serial launches, once per geometry.
 int qc_schwarz_device(qc_system *S) {
@@ -1369,8 +1363,8 @@ int qc_schwarz_device(qc_system *S) {
     // (the classes' launches are serial on the handle's stream and independent of the host; their temporary lists are packed into ONE
     // device buffer - one allocation, one copy, one wait for the whole pass: an allocation, two synchronous copies and a wait per class
     // made it 4 ms for H2O/cc-pVTZ, most of a cold handle's set-up; 3.6 ms still with one wait but 35 allocations and 50 copies)
-    QcTmpDev<double> dq;
-    QC_HIP_CHECK(dq.alloc(np));
+    QcDev<double> dq;
+    if (dq.alloc(np) != QC_OK) return QC_ERR_HIP;
     double *const d_q = dq.p;
     QC_HIP_CHECK(hipMemsetAsync(d_q, 0, np * sizeof(double), S->stream));
     QcFockArgs fa{};
@@ -1415,9 +1409,9 @@ int qc_schwarz_device(qc_system *S) {
         }
         jobs.push_back(std::move(j));
     }
-    QcTmpDev<unsigned char> dblob;
+    QcDev<unsigned char> dblob;
     if (!blob.empty()) {
-        QC_HIP_CHECK(dblob.alloc(blob.size()));
+        if (dblob.alloc(blob.size()) != QC_OK) return QC_ERR_HIP;
         QC_HIP_CHECK(hipMemcpyAsync(dblob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, S->stream));
     }
     // The launches are independent (each writes its own pairs' entries) and most of them are a few waves working through one long
@@ -1466,8 +1460,8 @@ int qc_launch_eri_full(qc_system *S, double *d_out) {
             cc.LAB = c.LAB; cc.LCD = c.LCD; cc.LGC = c.col_lgc; cc.slot_words = c.col_slot_words; cc.lds_bytes = c.col_lds_bytes;
             qc_make_slots(S, c.tasks, 0, false, slots);
             if (slots.empty()) continue;
-            QcTmpDev<QcSlot> d;
-            QC_HIP_CHECK(d.alloc(slots.size()));
+            QcDev<QcSlot> d;
+            if (d.alloc(slots.size()) != QC_OK) return QC_ERR_HIP;
             QC_HIP_CHECK(hipMemcpyAsync(d.p, slots.data(), slots.size() * sizeof(QcSlot), hipMemcpyHostToDevice, S->stream));
             int rc = launch_segments(S, qc_unit_of(cc.LAB, cc.LCD, false), {Seg{&cc, d.p, (int)slots.size()}}, S->stream, a);
             QC_HIP_CHECK(hipStreamSynchronize(S->stream));
@@ -1477,11 +1471,11 @@ int qc_launch_eri_full(qc_system *S, double *d_out) {
         if (c.bm) {
             const bool packed = qc_make_bundles(S, c.tasks, 0, bundles, ketlist);
             if (bundles.empty()) continue;
-            QcTmpDev<QcBundleDev> db; QcTmpDev<QcKetUnit> dk;
+            QcDev<QcBundleDev> db; QcDev<QcKetUnit> dk;
             std::vector<QcBundleDev> hb; std::vector<QcKetUnit> hu;
             qc_bm_device_lists(S, c.LCD, bundles, ketlist, packed, hb, hu);
-            QC_HIP_CHECK(db.alloc(hb.size()));
-            QC_HIP_CHECK(dk.alloc(hu.size()));
+            if (db.alloc(hb.size()) != QC_OK) return QC_ERR_HIP;
+            if (dk.alloc(hu.size()) != QC_OK) return QC_ERR_HIP;
             QC_HIP_CHECK(hipMemcpyAsync(db.p, hb.data(), hb.size() * sizeof(QcBundleDev), hipMemcpyHostToDevice, S->stream));
             QC_HIP_CHECK(hipMemcpyAsync(dk.p, hu.data(), hu.size() * sizeof(QcKetUnit), hipMemcpyHostToDevice, S->stream));
             int mx = 0;
@@ -1493,8 +1487,8 @@ int qc_launch_eri_full(qc_system *S, double *d_out) {
         }
         qc_make_slots(S, c.tasks, 0, false, slots);
         if (slots.empty()) continue;
-        QcTmpDev<QcSlot> d;
-        QC_HIP_CHECK(d.alloc(slots.size()));
+        QcDev<QcSlot> d;
+        if (d.alloc(slots.size()) != QC_OK) return QC_ERR_HIP;
         QC_HIP_CHECK(hipMemcpyAsync(d.p, slots.data(), slots.size() * sizeof(QcSlot), hipMemcpyHostToDevice, S->stream));
         int rc = launch_segments(S, qc_unit_of(c.LAB, c.LCD, false), {Seg{&c, d.p, (int)slots.size()}}, S->stream, a);
         QC_HIP_CHECK(hipStreamSynchronize(S->stream));

@@ -18,12 +18,14 @@
 //    adds each quartet's twelve numbers with one lane, in task order; rows go to a slab [workgroup][3 natoms].
 //  * one-electron terms (qc_grad1_kernel): one wave per shell pair, lanes over primitive pairs (x nuclei for V), the same slab rows.
 //  * qc_grad_sum_kernel: one workgroup adds the slab rows in row order.
-// The Boys function is evaluated by the Kummer series + downward recursion of qc_one_electron.hip (exact to the last digits at every
-// order this needs, up to F_13 for (ff|ff)); the Fock kernels' interpolation table is not read.
+// Hermite expansions, Boys function (Kummer series + downward recursion, exact to the last digits at every order this needs, up to
+// F_13 for (ff|ff); the Fock kernels' interpolation table is not read), the R recurrence step, the sums of one Cartesian pair and the
+// Cartesian component order come from qc_md.h, shared with the one-electron kernel and the host; shells and primitives from the
+// handle's blob (qc_shell_blob).
 #include <algorithm>
 #include <cmath>
 
-#include "qc_internal.h"
+#include "qc_md.h"
 
 namespace {
 
@@ -42,57 +44,6 @@ constexpr HermTab make_htab() {
 }
 __constant__ HermTab c_htab = make_htab();
 
-// Cartesian exponents of component x of a shell of order L: c_cart[qc_cartoff(L) + x], the order of cart_list() (qc_system.cpp)
-__constant__ unsigned char c_cart[20][3] = {
-    {0, 0, 0},
-    {1, 0, 0}, {0, 1, 0}, {0, 0, 1},
-    {2, 0, 0}, {1, 1, 0}, {1, 0, 1}, {0, 2, 0}, {0, 1, 1}, {0, 0, 2},
-    {3, 0, 0}, {2, 1, 0}, {2, 0, 1}, {1, 2, 0}, {1, 1, 1}, {1, 0, 2}, {0, 3, 0}, {0, 2, 1}, {0, 1, 2}, {0, 0, 3}};
-__host__ __device__ constexpr int cartoff(int L) { return L * (L + 1) * (L + 2) / 6; }
-
-struct GShell { double A[3]; int L, nprim, ncart, nfunc, off, coff, poff, toff, atom, pad; };
-
-// 1-D Hermite expansion E^{ij}_t of x_A^i x_B^j exp(-a x_A^2 - b x_B^2), i <= imax, j <= jmax, t < tdim (= imax + jmax + 1),
-// stored E[(i * (jmax + 1) + j) * tdim + t]; every entry with t > i + j is zero
-__device__ void herm_e(double *E, int imax, int jmax, int tdim, double a, double b, double Q) {
-    const double p = a + b, h = 0.5 / p, xpa = -b / p * Q, xpb = a / p * Q;
-    const int sj = tdim, si = (jmax + 1) * tdim;
-    for (int k = 0; k < (imax + 1) * si; ++k) E[k] = 0.0;
-    E[0] = exp(-a * b / p * Q * Q);
-    for (int i = 1; i <= imax; ++i)
-        for (int t = 0; t <= i; ++t) {
-            const double *e = E + (i - 1) * si;
-            E[i * si + t] = (t > 0 ? h * e[t - 1] : 0.0) + xpa * e[t] + (t + 1 < tdim ? (t + 1) * e[t + 1] : 0.0);
-        }
-    for (int i = 0; i <= imax; ++i)
-        for (int j = 1; j <= jmax; ++j)
-            for (int t = 0; t <= i + j; ++t) {
-                const double *e = E + i * si + (j - 1) * sj;
-                E[i * si + j * sj + t] = (t > 0 ? h * e[t - 1] : 0.0) + xpb * e[t] + (t + 1 < tdim ? (t + 1) * e[t + 1] : 0.0);
-            }
-}
-
-// F_n(x), n = 0..nmax (as qc_one_electron.hip)
-__device__ void boys_series(int nmax, double x, double *F) {
-    const double ex = exp(-x);
-    if (x < 38.0) {
-        double term = 1.0 / (2 * nmax + 1), sum = term;
-        for (int k = 1; k < 500; ++k) { term *= 2.0 * x / (2 * nmax + 2 * k + 1); sum += term; if (term < 1e-18 * sum) break; }
-        F[nmax] = ex * sum;
-        for (int n = nmax; n > 0; --n) F[n - 1] = (2.0 * x * F[n] + ex) / (2 * n - 1);
-    } else {
-        F[0] = 0.5 * sqrt(M_PI / x) * erf(sqrt(x));
-        for (int n = 0; n < nmax; ++n) F[n + 1] = ((2 * n + 1) * F[n] - ex) / (2.0 * x);
-    }
-}
-
-// value of R^n_tuv from the table of order n + 1 (entry h of the level n; X = P - C or P - Q)
-__device__ inline double r_step(const double *Rn1, int t, int u, int v, const double *X) {
-    if (t) return X[0] * Rn1[qc_hidx(t - 1, u, v)] + (t > 1 ? (t - 1) * Rn1[qc_hidx(t - 2, u, v)] : 0.0);
-    if (u) return X[1] * Rn1[qc_hidx(t, u - 1, v)] + (u > 1 ? (u - 1) * Rn1[qc_hidx(t, u - 2, v)] : 0.0);
-    return X[2] * Rn1[qc_hidx(t, u, v - 1)] + (v > 1 ? (v - 1) * Rn1[qc_hidx(t, u, v - 2)] : 0.0);
-}
-
 __device__ inline double wave_sum(double v) {        // fixed butterfly: every lane ends with the same, order-independent value
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -100,13 +51,13 @@ __device__ inline double wave_sum(double v) {        // fixed butterfly: every l
 
 // ---- density transform ---------------------------------------------------------------------------------------------------------
 // dst[m][i][j] (nc x nc, Cartesian) = sum_{f,g} T_A[f][x] src[m][offA + f][offB + g] T_B[g][y] for Cartesian i = coffA + x, j = coffB + y
-__global__ __launch_bounds__(256) void cart_transform_kernel(int n, int nc, const GShell *__restrict__ sh, const int *__restrict__ cshell,
+__global__ __launch_bounds__(256) void cart_transform_kernel(int n, int nc, const QcDevShell *__restrict__ sh, const int *__restrict__ cshell,
                                                              const double *__restrict__ Tm, const double *__restrict__ src, double *__restrict__ dst) {
     const size_t ij = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ij >= (size_t)nc * nc) return;
     const int m = blockIdx.y;
     const int i = (int)(ij / nc), j = (int)(ij - (size_t)i * nc);
-    const GShell A = sh[cshell[i]], B = sh[cshell[j]];
+    const QcDevShell A = sh[cshell[i]], B = sh[cshell[j]];
     const int x = i - A.coff, y = j - B.coff;
     const double *S = src + (size_t)m * n * n, *Ta = Tm + A.toff, *Tb = Tm + B.toff;
     double acc = 0.0;
@@ -139,33 +90,10 @@ __global__ void scale_cols_kernel(int n, int nocc, double occ, const double *__r
 // ---- one-electron terms --------------------------------------------------------------------------------------------------------
 constexpr int EI1 = QC_LMAX + 2, EJ1 = QC_LMAX + 3, ET1 = EI1 + EJ1 + 1;   // i <= la + 1, j <= lb + 2
 
-struct E1 {
-    double v[EI1 * EJ1 * ET1];
-    int jm, td;
-    __device__ double g(int i, int j, int t) const { return (i < 0 || j < 0 || t < 0 || t > i + j) ? 0.0 : v[(i * (jm + 1) + j) * td + t]; }
-};
-
-__device__ double ovl1(const E1 *E, const int *a, const int *b) { return E[0].g(a[0], b[0], 0) * E[1].g(a[1], b[1], 0) * E[2].g(a[2], b[2], 0); }
-__device__ double kin1(const E1 *E, const int *a, const int *b, double eb) {      // <a| -1/2 nabla^2 |b> / (pi/p)^{3/2}
-    double s1[3], t1[3];
-    for (int k = 0; k < 3; ++k) {
-        s1[k] = E[k].g(a[k], b[k], 0);
-        t1[k] = 4.0 * eb * eb * E[k].g(a[k], b[k] + 2, 0) - 2.0 * eb * (2 * b[k] + 1) * s1[k];
-        if (b[k] >= 2) t1[k] += b[k] * (b[k] - 1) * E[k].g(a[k], b[k] - 2, 0);
-    }
-    return -0.5 * (t1[0] * s1[1] * s1[2] + s1[0] * t1[1] * s1[2] + s1[0] * s1[1] * t1[2]);
-}
-__device__ double nuc1(const E1 *E, const int *a, const int *b, const double *R) {     // sum_tuv E E E R_tuv
-    if (a[0] < 0 || a[1] < 0 || a[2] < 0 || b[0] < 0 || b[1] < 0 || b[2] < 0) return 0.0;
-    double acc = 0.0;
-    for (int t = 0; t <= a[0] + b[0]; ++t)
-        for (int u = 0; u <= a[1] + b[1]; ++u)
-            for (int v = 0; v <= a[2] + b[2]; ++v) acc += E[0].g(a[0], b[0], t) * E[1].g(a[1], b[1], u) * E[2].g(a[2], b[2], v) * R[qc_hidx(t, u, v)];
-    return acc;
-}
+using E1 = QcMdE1<EI1 * EJ1 * ET1>;
 
 // Slab row of workgroup w: [core (3 natoms) | overlap (3 natoms)].  One wave per shell pair (a >= b), statically dealt.
-__global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const GShell *__restrict__ sh, const double *__restrict__ exps, const double *__restrict__ coefs,
+__global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const QcDevShell *__restrict__ sh, const double *__restrict__ exps, const double *__restrict__ coefs,
                                                       int natoms, const int *__restrict__ Z, const double *__restrict__ xyz, int nc,
                                                       const double *__restrict__ Pc, const double *__restrict__ Wc, double *__restrict__ slab) {
     extern __shared__ double row[];                   // 6 natoms
@@ -177,7 +105,7 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const GShell 
         int a = 0, rem = pr;
         while (rem > a) { rem -= a + 1; ++a; }
         const int b = rem;
-        const GShell A = sh[a], B = sh[b];
+        const QcDevShell A = sh[a], B = sh[b];
         const double f = a == b ? 1.0 : 2.0;
         const int npp = A.nprim * B.nprim;
         // overlap (x W) and kinetic (x P): d/dA only, d/dB = -d/dA
@@ -186,19 +114,19 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const GShell 
             const int i = pp / B.nprim, j = pp - i * B.nprim;
             const double ea = exps[A.poff + i], eb = exps[B.poff + j], p = ea + eb, cc = coefs[A.poff + i] * coefs[B.poff + j] * pow(M_PI / p, 1.5);
             E1 E[3];
-            for (int k = 0; k < 3; ++k) { E[k].jm = B.L + 2; E[k].td = A.L + B.L + 4; herm_e(E[k].v, A.L + 1, B.L + 2, A.L + B.L + 4, ea, eb, A.A[k] - B.A[k]); }
+            for (int k = 0; k < 3; ++k) E[k].fill(A.L + 1, B.L + 2, ea, eb, A.A[k] - B.A[k]);
             for (int x = 0; x < A.ncart; ++x) {
-                const unsigned char *ax = c_cart[cartoff(A.L) + x];
+                const unsigned char *ax = qc_md_cart(A.L, x);
                 for (int y = 0; y < B.ncart; ++y) {
-                    const unsigned char *by = c_cart[cartoff(B.L) + y];
+                    const unsigned char *by = qc_md_cart(B.L, y);
                     const int bi[3] = {by[0], by[1], by[2]};
                     const double w = cc * Wc[(size_t)(A.coff + x) * nc + B.coff + y], pv = cc * Pc[(size_t)(A.coff + x) * nc + B.coff + y];
                     for (int k = 0; k < 3; ++k) {
                         int up[3] = {ax[0], ax[1], ax[2]}, dn[3] = {ax[0], ax[1], ax[2]};
                         ++up[k]; --dn[k];
-                        const double lo = ax[k] ? ax[k] * ovl1(E, dn, bi) : 0.0, klo = ax[k] ? ax[k] * kin1(E, dn, bi, eb) : 0.0;
-                        sA[k] += w * (2.0 * ea * ovl1(E, up, bi) - lo);
-                        tA[k] += pv * (2.0 * ea * kin1(E, up, bi, eb) - klo);
+                        const double lo = ax[k] ? ax[k] * qc_md_ovl(E, dn, bi) : 0.0, klo = ax[k] ? ax[k] * (-0.5 * qc_md_kin(E, dn, bi, eb)) : 0.0;
+                        sA[k] += w * (2.0 * ea * qc_md_ovl(E, up, bi) - lo);
+                        tA[k] += pv * (2.0 * ea * (-0.5 * qc_md_kin(E, up, bi, eb)) - klo);
                     }
                 }
             }
@@ -219,36 +147,35 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const GShell 
                 E1 E[3];
                 double PC[3];
                 for (int k = 0; k < 3; ++k) {
-                    E[k].jm = B.L + 2; E[k].td = A.L + B.L + 4;
-                    herm_e(E[k].v, A.L + 1, B.L + 2, A.L + B.L + 4, ea, eb, A.A[k] - B.A[k]);
+                    E[k].fill(A.L + 1, B.L + 2, ea, eb, A.A[k] - B.A[k]);
                     PC[k] = (ea * A.A[k] + eb * B.A[k]) / p - xyz[3 * c + k];
                 }
                 const int L = A.L + B.L + 1;
                 double Rb[2][qc_nherm(QC_LPAIR + 1)], F[QC_LPAIR + 2];
-                boys_series(L, p * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]), F);
+                qc_md_boys(L, p * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]), F);
                 for (int n = L; n >= 0; --n) {
                     double *Rn = Rb[n & 1];
                     const double *Rn1 = Rb[(n + 1) & 1];
-                    Rn[0] = pow(-2.0 * p, n) * F[n];
-                    for (int h = 1; h < qc_nherm(L - n); ++h) Rn[h] = r_step(Rn1, c_htab.t[h], c_htab.u[h], c_htab.v[h], PC);
+                    Rn[0] = pow(-2.0 * p, n) * F[n];          // (the seeds: pow here, see qc_md.h)
+                    for (int h = 1; h < qc_nherm(L - n); ++h) Rn[h] = qc_md_r_step(Rn1, c_htab.t[h], c_htab.u[h], c_htab.v[h], PC);
                 }
                 const double *R = Rb[0];
                 for (int x = 0; x < A.ncart; ++x) {
-                    const unsigned char *ax = c_cart[cartoff(A.L) + x];
+                    const unsigned char *ax = qc_md_cart(A.L, x);
                     for (int y = 0; y < B.ncart; ++y) {
-                        const unsigned char *by = c_cart[cartoff(B.L) + y];
+                        const unsigned char *by = qc_md_cart(B.L, y);
                         const double pv = cc * Pc[(size_t)(A.coff + x) * nc + B.coff + y];
                         for (int k = 0; k < 3; ++k) {
                             int ai[3] = {ax[0], ax[1], ax[2]}, bi[3] = {by[0], by[1], by[2]};
                             ++ai[k];
-                            double dA = 2.0 * ea * nuc1(E, ai, bi, R);
+                            double dA = 2.0 * ea * qc_md_nuc(E, ai, bi, R);
                             ai[k] -= 2;
-                            if (ax[k]) dA -= ax[k] * nuc1(E, ai, bi, R);
+                            if (ax[k]) dA -= ax[k] * qc_md_nuc(E, ai, bi, R);
                             ai[k] += 1;
                             ++bi[k];
-                            double dB = 2.0 * eb * nuc1(E, ai, bi, R);
+                            double dB = 2.0 * eb * qc_md_nuc(E, ai, bi, R);
                             bi[k] -= 2;
-                            if (by[k]) dB -= by[k] * nuc1(E, ai, bi, R);
+                            if (by[k]) dB -= by[k] * qc_md_nuc(E, ai, bi, R);
                             vA[k] += pv * dA;
                             vB[k] += pv * dB;
                         }
@@ -281,7 +208,7 @@ __host__ __device__ inline int group_words(int la, int lb, int lc, int ld) {
 // Dynamic LDS: [Gamma block gmax][groups x ws][atom row 3 natoms].  One wave per workgroup; groups of gs = 64 >> glog lanes.
 // The slab row of the workgroup is read at the start and written back at the end (one row across the launches of all classes).
 __global__ __launch_bounds__(64) void qc_grad2_kernel(const GTask *__restrict__ tasks, int ntasks, int glog, int ws, int gmax,
-                                                      const GShell *__restrict__ sh, const double *__restrict__ exps, const double *__restrict__ coefs,
+                                                      const QcDevShell *__restrict__ sh, const double *__restrict__ exps, const double *__restrict__ coefs,
                                                       int nc, const double *__restrict__ Pt, const double *__restrict__ Pa, const double *__restrict__ Pb,
                                                       int natoms, double *__restrict__ slab) {
     extern __shared__ double lds[];
@@ -290,7 +217,7 @@ __global__ __launch_bounds__(64) void qc_grad2_kernel(const GTask *__restrict__ 
     for (int k = lane; k < na3; k += 64) row[k] = slab[(size_t)blockIdx.x * na3 + k];
     for (int ti = blockIdx.x; ti < ntasks; ti += gridDim.x) {
         const GTask tk = tasks[ti];
-        const GShell A = sh[tk.sa], B = sh[tk.sb], Cs = sh[tk.sc], D = sh[tk.sd];
+        const QcDevShell A = sh[tk.sa], B = sh[tk.sb], Cs = sh[tk.sc], D = sh[tk.sd];
         const int nab = A.ncart * B.ncart, ncd = Cs.ncart * D.ncart;
         const int lab = A.L + B.L, lcd = Cs.L + D.L, L = lab + lcd + 1;
         // Gamma_abcd of the block (Cartesian), exchange symmetrised
@@ -323,10 +250,10 @@ __global__ __launch_bounds__(64) void qc_grad2_kernel(const GTask *__restrict__ 
             const double pref = 2.0 * pow(M_PI, 2.5) / (p * q * sqrt(p + q)) * coefs[A.poff + i] * coefs[B.poff + j] * coefs[Cs.poff + k] * coefs[D.poff + l];
             if (act) {
                 for (int e = gl; e < 6; e += gs) {
-                    if (e < 3) herm_e(Eb + e * sEb, A.L + 1, B.L + 1, tb, ea, eb, A.A[e] - B.A[e]);
-                    else herm_e(Ek + (e - 3) * sEk, Cs.L + 1, D.L + 1, tk_, ec, ed, Cs.A[e - 3] - D.A[e - 3]);
+                    if (e < 3) qc_md_herm_e(Eb + e * sEb, A.L + 1, B.L + 1, tb, ea, eb, A.A[e] - B.A[e]);
+                    else qc_md_herm_e(Ek + (e - 3) * sEk, Cs.L + 1, D.L + 1, tk_, ec, ed, Cs.A[e - 3] - D.A[e - 3]);
                 }
-                if (gl == 0) boys_series(L, alpha * (PQ[0] * PQ[0] + PQ[1] * PQ[1] + PQ[2] * PQ[2]), Fv);
+                if (gl == 0) qc_md_boys(L, alpha * (PQ[0] * PQ[0] + PQ[1] * PQ[1] + PQ[2] * PQ[2]), Fv);
             }
             __syncthreads();
             for (int n = L; n >= 0; --n) {          // R^n from R^{n+1}; R^0 ends in R0
@@ -334,17 +261,17 @@ __global__ __launch_bounds__(64) void qc_grad2_kernel(const GTask *__restrict__ 
                 const double *Rn1 = (n & 1) ? R0 : R1;
                 if (act)
                     for (int h = gl; h < qc_nherm(L - n); h += gs)
-                        Rn[h] = h == 0 ? pow(-2.0 * alpha, n) * Fv[n] : r_step(Rn1, c_htab.t[h], c_htab.u[h], c_htab.v[h], PQ);
+                        Rn[h] = h == 0 ? pow(-2.0 * alpha, n) * Fv[n] : qc_md_r_step(Rn1, c_htab.t[h], c_htab.u[h], c_htab.v[h], PQ);
                 __syncthreads();
             }
             for (int ab = 0; ab < nab; ++ab) {
-                const unsigned char *ax = c_cart[cartoff(A.L) + ab / B.ncart], *bx = c_cart[cartoff(B.L) + ab % B.ncart];
+                const unsigned char *ax = qc_md_cart(A.L, ab / B.ncart), *bx = qc_md_cart(B.L, ab % B.ncart);
                 if (act)
                     for (int h = gl; h < nhK1; h += gs) {       // ket Hermite densities of this bra pair
                         const int tt[3] = {c_htab.t[h], c_htab.u[h], c_htab.v[h]};
                         double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
                         for (int cd = 0; cd < ncd; ++cd) {
-                            const unsigned char *cx = c_cart[cartoff(Cs.L) + cd / D.ncart], *dx = c_cart[cartoff(D.L) + cd % D.ncart];
+                            const unsigned char *cx = qc_md_cart(Cs.L, cd / D.ncart), *dx = qc_md_cart(D.L, cd % D.ncart);
                             double e[3], de[3];
                             for (int x = 0; x < 3; ++x) {
                                 const double *Ex = Ek + x * sEk;
@@ -424,13 +351,6 @@ __global__ __launch_bounds__(256) void qc_grad_sum_kernel(int na3, int rows1, co
 constexpr int G1_ROWS = 512, G2_ROWS = 1024;
 constexpr size_t LDS_LIMIT = 160 * 1024, LDS_GROUPS = 64 * 1024;
 
-struct Buf {
-    void *p = nullptr;
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? QC_OK : QC_ERR_HIP; }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 // The terms core / overlap / two-electron of the gradient (3 x 3 natoms doubles, host `terms3`) from function-basis densities on the
@@ -440,23 +360,10 @@ int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *
     const size_t nn = (size_t)n * n;
     hipStream_t st = S->stream;
     if ((size_t)2 * na3 * 8 > 32 * 1024) return QC_ERR_UNSUPPORTED;          // the atom rows live in LDS
-    // shells with Cartesian offsets, primitives, transforms, nuclei
-    std::vector<GShell> hs(nsh);
-    std::vector<double> ex, co, tm;
-    std::vector<int> cshell;
-    for (int s = 0; s < nsh; ++s) {
-        const QcShell &q = S->shells[s];
-        GShell d{};
-        for (int k = 0; k < 3; ++k) d.A[k] = q.A[k];
-        d.L = q.L; d.nprim = q.nprim; d.ncart = q.ncart; d.nfunc = q.nfunc; d.off = q.off; d.atom = q.atom;
-        d.coff = (int)cshell.size(); d.poff = (int)ex.size(); d.toff = (int)tm.size();
-        for (int x = 0; x < q.ncart; ++x) cshell.push_back(s);
-        ex.insert(ex.end(), q.exps.begin(), q.exps.end());
-        co.insert(co.end(), q.coefs.begin(), q.coefs.end());
-        tm.insert(tm.end(), q.T.begin(), q.T.end());
-        hs[s] = d;
-    }
-    const int nc = (int)cshell.size();
+    const QcShellBlob *B;
+    int rc = qc_shell_blob(S, &B);
+    if (rc != QC_OK) return rc;
+    const int nc = B->nc;
     const size_t ncc = (size_t)nc * nc;
     // the two-electron work: the handle's unique quartets after Schwarz screening, bucketed by total order (one launch each)
     const bool screen = !S->pairQ.empty() && S->schwarz_tau > 0.0;
@@ -478,44 +385,29 @@ int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *
     flat.reserve(boff.back());
     for (const auto &v : bucket) flat.insert(flat.end(), v.begin(), v.end());
 
-    const size_t o_sh = 0, o_ex = o_sh + ((nsh * sizeof(GShell) + 255) & ~(size_t)255), o_co = o_ex + ((ex.size() * 8 + 255) & ~(size_t)255);
-    const size_t o_tm = o_co + ((co.size() * 8 + 255) & ~(size_t)255), o_cs = o_tm + ((tm.size() * 8 + 255) & ~(size_t)255);
-    const size_t o_z = o_cs + ((cshell.size() * 4 + 255) & ~(size_t)255), o_x = o_z + ((na * 4 + 255) & ~(size_t)255);
-    const size_t o_tk = o_x + ((na3 * 8 + 255) & ~(size_t)255), o_end = o_tk + flat.size() * sizeof(GTask);
-    Buf meta, fb, cb, s1, s2, out;
-    if (meta.alloc(o_end) || fb.alloc(4 * nn * 8) || cb.alloc(4 * ncc * 8) || s1.alloc((size_t)G1_ROWS * 2 * na3 * 8) ||
-        s2.alloc((size_t)G2_ROWS * na3 * 8) || out.alloc(3 * na3 * 8))
+    // (the task list follows the current Schwarz threshold: built and uploaded per call)
+    QcDev<GTask> tasks;
+    DevBuf fb, cb, s1, s2, out;
+    if (tasks.alloc(flat.size()) != QC_OK || fb.alloc(4 * nn) != QC_OK || cb.alloc(4 * ncc) != QC_OK || s1.alloc((size_t)G1_ROWS * 2 * na3) != QC_OK ||
+        s2.alloc((size_t)G2_ROWS * na3) != QC_OK || out.alloc(3 * na3) != QC_OK)
         return QC_ERR_HIP;
-    char *m = meta.as<char>();
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_sh, hs.data(), nsh * sizeof(GShell), hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_ex, ex.data(), ex.size() * 8, hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_co, co.data(), co.size() * 8, hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_tm, tm.data(), tm.size() * 8, hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_cs, cshell.data(), cshell.size() * 4, hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_z, S->Z.data(), na * 4, hipMemcpyHostToDevice, st));
-    QC_HIP_CHECK(hipMemcpyAsync(m + o_x, S->xyz.data(), na3 * 8, hipMemcpyHostToDevice, st));
-    if (!flat.empty()) QC_HIP_CHECK(hipMemcpyAsync(m + o_tk, flat.data(), flat.size() * sizeof(GTask), hipMemcpyHostToDevice, st));
-    const GShell *dsh = reinterpret_cast<const GShell *>(m + o_sh);
-    const double *dex = reinterpret_cast<const double *>(m + o_ex), *dco = reinterpret_cast<const double *>(m + o_co);
-    const double *dtm = reinterpret_cast<const double *>(m + o_tm), *dxyz = reinterpret_cast<const double *>(m + o_x);
-    const int *dcs = reinterpret_cast<const int *>(m + o_cs), *dz = reinterpret_cast<const int *>(m + o_z);
-    const GTask *dtk = reinterpret_cast<const GTask *>(m + o_tk);
+    if (!flat.empty()) QC_HIP_CHECK(hipMemcpyAsync(tasks.p, flat.data(), flat.size() * sizeof(GTask), hipMemcpyHostToDevice, st));
 
     hipEvent_t ev[5];
     for (auto &e : ev) QC_HIP_CHECK(hipEventCreate(&e));
     struct EvDel { hipEvent_t *e; ~EvDel() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(e[i]); } } evdel{ev};
     QC_HIP_CHECK(hipEventRecord(ev[0], st));
     // 1. [Pt, Pa, Pb, W] -> Cartesian
-    double *F = fb.as<double>(), *Cc = cb.as<double>();
+    double *F = fb.p, *Cc = cb.p;
     hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (int)nn, nspin, dP, F);
     QC_HIP_CHECK(hipMemcpyAsync(F + 3 * nn, dW, nn * 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(cart_transform_kernel, dim3((unsigned)((ncc + 255) / 256), 4), dim3(256), 0, st, n, nc, dsh, dcs, dtm, F, Cc);
+    hipLaunchKernelGGL(cart_transform_kernel, dim3((unsigned)((ncc + 255) / 256), 4), dim3(256), 0, st, n, nc, B->sh, B->cshell, B->T, F, Cc);
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipEventRecord(ev[1], st));
     // 2. one-electron terms
     const int npairs = nsh * (nsh + 1) / 2, g1 = std::min(npairs, G1_ROWS);
     QC_HIP_CHECK(hipMemsetAsync(s1.p, 0, (size_t)G1_ROWS * 2 * na3 * 8, st));
-    hipLaunchKernelGGL(qc_grad1_kernel, dim3(g1), dim3(64), 2 * na3 * 8, st, nsh, dsh, dex, dco, na, dz, dxyz, nc, Cc, Cc + 3 * ncc, s1.as<double>());
+    hipLaunchKernelGGL(qc_grad1_kernel, dim3(g1), dim3(64), 2 * na3 * 8, st, nsh, B->sh, B->exps, B->coefs, na, B->Z, B->xyz, nc, Cc, Cc + 3 * ncc, s1.p);
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipEventRecord(ev[2], st));
     // 3. two-electron term, one launch per total order
@@ -529,13 +421,13 @@ int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *
         while (glog > 0 && ((size_t)bws[b] << glog) * 8 > LDS_GROUPS) --glog;
         const size_t lds = ((size_t)bg[b] + ((size_t)bws[b] << glog) + na3) * 8;
         if (lds > LDS_LIMIT) return QC_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(qc_grad2_kernel, dim3(std::min(nt, G2_ROWS)), dim3(64), lds, st, dtk + boff[b], nt, glog, bws[b], bg[b], dsh, dex, dco, nc,
-                           Cc, Cc + ncc, Cc + 2 * ncc, na, s2.as<double>());
+        hipLaunchKernelGGL(qc_grad2_kernel, dim3(std::min(nt, G2_ROWS)), dim3(64), lds, st, tasks.p + boff[b], nt, glog, bws[b], bg[b], B->sh, B->exps,
+                           B->coefs, nc, Cc, Cc + ncc, Cc + 2 * ncc, na, s2.p);
         QC_HIP_CHECK(hipGetLastError());
     }
     QC_HIP_CHECK(hipEventRecord(ev[3], st));
     // 4. fixed-order sum of the slab rows
-    hipLaunchKernelGGL(qc_grad_sum_kernel, dim3(1), dim3(256), 0, st, na3, g1, s1.as<double>(), G2_ROWS, s2.as<double>(), out.as<double>());
+    hipLaunchKernelGGL(qc_grad_sum_kernel, dim3(1), dim3(256), 0, st, na3, g1, s1.p, G2_ROWS, s2.p, out.p);
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipEventRecord(ev[4], st));
     QC_HIP_CHECK(hipMemcpyAsync(terms3, out.p, 3 * na3 * 8, hipMemcpyDeviceToHost, st));
@@ -550,16 +442,16 @@ int qc_gradient_w_device(qc_system *S, int nspin, const double *dC, const double
     const int n = S->nbasis;
     const size_t nn = (size_t)n * n;
     hipStream_t st = S->stream;
-    double *Ce = nullptr;
-    QC_HIP_CHECK(hipMalloc(&Ce, nn * 8));
-    struct Del { double *p; hipStream_t s; ~Del() { (void)hipStreamSynchronize(s); (void)hipFree(p); } } del{Ce, st};
+    DevBuf Ce;
+    if (Ce.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};     // before Ce is freed: the work below reads it
     const double occ = nspin == 1 ? 2.0 : 1.0;
     QC_HIP_CHECK(hipMemsetAsync(dW, 0, nn * 8, st));
     for (int s = 0; s < nspin; ++s) {
         if (nocc[s] <= 0) continue;
-        hipLaunchKernelGGL(scale_cols_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, n, nocc[s], occ, dC + s * nn, dEps + (size_t)s * n, Ce);
+        hipLaunchKernelGGL(scale_cols_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, n, nocc[s], occ, dC + s * nn, dEps + (size_t)s * n, Ce.p);
         QC_HIP_CHECK(hipGetLastError());
-        qc_gemm(st, n, n, nocc[s], 1.0, Ce, n, false, dC + s * nn, n, true, 1.0, dW, n);
+        qc_gemm(st, n, n, nocc[s], 1.0, Ce.p, n, false, dC + s * nn, n, true, 1.0, dW, n);
     }
     return QC_OK;
 }

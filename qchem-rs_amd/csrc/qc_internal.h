@@ -4,6 +4,7 @@
 #include <rccl/rccl.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -168,8 +169,7 @@ struct qc_system {
     hipEvent_t ev_fork = nullptr, ev_join[QC_NSTREAMS] = {};
     unsigned spin_target = 0;                // join counter of the spin-parallel Roothaan steps (d_join[4])
     double *d_pairdata = nullptr, *d_pairdataT = nullptr, *d_pspack = nullptr;
-    void *d_shells = nullptr;                // shells / primitives / transforms / nuclei for the one-electron kernels (one blob)
-    size_t shell_blob_off[5] = {};
+    struct QcShellBlob *shell_blob = nullptr; // shells / primitives / transforms / nuclei for the one-electron and gradient kernels (qc_shell_blob)
     QcPairDesc *d_pairs = nullptr;
     double *d_boys = nullptr;
     int *d_rplan = nullptr;
@@ -335,11 +335,27 @@ constexpr int QC_EIG_STATE = 0, QC_EIG_LAST = 1, QC_EIG_CLEAN = 2, QC_EIG_PASSES
 constexpr int QC_EIG_RUNNING = 0, QC_EIG_DONE = 1, QC_EIG_ROTATE = 2;
 constexpr int QC_SYNC_WORDS = 4 + QC_CTL_WORDS / 2;
 
-struct DevBuf {
-    double *p = nullptr;
-    int alloc(size_t count) { return hipMalloc(&p, count * sizeof(double)) == hipSuccess ? QC_OK : QC_ERR_HIP; }
-    ~DevBuf() { if (p) (void)hipFree(p); }
+// Owning device allocation of `count` objects T.  alloc: QC_OK or QC_ERR_HIP; a zero count leaves p null and succeeds.
+template <class T> struct QcDev {
+    T *p = nullptr;
+    QcDev() = default;
+    QcDev(const QcDev &) = delete;
+    QcDev &operator=(const QcDev &) = delete;
+    int alloc(size_t count) { return !count || hipMalloc(&p, count * sizeof(T)) == hipSuccess ? QC_OK : QC_ERR_HIP; }
+    ~QcDev() { if (p) (void)hipFree(p); }
 };
+using DevBuf = QcDev<double>;
+inline double qc_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- shells, primitives, transforms and nuclei on the device: one blob per handle, uploaded at the first use (qc_one_electron.hip)
+// coff: first Cartesian component of the shell in the Cartesian basis (nc components in all); poff / toff: offsets into exps, coefs / T
+struct QcDevShell { double A[3]; int L, nprim, ncart, nfunc, off, coff, poff, toff, atom, pad; };
+struct QcShellBlob {
+    const QcDevShell *sh; const double *exps, *coefs, *T; const int *Z; const double *xyz;
+    const int *cshell; int nc;              // shell of each Cartesian component
+    QcDev<unsigned char> mem;
+};
+int qc_shell_blob(qc_system *S, const QcShellBlob **out);
 
 // ---- eigensolvers (qc_linalg.hip, qc_eig_tridiag.hip).  dA: the symmetric matrix (left intact), dV0: start vectors, dV: sorted
 // eigenvectors, dw: ascending eigenvalues; all on `st`.  QcEigWork: scratch of one eigensolve in flight, allocated once for a given n -
@@ -348,9 +364,8 @@ struct DevBuf {
 inline size_t qc_eig_small_doubles(int n) { return (size_t)3 * n + 32 + 8; }
 struct QcEigWork {
     DevBuf work, t1, t2, t3, t4, x0, tri, small;
-    int *ctl = nullptr;
+    QcDev<int> ctl;
     int alloc(int n);
-    ~QcEigWork() { if (ctl) (void)hipFree(ctl); }
 };
 // Jacobi kernels: at most this many sweeps; they end after one that met no relative coupling above the tolerance (the sweep itself
 // leaves ~tolerance^2 behind).  notconv (device int, nullable): set to 1 when the sweeps ran out before the criterion was met.

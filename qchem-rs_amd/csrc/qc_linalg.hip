@@ -416,7 +416,7 @@ int QcEigWork::alloc(int n) {
     const size_t nn = (size_t)n * n;
     for (DevBuf *b : {&work, &t1, &t2, &t3, &t4, &x0}) if (b->alloc(nn) != QC_OK) return QC_ERR_HIP;
     if (tri.alloc(qc_eig_tridiag_work_doubles(n)) != QC_OK || small.alloc(qc_eig_small_doubles(n)) != QC_OK) return QC_ERR_HIP;
-    return hipMalloc(&ctl, QC_CTL_EIG_STRIDE * sizeof(int)) == hipSuccess ? QC_OK : QC_ERR_HIP;
+    return ctl.alloc(QC_CTL_EIG_STRIDE);
 }
 
 bool qc_eig_force_jacobi() { static const bool force = getenv("QC_EIG_JACOBI") != nullptr; return force; }

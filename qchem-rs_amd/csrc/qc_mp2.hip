@@ -10,7 +10,6 @@
 // A pair kernel then sums e_ij over (a,b) for every occupied pair, and one workgroup adds the pair sums in a fixed order:
 // no float atomics, so a call is bitwise reproducible.
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 
 #include "qc_internal.h"
@@ -194,17 +193,6 @@ __global__ __launch_bounds__(256) void qc_mp2_sum_kernel(const double *__restric
     if (t == 0) { out[0] = r_os[0]; out[1] = r_ss[0]; }
 }
 
-struct Buf {
-    double *p = nullptr;
-    hipError_t alloc(size_t count) { return count ? hipMalloc(&p, count * sizeof(double)) : hipSuccess; }
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 int qc_mp2_validate(int n, int nspin, const double *eps, const int32_t *nocc, int n_frozen) {
@@ -257,21 +245,17 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
     if (need * 1.05 > (double)free_b) return QC_ERR_UNSUPPORTED;
 
     // 1. the AO tensor
-    const double t0 = now_ms();
-    Buf I, T1, T2, T3, W, P, R;
-    QC_HIP_CHECK(I.alloc(n4));
+    const double t0 = qc_now_ms();
+    DevBuf I, T1, T2, T3, W, P, R;
+    if (I.alloc(n4) != QC_OK) return QC_ERR_HIP;
     QC_HIP_CHECK(hipMemsetAsync(I.p, 0, n4 * sizeof(double), st));
     int rc = qc_launch_eri_full(S, I.p);
     if (rc != QC_OK) return rc;
     QC_HIP_CHECK(hipStreamSynchronize(st));
-    const double t1 = now_ms();
+    const double t1 = qc_now_ms();
     // 2. quarter transformations
-    QC_HIP_CHECK(T1.alloc(t1_max));
-    QC_HIP_CHECK(T2.alloc(t2_total));
-    QC_HIP_CHECK(T3.alloc(t3_max));
-    QC_HIP_CHECK(W.alloc(w_total));
-    QC_HIP_CHECK(P.alloc(2 * p_total));
-    QC_HIP_CHECK(R.alloc(2));
+    if (T1.alloc(t1_max) != QC_OK || T2.alloc(t2_total) != QC_OK || T3.alloc(t3_max) != QC_OK || W.alloc(w_total) != QC_OK ||
+        P.alloc(2 * p_total) != QC_OK || R.alloc(2) != QC_OK) return QC_ERR_HIP;
     for (int s = 0; s < nspin; ++s) {
         if (o[s] == 0 || v[s] == 0) continue;
         const double *Cs = dC + s * nn;
@@ -291,7 +275,7 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
     }
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipStreamSynchronize(st));
-    const double t2 = now_ms();
+    const double t2 = qc_now_ms();
     // 3. pair energies, then their fixed-order sum
     for (const auto &b : blks) {
         const int o1 = o[b.s1], v1 = v[b.s1], o2 = o[b.s2], v2 = v[b.s2];
@@ -305,7 +289,7 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
     double e[2] = {0.0, 0.0};
     QC_HIP_CHECK(hipMemcpyAsync(e, R.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipStreamSynchronize(st));
-    const double t3 = now_ms();
+    const double t3 = qc_now_ms();
     out->e_os = e[0]; out->e_ss = e[1]; out->e_corr = e[0] + e[1];
     out->ms_tensor = t1 - t0; out->ms_transform = t2 - t1; out->ms_energy = t3 - t2;
     return QC_OK;

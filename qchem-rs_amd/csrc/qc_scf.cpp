@@ -4,7 +4,6 @@
 // unrestricted_hartree_fock (uhf.rs:36-167) - guess, DIIS windows, update order, energy expression, diagonal-only
 // convergence test - with every matrix resident in HBM and every step a HIP kernel, the DIIS (<= 9 x 9) QR solve
 // included; the host takes the convergence decision from two scalars it reads back once per pass.
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -16,32 +15,21 @@
 
 namespace {
 
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 // Diis (diis.rs:6-60) with the sample window, the B matrix and the QR solve in HBM / on the device: nothing of it
 // synchronises with the host.  Samples live in ring slots; `slots` lists them newest first.  A singular system
 // ("DIIS failed", rhf.rs:73) raises *d_flag, which the SCF step reads back together with the energy.
 struct DeviceDiis {
     int minlen, maxlen, n;
     std::deque<int> slots;
-    std::vector<double *> pool;            // err of slot s = pool[2s], fock = pool[2s + 1]
-    double *d_dots = nullptr, *d_B = nullptr, *d_c = nullptr;
+    std::vector<DevBuf> pool;              // err of slot s = pool[2s], fock = pool[2s + 1]
+    DevBuf d_dots, d_B, d_c;
     DeviceDiis(int mn, int mx, int n_) : minlen(mn), maxlen(mx), n(n_) {}
-    ~DeviceDiis() {
-        for (auto p : pool) (void)hipFree(p);
-        if (d_dots) (void)hipFree(d_dots);
-        if (d_B) (void)hipFree(d_B);
-        if (d_c) (void)hipFree(d_c);
-    }
     int init() {
         if (maxlen > 11) return QC_ERR_INVALID;
-        for (int i = 0; i < 2 * maxlen; ++i) { double *p; if (hipMalloc(&p, sizeof(double) * n * n) != hipSuccess) return QC_ERR_HIP; pool.push_back(p); }
-        if (hipMalloc(&d_dots, 16 * sizeof(double)) != hipSuccess || hipMalloc(&d_c, 16 * sizeof(double)) != hipSuccess ||
-            hipMalloc(&d_B, sizeof(double) * maxlen * maxlen) != hipSuccess) return QC_ERR_HIP;
-        return hipMemset(d_B, 0, sizeof(double) * maxlen * maxlen) == hipSuccess ? QC_OK : QC_ERR_HIP;
+        pool = std::vector<DevBuf>(2 * maxlen);
+        for (auto &b : pool) if (b.alloc((size_t)n * n) != QC_OK) return QC_ERR_HIP;
+        if (d_dots.alloc(16) != QC_OK || d_c.alloc(16) != QC_OK || d_B.alloc((size_t)maxlen * maxlen) != QC_OK) return QC_ERR_HIP;
+        return hipMemset(d_B.p, 0, sizeof(double) * maxlen * maxlen) == hipSuccess ? QC_OK : QC_ERR_HIP;
     }
     // claim the slot of the next sample (push_front + truncate, diis.rs:29-30: the oldest slot is recycled); the caller
     // writes the error and Fock matrices straight into the returned buffers
@@ -49,21 +37,21 @@ struct DeviceDiis {
         int s;
         if ((int)slots.size() == maxlen) { s = slots.back(); slots.pop_back(); } else s = (int)slots.size();
         slots.push_front(s);
-        *d_err = pool[2 * s]; *d_fock = pool[2 * s + 1];
+        *d_err = pool[2 * s].p; *d_fock = pool[2 * s + 1].p;
     }
     // enqueues: new row of B, coefficient solve, extrapolated Fock matrix into d_out
     int extrapolate(hipStream_t st, double *d_out, int *d_flag) {
         const int m = (int)slots.size();
         const double *ys[12], *fs[12];
         int sl[12];
-        for (int j = 0; j < m; ++j) { sl[j] = slots[j]; ys[j] = pool[2 * slots[j]]; fs[j] = pool[2 * slots[j] + 1]; }
-        qc_dots(st, n, ys[0], ys, m, d_dots);                                         // <e_0, e_j>, diis.rs:43-45
+        for (int j = 0; j < m; ++j) { sl[j] = slots[j]; ys[j] = pool[2 * slots[j]].p; fs[j] = pool[2 * slots[j] + 1].p; }
+        qc_dots(st, n, ys[0], ys, m, d_dots.p);                                        // <e_0, e_j>, diis.rs:43-45
         // (sensitivity probe, QC_DIIS_PERTURB: one dot product moved by one unit in the last place - what a different summation
         // order does - to see how far a run's trajectory depends on such bits)
         static const bool perturb = getenv("QC_DIIS_PERTURB") != nullptr;
-        if (perturb && m > 1) qc_axpby(st, 1, 1.0 + 0x1p-52, d_dots + 1, 0.0, nullptr, d_dots + 1);
-        qc_diis_solve(st, m, minlen, maxlen, sl, d_dots, d_B, d_c, d_flag);           // (1, 0, ...) while m < minlen
-        qc_lincomb_dev(st, n, fs, d_c, m, d_out);                                     // diis.rs:52-58
+        if (perturb && m > 1) qc_axpby(st, 1, 1.0 + 0x1p-52, d_dots.p + 1, 0.0, nullptr, d_dots.p + 1);
+        qc_diis_solve(st, m, minlen, maxlen, sl, d_dots.p, d_B.p, d_c.p, d_flag);         // (1, 0, ...) while m < minlen
+        qc_lincomb_dev(st, n, fs, d_c.p, m, d_out);                               // diis.rs:52-58
         return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
     }
 };
@@ -86,14 +74,10 @@ struct ScfWork {
     bool cold[2] = {false, false};         // this pass's eigensolve of the spin started from the tridiagonal path (no previous vectors involved)
     int npass[2] = {3, 3};                 // refinement passes enqueued per eigensolve (follows what the last one needed)
     int mode[2] = {2, 2};                  // eigensolve of the next pass: 0 refinement, 1 two Jacobi sweeps + refinement, 2 Jacobi
-    int *ctl = nullptr;                    // the pass's QC_CTL_WORDS device control words
+    QcDev<int> ctl;                        // the pass's QC_CTL_WORDS device control words
     double *h_scal = nullptr;              // pinned read-back: the QC_SYNC_WORDS words of pass scalars, then (multi-rank) their complements
-    unsigned long long *d_sync = nullptr;  // multi-rank runs: the same words + their bitwise complements, all-reduced (max) across the ranks
-    ~ScfWork() {
-        if (ctl) (void)hipFree(ctl);
-        if (h_scal) (void)hipHostFree(h_scal);
-        if (d_sync) (void)hipFree(d_sync);
-    }
+    QcDev<unsigned long long> d_sync;      // multi-rank runs: the same words + their bitwise complements, all-reduced (max) across the ranks
+    ~ScfWork() { if (h_scal) (void)hipHostFree(h_scal); }
     int init(int n_, int nsets) {
         n = n_;
         const size_t nn = (size_t)n * n;
@@ -102,19 +86,18 @@ struct ScfWork {
         for (int b = 0; b < nsets; ++b)
             if (eig[b].alloc(n) != QC_OK || Fp[b].alloc(nn) != QC_OK || Fd[b].alloc(nn) != QC_OK) return QC_ERR_HIP;
         if (w.alloc(n) != QC_OK || scal.alloc(16) != QC_OK) return QC_ERR_HIP;
-        if (hipMalloc(&ctl, QC_CTL_WORDS * sizeof(int)) != hipSuccess || hipMemset(ctl, 0, QC_CTL_WORDS * sizeof(int)) != hipSuccess) return QC_ERR_HIP;
+        if (ctl.alloc(QC_CTL_WORDS) != QC_OK || hipMemset(ctl.p, 0, QC_CTL_WORDS * sizeof(int)) != hipSuccess) return QC_ERR_HIP;
         if (hipHostMalloc(&h_scal, (2 * QC_SYNC_WORDS + 1) * sizeof(double)) != hipSuccess) return QC_ERR_HIP;
         std::memset(h_scal, 0, (2 * QC_SYNC_WORDS + 1) * sizeof(double));     // (the last word: sequence number of the pass, see scf_iterate)
-        if (hipMalloc(&d_sync, 2 * QC_SYNC_WORDS * sizeof(unsigned long long)) != hipSuccess) return QC_ERR_HIP;
-        return QC_OK;
+        return d_sync.alloc(2 * QC_SYNC_WORDS);
     }
 };
 
 // sorted_eigs on device (utils.rs:20-36): Fp -> (Cp, w)
 int device_sorted_eigs(qc_system *S, ScfWork &W, double *dA, double *dV, double *dw) {
     // (set-up eigensolves: synchronous)
-    if (W.rotations_only) return qc_eig_device(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl + QC_CTL_NOTCONV);
-    return qc_eig_cold_sync(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl + QC_CTL_SETUP, W.ctl + QC_CTL_NOTCONV);
+    if (W.rotations_only) return qc_eig_device(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl.p + QC_CTL_NOTCONV);
+    return qc_eig_cold_sync(S->stream, W.n, dA, dV, dw, W.eig[0], W.ctl.p + QC_CTL_SETUP, W.ctl.p + QC_CTL_NOTCONV);
 }
 
 // start-up shared by both drivers: H = T + V, X = S^-1/2 (rhf.rs:124-131), Hückel matrix (rhf.rs:141-143)
@@ -181,12 +164,12 @@ int roothaan_enqueue(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *d
     const int n = S->nbasis;
     QcEigWork &E = W.eig[b];
     double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const ctl = W.ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin, *const notconv = W.ctl + QC_CTL_NOTCONV;
+    int *const ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin, *const notconv = W.ctl.p + QC_CTL_NOTCONV;
     if (!have_F) qc_axpby(st, n, 1.0, W.H.p, 1.0, dG, dF);                               // F (else written by the build's closing kernel)
     qc_gemm(st, n, n, n, 1.0, dF, n, false, dD, n, false, 0.0, E.t2.p, n);                  // F D
     qc_gemm(st, n, n, n, 1.0, E.t2.p, n, false, W.S.p, n, false, 0.0, W.Fp[b].p, n);        // F D S
     qc_sub_transpose(st, n, W.Fp[b].p, dE);                                                 // e = FDS - (FDS)^T = FDS - SDF
-    int rc = diis.extrapolate(st, W.Fd[b].p, W.ctl + QC_CTL_DIIS);
+    int rc = diis.extrapolate(st, W.Fd[b].p, W.ctl.p + QC_CTL_DIIS);
     if (rc != QC_OK) return rc;
     qc_gemm(st, n, n, n, 1.0, W.Fd[b].p, n, false, W.X.p, n, false, 0.0, E.t1.p, n);        // F X
     qc_gemm(st, n, n, n, 1.0, W.X.p, n, true, E.t1.p, n, false, 0.0, Fps, n);               // X^T (F X)
@@ -219,17 +202,17 @@ int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG,
     a.E_out = dE;
     a.m = (int)diis.slots.size(); a.minlen = diis.minlen; a.maxlen = diis.maxlen;
     a.dots_generic = W.rotations_only ? 1 : 0;
-    for (int j = 0; j < a.m; ++j) { a.slot[j] = diis.slots[j]; a.errs[j] = diis.pool[2 * diis.slots[j]]; a.focks[j] = diis.pool[2 * diis.slots[j] + 1]; }
-    a.Bmat = diis.d_B; a.c_out = diis.d_c; a.diis_flag = W.ctl + QC_CTL_DIIS;
+    for (int j = 0; j < a.m; ++j) { a.slot[j] = diis.slots[j]; a.errs[j] = diis.pool[2 * diis.slots[j]].p; a.focks[j] = diis.pool[2 * diis.slots[j] + 1].p; }
+    a.Bmat = diis.d_B.p; a.c_out = diis.d_c.p; a.diis_flag = W.ctl.p + QC_CTL_DIIS;
     a.Fp = W.Fps[spin].p;
-    a.ctl = W.ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin;
+    a.ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin;
     a.Cp_out = W.CpNew[spin].p; a.w_out = dw_out; a.C_out = dC; a.Dn = tl.Dn; a.Dold = tl.Dold; a.nocc = tl.nocc; a.dfac = tl.dfac;
     a.scal_out = tl.scal_out; a.ctl_all = tl.ctl_all; a.ctl_out = tl.ctl_out; a.fxs_out = tl.fxs_out; a.imax = S->imax;
     a.seq_out = tl.seq_out; a.seq = tl.seq;
     a.tl = S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
     QcEigWork &E = W.eig[b];
     double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const notconv = W.ctl + QC_CTL_NOTCONV;
+    int *const notconv = W.ctl.p + QC_CTL_NOTCONV;
     const EigRoute route = eig_route(W, spin, n);
     W.cold[spin] = route == EigRoute::Tridiag;
     int rc = QC_OK;
@@ -257,7 +240,7 @@ int roothaan_redo_eig(qc_system *S, ScfWork &W, double *dw_out, double *dC, int 
     hipStream_t st = S->stream;
     QcEigWork &E = W.eig[0];
     double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const notconv = W.ctl + QC_CTL_NOTCONV;
+    int *const notconv = W.ctl.p + QC_CTL_NOTCONV;
     const EigRoute again = W.cold[spin] ? (W.have_prev[spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold)
                                         : (W.rotations_only ? EigRoute::Refine : EigRoute::Tridiag);
     int rc = QC_OK;
@@ -265,7 +248,7 @@ int roothaan_redo_eig(qc_system *S, ScfWork &W, double *dw_out, double *dC, int 
     case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
     case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); break;
     case EigRoute::Refine: rc = qc_eig_device_refine(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
-    case EigRoute::Tridiag: rc = qc_eig_cold_sync(st, n, Fps, CpNew, dw_out, E, W.ctl + QC_CTL_SETUP, notconv); break;
+    case EigRoute::Tridiag: rc = qc_eig_cold_sync(st, n, Fps, CpNew, dw_out, E, W.ctl.p + QC_CTL_SETUP, notconv); break;
     }
     if (rc != QC_OK) return rc;
     qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, CpNew, n, false, 0.0, dC, n);
@@ -318,10 +301,10 @@ static void scf_state_delete(qc_scf_state *st) {
 // (hDa / hDb non-null: the caller's densities, host, in place of the Hueckel guess - qc_scf_begin_*_from)
 static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out, const double *hDa = nullptr, const double *hDb = nullptr) {
     if (!S || !out) return QC_ERR_INVALID;
-    const double t0 = now_ms();
+    const double t0 = qc_now_ms();
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
     double tt = t0;
-    auto lap = [&](const char *what) { if (sdbg) { const double t = now_ms(); fprintf(stderr, "[setup] %-28s %.3f ms\n", what, t - tt); tt = t; } };
+    auto lap = [&](const char *what) { if (sdbg) { const double t = qc_now_ms(); fprintf(stderr, "[setup] %-28s %.3f ms\n", what, t - tt); tt = t; } };
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
     lap("qc_device_init (total)");
@@ -367,7 +350,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
         size_t free_b = 0, total_b = 0;
         QC_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
         if ((double)n4 * 8.0 * 2.2 > (double)free_b) return QC_ERR_UNSUPPORTED;
-        const double tt0 = now_ms();
+        const double tt0 = qc_now_ms();
         DevBuf I;
         if (I.alloc(n4) != QC_OK || st->T4.alloc(n4) != QC_OK) return QC_ERR_HIP;
         QC_HIP_CHECK(hipMemsetAsync(I.p, 0, n4 * sizeof(double), S->stream));
@@ -381,7 +364,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
         }
         QC_HIP_CHECK(hipStreamSynchronize(S->stream));
         st->stored = true;
-        st->ms_tensor = now_ms() - tt0;
+        st->ms_tensor = qc_now_ms() - tt0;
     }
     for (int s = 0; s < nspin; ++s) {                                     // Diis::new(4,6) rhf.rs:65 / (2,8) uhf.rs:76-78
         st->diis[s] = uhf ? new DeviceDiis(2, 8, n) : new DeviceDiis(4, 6, n);
@@ -389,10 +372,10 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     }
     for (auto &set : st->evs) for (hipEvent_t &e : set) QC_HIP_CHECK(hipEventCreate(&e));
     int eig_flag = 0;                                                     // the eigensolves of X and of the Hueckel guess
-    QC_HIP_CHECK(hipMemcpyAsync(&eig_flag, st->W.ctl + QC_CTL_NOTCONV, sizeof(int), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(&eig_flag, st->W.ctl.p + QC_CTL_NOTCONV, sizeof(int), hipMemcpyDeviceToHost, S->stream));
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
     if (eig_flag) return QC_EIG_NOT_CONVERGED;
-    st->ms_setup = now_ms() - t0;
+    st->ms_setup = qc_now_ms() - t0;
     *out = guard.release();
     return QC_OK;
 }
@@ -427,7 +410,7 @@ static hipError_t wait_event(hipEvent_t ev) {
     double t0 = 0.0;
     while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
         if ((++spins & 0x3fff) == 0) {
-            const double t = now_ms();
+            const double t = qc_now_ms();
             if (t0 == 0.0) t0 = t;
             else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return hipErrorLaunchTimeOut; }
         }
@@ -448,7 +431,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     hipStream_t sm = S->stream;
     const int nspin = st->uhf ? 2 : 1;
     int rc;
-    const double th0 = now_ms();
+    const double th0 = qc_now_ms();
     qc_stamp("enter pass");
     if ((rc = qc_tl_begin_pass(S)) != QC_OK) return rc;
     st->ev_cur ^= 1;
@@ -475,11 +458,11 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         QC_HIP_CHECK(hipEventRecord(ev0, sm));
         qc_stamp("ev0");
         const int tunes0 = S->tune_count;
-        const double tt0 = now_ms();
+        const double tt0 = qc_now_ms();
         if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dG + nn : nullptr, st->uhf,
                                        &st->twin, W.H.p, dF[0], dF[1], &have_F, st)) != QC_OK) return rc;
         st->cur_build_tuned = S->tune_count != tunes0;
-        if (st->cur_build_tuned) st->ms_tuner += now_ms() - tt0;
+        if (st->cur_build_tuned) st->ms_tuner += qc_now_ms() - tt0;
         st->cur_build_gen = S->assign_gen;
     }
     qc_stamp("build out");
@@ -511,22 +494,22 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     // deterministic and starts from bit-identical G (integer all-reduce), so the copies agree; this makes a divergence an
     // error on all ranks in the same pass instead of a hang in the next all-reduce.
     const bool multi = S->comm != nullptr;
-    double *scal_out = multi ? reinterpret_cast<double *>(W.d_sync) : W.h_scal;
-    int *ctl_out = multi ? reinterpret_cast<int *>(W.d_sync + 4) : h_ctl;
+    double *scal_out = multi ? reinterpret_cast<double *>(W.d_sync.p) : W.h_scal;
+    int *ctl_out = multi ? reinterpret_cast<int *>(W.d_sync.p + 4) : h_ctl;
     bool dens_done[2] = {false, spin_par};                               // (the beta density of a spin-parallel pass was formed on the side stream)
     auto density_and_scalars = [&](int s, bool hand_over) -> int {
         if (dens_done[s]) dens_done[s] = false;                          // (once: a repeat of the eigensolve forms it again, here)
         else if (st->nocc[s] > 0) qc_gemm(sm, n, n, st->nocc[s], st->uhf ? 1.0 : 2.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
         else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), sm));
         // energy and rms straight into pinned host memory; the last spin's kernel also hands over and clears the control words
-        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, dG + s * nn, scal_out + 2 * s, hand_over ? W.ctl : nullptr, ctl_out);
+        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, dG + s * nn, scal_out + 2 * s, hand_over ? W.ctl.p : nullptr, ctl_out);
         return QC_OK;
     };
     auto publish_scalars = [&]() -> int {
         if (!multi) return QC_OK;
-        qc_sync_pack(sm, W.d_sync, QC_SYNC_WORDS);
-        if (qc_rccl().AllReduce(W.d_sync, W.d_sync, 2 * QC_SYNC_WORDS, ncclUint64, ncclMax, (ncclComm_t)S->comm, sm) != ncclSuccess) return QC_ERR_RCCL;
-        QC_HIP_CHECK(hipMemcpyAsync(W.h_scal, W.d_sync, 2 * QC_SYNC_WORDS * sizeof(double), hipMemcpyDeviceToHost, sm));
+        qc_sync_pack(sm, W.d_sync.p, QC_SYNC_WORDS);
+        if (qc_rccl().AllReduce(W.d_sync.p, W.d_sync.p, 2 * QC_SYNC_WORDS, ncclUint64, ncclMax, (ncclComm_t)S->comm, sm) != ncclSuccess) return QC_ERR_RCCL;
+        QC_HIP_CHECK(hipMemcpyAsync(W.h_scal, W.d_sync.p, 2 * QC_SYNC_WORDS * sizeof(double), hipMemcpyDeviceToHost, sm));
         return QC_OK;
     };
     auto ranks_agree = [&]() -> bool {
@@ -535,7 +518,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         for (int i = 0; i < QC_SYNC_WORDS; ++i) if (w[QC_SYNC_WORDS + i] != ~w[i]) return false;
         return true;
     };
-    if (multi && nspin == 1) QC_HIP_CHECK(hipMemsetAsync(W.d_sync + 2, 0, 2 * sizeof(double), sm));       // unused spin slot
+    if (multi && nspin == 1) QC_HIP_CHECK(hipMemsetAsync(W.d_sync.p + 2, 0, 2 * sizeof(double), sm));       // unused spin slot
     bool scale_in_kernel = false;
     // Single-rank runs on the one-workgroup path: the kernel that ends the pass stores the pass's sequence number into pinned memory
     // after the scalars and control words, and the host polls THAT instead of the event behind it (a few microseconds earlier per pass).
@@ -553,13 +536,13 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
             if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl,
                                      s == 1 ? side : nullptr, s)) != QC_OK) return rc;
         }
-        if ((rc = qc_spin_join_end(S, W.ctl, ctl_out, seq_wait ? h_seq : nullptr, st->pass_seq + 1)) != QC_OK) return rc;
+        if ((rc = qc_spin_join_end(S, W.ctl.p, ctl_out, seq_wait ? h_seq : nullptr, st->pass_seq + 1)) != QC_OK) return rc;
     } else if (W.small_fused) {
         for (int s = 0; s < nspin; ++s) {
             // (RHF, direct fixed-point builds: the kernel that forms the new density also leaves the next build's fixed-point unit)
             const bool scale_here = !st->uhf && !st->stored && S->accum_fx;
             scale_in_kernel = scale_here;
-            SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl : nullptr, ctl_out,
+            SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl.p : nullptr, ctl_out,
                          scale_here ? S->d_fxs : nullptr};
             if (seq_wait && s == nspin - 1) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
             if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
@@ -573,7 +556,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     qc_stamp("roothaan out");
     QC_HIP_CHECK(hipEventRecord(ev2, sm));
     qc_stamp("ev2");
-    const double th1 = now_ms();
+    const double th1 = qc_now_ms();
     if (seq_wait) {
         const unsigned want = st->pass_seq + 1;
         unsigned spins = 0;
@@ -582,7 +565,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
             if ((++spins & 0xfff) == 0) {                   // (a failed launch or a fault never stores the word: the event knows)
                 const hipError_t e = hipEventQuery(ev2);
                 if (e == hipErrorNotReady) {
-                    const double t = now_ms();
+                    const double t = qc_now_ms();
                     if (t0 == 0.0) t0 = t;
                     else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return QC_ERR_HIP; }
                     continue;
@@ -597,7 +580,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         // leaves the fixed-point unit itself and the fold left the planes clean.)
         if (!st->stored && S->prep_enqueued) QC_HIP_CHECK(wait_event(ev2));
     } else QC_HIP_CHECK(wait_event(ev2));
-    const double th2 = now_ms();
+    const double th2 = qc_now_ms();
     qc_stamp("pass seen");
     if ((rc = qc_join_check(S)) != QC_OK) return rc;                     // (the join of this pass's build is in front of everything waited for)
     qc_gate_quiet(S);                                                    // (nothing of this handle waits on the device any more)
@@ -610,7 +593,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     if (dbg) {   // the pass's DIIS coefficients (diis.rs:50-51), newest sample first
         double c[12] = {0};
         const int m = (int)st->diis[0]->slots.size();
-        (void)hipMemcpy(c, st->diis[0]->d_c, m * sizeof(double), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(c, st->diis[0]->d_c.p, m * sizeof(double), hipMemcpyDeviceToHost);
         fprintf(stderr, "[scf] diis c:");
         for (int j = 0; j < m; ++j) fprintf(stderr, " %.3e", c[j]);
         fprintf(stderr, "\n");
@@ -636,8 +619,8 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         st->redos += 1;
         // the repeated eigensolves report through the same control words (Jacobi sweeps exhausted: QC_CTL_NOTCONV): hand them over again,
         // whichever spin was repeated, and clear them for the next pass
-        QC_HIP_CHECK(hipMemcpyAsync(ctl_out, W.ctl, QC_CTL_WORDS * sizeof(int), hipMemcpyDefault, sm));
-        QC_HIP_CHECK(hipMemsetAsync(W.ctl, 0, QC_CTL_WORDS * sizeof(int), sm));
+        QC_HIP_CHECK(hipMemcpyAsync(ctl_out, W.ctl.p, QC_CTL_WORDS * sizeof(int), hipMemcpyDefault, sm));
+        QC_HIP_CHECK(hipMemsetAsync(W.ctl.p, 0, QC_CTL_WORDS * sizeof(int), sm));
         if ((rc = publish_scalars()) != QC_OK) return rc;
         scale_in_kernel = false;
         if ((rc = prepare_next()) != QC_OK) return rc;                    // (the density changed)
@@ -676,7 +659,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
 
 static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, bool uhf) {
     if (!S || !cfg || !out || !out->orbital_energies || (uhf && !out->orbital_energies_beta)) return QC_ERR_INVALID;
-    const double t_begin = now_ms();
+    const double t_begin = qc_now_ms();
     qc_scf_state *st = nullptr;
     int rc = scf_begin(S, uhf, cfg->n_alpha, cfg->n_beta, &st);
     if (rc != QC_OK) return rc;
@@ -704,7 +687,7 @@ static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, boo
     }
     scf_flush_timing(st);
     out->ms_setup = st->ms_setup; out->ms_fock_total = st->ms_fock; out->ms_linalg_total = st->ms_linalg;
-    out->ms_total = now_ms() - t_begin;
+    out->ms_total = qc_now_ms() - t_begin;
     out->ms_tuner = st->ms_tuner;
     return status;
 }

@@ -12,7 +12,6 @@
 // index order, the 64 lanes of a wave by a shuffle tree, the waves in order) and the Fock build accumulates integers: a call is bitwise
 // reproducible.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -26,11 +25,6 @@ constexpr int QC_STAB_MAXROOTS = 8;
 constexpr int QC_STAB_MAXSUB = 40;            // rows of the subspace: full -> collapse onto the Ritz vectors of the requested roots
 constexpr double QC_STAB_DENOM_FLOOR = 1e-4;  // |e_a - e_i - theta| of the diagonal preconditioner is not allowed below this
 constexpr double QC_STAB_KEEP = 1e-4;         // a correction vector that loses more than this factor to the orthogonalisation is dropped
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // sum of `s` over the workgroup, the same bits in every thread: lanes by a shuffle tree, waves in index order (sh: 16 doubles)
 __device__ __forceinline__ double qc_stab_block_sum(double s, double *sh) {
@@ -224,14 +218,14 @@ struct StabSigma {
             hipLaunchKernelGGL(qc_stab_symmetrize_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, n, rhf_build ? 2.0 : 1.0, Q.p, Db,
                                triplet ? D1.p + nn : nullptr);
         }
-        const double t0 = now_ms();
+        const double t0 = qc_now_ms();
         int rc = rhf_build ? qc_fock_build_device(S, D1.p, nullptr, G.p, nullptr, false)
                            : qc_fock_build_device(S, D1.p, D1.p + nn, G.p, G.p + nn, true);
         if (rc != QC_OK) return rc;
         QC_HIP_CHECK(hipStreamSynchronize(st));
         if ((rc = qc_join_check(S)) != QC_OK) return rc;
         qc_gate_quiet(S);
-        ms_builds += now_ms() - t0; builds += 1;
+        ms_builds += qc_now_ms() - t0; builds += 1;
         for (int b = 0; b < L.nblk; ++b) {
             if (L.o[b] == 0 || L.v[b] == 0) continue;
             const double *Cb = dC + b * nn;
@@ -246,11 +240,6 @@ struct StabSigma {
     }
 };
 
-struct DevInts {
-    int *p = nullptr;
-    ~DevInts() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 int qc_stability_dim(int n, bool uhf, const int *nocc) { return StabLayout(n, uhf, nocc).dim; }
@@ -258,7 +247,7 @@ int qc_stability_dim(int n, bool uhf, const int *nocc) { return StabLayout(n, uh
 // Lowest `nroots` eigenpairs of (A + B) at the orbitals dC / energies dEps (device; nblk blocks).  io: kind, nroots, tol, max_iterations
 // checked by the caller.  vectors (host, nullable): nroots x dim.
 int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_stability *io, double *vectors) {
-    const double t_begin = now_ms();
+    const double t_begin = qc_now_ms();
     const int n = S->nbasis, nroots = io->nroots;
     const StabLayout L(n, uhf, nocc);
     const int dim = L.dim;
@@ -280,12 +269,11 @@ int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *d
 
     StabSigma sigma(S, L, uhf, io->kind, dC, dDe.p);
     DevBuf V, Sg, Wk, dM, dY, dTheta, dInfo;
-    DevInts dCnt;
+    QcDev<int> dCnt;
     const size_t rows = (size_t)msub + 1;
     if (sigma.alloc() != QC_OK || V.alloc(rows * dim) != QC_OK || Sg.alloc(rows * dim) != QC_OK || Wk.alloc(2 * (size_t)QC_STAB_MAXROOTS * dim) != QC_OK ||
         dM.alloc((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB) != QC_OK || dY.alloc((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB) != QC_OK ||
-        dTheta.alloc(QC_STAB_MAXROOTS) != QC_OK || dInfo.alloc(2 * (QC_STAB_MAXSUB + 1)) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipMalloc(&dCnt.p, sizeof(int)));
+        dTheta.alloc(QC_STAB_MAXROOTS) != QC_OK || dInfo.alloc(2 * (QC_STAB_MAXSUB + 1)) != QC_OK || dCnt.alloc(1) != QC_OK) return QC_ERR_HIP;
 
     // Start vectors: unit vectors on the smallest e_a - e_i (ties: lower index first); a subspace that can hold the whole space starts as
     // the whole space.  Unit vectors carry the symmetry of one orbital pair, and a Krylov space never leaves the symmetries it starts
@@ -379,7 +367,7 @@ int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *d
     }
     QC_HIP_CHECK(hipGetLastError());
     io->ms_builds = sigma.ms_builds;
-    io->ms_total = now_ms() - t_begin;
+    io->ms_total = qc_now_ms() - t_begin;
     return converged ? QC_OK : QC_NOT_CONVERGED;
 }
 

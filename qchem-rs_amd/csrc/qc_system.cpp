@@ -14,23 +14,16 @@
 
 #include <cstdlib>
 
-#include "qc_internal.h"
+#include "qc_md.h"
 
 namespace {
 
 double dfact(int n) { double r = 1.0; for (; n > 1; n -= 2) r *= n; return r; }
 double binom(int n, int k) { if (k < 0 || k > n) return 0.0; double r = 1.0; for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i; return r; }
 
-struct Cart { int x, y, z; };
-std::vector<Cart> cart_list(int L) {
-    std::vector<Cart> v;
-    for (int lx = L; lx >= 0; --lx) for (int ly = L - lx; ly >= 0; --ly) v.push_back({lx, ly, L - lx - ly});
-    return v;
-}
-
 // real solid harmonic S_lm in Cartesian monomials, Helgaker-Jorgensen-Olsen eq. 6.4.47 (scale fixed afterwards)
-std::vector<double> solid_row(int l, int m, const std::vector<Cart> &cl) {
-    std::vector<double> row(cl.size(), 0.0);
+std::vector<double> solid_row(int l, int m) {
+    std::vector<double> row(qc_ncart(l), 0.0);
     const int am = std::abs(m), neg = m < 0 ? 1 : 0;
     for (int t = 0; 2 * t <= l - am; ++t)
         for (int u = 0; u <= t; ++u)
@@ -39,77 +32,40 @@ std::vector<double> solid_row(int l, int m, const std::vector<Cart> &cl) {
                 double c = ((t + k) & 1 ? -1.0 : 1.0) * std::pow(0.25, t) * binom(l, t) * binom(l - t, am + t) * binom(t, u) * binom(am, tv);
                 const int ex = 2 * t + am - 2 * u - tv, ey = 2 * u + tv, ez = l - 2 * t - am;
                 if (ex < 0) continue;
-                for (size_t i = 0; i < cl.size(); ++i)
-                    if (cl[i].x == ex && cl[i].y == ey && cl[i].z == ez) row[i] += c;
+                for (int i = 0; i < qc_ncart(l); ++i) {
+                    const unsigned char *ci = qc_md_cart(l, i);
+                    if (ci[0] == ex && ci[1] == ey && ci[2] == ez) row[i] += c;
+                }
             }
     return row;
 }
 
 double mono_overlap_1d(int n, double p) { return (n & 1) ? 0.0 : dfact(n - 1) / std::pow(2.0 * p, n / 2) * std::sqrt(M_PI / p); }
 
-// 1-D Hermite expansion coefficients E[i][j][t], i<=imax, j<=jmax (flat, stride helpers)
-struct E1 {
-    int imax, jmax, tdim;
-    std::vector<double> v;
-    E1(int im, int jm) : imax(im), jmax(jm), tdim(im + jm + 2), v((size_t)(im + 1) * (jm + 1) * (im + jm + 2), 0.0) {}
-    double &at(int i, int j, int t) { return v[((size_t)i * (jmax + 1) + j) * tdim + t]; }
-    double get(int i, int j, int t) const { return (t < 0 || t > i + j) ? 0.0 : v[((size_t)i * (jmax + 1) + j) * tdim + t]; }
-};
-E1 hermite_e(int imax, int jmax, double a, double b, double Q) {
-    E1 E(imax, jmax);
-    const double p = a + b, h = 0.5 / p, xpa = -b / p * Q, xpb = a / p * Q;
-    E.at(0, 0, 0) = std::exp(-a * b / p * Q * Q);
-    for (int i = 1; i <= imax; ++i)
-        for (int t = 0; t <= i; ++t)
-            E.at(i, 0, t) = h * E.get(i - 1, 0, t - 1) + xpa * E.get(i - 1, 0, t) + (t + 1) * E.get(i - 1, 0, t + 1);
-    for (int j = 1; j <= jmax; ++j)
-        for (int i = 0; i <= imax; ++i)
-            for (int t = 0; t <= i + j; ++t)
-                E.at(i, j, t) = h * E.get(i, j - 1, t - 1) + xpb * E.get(i, j - 1, t) + (t + 1) * E.get(i, j - 1, t + 1);
-    return E;
-}
+// one axis' expansion table, i <= la, j <= lb + 2 (kinetic energy)
+using E1 = QcMdE1<(QC_LMAX + 1) * (QC_LMAX + 3) * (2 * QC_LMAX + 3)>;
 
 // Hermite Coulomb integrals R^0_tuv, t+u+v <= L (host, for the nuclear-attraction matrix)
 void hermite_r_host(int L, double alpha, const double PC[3], std::vector<double> &R0) {
     std::vector<std::vector<double>> W(L + 1, std::vector<double>(qc_nherm(L), 0.0));
     std::vector<double> F(L + 1);
-    qc_boys_host(L, alpha * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]), F.data());
+    qc_md_boys(L, alpha * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]), F.data());
     double f = 1.0;
-    for (int n = 0; n <= L; ++n) { W[n][0] = f * F[n]; f *= -2.0 * alpha; }
+    for (int n = 0; n <= L; ++n) { W[n][0] = f * F[n]; f *= -2.0 * alpha; }      // (the seeds: a running product here, see qc_md.h)
     for (int N = 1; N <= L; ++N)
         for (int n = 0; n + N <= L; ++n)
             for (int t = N; t >= 0; --t)
-                for (int u = N - t; u >= 0; --u) {
-                    const int v = N - t - u;
-                    double val;
-                    if (t) val = PC[0] * W[n + 1][qc_hidx(t - 1, u, v)] + (t > 1 ? (t - 1) * W[n + 1][qc_hidx(t - 2, u, v)] : 0.0);
-                    else if (u) val = PC[1] * W[n + 1][qc_hidx(t, u - 1, v)] + (u > 1 ? (u - 1) * W[n + 1][qc_hidx(t, u - 2, v)] : 0.0);
-                    else val = PC[2] * W[n + 1][qc_hidx(t, u, v - 1)] + (v > 1 ? (v - 1) * W[n + 1][qc_hidx(t, u, v - 2)] : 0.0);
-                    W[n][qc_hidx(t, u, v)] = val;
-                }
+                for (int u = N - t; u >= 0; --u) W[n][qc_hidx(t, u, N - t - u)] = qc_md_r_step(W[n + 1].data(), t, u, N - t - u, PC);
     R0 = W[0];
 }
 
 }  // namespace
 
-// F_n(x), n = 0..nmax: Kummer series at nmax + downward recursion; erf + upward recursion for large x.
-void qc_boys_host(int nmax, double x, double *F) {
-    const double ex = std::exp(-x);
-    if (x < 38.0) {
-        double term = 1.0 / (2 * nmax + 1), sum = term;
-        for (int k = 1; k < 500; ++k) { term *= 2.0 * x / (2 * nmax + 2 * k + 1); sum += term; if (term < 1e-18 * sum) break; }
-        F[nmax] = ex * sum;
-        for (int n = nmax; n > 0; --n) F[n - 1] = (2.0 * x * F[n] + ex) / (2 * n - 1);
-    } else {
-        F[0] = 0.5 * std::sqrt(M_PI / x) * std::erf(std::sqrt(x));
-        for (int n = 0; n < nmax; ++n) F[n + 1] = ((2 * n + 1) * F[n] - ex) / (2.0 * x);
-    }
-}
+void qc_boys_host(int nmax, double x, double *F) { qc_md_boys(nmax, x, F); }
 
 static void normalise_shell(QcShell &sh) {
     const int L = sh.L;
-    auto cl = cart_list(L);
-    sh.ncart = (int)cl.size();
+    sh.ncart = qc_ncart(L);
     sh.nfunc = sh.pure ? 2 * L + 1 : sh.ncart;
     for (int i = 0; i < sh.nprim; ++i) {
         const double a = sh.exps[i];
@@ -117,7 +73,7 @@ static void normalise_shell(QcShell &sh) {
     }
     sh.T.assign((size_t)sh.nfunc * sh.ncart, 0.0);
     if (sh.pure) {
-        for (int m = -L; m <= L; ++m) { auto r = solid_row(L, m, cl); std::copy(r.begin(), r.end(), sh.T.begin() + (size_t)(m + L) * sh.ncart); }
+        for (int m = -L; m <= L; ++m) { auto r = solid_row(L, m); std::copy(r.begin(), r.end(), sh.T.begin() + (size_t)(m + L) * sh.ncart); }
     } else {
         for (int c = 0; c < sh.ncart; ++c) sh.T[(size_t)c * sh.ncart + c] = 1.0;
     }
@@ -125,12 +81,12 @@ static void normalise_shell(QcShell &sh) {
     std::vector<double> M((size_t)sh.ncart * sh.ncart, 0.0);
     for (int c1 = 0; c1 < sh.ncart; ++c1)
         for (int c2 = 0; c2 < sh.ncart; ++c2) {
+            const unsigned char *l1 = qc_md_cart(L, c1), *l2 = qc_md_cart(L, c2);
             double s = 0.0;
             for (int i = 0; i < sh.nprim; ++i)
                 for (int j = 0; j < sh.nprim; ++j) {
                     const double p = sh.exps[i] + sh.exps[j];
-                    s += sh.coefs[i] * sh.coefs[j] * mono_overlap_1d(cl[c1].x + cl[c2].x, p) * mono_overlap_1d(cl[c1].y + cl[c2].y, p) *
-                         mono_overlap_1d(cl[c1].z + cl[c2].z, p);
+                    s += sh.coefs[i] * sh.coefs[j] * mono_overlap_1d(l1[0] + l2[0], p) * mono_overlap_1d(l1[1] + l2[1], p) * mono_overlap_1d(l1[2] + l2[2], p);
                 }
             M[(size_t)c1 * sh.ncart + c2] = s;
         }
@@ -149,28 +105,30 @@ static void pair_hermite_matrix(const QcShell &A, const QcShell &B, int i, int j
     const double a = A.exps[i], b = B.exps[j], p = a + b;
     for (int k = 0; k < 3; ++k) P[k] = (a * A.A[k] + b * B.A[k]) / p;
     *p_out = p;
-    E1 Ex = hermite_e(la, lb, a, b, A.A[0] - B.A[0]), Ey = hermite_e(la, lb, a, b, A.A[1] - B.A[1]), Ez = hermite_e(la, lb, a, b, A.A[2] - B.A[2]);
-    auto ca = cart_list(la), cb = cart_list(lb);
+    E1 E[3];
+    for (int k = 0; k < 3; ++k) E[k].fill(la, lb, a, b, A.A[k] - B.A[k]);
+    const size_t nca = A.ncart, ncb = B.ncart;
     const double cc = A.coefs[i] * B.coefs[j] * scale;
-    std::vector<double> Ec((size_t)ca.size() * cb.size() * nh, 0.0);
-    for (size_t x = 0; x < ca.size(); ++x)
-        for (size_t y = 0; y < cb.size(); ++y) {
-            double *row = &Ec[(x * cb.size() + y) * nh];
-            for (int t = 0; t <= ca[x].x + cb[y].x; ++t)
-                for (int u = 0; u <= ca[x].y + cb[y].y; ++u)
-                    for (int v = 0; v <= ca[x].z + cb[y].z; ++v)
-                        row[qc_hidx(t, u, v)] = cc * Ex.get(ca[x].x, cb[y].x, t) * Ey.get(ca[x].y, cb[y].y, u) * Ez.get(ca[x].z, cb[y].z, v);
+    std::vector<double> Ec(nca * ncb * nh, 0.0);
+    for (size_t x = 0; x < nca; ++x)
+        for (size_t y = 0; y < ncb; ++y) {
+            const unsigned char *ca = qc_md_cart(la, (int)x), *cb = qc_md_cart(lb, (int)y);
+            double *row = &Ec[(x * ncb + y) * nh];
+            for (int t = 0; t <= ca[0] + cb[0]; ++t)
+                for (int u = 0; u <= ca[1] + cb[1]; ++u)
+                    for (int v = 0; v <= ca[2] + cb[2]; ++v)
+                        row[qc_hidx(t, u, v)] = cc * E[0].g(ca[0], cb[0], t) * E[1].g(ca[1], cb[1], u) * E[2].g(ca[2], cb[2], v);
         }
     std::fill(out, out + (size_t)nh * nab, 0.0);
     for (int fa = 0; fa < A.nfunc; ++fa)
-        for (size_t x = 0; x < ca.size(); ++x) {
+        for (size_t x = 0; x < nca; ++x) {
             const double ta = A.T[(size_t)fa * A.ncart + x];
             if (ta == 0.0) continue;
             for (int fb = 0; fb < B.nfunc; ++fb)
-                for (size_t y = 0; y < cb.size(); ++y) {
+                for (size_t y = 0; y < ncb; ++y) {
                     const double tb = ta * B.T[(size_t)fb * B.ncart + y];
                     if (tb == 0.0) continue;
-                    const double *row = &Ec[(x * cb.size() + y) * nh];
+                    const double *row = &Ec[(x * ncb + y) * nh];
                     for (int h = 0; h < nh; ++h) out[(size_t)h * nab + fa * B.nfunc + fb] += tb * row[h];
                 }
         }
@@ -760,51 +718,40 @@ void qc_host_one_electron(const qc_system *S, int which, double *out) {
     for (int a = 0; a < S->nshells; ++a)
         for (int b = 0; b <= a; ++b) {
             const QcShell &A = S->shells[a], &B = S->shells[b];
-            auto ca = cart_list(A.L), cb = cart_list(B.L);
-            std::vector<double> cart(ca.size() * cb.size(), 0.0);
+            const size_t nca = A.ncart, ncb = B.ncart;
+            std::vector<double> cart(nca * ncb, 0.0);
             for (int i = 0; i < A.nprim; ++i)
                 for (int j = 0; j < B.nprim; ++j) {
                     const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
                     double P[3];
                     for (int k = 0; k < 3; ++k) P[k] = (ea * A.A[k] + eb * B.A[k]) / p;
-                    E1 E[3] = {hermite_e(A.L, B.L + 2, ea, eb, A.A[0] - B.A[0]), hermite_e(A.L, B.L + 2, ea, eb, A.A[1] - B.A[1]),
-                               hermite_e(A.L, B.L + 2, ea, eb, A.A[2] - B.A[2])};
+                    E1 E[3];
+                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L + 2, ea, eb, A.A[k] - B.A[k]);
                     const double s3 = std::pow(M_PI / p, 1.5);
-                    for (size_t x = 0; x < ca.size(); ++x)
-                        for (size_t y = 0; y < cb.size(); ++y) {
-                            const int ai[3] = {ca[x].x, ca[x].y, ca[x].z}, bi[3] = {cb[y].x, cb[y].y, cb[y].z};
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
                             double val = 0.0;
                             if (which == 0) {
-                                val = s3 * E[0].get(ai[0], bi[0], 0) * E[1].get(ai[1], bi[1], 0) * E[2].get(ai[2], bi[2], 0);
+                                val = qc_md_ovl(E, ai, bi, s3);
                             } else if (which == 1) {
-                                // -1/2 d^2/dx^2 acting on the ket primitive, one axis at a time
-                                double s1[3], t1[3];
-                                for (int k = 0; k < 3; ++k) {
-                                    s1[k] = E[k].get(ai[k], bi[k], 0);
-                                    t1[k] = 4.0 * eb * eb * E[k].get(ai[k], bi[k] + 2, 0) - 2.0 * eb * (2 * bi[k] + 1) * s1[k];
-                                    if (bi[k] >= 2) t1[k] += bi[k] * (bi[k] - 1) * E[k].get(ai[k], bi[k] - 2, 0);
-                                }
-                                val = -0.5 * s3 * (t1[0] * s1[1] * s1[2] + s1[0] * t1[1] * s1[2] + s1[0] * s1[1] * t1[2]);
+                                val = -0.5 * s3 * qc_md_kin(E, ai, bi, eb);
                             } else {
                                 for (int c = 0; c < S->natoms; ++c) {
                                     const double PC[3] = {P[0] - S->xyz[3 * c], P[1] - S->xyz[3 * c + 1], P[2] - S->xyz[3 * c + 2]};
                                     hermite_r_host(A.L + B.L, p, PC, R0);
-                                    double acc = 0.0;
-                                    for (int t = 0; t <= ai[0] + bi[0]; ++t)
-                                        for (int u = 0; u <= ai[1] + bi[1]; ++u)
-                                            for (int v = 0; v <= ai[2] + bi[2]; ++v)
-                                                acc += E[0].get(ai[0], bi[0], t) * E[1].get(ai[1], bi[1], u) * E[2].get(ai[2], bi[2], v) * R0[qc_hidx(t, u, v)];
-                                    val -= S->Z[c] * 2.0 * M_PI / p * acc;
+                                    val -= S->Z[c] * 2.0 * M_PI / p * qc_md_nuc(E, ai, bi, R0.data());
                                 }
                             }
-                            cart[x * cb.size() + y] += cc * val;
+                            cart[x * ncb + y] += cc * val;
                         }
                 }
             for (int fa = 0; fa < A.nfunc; ++fa)
                 for (int fb = 0; fb < B.nfunc; ++fb) {
                     double v = 0.0;
-                    for (size_t x = 0; x < ca.size(); ++x)
-                        for (size_t y = 0; y < cb.size(); ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * cb.size() + y];
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * ncb + y];
                     out[(size_t)(A.off + fa) * n + B.off + fb] = v;
                     out[(size_t)(B.off + fb) * n + A.off + fa] = v;
                 }

@@ -76,7 +76,7 @@ def far_boys_argument(m):
 
 
 T_LOW, T_HIGH = 40.0, 59.0           # Boys arguments of the two far() systems of the tests
-BOYS_SERIES_SWITCH = 38.0            # boys_series (qc_one_electron.hip, qc_grad.hip): asymptotic form from here on
+BOYS_SERIES_SWITCH = 38.0            # qc_md_boys (qc_md.h): asymptotic form from here on
 BOYS_XMAX = 41.9                     # QC_BOYS_XMAX (qc_internal.h): end of the table of qc_boys<L>
 
 BUILDERS = {"tetra-pure-1": lambda: tetra(True, 1), "tetra-cart-1": lambda: tetra(False, 1),

@@ -6,7 +6,7 @@ primitive pairs; and no d / f quartet met a Boys argument beyond the table with 
   tetra   four centres, no shared coordinate, s..f on each: every (LAB, LCD) class with four distinct centres, at n = 64 (pure, the
           one-workgroup limit) and n = 80 (Cartesian, generic launches)                              [gap: quartets at general position]
   deep    169 primitive pairs in the same-centre ss and ps kets: bra-major lists of plain pair indices       [gap: K > 127 ket pairs]
-  far     single-primitive s..f shells on two centres at T = 40 (last table rows of qc_boys, above the 38 switch of boys_series) and
+  far     single-primitive s..f shells on two centres at T = 40 (last table rows of qc_boys, above the 38 switch of qc_md_boys) and
           T = 59 (beyond QC_BOYS_XMAX)                                                       [gap: high-order Boys beyond the table]
   and gradient terms of tetra, deep and far at T = 40 against the oracle's five-point stencil      [gap: gradient off a plane]
 
@@ -168,7 +168,7 @@ def test_route_switches_on_tetra(route, refs, monkeypatch):
 @pytest.mark.parametrize("name", list(BUILDERS))
 def test_one_electron_matrices_at_general_position(name):
     """S, T and V of qc_one_electron.hip on every builder: f.f pairs off every axis, 13-primitive shells (exponents up to 1750),
-    and nuclear attraction at Boys arguments on both sides of the 38 switch of boys_series."""
+    and nuclear attraction at Boys arguments on both sides of the 38 switch of qc_md_boys."""
     import qchem_rs_amd as q
     from oracle.oracle import Oracle
     m = BUILDERS[name]()[0]
@@ -206,7 +206,7 @@ def _densities(n):
 def test_gradient_terms_match_oracle_finite_differences_off_every_plane(case):
     """The four terms of qc_gradient at fixed random densities against the stencil: quartets on four distinct centres (centre D by
     translational invariance from three computed ones), every y derivative alive, f shells pure and Cartesian; deep with its
-    169-primitive pairs on all nine coordinates (one case per atom); far at T = 40, where boys_series runs its asymptotic branch at orders up to 13."""
+    169-primitive pairs on all nine coordinates (one case per atom); far at T = 40, where qc_md_boys runs its asymptotic branch at orders up to 13."""
     import qchem_rs_amd as q
     name = case.split("-atom")[0]
     m = BUILDERS[name]()[0]
