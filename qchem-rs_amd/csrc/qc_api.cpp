@@ -1,5 +1,5 @@
-// qc_api.cpp - system creation, the Fock-build and eigensolver entry points, sharding / communicator and profiling entry points of the
-// C ABI (include/qchem_hip.h).  The SCF drivers and the step API: qc_scf.cpp.
+// qc_api.cpp - the C ABI (include/qchem_hip.h) and nothing else: system creation, the Fock-build and eigensolver entry points, sharding /
+// communicator and profiling entry points.  The SCF drivers and the step API: qc_scf.cpp; the build itself: qc_fock.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -22,16 +22,16 @@ int profile_builds(qc_system *S, const double *dD, double *dG, int reps, bool pe
     const int n = S->nbasis;
     const size_t nn = (size_t)n * n;
     std::vector<float> one(acc.size(), 0.f);
-    S->prepared = false; S->gt_clean = false;
-    if (S->accum_fx) qc_fx_scale(S->stream, n, dD, nullptr, S->imax, S->d_fxs);
+    S->prep.invalidate();
+    if (S->accum_fx) qc_fx_scale(S->stream, n, dD, nullptr, S->imax, S->dev.d_fxs.p);
     Event ev0, ev1;
     if (ev0.create() != QC_OK || ev1.create() != QC_OK) return QC_ERR_HIP;
     hipEvent_t e0 = ev0.e, e1 = ev1.e;
     for (int r = 0; r < reps; ++r) {
-        QC_HIP_CHECK(hipMemsetAsync(S->d_Gtmp, 0, (size_t)2 * QC_NREP * nn * sizeof(double), S->stream));
+        QC_HIP_CHECK(hipMemsetAsync(S->dev.d_Gtmp.p, 0, (size_t)2 * QC_NREP * nn * sizeof(double), S->stream));
         QcFockArgs a{};
-        a.nrep = QC_NREP; a.rep_stride = nn; a.fxs = S->accum_fx ? S->d_fxs : nullptr; a.fx_lo = (size_t)QC_NREP * nn;
-        a.Dj = dD; a.Dk0 = dD; a.Dk1 = nullptr; a.cK = 0.5; a.G0 = S->d_Gtmp; a.G1 = S->d_Gtmp + nn;
+        a.nrep = QC_NREP; a.rep_stride = nn; a.fxs = S->accum_fx ? S->dev.d_fxs.p : nullptr; a.fx_lo = (size_t)QC_NREP * nn;
+        a.Dj = dD; a.Dk0 = dD; a.Dk1 = nullptr; a.cK = 0.5; a.G0 = S->dev.d_Gtmp.p; a.G1 = S->dev.d_Gtmp.p + nn;
         int rc = qc_launch_fock_classes(S, a, per_unit ? nullptr : one.data(), per_unit ? one.data() : nullptr);
         if (rc != QC_OK) return rc;
         for (size_t i = 0; i < acc.size(); ++i) acc[i] += one[i];
@@ -58,12 +58,12 @@ int sym_eig_host(qc_system *S, int n, const double *A, const double *V0, double 
     QC_HIP_CHECK(hipMemcpyAsync(dA.p, A, nn * sizeof(double), hipMemcpyHostToDevice, st));
     if (V0) QC_HIP_CHECK(hipMemcpyAsync(dV0.p, V0, nn * sizeof(double), hipMemcpyHostToDevice, st));
     int flag = 0;
-    QC_HIP_CHECK(hipMemsetAsync(S->d_flag, 0, (V0 ? 1 : 4) * sizeof(int), st));
-    rc = V0 ? qc_eig_device_refine(st, n, dA.p, dV0.p, dV.p, dw.p, E, S->d_flag) : qc_eig_cold_sync(st, n, dA.p, dV.p, dw.p, E, E.ctl.p, S->d_flag);
+    QC_HIP_CHECK(hipMemsetAsync(S->dev.d_flag.p, 0, (V0 ? 1 : 4) * sizeof(int), st));
+    rc = V0 ? qc_eig_device_refine(st, n, dA.p, dV0.p, dV.p, dw.p, E, S->dev.d_flag.p) : qc_eig_cold_sync(st, n, dA.p, dV.p, dw.p, E, E.ctl.p, S->dev.d_flag.p);
     if (rc != QC_OK) return rc;
     QC_HIP_CHECK(hipMemcpyAsync(V, dV.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipMemcpyAsync(w, dw.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    QC_HIP_CHECK(hipMemcpyAsync(&flag, S->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    QC_HIP_CHECK(hipMemcpyAsync(&flag, S->dev.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipStreamSynchronize(st));
     return flag ? QC_EIG_NOT_CONVERGED : QC_OK;
 }
@@ -150,8 +150,8 @@ int qc_one_electron_gpu(qc_system *S, int which, double *out) {
 int qc_set_stream(qc_system *S, void *hip_stream) {
     if (!S) return QC_ERR_INVALID;
     if (S->own_stream && S->stream) { (void)hipStreamDestroy(S->stream); S->own_stream = false; }
-    S->lanes_probed = false;                                     // (which side stream shares the pipe of the caller's stream was not measured)
-    S->prepared = false; S->gt_clean = false;                    // (the preliminaries of a prepared build were enqueued on the old stream)
+    S->lanes.lanes_probed = false;                                     // (which side stream shares the pipe of the caller's stream was not measured)
+    S->prep.invalidate();                    // (the preliminaries of a prepared build were enqueued on the old stream)
     S->stream = (hipStream_t)hip_stream;
     if (!S->stream && S->device_ready) { QC_HIP_CHECK(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)); S->own_stream = true; }
     return QC_OK;
@@ -173,112 +173,6 @@ int qc_eri_full(qc_system *S, double *out) {
     return QC_OK;
 }
 
-}  // extern "C"
-
-// Everything of a fixed-point build that depends on the densities alone, enqueued ahead of time (the SCF pass does this as soon as
-// its new density exists, so that it runs while the host turns around): zeroed accumulator planes, this build's fixed-point unit,
-// the UHF density sum.  qc_fock_build_device recognises the densities and then goes straight to the class kernels.
-int qc_fock_prepare_device(qc_system *S, const double *dDa, const double *dDb, bool uhf, const void *owner, bool scale_done) {
-    S->prepared = false;
-    S->prep_enqueued = false;
-    if (!S->accum_fx) return QC_OK;
-    const int n = S->nbasis;
-    const size_t nn = (size_t)n * n, plane = (size_t)QC_NREP * (uhf ? 2 : 1) * nn;
-    // (the closing fold of the last build zeroes the replicas it reads: no memset then)
-    const bool zero = !(S->gt_clean && S->gt_clean_nspin == (uhf ? 2 : 1));
-    if (zero) QC_HIP_CHECK(hipMemsetAsync(S->d_Gtmp, 0, 2 * plane * sizeof(double), S->stream));
-    S->gt_clean = true; S->gt_clean_nspin = uhf ? 2 : 1;
-    if (!scale_done) qc_fx_scale(S->stream, n, dDa, uhf ? dDb : nullptr, S->imax, S->d_fxs);
-    if (uhf) qc_axpby(S->stream, n, 1.0, dDa, 1.0, dDb, S->d_Dj);
-    // (the build that finds these preliminaries starts its side streams without a fork event: whoever lets the host go on before the
-    // handle's stream has drained must know that something was put on it here)
-    S->prep_enqueued = zero || !scale_done || uhf;
-    S->prepared = true; S->prep_Da = dDa; S->prep_Db = uhf ? dDb : nullptr; S->prep_owner = owner;
-    return QC_OK;
-}
-
-int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, double *dGa, double *dGb, bool uhf, int *twin_cache,
-                         const double *dH, double *dFa, double *dFb, bool *f_done, const void *owner) {
-    const int n = S->nbasis;
-    const size_t nn = (size_t)n * n;
-    hipStream_t st = S->stream;
-    const bool fx = S->accum_fx != 0;
-    const double *fxs = fx ? S->d_fxs : nullptr;
-    // Spin symmetry: the reference evaluates both spins with identical arithmetic (uhf.rs:210-227), so bitwise-equal
-    // densities give bitwise-equal G (its closed-shell UHF never breaks symmetry).  The fixed-point
-    // accumulation keeps that property by construction: every contribution is the same sequence of operations for either
-    // spin and integer sums do not depend on their order.  Only the f64-atomic mode (kept for A/B measurements) needs help:
-    // there equal spins are detected and digested once.  Inside an SCF run the answer cannot change, so the drivers pass a
-    // cache and only their first build pays the host round trip.
-    bool twin = false;
-    if (uhf && !fx) {
-        if (twin_cache && *twin_cache >= 0) twin = *twin_cache != 0;
-        else {
-            int diff = 1;
-            QC_HIP_CHECK(hipMemsetAsync(S->d_flag, 0, sizeof(int), st));
-            qc_count_diff(st, nn, dDa, dDb, S->d_flag);
-            QC_HIP_CHECK(hipMemcpyAsync(&diff, S->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-            QC_HIP_CHECK(hipStreamSynchronize(st));
-            twin = (diff == 0);
-            if (twin_cache) *twin_cache = twin ? 1 : 0;
-        }
-    }
-    const bool two = uhf && !twin;
-    const int nspin = two ? 2 : 1;
-    // accumulation phase: zero the replicas, density sum, every class kernel on the side streams, replica fold
-    const size_t plane = (size_t)QC_NREP * nspin * nn;          // one accumulator plane: [replica][spin][n*n]
-    const bool ready = fx && S->prepared && owner != nullptr && S->prep_owner == owner && S->prep_Da == dDa && S->prep_Db == (uhf ? dDb : nullptr);   // qc_fock_prepare_device ran for these
-    S->prepared = false;
-    QcFockArgs a{};
-    // Replicas in use (the planes keep their layout): 8 for n <= 64, all 32 above.  Replicas spread the atomics of hot elements, and the
-    // closing fold reads and zeroes every one of them: at n = 58 that is 1.7 MB with 32 replicas, and the H2O/cc-pVTZ iteration takes 0.308 ms
-    // with 8 against 0.313 with 32 (0.312 with 16, 0.319 with 4, 0.349 with 2; three alternating runs each); benzene/cc-pVDZ (n = 114) shows
-    // no difference between 8, 16 and 32.  QC_NREP_USE: experiment switch.
-    const char *nrep_s = getenv("QC_NREP_USE");                 // (read per build: a test switches it inside one process)
-    const int nrep_env = nrep_s ? std::max(1, std::min(QC_NREP, atoi(nrep_s))) : 0;
-    const int nrep_use = nrep_env ? nrep_env : (n <= 64 ? 8 : QC_NREP);
-    a.nrep = nrep_use; a.rep_stride = nspin * nn; a.fxs = fxs; a.fx_lo = plane;
-    if (!ready) {
-        QC_HIP_CHECK(hipMemsetAsync(S->d_Gtmp, 0, (fx ? 2 : 1) * plane * sizeof(double), st));
-        if (fx) qc_fx_scale(st, n, dDa, uhf ? dDb : nullptr, S->imax, S->d_fxs);      // this build's fixed-point unit, from its densities
-    }
-    S->gt_clean = false;                                    // (the class kernels are about to accumulate into the planes)
-    if (uhf) {
-        if (!ready) qc_axpby(st, n, 1.0, dDa, 1.0, dDb, S->d_Dj);
-        a.Dj = S->d_Dj; a.Dk0 = dDa; a.Dk1 = two ? dDb : nullptr; a.cK = 1.0;
-    } else {
-        a.Dj = dDa; a.Dk0 = dDa; a.Dk1 = nullptr; a.cK = 0.5;
-    }
-    a.G0 = S->d_Gtmp; a.G1 = S->d_Gtmp + nn;
-    int rc = qc_launch_fock_classes(S, a, nullptr, nullptr, ready);
-    if (rc != QC_OK) return rc;
-    if (fx && !S->comm && S->nranks == 1) {
-        // (one launch instead of fold + symmetrise: nothing needs the folded planes)
-        qc_fold_symmetrize(st, n, nrep_use, nspin * nn, S->d_Gtmp, plane, dGa, dH, dH ? dFa : nullptr, fxs, S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 1) : nullptr);
-        if (two) qc_fold_symmetrize(st, n, nrep_use, nspin * nn, S->d_Gtmp + nn, plane, dGb, dH, dH ? dFb : nullptr, fxs);
-        else if (uhf) QC_HIP_CHECK(hipMemcpyAsync(dGb, dGa, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        S->gt_clean = true; S->gt_clean_nspin = nspin;      // every replica element of the planes in use was read and zeroed
-        if (f_done) *f_done = dH != nullptr && dFa != nullptr && (!uhf || (two && dFb != nullptr));
-        return QC_OK;
-    }
-    qc_reduce_replicas(st, nspin * nn, nrep_use, nspin * nn, S->d_Gtmp, S->d_Gred, fx, plane);
-    if (S->comm) {
-        // partial Fock matrices -> full, one all-reduce per build ([Ga|Gb] concatenated for UHF; hi and lo planes back to
-        // back).  Fixed-point partials are summed as integers: the result is bit-identical on every rank, whatever the ring
-        // order.  (Against a build with another shard layout - the single-GPU build included - it agrees to ~1e-13, not bit for
-        // bit: the bra-major kernels pre-sum the exchange rows of a 64-ket bundle in an f64 LDS buffer, and which kets share a
-        // bundle depends on the shard.)
-        if (qc_rccl().AllReduce(S->d_Gred, S->d_Gred, (fx ? 2 : 1) * nspin * nn, fx ? ncclInt64 : ncclDouble, ncclSum, (ncclComm_t)S->comm, st) != ncclSuccess) return QC_ERR_RCCL;
-    }
-    qc_symmetrize_add(st, n, S->d_Gred, nspin * nn, dGa, dH, dH ? dFa : nullptr, fxs);
-    if (two) qc_symmetrize_add(st, n, S->d_Gred + nn, nspin * nn, dGb, dH, dH ? dFb : nullptr, fxs);
-    else if (uhf) QC_HIP_CHECK(hipMemcpyAsync(dGb, dGa, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (f_done) *f_done = dH != nullptr && dFa != nullptr && (!uhf || (two && dFb != nullptr));
-    return QC_OK;
-}
-
-extern "C" {
-
 int qc_fock_rhf_device(qc_system *S, const double *dD, double *dG) {
     if (!S || !dD || !dG) return QC_ERR_INVALID;
     int rc = qc_device_init(S);
@@ -297,10 +191,10 @@ int qc_fock_rhf(qc_system *S, const double *D, double *G) {
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
     const size_t nn = (size_t)S->nbasis * S->nbasis;
-    QC_HIP_CHECK(hipMemcpyAsync(S->d_D, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    rc = qc_fock_build_device(S, S->d_D, nullptr, S->d_G, nullptr, false);
+    QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_D.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    rc = qc_fock_build_device(S, S->dev.d_D.p, nullptr, S->dev.d_G.p, nullptr, false);
     if (rc != QC_OK) return rc;
-    QC_HIP_CHECK(hipMemcpyAsync(G, S->d_G, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(G, S->dev.d_G.p, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
     if ((rc = qc_join_check(S)) != QC_OK) return rc;        // (a join that gave up folded an incomplete matrix: this call fails)
     qc_gate_quiet(S);
@@ -312,12 +206,12 @@ int qc_fock_uhf(qc_system *S, const double *Da, const double *Db, double *Ga, do
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
     const size_t nn = (size_t)S->nbasis * S->nbasis;
-    QC_HIP_CHECK(hipMemcpyAsync(S->d_D, Da, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    QC_HIP_CHECK(hipMemcpyAsync(S->d_D + nn, Db, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    rc = qc_fock_build_device(S, S->d_D, S->d_D + nn, S->d_G, S->d_G + nn, true);
+    QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_D.p, Da, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_D.p + nn, Db, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    rc = qc_fock_build_device(S, S->dev.d_D.p, S->dev.d_D.p + nn, S->dev.d_G.p, S->dev.d_G.p + nn, true);
     if (rc != QC_OK) return rc;
-    QC_HIP_CHECK(hipMemcpyAsync(Ga, S->d_G, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    QC_HIP_CHECK(hipMemcpyAsync(Gb, S->d_G + nn, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(Ga, S->dev.d_G.p, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipMemcpyAsync(Gb, S->dev.d_G.p + nn, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
     if ((rc = qc_join_check(S)) != QC_OK) return rc;
     qc_gate_quiet(S);
@@ -367,7 +261,7 @@ int qc_gradient_timings(const qc_system *S, double *ms) {
 int qc_set_accumulation(qc_system *S, int fixed_point) {
     if (!S || (fixed_point != 0 && fixed_point != 1)) return QC_ERR_INVALID;
     S->accum_fx = fixed_point;
-    S->prepared = false; S->gt_clean = false;                    // (a prepared build zeroed the planes of the other mode)
+    S->prep.invalidate();                    // (a prepared build zeroed the planes of the other mode)
     return QC_OK;
 }
 
@@ -401,8 +295,8 @@ int qc_dispatch_lanes(qc_system *S, int32_t *nlanes, int32_t slot_stream[8]) {
     if (!S || !nlanes) return QC_ERR_INVALID;
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
-    *nlanes = S->nlanes;
-    if (slot_stream) { for (int k = 0; k < QC_NSTREAMS; ++k) slot_stream[k] = S->slot_side[k]; slot_stream[QC_NSTREAMS] = S->lane0_is_main ? 1 : 0; }
+    *nlanes = S->lanes.nlanes;
+    if (slot_stream) { for (int k = 0; k < QC_NSTREAMS; ++k) slot_stream[k] = S->lanes.slot_side[k]; slot_stream[QC_NSTREAMS] = S->lanes.lane0_is_main ? 1 : 0; }
     return QC_OK;
 }
 

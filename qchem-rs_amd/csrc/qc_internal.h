@@ -7,6 +7,8 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -132,6 +134,117 @@ struct QcClass {
     double bytes_alg = 0, flops_alg = 0;
 };
 
+// Owning device allocation of `count` objects T.  alloc: QC_OK or QC_ERR_HIP; a zero count leaves p null and succeeds.
+template <class T> struct QcDev {
+    T *p = nullptr;
+    QcDev() = default;
+    QcDev(const QcDev &) = delete; QcDev &operator=(const QcDev &) = delete;
+    int alloc(size_t count) { return !count || hipMalloc(&p, count * sizeof(T)) == hipSuccess ? QC_OK : QC_ERR_HIP; }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    ~QcDev() { reset(); }
+};
+using DevBuf = QcDev<double>;
+// host copy of several lists that go to the device in one piece; put: the offset of the copy, 256-byte aligned
+struct QcBlob {
+    std::vector<unsigned char> bytes;
+    size_t put(const void *src, size_t n) { const size_t off = (bytes.size() + 255) & ~(size_t)255; bytes.resize(off + n); if (n) std::memcpy(bytes.data() + off, src, n); return off; }
+};
+// a member struct of the handle back in its initial state: what it owned is released by its members' destructors
+template <class T> void qc_renew(T &x) { x.~T(); new (&x) T(); }
+inline double qc_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// QC_SETUP_DEBUG: "[tag] what   ms since the last lap" (qc_build_model, qc_device_init, scf_begin)
+struct QcLap {
+    const char *tag; bool on; double tt = qc_now_ms();
+    void operator()(const char *what) { if (on) { const double t = qc_now_ms(); fprintf(stderr, "[%s] %-28s %.3f ms\n", tag, what, t - tt); tt = t; } }
+};
+
+// ---- the device side of a handle, in parts (qc_device.cpp sets them up and tears them down)
+// what the kernels read and write: filled by qc_device_init in this order, released as a whole by qc_device_free
+struct QcDeviceData {
+    QcDev<double> d_pairdata, d_pairdataT, d_pspack;
+    QcDev<QcPairDesc> d_pairs;
+    QcDev<double> d_boys;
+    QcDev<int> d_rplan;          // recurrence plans of the Hermite-Coulomb tables (qc_build_rplan)
+    QcDev<unsigned> d_gidx;      // gather records of the matrix-core classes (qc_build_gidx)
+    QcDev<double> d_D, d_G;      // 2 * n*n each (alpha/beta or Dj/Dk)
+    QcDev<double> d_Gtmp;        // accumulation target: [plane (hi, lo)][replica][spin][n*n]
+    QcDev<double> d_Gred;        // replicas folded: [plane][spin][n*n]
+    QcDev<double> d_Dj;
+    QcDev<double> d_fxs;         // [2^S, 2^-S]: fixed-point scale of the current build
+    QcDev<int> d_flag;
+    QcDev<unsigned char> d_lists; // the work lists of all classes (QcClass::d_slots / d_bundles / d_ketlist point into it)
+    QcDev<unsigned> d_join;      // [0] counter of the device-side join of a build's side streams (qc_join_mark / qc_join_wait);
+                                 // [3] scratch of the lane probe's markers, [4] counter of the spin-parallel Roothaan steps
+};
+// Side streams, their events and the dispatch lanes measured on them (qc_lane_probe): the chip dispatches at most FOUR kernels at a
+// time - hardware queues sit in pairs on four pipes, and a pipe works on one dispatch until all its workgroups are launched.
+// slot_side[k] = side stream behind assignment slot k; the first `nlanes` slots are on distinct pipes, slot 0 on the pipe of the handle's
+// own stream (when one of the side streams shares it).  A handle that goes away leaves this struct, with its own stream, in the stream pool.
+struct QcLanes {
+    hipStream_t side[QC_NSTREAMS] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[QC_NSTREAMS] = {};
+    int slot_side[QC_NSTREAMS] = {0, 1, 2, 3, 4, 5, 6};
+    int nlanes = QC_NSTREAMS;
+    bool lane0_is_main = false;
+    bool lanes_probed = false;               // slot_side / nlanes were measured on this handle's own stream set (qc_lane_probe)
+};
+// device-side joins of the handle's streams (qc_streams.hip); the counters they wait for are d_join
+struct QcJoin {
+    unsigned target = 0;                     // join counter of a build's side streams (d_join[0])
+    unsigned spin_target = 0;                // join counter of the spin-parallel Roothaan steps (d_join[4])
+    long long wait_limit = 0;                // device-side waits give up after this many ticks of the 100 MHz clock (qc_wait_limit)
+    std::atomic<bool> waits_in_flight{false}; // device-side waits were issued and the host has not seen the handle's stream drained since (qc_gate)
+    bool by_events = false;                  // dispatches are serialised here (qc_join_probe): the side streams are joined through events
+    int *h_timeout = nullptr;                // pinned (freed by qc_device_free): set by a device-side wait that gave up (the launches it waited for never finished)
+};
+// accumulators zeroed, fixed-point scale (and the UHF density sum) already enqueued for a build from exactly these densities, and the host
+// has waited for the handle's stream since (qc_fock_prepare_device): the build then starts its side streams without a fork
+struct QcPrepared {
+    bool prepared = false;
+    bool gt_clean = false;                   // the accumulator planes (d_Gtmp) are known to be zero for the layout `gt_clean_nspin` (left so by the closing fold)
+    int gt_clean_nspin = 0;
+    const double *Da = nullptr, *Db = nullptr;
+    const void *owner = nullptr;             // the qc_scf_state that enqueued them (addresses alone could be recycled by a later state)
+    bool enqueued = false;                   // qc_fock_prepare_device put work on the handle's stream (see scf_iterate)
+    void invalidate() { prepared = false; gt_clean = false; }   // nothing on the handle's stream or in the planes may be taken for granted
+};
+// refinement of the stream assignment in instalments paid for by use (qc_assign.hip, "Refinement of the stream assignment")
+struct QcOnline {
+    bool frozen = false;
+    std::vector<int> best, trial;
+    std::vector<std::vector<int>> nb, tried;   // neighbourhood of `best` (swept in order from nb_pos) / every assignment measured so far
+    size_t nb_pos = 0;
+    std::vector<std::vector<int>> cands;   // proposals of the first build (longest-first on in-build durations): tried before random neighbours
+    double base_ms = 0.0;                  // build time of `best` as the search measured it
+    bool seeded = false;                   // the proposals of the instrumented builds have been made (first instalment of the search)
+    int trials = 0, rejects = 0, kicks = 0;   // (kicks: restarts of the local search from a perturbed copy of the best assignment known)
+    long builds = 0, spent = 0;            // builds asked of this handle / extra builds the search has run
+    unsigned rng = 2463534242u;
+    double seen_sum = 0.0; long seen_n = 0;   // build times reported by SCF passes under the current assignment
+    // finals (qc_fock_feedback): the three fastest assignments of the search, sampled inside SCF passes - a build that follows a Roothaan
+    // step and a host turn-around is not the back-to-back build the search times, and which of them is fastest THERE differs
+    std::vector<std::pair<float, std::vector<int>>> top;
+    std::vector<double> fin_sum; std::vector<int> fin_n;
+    int fin_cur = 0;
+    bool settled = false;                     // search and finals are over
+};
+struct QcAssign {
+    std::vector<float> unit_ms;              // measured serial time of each launch unit (autotuned once per shard)
+    std::vector<int> unit_stream;            // side stream of each launch unit (longest-processing-time assignment)
+    std::vector<float> unit_weight;          // durations that order the launches (measured inside concurrent builds)
+    QcOnline on;
+    bool cand_skip = false;                  // the next build is the first under a new assignment: not a sample
+    unsigned gen = 0;                        // counts the changes of the stream assignment: a build's time is a sample of the assignment it ran under
+    int tune_count = 0;                      // first builds (launches timed alone) on this shard layout
+};
+// QC_DEV_TIMELINE: ring of QC_TL_PASSES sets of QC_TL_SLOTS kernel slots (QC_TL_W clock words each, qc_tl_stamp), one set per SCF pass; cur = the set
+// of the pass being enqueued (null: off, or the ring is full); dumped when an SCF state of the handle ends (qc_tl_dump)
+struct QcTimeline {
+    QcDev<unsigned long long> d_tl;
+    unsigned long long *cur = nullptr;
+    int pass = 0;
+};
+
 struct qc_system {
     int natoms = 0, nshells = 0, nbasis = 0, nelec = 0;
     std::vector<int> Z;
@@ -153,81 +266,20 @@ struct qc_system {
     int64_t nscreened = 0;                      // quartets (of the whole list, all ranks) dropped by the Schwarz bound
     int64_t nquartets = 0;
     int rank = 0, nranks = 1;
-    // device
+    // device (the parts: above)
     bool device_ready = false;
     int device = -1;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipStream_t side[QC_NSTREAMS] = {};
-    // Dispatch lanes (qc_lane_probe): the chip dispatches at most FOUR kernels at a time - hardware queues sit in pairs on four pipes, and a
-    // pipe works on one dispatch until all its workgroups are launched.  slot_side[k] = side stream behind assignment slot k; the first
-    // `nlanes` slots are on distinct pipes, slot 0 on the pipe of the handle's own stream (when one of the side streams shares it).
-    int slot_side[QC_NSTREAMS] = {0, 1, 2, 3, 4, 5, 6};
-    int nlanes = QC_NSTREAMS;
-    bool lane0_is_main = false;
-    bool lanes_probed = false;               // slot_side / nlanes were measured on this handle's own stream set (qc_lane_probe)
-    hipEvent_t ev_fork = nullptr, ev_join[QC_NSTREAMS] = {};
-    unsigned spin_target = 0;                // join counter of the spin-parallel Roothaan steps (d_join[4])
-    double *d_pairdata = nullptr, *d_pairdataT = nullptr, *d_pspack = nullptr;
+    QcDeviceData dev;
+    QcLanes lanes;
+    QcJoin join;
+    QcPrepared prep;
+    QcAssign assign;
+    QcTimeline tl;
     struct QcShellBlob *shell_blob = nullptr; // shells / primitives / transforms / nuclei for the one-electron and gradient kernels (qc_shell_blob)
-    QcPairDesc *d_pairs = nullptr;
-    double *d_boys = nullptr;
-    int *d_rplan = nullptr;
-    unsigned *d_gidx = nullptr;   // gather records of the matrix-core classes (qc_build_gidx)       // recurrence plans of the Hermite-Coulomb tables (qc_build_rplan)
-    double *d_D = nullptr, *d_G = nullptr;   // 2 * n*n each (alpha/beta or Dj/Dk)
-    double *d_Gtmp = nullptr;                // accumulation target: [plane (hi, lo)][replica][spin][n*n]
-    double *d_Gred = nullptr;                // replicas folded: [plane][spin][n*n]
-    double *d_Dj = nullptr;
-    double *d_fxs = nullptr;                 // [2^S, 2^-S]: fixed-point scale of the current build
-    int *d_flag = nullptr;
-    // QC_DEV_TIMELINE: ring of QC_TL_PASSES sets of QC_TL_SLOTS kernel slots (QC_TL_W clock words each, qc_tl_stamp), one set per SCF pass; tl_cur = the set
-    // of the pass being enqueued (null: off, or the ring is full); dumped when an SCF state of the handle ends (qc_tl_dump)
-    unsigned char *d_lists = nullptr;        // the work lists of all classes (QcClass::d_slots / d_bundles / d_ketlist point into it)
-    unsigned long long *d_tl = nullptr, *tl_cur = nullptr;
-    int tl_pass = 0;
-    unsigned *d_join = nullptr;              // [0] counter of the device-side join of a build's side streams (qc_join_mark / qc_join_wait);
-                                             // [3] scratch of the lane probe's markers, [4] counter of the spin-parallel Roothaan steps
-    int *h_join_timeout = nullptr;           // pinned: set by a device-side wait that gave up (the launches it waited for never finished)
-    unsigned join_target = 0;
-    long long wait_limit = 0;                // device-side waits give up after this many ticks of the 100 MHz clock (qc_wait_limit)
-    std::atomic<bool> waits_in_flight{false}; // device-side waits were issued and the host has not seen the handle's stream drained since (qc_gate)
-    bool prep_enqueued = false;              // qc_fock_prepare_device put work on the handle's stream (see scf_iterate)
-    bool join_by_events = false;             // dispatches are serialised here (qc_join_probe): the side streams are joined through events
     struct QcLaunchPlan *launch_plan = nullptr; // launch units and their segments of the current work lists (qc_fock.hip)
     void *comm = nullptr;                    // ncclComm_t
-    std::vector<float> unit_ms;              // measured serial time of each launch unit (autotuned once per shard)
-    std::vector<int> unit_stream;            // side stream of each launch unit (longest-processing-time assignment)
-    std::vector<float> unit_weight;          // durations that order the launches (measured inside concurrent builds)
-    // refinement of the stream assignment in instalments paid for by use (qc_fock.hip, "Refinement of the stream assignment")
-    struct QcOnline {
-        bool frozen = false;
-        std::vector<int> best, trial;
-        std::vector<std::vector<int>> nb, tried;   // neighbourhood of `best` (swept in order from nb_pos) / every assignment measured so far
-        size_t nb_pos = 0;
-        std::vector<std::vector<int>> cands;   // proposals of the first build (longest-first on in-build durations): tried before random neighbours
-        double base_ms = 0.0;                  // build time of `best` as the search measured it
-        bool seeded = false;                   // the proposals of the instrumented builds have been made (first instalment of the search)
-        int trials = 0, rejects = 0, kicks = 0;   // (kicks: restarts of the local search from a perturbed copy of the best assignment known)
-        long builds = 0, spent = 0;            // builds asked of this handle / extra builds the search has run
-        unsigned rng = 2463534242u;
-        double seen_sum = 0.0; long seen_n = 0;   // build times reported by SCF passes under the current assignment
-        // finals (qc_fock_feedback): the three fastest assignments of the search, sampled inside SCF passes - a build that follows a Roothaan
-        // step and a host turn-around is not the back-to-back build the search times, and which of them is fastest THERE differs
-        std::vector<std::pair<float, std::vector<int>>> top;
-        std::vector<double> fin_sum; std::vector<int> fin_n;
-        int fin_cur = 0;
-        bool settled = false;                     // search and finals are over
-    } on;
-    bool cand_skip = false;                  // the next build is the first under a new assignment: not a sample
-    unsigned assign_gen = 0;                 // counts the changes of the stream assignment: a build's time is a sample of the assignment it ran under
-    int tune_count = 0;                      // first builds (launches timed alone) on this shard layout
-    // accumulators zeroed, fixed-point scale (and the UHF density sum) already enqueued for a build from exactly these densities, and the host
-    // has waited for the handle's stream since (qc_fock_prepare_device): the build then starts its side streams without a fork
-    bool prepared = false;
-    bool gt_clean = false;                   // the accumulator planes (d_Gtmp) are known to be zero for the layout `gt_clean_nspin` (left so by the closing fold)
-    int gt_clean_nspin = 0;
-    const double *prep_Da = nullptr, *prep_Db = nullptr;
-    const void *prep_owner = nullptr;        // the qc_scf_state that enqueued them (addresses alone could be recycled by a later state)
     int live_states = 0;                     // qc_scf_state objects that still point at this handle
     bool zombie = false;                     // qc_system_destroy was called while states were alive: the last qc_scf_end frees the handle
     int fock_mode = 0;                       // 0 direct (default), 1 stored tensor (the reference's own algorithm)
@@ -244,7 +296,6 @@ void qc_build_model(qc_system *S);
 // (meta_only: the classes' LDS / slot sizes only, from the whole task lists - what the Schwarz pass of the device set-up needs before the
 // screened lists can exist; the lists are then built once, behind that pass, or on demand: qc_ensure_lists)
 void qc_build_shards(qc_system *S, bool meta_only = false);
-inline void qc_ensure_lists(qc_system *S);
 void qc_host_one_electron(const qc_system *S, int which, double *out);
 void qc_boys_host(int nmax, double x, double *F);
 
@@ -255,9 +306,15 @@ constexpr int QC_BOYS_NGRID = 421;             // x up to 42
 constexpr double QC_BOYS_XMAX = 41.9;          // beyond: asymptotic + upward recursion
 constexpr int QC_BOYS_NORD = QC_LTOT + 8;      // orders kept per grid point
 
-// ---- device side (qc_fock.hip / qc_linalg.hip)
+// ---- device side of a handle (qc_device.cpp).  init: QC_OK with everything in place, or an error with the handle as it was found
 int qc_device_init(qc_system *S);
 void qc_device_free(qc_system *S);
+int qc_ds_order_probe(hipStream_t st, double *d_out64);      // (qc_fock_bm.hip) 64 sums of the same 64-lane DS add: equal bits = the order is fixed
+// Device records of a bra-major work list (QcBundleDev / QcKetUnit) from the host lists of qc_make_bundles
+void qc_bm_device_lists(const qc_system *S, int lcd, const std::vector<QcBundle> &bundles, const std::vector<int> &ketlist, bool packed,
+                        std::vector<QcBundleDev> &db, std::vector<QcKetUnit> &du);
+void qc_drop_launch_plan(qc_system *S);                      // (qc_fock.hip) the launch plan follows the work lists
+// ---- the Fock build (qc_fock.hip), the stream assignment (qc_assign.hip), dense linear algebra (qc_linalg.hip)
 // digestion modes
 struct QcFockArgs {
     const double *Dj;     // density contracted into J (n*n)
@@ -299,6 +356,21 @@ int qc_launch_fock_classes(qc_system *S, const QcFockArgs &a, float *class_ms /*
 // hipEvent time of a build inside an SCF pass that ran under stream assignment `gen` (no-op once the choice is made)
 void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen);
 void qc_assignment_freeze(qc_system *S);
+// ---- queues, pipes and cross-stream waits (qc_streams.hip)
+// The issue of a build - the only place where cross-stream dependencies are created - goes through a per-device gate (QcGate): the holder
+// issues alone; `waits`: the issue under this hold put device-side waits in flight
+struct QcGateHold { struct QcGate &g; qc_system *S; bool waits = false; explicit QcGateHold(qc_system *S_); ~QcGateHold(); };
+void qc_gate_quiet(qc_system *S);                          // the host has seen the handle's stream drained: none of its waits is in flight
+void qc_gate_forget(qc_system *S);                         // the handle goes away
+// stream sets of handles that went away (the handle's own stream + its QcLanes).  take: into a handle without a stream; give: false = not pooled
+bool qc_stream_pool_take(qc_system *S), qc_stream_pool_give(qc_system *S);
+int qc_lane_probe(qc_system *S);                           // measures S->lanes (slot_side, nlanes, lane0_is_main)
+int qc_join_probe(qc_system *S, bool *concurrent);         // do kernels of different streams run concurrently here?
+// device-side join: a one-lane marker on `st` counts itself in `cnt`; a one-lane kernel on the handle's stream waits until `cnt` has reached
+// `target` (gentle: the slow poll of waits that spin next to running kernels; tl: timeline slot or null), gives up after S->join.wait_limit
+void qc_join_mark(hipStream_t st, unsigned *cnt);
+int qc_join_wait(qc_system *S, unsigned *cnt, unsigned target, bool gentle, unsigned long long *tl);
+long long qc_wait_limit(const qc_system *S);
 // the beta step of a UHF pass on a side stream (another dispatch pipe than the handle's): fork = that stream, made to wait for what the
 // handle's stream holds so far; join = the handle's stream waits for it (marker + waiting kernel, under the per-device gate)
 hipStream_t qc_spin_fork(qc_system *S);
@@ -309,7 +381,7 @@ int qc_join_check(qc_system *S);                           // after a host wait:
 // build; printed as differences at the end of every pass).  No-ops unless the variable is set.
 void qc_stamp(const char *what);
 void qc_stamp_flush();
-void qc_gate_quiet(qc_system *S);                          // the host has seen the handle's stream drained: none of its waits is in flight
+// ---- the Fock build again
 // (scale_done: the fixed-point unit of these densities is already in d_fxs - written by the kernel that produced them)
 int qc_fock_prepare_device(qc_system *S, const double *dDa, const double *dDb, bool uhf, const void *owner, bool scale_done = false);
 // (dH with dFa / dFb: the Fock matrices H + G are written by the closing kernel as well; *f_done tells whether both were)
@@ -334,18 +406,6 @@ constexpr int QC_CTL_EIG = 0, QC_CTL_EIG_STRIDE = 4, QC_CTL_DIIS = 8, QC_CTL_NOT
 constexpr int QC_EIG_STATE = 0, QC_EIG_LAST = 1, QC_EIG_CLEAN = 2, QC_EIG_PASSES = 3;
 constexpr int QC_EIG_RUNNING = 0, QC_EIG_DONE = 1, QC_EIG_ROTATE = 2;
 constexpr int QC_SYNC_WORDS = 4 + QC_CTL_WORDS / 2;
-
-// Owning device allocation of `count` objects T.  alloc: QC_OK or QC_ERR_HIP; a zero count leaves p null and succeeds.
-template <class T> struct QcDev {
-    T *p = nullptr;
-    QcDev() = default;
-    QcDev(const QcDev &) = delete;
-    QcDev &operator=(const QcDev &) = delete;
-    int alloc(size_t count) { return !count || hipMalloc(&p, count * sizeof(T)) == hipSuccess ? QC_OK : QC_ERR_HIP; }
-    ~QcDev() { if (p) (void)hipFree(p); }
-};
-using DevBuf = QcDev<double>;
-inline double qc_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- shells, primitives, transforms and nuclei on the device: one blob per handle, uploaded at the first use (qc_one_electron.hip)
 // coff: first Cartesian component of the shell in the Cartesian basis (nc components in all); poff / toff: offsets into exps, coefs / T
@@ -472,7 +532,7 @@ int qc_scf_small_launch(hipStream_t st, const QcSmallArgs &a);
 constexpr int QC_TL_W = 34;   // (words per kernel slot: the launch's end is the maximum over 32 end words - plain stores, no atomics: 8000
                               // workgroups hammering ONE word with atomic min / max stretched an H2O/cc-pVTZ build from 172 to 231 us)
 constexpr int QC_TL_PASSES = 64, QC_TL_SLOTS = QC_NUNITS + 4;       // launch units | join wait | fold | Roothaan kernel, first / second launch
-int qc_tl_begin_pass(qc_system *S);                                 // (no-op unless QC_DEV_TIMELINE is set)
+int qc_tl_begin_pass(qc_system *S);                                 // (qc_streams.hip; no-op unless QC_DEV_TIMELINE is set)
 void qc_tl_dump(qc_system *S);
 size_t qc_scf_small_lds_bytes(int n);
 

@@ -209,7 +209,7 @@ int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG,
     a.Cp_out = W.CpNew[spin].p; a.w_out = dw_out; a.C_out = dC; a.Dn = tl.Dn; a.Dold = tl.Dold; a.nocc = tl.nocc; a.dfac = tl.dfac;
     a.scal_out = tl.scal_out; a.ctl_all = tl.ctl_all; a.ctl_out = tl.ctl_out; a.fxs_out = tl.fxs_out; a.imax = S->imax;
     a.seq_out = tl.seq_out; a.seq = tl.seq;
-    a.tl = S->tl_cur ? S->tl_cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
+    a.tl = S->tl.cur ? S->tl.cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
     QcEigWork &E = W.eig[b];
     double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
     int *const notconv = W.ctl.p + QC_CTL_NOTCONV;
@@ -285,7 +285,7 @@ struct qc_scf_state {
     bool event_wait = getenv("QC_EVENT_WAIT") != nullptr;      // (A/B switch, read per SCF state: the stream's event instead)
     bool timing_pending = false;               // ... and whose event times (set `pending_set`) have not been read yet
     ~qc_scf_state() {
-        if (S && S->prep_owner == this) { S->prepared = false; S->prep_owner = nullptr; }
+        if (S && S->prep.owner == this) { S->prep.prepared = false; S->prep.owner = nullptr; }
         delete diis[0]; delete diis[1];
         if (S && S->stream) { (void)hipStreamSynchronize(S->stream); qc_gate_quiet(S); qc_tl_dump(S); }
         for (auto &set : evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
@@ -303,8 +303,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     if (!S || !out) return QC_ERR_INVALID;
     const double t0 = qc_now_ms();
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
-    double tt = t0;
-    auto lap = [&](const char *what) { if (sdbg) { const double t = qc_now_ms(); fprintf(stderr, "[setup] %-28s %.3f ms\n", what, t - tt); tt = t; } };
+    QcLap lap{"setup", sdbg, t0};
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
     lap("qc_device_init (total)");
@@ -453,17 +452,17 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         } else {
             if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, dG)) != QC_OK) return rc;   // rhf.rs:152-167
         }
-        st->cur_build_tuned = false; st->cur_build_gen = S->assign_gen;
+        st->cur_build_tuned = false; st->cur_build_gen = S->assign.gen;
     } else {
         QC_HIP_CHECK(hipEventRecord(ev0, sm));
         qc_stamp("ev0");
-        const int tunes0 = S->tune_count;
+        const int tunes0 = S->assign.tune_count;
         const double tt0 = qc_now_ms();
         if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dG + nn : nullptr, st->uhf,
                                        &st->twin, W.H.p, dF[0], dF[1], &have_F, st)) != QC_OK) return rc;
-        st->cur_build_tuned = S->tune_count != tunes0;
+        st->cur_build_tuned = S->assign.tune_count != tunes0;
         if (st->cur_build_tuned) st->ms_tuner += qc_now_ms() - tt0;
-        st->cur_build_gen = S->assign_gen;
+        st->cur_build_gen = S->assign.gen;
     }
     qc_stamp("build out");
     scf_flush_timing(st);                                                 // (the previous pass's times, now that this pass's build is out)
@@ -472,7 +471,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     // UHF: the two spins' steps are independent (uhf.rs:84-135 runs them one after the other) - the beta step goes to a side stream on
     // another dispatch pipe, behind an event of the build's closing kernel, and meets the handle's stream again before the scalars
     // (device-side join).  Same kernels, same arithmetic, per spin: results are bit for bit those of the serial order (QC_NO_SPIN_PARALLEL).
-    const bool spin_par = st->uhf && !W.small_fused && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events;
+    const bool spin_par = st->uhf && !W.small_fused && st->spin_parallel && S->lanes.nlanes >= 2 && !S->join.by_events;
     if (!W.small_fused) {
         hipStream_t side = spin_par ? qc_spin_fork(S) : nullptr;
         if (spin_par && !side) return QC_ERR_HIP;
@@ -527,7 +526,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     // UHF on the one-workgroup path: the two spins' kernels side by side as well - beta on a side stream of another dispatch pipe behind an
     // event of the build's closing kernel, with the second set of work buffers; the kernel that joins the streams on the device also hands
     // the control words over and stores the sequence word (qc_spin_join_end).  Same kernels per spin: bit for bit the serial order.
-    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->nlanes >= 2 && !S->join_by_events && !multi;
+    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->lanes.nlanes >= 2 && !S->join.by_events && !multi;
     if (small_par) {
         hipStream_t side = qc_spin_fork(S);
         if (!side) return QC_ERR_HIP;
@@ -543,7 +542,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
             const bool scale_here = !st->uhf && !st->stored && S->accum_fx;
             scale_in_kernel = scale_here;
             SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl.p : nullptr, ctl_out,
-                         scale_here ? S->d_fxs : nullptr};
+                         scale_here ? S->dev.d_fxs.p : nullptr};
             if (seq_wait && s == nspin - 1) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
             if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
         }
@@ -578,7 +577,7 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         // sum and fixed-point unit; a memset after a mode change), the next build's side streams - which start without a fork event -
         // must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there: the kernel
         // leaves the fixed-point unit itself and the fold left the planes clean.)
-        if (!st->stored && S->prep_enqueued) QC_HIP_CHECK(wait_event(ev2));
+        if (!st->stored && S->prep.enqueued) QC_HIP_CHECK(wait_event(ev2));
     } else QC_HIP_CHECK(wait_event(ev2));
     const double th2 = qc_now_ms();
     qc_stamp("pass seen");
@@ -766,28 +765,23 @@ namespace {
 struct FockPrepSave {
     qc_system *S;
     DevBuf fxs, Dj;
-    bool prepared, gt_clean, prep_enqueued;
-    int gt_clean_nspin;
-    const double *prep_Da, *prep_Db;
-    const void *prep_owner;
-    explicit FockPrepSave(qc_system *S_) : S(S_), prepared(S_->prepared), gt_clean(S_->gt_clean), prep_enqueued(S_->prep_enqueued),
-        gt_clean_nspin(S_->gt_clean_nspin), prep_Da(S_->prep_Da), prep_Db(S_->prep_Db), prep_owner(S_->prep_owner) {}
+    const QcPrepared prep;
+    explicit FockPrepSave(qc_system *S_) : S(S_), prep(S_->prep) {}
     int save() {
         const size_t nn = (size_t)S->nbasis * S->nbasis;
         if (fxs.alloc(2) != QC_OK || Dj.alloc(nn) != QC_OK) return QC_ERR_HIP;
         QC_HIP_CHECK(hipStreamSynchronize(S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(fxs.p, S->d_fxs, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(Dj.p, S->d_Dj, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(fxs.p, S->dev.d_fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(Dj.p, S->dev.d_Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
         return QC_OK;
     }
     int restore() {
         const size_t nn = (size_t)S->nbasis * S->nbasis;
-        QC_HIP_CHECK(hipMemcpyAsync(S->d_fxs, fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(S->d_Dj, Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_fxs.p, fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_Dj.p, Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
         QC_HIP_CHECK(hipStreamSynchronize(S->stream));
         // (a build that ran in between left the planes clean for ITS layout; the saved flags speak of the state's layout, which is zero too)
-        S->prepared = prepared; S->gt_clean = gt_clean && S->gt_clean; S->gt_clean_nspin = gt_clean_nspin; S->prep_enqueued = prep_enqueued;
-        S->prep_Da = prep_Da; S->prep_Db = prep_Db; S->prep_owner = prep_owner;
+        const bool clean = prep.gt_clean && S->prep.gt_clean; S->prep = prep; S->prep.gt_clean = clean;
         return QC_OK;
     }
 };
@@ -879,7 +873,7 @@ int qc_scf_counters(qc_scf_state *st, double *out, int n) {
     scf_flush_timing(st);
     const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->ms_fock, st->ms_linalg, (double)st->builds_timed, st->ms_tuner, (double)st->passes,
                                         0.0, 0.0 /* reserved */, (double)st->redos,
-                                        (double)st->S->on.trials, st->S->on.settled ? 1.0 : 0.0};
+                                        (double)st->S->assign.on.trials, st->S->assign.on.settled ? 1.0 : 0.0};
     for (int i = 0; i < n && i < QC_SCF_NCOUNTERS; ++i) out[i] = v[i];
     return QC_OK;
 }

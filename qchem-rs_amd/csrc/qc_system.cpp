@@ -7,7 +7,6 @@
 // per-rank shards.  Also holds the host implementation of molint::overlap/kinetic/nuclear (rhf.rs:41-43), which
 // SURVEY.md 8f ranks as "next" for the GPU.  Integral formulas: McMurchie-Davidson.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -136,9 +135,7 @@ static void pair_hermite_matrix(const QcShell &A, const QcShell &B, int i, int j
 
 void qc_build_model(qc_system *S) {
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
-    auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tt = tnow();
-    auto lap = [&](const char *what) { if (sdbg) { const double t = tnow(); fprintf(stderr, "[model] %-28s %.3f ms\n", what, t - tt); tt = t; } };
+    QcLap lap{"model", sdbg};
     int off = 0;
     for (auto &sh : S->shells) {
         for (int k = 0; k < 3; ++k) sh.A[k] = S->xyz[3 * sh.atom + k];
@@ -509,9 +506,8 @@ void qc_build_shards(qc_system *S, bool meta_only) {
     S->lists_stale = meta_only;
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
     double tacc[6] = {0, 0, 0, 0, 0, 0};
-    auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tlast = tnow();
-    auto acc = [&](int k) { if (sdbg) { const double t = tnow(); tacc[k] += t - tlast; tlast = t; } };
+    double tlast = qc_now_ms();
+    auto acc = [&](int k) { if (sdbg) { const double t = qc_now_ms(); tacc[k] += t - tlast; tlast = t; } };
     // Schwarz screening (once the factors exist - they come from a device pass): |(ab|cd)| <= Q_ab Q_cd, quartets below
     // schwarz_tau are not evaluated.  Density-independent, so the work lists stay static; the reference visits every quartet
     // (its own TODO, uhf.rs:49-50), throughput figures keep counting the enumerated ones.

@@ -579,7 +579,7 @@ def test_a_wait_that_gives_up_fails_the_call_that_waited(monkeypatch):
 
 def test_two_handles_from_two_threads():
     """`distinct handles may be used from distinct threads` (include/qchem_hip.h): two SCF runs on one device at the same time - both
-    with device-side waits - end bit-identical to the same runs alone (per-device issue gate, qc_fock.hip)."""
+    with device-side waits - end bit-identical to the same runs alone (per-device issue gate, qc_streams.hip)."""
     import threading
     import qchem_rs_amd as q
     mols = [load_system("water", "cc-pVTZ"), load_system("ethylene", "cc-pVDZ")]
@@ -643,7 +643,7 @@ def test_spin_parallel_roothaan_steps_do_not_change_a_bit(mol, basis, na, nb, mo
 
 
 def test_assignment_search_and_replica_count_never_show(monkeypatch):
-    """Which launch goes to which dispatch lane is searched while the handle is used (qc_fock.hip: trials of neighbouring assignments,
+    """Which launch goes to which dispatch lane is searched while the handle is used (qc_assign.hip: trials of neighbouring assignments,
     restarts from perturbed copies of the best, finals) and how many accumulator replicas are in use is a tuning matter (8 for n <= 64):
     neither may change a bit of any build or of any SCF run - and the search ends, by itself or when a harness says so."""
     import qchem_rs_amd as q
@@ -741,6 +741,45 @@ def test_dispatch_lanes_are_measured():
     assert 1 <= n <= 7
     if os.environ.get("GPU_MAX_HW_QUEUES") == "8" and not os.environ.get("QC_NO_LANES"):
         assert n == 4 and lane0_main, (n, slots, lane0_main)
+
+
+def test_handle_lifecycle():
+    """What the device side of a handle goes through from its creation to its end (qc_device.cpp, the stream pool of qc_streams.hip,
+    qc_system_destroy): a handle that closes leaves its stream set to the next one, which reports the same dispatch lanes and builds the
+    same bits; a handle closed under a live SCF state stays until that state ends, and the state's passes are those of an undisturbed run;
+    the device is in order afterwards.  water/6-31G** (n = 25): a bra-major and a column class in one build."""
+    import qchem_rs_amd as q
+    m = load_system("water", "6-31G_st_st")
+    D = _rand_sym(25, 11)
+    s1 = q.System(m)
+    G = s1.fock_rhf(D)
+    lanes = s1.dispatch_lanes()
+    s1.close()
+    s2 = q.System(m)
+    if not os.environ.get("QC_NO_LANES") and not os.environ.get("QC_NO_STREAM_POOL"):
+        assert s2.dispatch_lanes() == lanes                        # (the pooled stream set came back with its measured lanes)
+    assert np.array_equal(s2.fock_rhf(D), G)
+    s2.close()
+
+    def passes(close_handle_after):
+        h = q.System(m)
+        st = q.ScfStepper(h)
+        tr = []
+        for k in range(5):
+            if k == close_handle_after:
+                h.close()                                          # the state keeps the handle alive
+            tr.append(st.iterate())
+        w = st.orbital_energies()
+        st.close()                                                 # (the last state of a closed handle frees it)
+        h.close()
+        return tr, w
+
+    ref, w_ref = passes(None)
+    tr, w = passes(2)
+    assert tr == ref and np.array_equal(w, w_ref)
+    s4 = q.System(m)
+    assert np.array_equal(s4.fock_rhf(D), G)
+    s4.close()
 
 
 def test_scf_runs_are_bitwise_reproducible():
