@@ -60,6 +60,24 @@ pub struct QcStability {
     pub ms_builds: f64,
 }
 
+/// qc_polarizability (include/qchem_hip.h): in max_iterations (0: 100), tol (0: 1e-6); out alpha (row-major, symmetrised), residual
+/// norms, the asymmetry before symmetrisation, counts and times.
+#[repr(C)]
+pub struct QcPolarizability {
+    pub max_iterations: i32,
+    pub reserved0: i32,
+    pub tol: f64,
+    pub alpha: [f64; 9],
+    pub residuals: [f64; 3],
+    pub asymmetry: f64,
+    pub nconverged: i32,
+    pub iterations: i32,
+    pub builds: i32,
+    pub reserved1: i32,
+    pub ms_total: f64,
+    pub ms_builds: f64,
+}
+
 pub const QC_OK: c_int = 0;
 pub const QC_NOT_CONVERGED: c_int = 1;
 pub const QC_DIIS_SINGULAR: c_int = 2;
@@ -118,6 +136,15 @@ extern "C" {
     pub fn qc_scf_begin_rhf_from(sys: *mut QcSystem, d: *const f64, out: *mut *mut QcScfState) -> c_int;
     pub fn qc_scf_begin_uhf_from(sys: *mut QcSystem, n_alpha: c_int, n_beta: c_int, da: *const f64, db: *const f64,
                                  out: *mut *mut QcScfState) -> c_int;
+    /// Dipole matrices <a|(r - origin)_k|b>, k = x, y, z: 3*n*n doubles; origin: three doubles or null (0, 0, 0).  Host only.
+    pub fn qc_dipole_matrices(sys: *const QcSystem, origin: *const f64, out: *mut f64) -> c_int;
+    /// The same from the GPU kernel the SCF properties use.
+    pub fn qc_dipole_matrices_gpu(sys: *mut QcSystem, origin: *const f64, out: *mut f64) -> c_int;
+    /// Dipole moment (e bohr) of the state's density: mu[3]; mu_nuclear[3] (nullable): the nuclear part.  The state is left as it was.
+    pub fn qc_scf_dipole(st: *mut QcScfState, origin: *const f64, mu: *mut f64, mu_nuclear: *mut f64) -> c_int;
+    /// Static dipole polarizability (bohr^3) by coupled-perturbed HF at the state's last orbitals; response: null or 3 x
+    /// qc_scf_stability_dim(st, 0) doubles.  The state is left as it was.
+    pub fn qc_scf_polarizability(st: *mut QcScfState, io: *mut QcPolarizability, response: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

@@ -124,3 +124,24 @@ pub fn lowest_hessian_eigenvalue(st: *mut ffi::QcScfState, kind: i32) -> Option<
         _ => None,
     }
 }
+
+/// Dipole moment (e bohr, origin 0) of a state's density (`qc_scf_dipole`).  None on any error.  (Uncompiled, like the rest of this crate.)
+pub fn dipole_moment(st: *mut ffi::QcScfState) -> Option<[f64; 3]> {
+    let mut mu = [0.0f64; 3];
+    match unsafe { ffi::qc_scf_dipole(st, std::ptr::null(), mu.as_mut_ptr(), null_mut()) } {
+        ffi::QC_OK => Some(mu),
+        _ => None,
+    }
+}
+
+/// Static dipole polarizability (bohr^3, row-major 3 x 3, symmetrised) of a state that has done at least one pass
+/// (`qc_scf_polarizability`, default tolerance).  None on any error or when the response equations do not converge.  The state is left
+/// as it was.
+pub fn static_polarizability(st: *mut ffi::QcScfState) -> Option<[f64; 9]> {
+    let mut io = ffi::QcPolarizability { max_iterations: 0, reserved0: 0, tol: 0.0, alpha: [0.0; 9], residuals: [0.0; 3], asymmetry: 0.0,
+                                         nconverged: 0, iterations: 0, builds: 0, reserved1: 0, ms_total: 0.0, ms_builds: 0.0 };
+    match unsafe { ffi::qc_scf_polarizability(st, &mut io, null_mut()) } {
+        ffi::QC_OK => Some(io.alpha),
+        _ => None,
+    }
+}

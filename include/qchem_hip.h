@@ -238,6 +238,43 @@ int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors /* null
  * electronic energy of the returned determinant.  Errors as qc_scf_stability; the state is left exactly as it was. */
 int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double angle, double *Da, double *Db, double *energy);
 
+/* ---- dipole moment and static dipole polarizability (after SCF, not in the reference).  Atomic units throughout (e bohr; bohr^3).
+ * The three dipole matrices M_k = <a| (r - O)_k |b>, k = x, y, z, one after the other (3*n*n doubles, each exactly symmetric), in the
+ * library's basis functions: same normalisation and Cartesian-to-pure transform as the overlap.  origin: three doubles, NULL = (0, 0, 0).
+ * The first needs no device (like the overlap); the second runs the GPU kernel the properties below use. */
+int qc_dipole_matrices(const qc_system *sys, const double *origin, double *out);
+int qc_dipole_matrices_gpu(qc_system *sys, const double *origin, double *out);
+
+/* mu_k = sum_A Z_A (R_A - O)_k - tr(P_t M_k) with P_t = P_alpha + P_beta the state's density on the device (what qc_scf_density
+ * returns; available from qc_scf_begin_* on).  mu_nuclear (nullable): the first sum alone, computed on the host.  The trace is a fixed-order
+ * reduction: two calls give the same bits.  For a neutral system mu does not depend on the origin.  The state is left exactly as it was. */
+int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double mu_nuclear[3]);
+
+/* Static dipole polarizability by coupled-perturbed Hartree-Fock at the state's last C and orbital energies: (A + B) U^q = r^q for the
+ * three directions, r^q = C_occ^T M_q C_virt per spin block, alpha_pq = c r^p . U^q with c = 4 (RHF, the singlet operator) or 2 (UHF,
+ * the internal operator); vectors laid out as for qc_scf_stability (length: qc_scf_stability_dim of kind 0).  (A + B) x is the product of the stability
+ * analysis: one direct Fock build per trial vector, always the direct build, no n^4 storage.  Reduced-space iteration with one subspace
+ * of at most 40 vectors shared by the three right-hand sides; the projected systems are solved on the host by LU.  A right-hand side that
+ * is exactly zero costs no build, and its row and column of alpha are exactly zero.  At a converged, stable state alpha is minus the
+ * second derivative of the energy with respect to a uniform field; the canonical-orbital diagonal e_a - e_i is used as for stability.
+ * In:  tol: residual 2-norm every system must reach (0: 1e-6); max_iterations (0: 100).
+ * Out: alpha row-major, symmetrised 1/2 (alpha_pq + alpha_qp); asymmetry: the largest |alpha_pq - alpha_qp| before that; residual norms,
+ * systems converged, iterations, Fock builds, wall time of the call and of its builds (ms).  response (nullable): the three U^q on the host.
+ * QC_NOT_CONVERGED when the iterations run out or a projected system is singular: alpha, response and residuals then all belong to the
+ * last estimate that could be formed (before the first solve that is U = 0, whose residuals are the norms of the right-hand sides).  QC_ERR_INVALID:
+ * null pointers, a negative or NaN tol, a negative max_iterations, a state before its first qc_scf_iterate - all checked before the
+ * device is touched.  No occupied-virtual pair at all: QC_OK, alpha = 0, no build.  QC_ERR_UNSUPPORTED on a sharded handle or one with a
+ * communicator.  Bitwise reproducible from call to call and across fresh handles.  The state is left exactly as it was. */
+typedef struct {
+    int32_t max_iterations, reserved0;
+    double tol;
+    double alpha[9];
+    double residuals[3], asymmetry;
+    int32_t nconverged, iterations, builds, reserved1;
+    double ms_total, ms_builds;
+} qc_polarizability;
+int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response /* nullable: 3 x dim doubles on the host */);
+
 /* qc_scf_begin_rhf / qc_scf_begin_uhf with the caller's densities (host, n*n, in the convention of qc_scf_density: the RHF density carries
  * the factor 2) in place of the Hueckel guess: DIIS windows empty, first eigensolve cold.  Null densities are QC_ERR_INVALID (checked
  * before the device is touched). */

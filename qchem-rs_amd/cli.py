@@ -15,6 +15,9 @@ Three additions, all opt-in:
     internal) and a `wave function: stable` / `unstable` line; `--json` then carries a "stability" object;
   * `--follow` runs hf.stabilize instead: converge, follow the lowest negative eigenvalue, converge again - one `cycle` line each - and
     prints the final determinant's lines (those of uhf once an rhf run has followed a triplet instability); `--json` carries "follow".
+  * `--dipole` adds the dipole moment of the converged determinant (origin 0): `dipole moment (a.u.): x y z`, the same in Debye, and
+    `|mu|`; `--polarizability` adds the static dipole polarizability (coupled-perturbed HF, bohr^3): three rows and the isotropic value;
+    `--json` then carries "dipole" / "polarizability" objects.  Neither combines with `--follow`.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -80,6 +83,8 @@ def build_parser() -> argparse.ArgumentParser:
                        help="leave the lowest N orbitals of each spin out of the MP2 sums (requires --mp2)")
         s.add_argument("--gradient", action="store_true", help="also print the analytic nuclear gradient (Eh/bohr) of the converged determinant")
         s.add_argument("--stability", action="store_true", help="also print the lowest eigenvalue(s) of the orbital Hessian and whether the determinant is a minimum")
+        s.add_argument("--dipole", action="store_true", help="also print the dipole moment of the converged determinant (a.u. and Debye)")
+        s.add_argument("--polarizability", action="store_true", help="also print the static dipole polarizability (coupled-perturbed HF, bohr^3)")
         s.add_argument("--follow", action="store_true", help="follow instabilities downhill until the determinant is stable (at most 8 cycles)")
     return p
 
@@ -91,8 +96,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--frozen-core requires --mp2")
     if args.frozen_core is not None and args.frozen_core < 0:
         p.error("--frozen-core must not be negative")
-    if args.follow and (args.mp2 or args.gradient):
-        p.error("--follow cannot be combined with --mp2 or --gradient")
+    if args.follow and (args.mp2 or args.gradient or args.dipole or args.polarizability):
+        p.error("--follow cannot be combined with --mp2, --gradient, --dipole or --polarizability")
     return args
 
 
@@ -109,6 +114,39 @@ def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
 def _print_gradient(system: MolecularSystem, g) -> None:
     for i, (atom, row) in enumerate(zip(system.atoms, g)):
         print("%d %d %.10f %.10f %.10f" % (i, atom.ordinal, row[0], row[1], row[2]))
+
+
+AU_TO_DEBYE = 2.541746473
+
+
+def _dipole_json(mu) -> dict:
+    norm = float((mu ** 2).sum() ** 0.5)
+    return {"au": mu.tolist(), "debye": (mu * AU_TO_DEBYE).tolist(), "norm_au": norm, "norm_debye": norm * AU_TO_DEBYE, "origin": [0.0, 0.0, 0.0]}
+
+
+def _print_dipole(d: dict) -> None:
+    print("dipole moment (a.u.): %.8f %.8f %.8f" % tuple(d["au"]))
+    print("dipole moment (Debye): %.8f %.8f %.8f" % tuple(d["debye"]))
+    print("|mu|: %.8f a.u. = %.8f Debye" % (d["norm_au"], d["norm_debye"]))
+
+
+def _polarizability_json(r: "hf.PolarizabilityOutput") -> dict:
+    return {"alpha": r.alpha.tolist(), "isotropic": r.isotropic, "residuals": r.residuals.tolist(), "converged": r.converged,
+            "iterations": r.iterations, "builds": r.builds, "timings_ms": {"total": r.ms_total, "builds": r.ms_builds}}
+
+
+def _print_polarizability(d: dict) -> None:
+    print("polarizability (a.u.):")
+    for row in d["alpha"]:
+        print("  %.8f %.8f %.8f" % tuple(row))
+    print("isotropic polarizability: %.8f" % d["isotropic"])
+    if not d["converged"]:
+        print("polarizability: the response equations did not converge", file=sys.stderr)
+
+
+def _properties(st, args):
+    """(dipole, polarizability) JSON objects of the flags given, from the converged state"""
+    return (_dipole_json(st.dipole()) if args.dipole else None, _polarizability_json(st.polarizability()) if args.polarizability else None)
 
 
 STABILITY_THRESHOLD = 1e-5        # eigenvalues above -threshold count as stable (exact zero modes come out as +-1e-9)
@@ -187,12 +225,13 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = grad = stab = None
+    mp2 = grad = stab = dip = pol = None
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.stability:
+    if args.stability or args.dipole or args.polarizability:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
-                                                             st.gradient() if args.gradient else None, _stability(st, False)))
-        out, (mp2, grad, stab) = res if res is not None else (None, (None, None, None))
+                                                             st.gradient() if args.gradient else None,
+                                                             _stability(st, False) if args.stability else None) + _properties(st, args))
+        out, (mp2, grad, stab, dip, pol) = res if res is not None else (None, (None,) * 5)
     elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
@@ -215,6 +254,10 @@ def run_rhf(args) -> int:
         _print_gradient(system, grad)
     if stab is not None:
         _print_stability(stab)
+    if dip is not None:
+        _print_dipole(dip)
+    if pol is not None:
+        _print_polarizability(pol)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -225,6 +268,10 @@ def run_rhf(args) -> int:
             doc["gradient"] = grad.tolist()
         if stab is not None:
             doc["stability"] = stab
+        if dip is not None:
+            doc["dipole"] = dip
+        if pol is not None:
+            doc["polarizability"] = pol
         print(json.dumps(doc))
     return 0
 
@@ -239,8 +286,8 @@ def run_uhf(args) -> int:
     if args.follow:
         return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
-    s2 = mp2 = grad = stab = None
-    if not extension and not args.mp2 and not args.gradient and not args.stability:
+    s2 = mp2 = grad = stab = dip = pol = None
+    if not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability:
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
@@ -261,6 +308,7 @@ def run_uhf(args) -> int:
                         grad = st.gradient()
                     if args.stability:
                         stab = _stability(st, True)
+                    dip, pol = _properties(st, args)
                     break
         finally:
             st.close()
@@ -282,6 +330,10 @@ def run_uhf(args) -> int:
         _print_gradient(system, grad)
     if stab is not None:
         _print_stability(stab)
+    if dip is not None:
+        _print_dipole(dip)
+    if pol is not None:
+        _print_polarizability(pol)
     if args.json:
         doc = {"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -294,6 +346,10 @@ def run_uhf(args) -> int:
             doc["gradient"] = grad.tolist()
         if stab is not None:
             doc["stability"] = stab
+        if dip is not None:
+            doc["dipole"] = dip
+        if pol is not None:
+            doc["polarizability"] = pol
         print(json.dumps(doc))
     return 0
 

@@ -147,6 +147,26 @@ int qc_one_electron_gpu(qc_system *S, int which, double *out) {
     return QC_OK;
 }
 
+int qc_dipole_matrices(const qc_system *S, const double *origin, double *out) {
+    if (!S || !out) return QC_ERR_INVALID;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    qc_host_dipole(S, origin ? origin : zero, out);
+    return QC_OK;
+}
+int qc_dipole_matrices_gpu(qc_system *S, const double *origin, double *out) {
+    if (!S || !out) return QC_ERR_INVALID;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    DevBuf M;
+    if (M.alloc(3 * nn) != QC_OK) return QC_ERR_HIP;
+    if ((rc = qc_dipole_device(S, origin ? origin : zero, M.p)) != QC_OK) return rc;
+    QC_HIP_CHECK(hipMemcpyAsync(out, M.p, 3 * nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    return QC_OK;
+}
+
 int qc_set_stream(qc_system *S, void *hip_stream) {
     if (!S) return QC_ERR_INVALID;
     if (S->own_stream && S->stream) { (void)hipStreamDestroy(S->stream); S->own_stream = false; }

@@ -297,6 +297,7 @@ void qc_build_model(qc_system *S);
 // screened lists can exist; the lists are then built once, behind that pass, or on demand: qc_ensure_lists)
 void qc_build_shards(qc_system *S, bool meta_only = false);
 void qc_host_one_electron(const qc_system *S, int which, double *out);
+void qc_host_dipole(const qc_system *S, const double *origin /* 3 */, double *out /* 3 n*n */);
 void qc_boys_host(int nmax, double x, double *F);
 
 // Boys tables, one per total Hermite order L: row k = F_{L+j}(x_k) / j!, j = 0..7, x_k = k * QC_BOYS_DX (64-byte rows);
@@ -352,6 +353,13 @@ int qc_schwarz_device(qc_system *S);     // fills pairQ / imax from the (P|P) qu
 // fixed-point scale of a build from its densities: out[0] = 2^S, out[1] = 2^-S, S = min(QC_FX_MAXBITS, 60 - ceil(log2(4 imax sum|D|)))
 void qc_fx_scale(hipStream_t st, int n, const double *Da, const double *Db /*nullable*/, double imax, double *out);
 int qc_one_electron_device(qc_system *S, int which /* 0 S, 1 T, 2 V */, double *d_out);
+int qc_dipole_device(qc_system *S, const double *origin /* 3, host */, double *d_out /* 3 n*n: x, y, z */);   // (qc_one_electron.hip)
+// properties of an SCF state (qc_response.hip).  dipole_trace: tr3[k] = tr((Pa + Pb) M_k) (dPb nullable; dM: 3 n*n; fixed-order sums).
+// polarizability: the coupled-perturbed HF equations (A + B) U^q = r^q for the three dipole directions at the orbitals dC / energies
+// dEps, by a reduced-space iteration on the Hessian-vector product of the stability analysis; io's inputs are checked by the caller,
+// response (host, nullable): 3 x dim.  Runs direct Fock builds on the handle: the caller puts FockPrepSave around it.
+int qc_dipole_trace_device(qc_system *S, const double *dPa, const double *dPb, const double *dM, double *tr3);
+int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_polarizability *io, double *response);
 int qc_launch_fock_classes(qc_system *S, const QcFockArgs &a, float *class_ms /*nullable*/, float *unit_ms = nullptr /*nullable, 14*/, bool nofork = false);
 // hipEvent time of a build inside an SCF pass that ran under stream assignment `gen` (no-op once the choice is made)
 void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen);

@@ -1,5 +1,5 @@
 // qc_md.h - the McMurchie-Davidson primitives every integral consumer outside the Fock kernels shares, host and device:
-// Hermite expansion E^{ij}_t, Boys function, the Hermite-Coulomb recurrence step, the overlap / kinetic / nuclear-attraction sums of
+// Hermite expansion E^{ij}_t, Boys function, the Hermite-Coulomb recurrence step, the overlap / kinetic / nuclear-attraction / dipole sums of
 // one Cartesian pair, and the order of the Cartesian components.  Users: the host model and host one-electron matrices
 // (qc_system.cpp), the one-electron kernel (qc_one_electron.hip), the gradient kernels (qc_grad.hip).  The Fock kernels keep their
 // own interpolated Boys function and staged tables.
@@ -105,6 +105,13 @@ __host__ __device__ inline double qc_md_r_step(const double *Rn1, int t, int u, 
 // (f: a factor that enters the product first - the SCF side's (pi/p)^{3/2}, whose products have always rounded in that order)
 template <class E1> __host__ __device__ inline double qc_md_ovl(const E1 *E, const int *a, const int *b, double f = 1.0) {
     return f * E[0].g(a[0], b[0], 0) * E[1].g(a[1], b[1], 0) * E[2].g(a[2], b[2], 0);
+}
+// <a| (r - O)_k |b> / (pi/p)^{3/2}: one more entry of the table of axis k, [E^k_1 + (P - O)_k E^k_0] E_0 E_0 (PO = (P - O)_k; f as in qc_md_ovl)
+template <class E1> __host__ __device__ inline double qc_md_dip(const E1 *E, const int *a, const int *b, int k, double PO, double f = 1.0) {
+    double s[3];
+    for (int q = 0; q < 3; ++q) s[q] = E[q].g(a[q], b[q], 0);
+    s[k] = E[k].g(a[k], b[k], 1) + PO * s[k];
+    return f * s[0] * s[1] * s[2];
 }
 // sum_axis <a| d^2/dx^2 |b> (second derivative of the ket primitive: b + 2, b, b - 2 terms; eb: its exponent); T = -1/2 (pi/p)^{3/2} x this
 template <class E1> __host__ __device__ inline double qc_md_kin(const E1 *E, const int *a, const int *b, double eb) {

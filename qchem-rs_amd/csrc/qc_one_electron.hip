@@ -1,4 +1,4 @@
-// qc_one_electron.hip - overlap, kinetic-energy and nuclear-attraction matrices on the GPU.
+// qc_one_electron.hip - overlap, kinetic-energy, nuclear-attraction and dipole matrices on the GPU.
 //
 // Replaces molint::overlap / kinetic / nuclear (call sites rhf.rs:41-43, uhf.rs:52-54) - the first "next" row of the
 // scope table: the last CPU-only start-up phase of an SCF run.  Same McMurchie-Davidson formulas as the
@@ -93,6 +93,56 @@ __global__ __launch_bounds__(64) void qc_one_electron_kernel(int which, int nshe
     }
 }
 
+// Dipole matrices out[k * n * n + ..] = <a| (r - O)_k |b>, k = x, y, z, in one launch: the same wave-per-shell-pair shape, the lanes share
+// out the primitive pairs and add into three Cartesian LDS blocks; the three components share the E tables (j <= L_b, t <= 1 is read).
+__global__ __launch_bounds__(64) void qc_dipole_kernel(int nshells, const QcDevShell *__restrict__ sh, const double *__restrict__ exps,
+                                                       const double *__restrict__ coefs, const double *__restrict__ Tm, double ox, double oy, double oz,
+                                                       int n, double *__restrict__ out) {
+    __shared__ double cart[3 * MAXC * MAXC];
+    int a = 0, rem = blockIdx.x;
+    while (rem > a) { rem -= a + 1; ++a; }
+    const int b = rem;
+    if (a >= nshells) return;
+    const QcDevShell A = sh[a], B = sh[b];
+    const int lane = threadIdx.x, nca = A.ncart, ncb = B.ncart;
+    for (int i = lane; i < 3 * MAXC * MAXC; i += 64) cart[i] = 0.0;
+    __syncthreads();
+    const double O[3] = {ox, oy, oz};
+    const int npp = A.nprim * B.nprim;
+    for (int pp = lane; pp < npp; pp += 64) {
+        const int i = pp / B.nprim, j = pp - i * B.nprim;
+        const double ea = exps[A.poff + i], eb = exps[B.poff + j], p = ea + eb, cc = coefs[A.poff + i] * coefs[B.poff + j];
+        double PO[3];
+        for (int k = 0; k < 3; ++k) PO[k] = (ea * A.A[k] + eb * B.A[k]) / p - O[k];
+        E1 E[3];
+        for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+        const double s3 = pow(M_PI / p, 1.5);
+        for (int x = 0; x < nca; ++x) {
+            const unsigned char *ax = qc_md_cart(A.L, x);
+            const int ai[3] = {ax[0], ax[1], ax[2]};
+            for (int y = 0; y < ncb; ++y) {
+                const unsigned char *by = qc_md_cart(B.L, y);
+                const int bi[3] = {by[0], by[1], by[2]};
+                for (int k = 0; k < 3; ++k)
+                    (void)__builtin_amdgcn_ds_atomic_fadd_f64((lds_double *)&cart[(k * MAXC + x) * MAXC + y], cc * qc_md_dip(E, ai, bi, k, PO[k], s3));
+            }
+        }
+    }
+    __syncthreads();
+    // Cartesian -> the shells' functions, both triangles, as above
+    const double *Ta = Tm + A.toff, *Tb = Tm + B.toff;
+    const size_t nn = (size_t)n * n;
+    for (int f = lane; f < 3 * A.nfunc * B.nfunc; f += 64) {
+        const int k = f / (A.nfunc * B.nfunc), fab = f - k * A.nfunc * B.nfunc, fa = fab / B.nfunc, fb = fab - fa * B.nfunc;
+        if (a == b && fb > fa) continue;
+        double v = 0.0;
+        for (int x = 0; x < nca; ++x)
+            for (int y = 0; y < ncb; ++y) v += Ta[fa * nca + x] * Tb[fb * ncb + y] * cart[(k * MAXC + x) * MAXC + y];
+        out[k * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+        out[k * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+    }
+}
+
 }  // namespace
 
 // The handle's shell blob: uploaded at the first call, in one allocation and one copy; a failure leaves the handle without one.
@@ -148,6 +198,17 @@ int qc_one_electron_device(qc_system *S, int which, double *d_out) {
     if (rc != QC_OK) return rc;
     const int npairs = S->nshells * (S->nshells + 1) / 2;
     hipLaunchKernelGGL(qc_one_electron_kernel, dim3(npairs), dim3(64), 0, S->stream, which, S->nshells, B->sh, B->exps, B->coefs, B->T, S->natoms, B->Z, B->xyz,
+                       S->nbasis, d_out);
+    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
+}
+
+// origin: three doubles on the host; d_out: 3 n x n device matrices (x, y, z)
+int qc_dipole_device(qc_system *S, const double *origin, double *d_out) {
+    const QcShellBlob *B;
+    const int rc = qc_shell_blob(S, &B);
+    if (rc != QC_OK) return rc;
+    const int npairs = S->nshells * (S->nshells + 1) / 2;
+    hipLaunchKernelGGL(qc_dipole_kernel, dim3(npairs), dim3(64), 0, S->stream, S->nshells, B->sh, B->exps, B->coefs, B->T, origin[0], origin[1], origin[2],
                        S->nbasis, d_out);
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }

@@ -817,6 +817,35 @@ int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double a
     const int rc2 = keep.restore();
     return rc != QC_OK ? rc : rc2;
 }
+// mu_k = sum_A Z_A (R_A - O)_k - tr(P_t M_k): the nuclear part on the host, the trace by a fixed-order reduction on the device
+int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double mu_nuclear[3]) {
+    if (!st || !mu) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    const double *O = origin ? origin : zero;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    double nuc[3] = {0.0, 0.0, 0.0}, tr[3];
+    for (int a = 0; a < S->natoms; ++a) for (int k = 0; k < 3; ++k) nuc[k] += S->Z[a] * (S->xyz[3 * a + k] - O[k]);
+    DevBuf M;
+    if (M.alloc(3 * nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    int rc = qc_dipole_device(S, O, M.p);
+    if (rc != QC_OK) return rc;
+    if ((rc = qc_dipole_trace_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, M.p, tr)) != QC_OK) return rc;
+    for (int k = 0; k < 3; ++k) { mu[k] = nuc[k] - tr[k]; if (mu_nuclear) mu_nuclear[k] = nuc[k]; }
+    return QC_OK;
+}
+int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response) {
+    if (!st || !io || st->passes == 0 || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    FockPrepSave keep(S);
+    int rc = keep.save();
+    if (rc != QC_OK) return rc;
+    rc = qc_polarizability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, response);   // (reads Cs / ws, writes nothing of the state)
+    const int rc2 = keep.restore();
+    return rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc);
+}
 int qc_scf_begin_rhf_from(qc_system *S, const double *D, qc_scf_state **out) {
     if (!S || !D || !out) return QC_ERR_INVALID;
     return scf_begin(S, false, 0, 0, out, D, nullptr);

@@ -753,3 +753,41 @@ void qc_host_one_electron(const qc_system *S, int which, double *out) {
                 }
         }
 }
+
+// ---- dipole matrices on the host: out[k * n * n + ..] = <a| (r - O)_k |b>, k = x, y, z; normalisation and transform T as for the overlap
+void qc_host_dipole(const qc_system *S, const double *origin, double *out) {
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    std::fill(out, out + 3 * nn, 0.0);
+    for (int a = 0; a < S->nshells; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const QcShell &A = S->shells[a], &B = S->shells[b];
+            const size_t nca = A.ncart, ncb = B.ncart;
+            std::vector<double> cart(3 * nca * ncb, 0.0);
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
+                    double PO[3];
+                    for (int k = 0; k < 3; ++k) PO[k] = (ea * A.A[k] + eb * B.A[k]) / p - origin[k];
+                    E1 E[3];
+                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+                    const double s3 = std::pow(M_PI / p, 1.5);
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
+                            for (int k = 0; k < 3; ++k) cart[(k * nca + x) * ncb + y] += cc * qc_md_dip(E, ai, bi, k, PO[k], s3);
+                        }
+                }
+            for (int k = 0; k < 3; ++k)
+                for (int fa = 0; fa < A.nfunc; ++fa)
+                    for (int fb = 0; fb < B.nfunc; ++fb) {
+                        if (a == b && fb > fa) continue;               // diagonal blocks: one triangle, mirrored (exactly symmetric output)
+                        double v = 0.0;
+                        for (size_t x = 0; x < nca; ++x)
+                            for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[(k * nca + x) * ncb + y];
+                        out[k * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+                        out[k * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+                    }
+        }
+}

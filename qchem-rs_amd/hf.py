@@ -45,7 +45,8 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_scf_orbital_energies", "qc_scf_density", "qc_scf_spin_square", "qc_scf_timings", "qc_scf_end", "qc_fock_profile_tiers", "qc_unit_quartets", "qc_sym_eig_warm", "qc_set_fock_mode", "qc_scf_tensor_ms", "qc_set_accumulation", "qc_set_schwarz", "qc_scf_matrix", "qc_rccl_info", "qc_measure_peaks",
            "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment",
            "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
-           "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from"]
+           "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from",
+           "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability"]
 
 
 class QcError(RuntimeError):
@@ -104,6 +105,29 @@ class StabilityOutput:
     ms_total: float
     ms_builds: float
     vectors: Optional[np.ndarray] = None
+
+
+class _Polarizability(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("reserved0", C.c_int32), ("tol", C.c_double), ("alpha", C.c_double * 9),
+                ("residuals", C.c_double * 3), ("asymmetry", C.c_double), ("nconverged", C.c_int32), ("iterations", C.c_int32),
+                ("builds", C.c_int32), ("reserved1", C.c_int32), ("ms_total", C.c_double), ("ms_builds", C.c_double)]
+
+
+@dataclass
+class PolarizabilityOutput:
+    """qc_polarizability: the static dipole polarizability (3, 3) in bohr^3, symmetrised; isotropic = trace / 3; residual norms of the three
+    response equations; asymmetry: the largest |alpha_pq - alpha_qp| before the symmetrisation; `response` (3, dim) when asked for.
+    converged: every equation reached the tolerance."""
+    alpha: np.ndarray
+    isotropic: float
+    residuals: np.ndarray
+    converged: bool
+    iterations: int
+    builds: int
+    ms_total: float
+    ms_builds: float
+    asymmetry: float = 0.0
+    response: Optional[np.ndarray] = None
 
 
 class WorkStats(C.Structure):
@@ -189,6 +213,10 @@ def lib():
         L.qc_scf_rotated_density.argtypes = [vp, C.c_int, vp, C.c_double, vp, vp, C.POINTER(C.c_double)]
         L.qc_scf_begin_rhf_from.argtypes = [vp, vp, C.POINTER(vp)]
         L.qc_scf_begin_uhf_from.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
+        L.qc_dipole_matrices.argtypes = [vp, vp, vp]
+        L.qc_dipole_matrices_gpu.argtypes = [vp, vp, vp]
+        L.qc_scf_dipole.argtypes = [vp, vp, vp, vp]
+        L.qc_scf_polarizability.argtypes = [vp, C.POINTER(_Polarizability), vp]
         _lib = L
     return _lib
 
@@ -244,6 +272,14 @@ class System:
         """S (0), T (1) or V (2) computed by the GPU kernels the SCF drivers use (qc_one_electron.hip)."""
         M = np.zeros((self.n, self.n))
         _check(lib().qc_one_electron_gpu(self._h, which, M.reshape(-1)), "qc_one_electron_gpu")
+        return M
+
+    def dipole_matrices(self, origin=None, gpu: bool = False):
+        """(3, n, n): M_k = <a| (r - origin)_k |b>, k = x, y, z (origin None: 0) - qc_dipole_matrices on the host, or with gpu=True the
+        kernel the SCF properties use (qc_dipole_matrices_gpu)."""
+        M = np.zeros((3, self.n, self.n))
+        fn = "qc_dipole_matrices_gpu" if gpu else "qc_dipole_matrices"
+        _check(getattr(lib(), fn)(self._h, _origin_ptr(origin), M.ctypes.data_as(C.c_void_p)), fn)
         return M
 
     def eri(self):
@@ -360,6 +396,16 @@ class System:
         return dict(class_ms=ms, class_id=cid, quartets=nq, bytes=by, flops=fl, total_ms=tot.value)
 
 
+def _origin_ptr(origin):
+    """three doubles for the C ABI (None: the null pointer = the coordinate origin); the array is kept alive by the returned object"""
+    if origin is None:
+        return None
+    o = np.ascontiguousarray(origin, np.float64).reshape(-1)
+    if o.size != 3:
+        raise QcError("origin needs three coordinates")
+    return (C.c_double * 3)(*o.tolist())
+
+
 PROFILE_UNITS = 20   # QC_PROFILE_UNITS in include/qchem_hip.h
 
 
@@ -458,6 +504,23 @@ class ScfStepper:
         rc = _check(lib().qc_scf_stability(self._st, C.byref(io), None if X is None else X.ctypes.data_as(C.c_void_p)), "qc_scf_stability")
         return StabilityOutput(int(kind), np.array(io.eigenvalues[:nroots]), np.array(io.residuals[:nroots]), rc == QC_OK, int(io.iterations),
                                int(io.builds), io.ms_total, io.ms_builds, X)
+
+    def dipole(self, origin=None, nuclear: bool = False):
+        """Dipole moment (3,) in e bohr of the state's density (qc_scf_dipole); origin None: 0.  nuclear=True: (mu, mu_nuclear)."""
+        mu, nuc = np.zeros(3), np.zeros(3)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(lib().qc_scf_dipole(self._st, _origin_ptr(origin), p(mu), p(nuc)), "qc_scf_dipole")
+        return (mu, nuc) if nuclear else mu
+
+    def polarizability(self, tol: float = 0.0, max_iterations: int = 0, response: bool = False) -> "PolarizabilityOutput":
+        """Static dipole polarizability by coupled-perturbed HF at the state's last orbitals (qc_scf_polarizability); the state is left as
+        it was.  tol 0: 1e-6; max_iterations 0: 100; response=True: the three solution vectors (3, stability_dim(0))."""
+        io = _Polarizability(max_iterations=int(max_iterations), tol=float(tol))
+        U = np.zeros((3, self.stability_dim(0))) if response else None
+        rc = _check(lib().qc_scf_polarizability(self._st, C.byref(io), None if U is None else U.ctypes.data_as(C.c_void_p)), "qc_scf_polarizability")
+        alpha = np.array(io.alpha).reshape(3, 3)
+        return PolarizabilityOutput(alpha, float(np.trace(alpha)) / 3.0, np.array(io.residuals), rc == QC_OK, int(io.iterations), int(io.builds),
+                                    io.ms_total, io.ms_builds, io.asymmetry, U)
 
     def rotated_density(self, x, angle: float = 0.0, kind: int = 0):
         """(D_alpha, D_beta, electronic energy) of the determinant rotated along x by `angle` radians (qc_scf_rotated_density);
@@ -641,15 +704,27 @@ def unrestricted_gradient(system, config: HartreeFockConfig, n_alpha: int, n_bet
     return _stepped(system, cfg, True, lambda st: st.gradient())
 
 
+def restricted_polarizability(system, config: HartreeFockConfig, tol: float = 0.0):
+    """(RestrictedHartreeFockOutput, PolarizabilityOutput), or None when the SCF does not converge."""
+    return _stepped(system, config, False, lambda st: st.polarizability(tol=tol))
+
+
+def unrestricted_polarizability(system, config: HartreeFockConfig, n_alpha: int, n_beta: int, tol: float = 0.0):
+    """(UnrestrictedHartreeFockOutput, PolarizabilityOutput), or None when the SCF does not converge."""
+    cfg = HartreeFockConfig(config.max_iterations, config.epsilon, int(n_alpha), int(n_beta))
+    return _stepped(system, cfg, True, lambda st: st.polarizability(tol=tol))
+
+
 @dataclass
 class StabilizeOutput:
     """Result of stabilize(): the last converged output (Restricted... while the state stayed RHF, Unrestricted... after an RHF -> UHF
     instability was followed or for a UHF start), per cycle (electronic energy, lowest eigenvalue, kind of that eigenvalue), whether the
-    last state is stable, and its <S^2>."""
+    last state is stable, its <S^2>, and its density."""
     output: object
     history: list
     stable: bool
     spin_square: float = 0.0
+    density: object = None            # the last state's density: D (RHF, factor 2 included) or (D_alpha, D_beta) - a start for ScfStepper(density=...)
 
 
 def stabilize(system, config: HartreeFockConfig, n_alpha: int = 0, n_beta: int = 0, max_cycles: int = 8, threshold: float = 1e-5,
@@ -694,7 +769,7 @@ def stabilize(system, config: HartreeFockConfig, n_alpha: int = 0, n_beta: int =
                 lowest = (0.0, 0)
             history.append((e, lowest[0], lowest[1]))
             if follow is None or cycle == max_cycles:
-                return StabilizeOutput(out, history, follow is None, s2)
+                return StabilizeOutput(out, history, follow is None, s2, (st.density(0), st.density(1)) if is_uhf else st.density(0))
             Da, Db, _ = st.rotated_density(follow[1], 0.0, kind=follow[0])
             if is_uhf:
                 density = (Da, Db)
