@@ -1,7 +1,7 @@
 // qc_eig_tridiag.hip - start vectors for the symmetric eigensolver by Householder tridiagonalisation (gfx950).
 //
 // Replaces the cold / far-from-converged eigensolves behind utils::sorted_eigs (hf/utils.rs:20-36; nalgebra's SymmetricEigen
-// does the same thing: tridiagonalise, then iterate on the tridiagonal matrix).  The parallel Jacobi kernels of qc_linalg.hip
+// does the same thing: tridiagonalise, then iterate on the tridiagonal matrix).  The parallel Jacobi kernels of qc_eig_jacobi.hip
 // touch the whole matrix in every one of their ~6 (n-1) steps and are bound by the LDS port of the single CU they run on
 // (2 n^2 doubles read and written per step: 1.8 us per step at n = 114, 1.1-1.6 ms per eigensolve).  Here
 //   1. qc_tridiag_kernel      A + pert = Q T Q^T: n-2 Householder steps in ONE workgroup, matrix resident in LDS (n <= 139, else in

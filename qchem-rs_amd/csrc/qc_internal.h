@@ -315,7 +315,7 @@ int qc_ds_order_probe(hipStream_t st, double *d_out64);      // (qc_fock_bm.hip)
 void qc_bm_device_lists(const qc_system *S, int lcd, const std::vector<QcBundle> &bundles, const std::vector<int> &ketlist, bool packed,
                         std::vector<QcBundleDev> &db, std::vector<QcKetUnit> &du);
 void qc_drop_launch_plan(qc_system *S);                      // (qc_fock.hip) the launch plan follows the work lists
-// ---- the Fock build (qc_fock.hip), the stream assignment (qc_assign.hip), dense linear algebra (qc_linalg.hip)
+// ---- the Fock build (qc_fock.hip), the stream assignment (qc_assign.hip), dense linear algebra (qc_linalg.hip, qc_eig_*.hip)
 // digestion modes
 struct QcFockArgs {
     const double *Dj;     // density contracted into J (n*n)
@@ -399,6 +399,8 @@ int qc_fock_build_device(qc_system *S, const double *dDa, const double *dDb, dou
 // dense linear algebra on the handle's stream (all row-major n x n, device pointers)
 void qc_gemm(hipStream_t st, int m, int n, int k, double alpha, const double *A, int lda, bool ta, const double *B,
              int ldb, bool tb, double beta, double *C, int ldc, const int *skip = nullptr /* device flag: non-zero = no-op */);
+void qc_gemm_pair(hipStream_t st, int n, const double *A0, bool ta0, const double *B0, double *C0, const double *A1, bool ta1,
+                  const double *B1, double *C1, const int *skip);
 void qc_diis_solve(hipStream_t st, int m, int minlen, int maxlen, const int *slots, const double *dots, double *B, double *c, int *flag);
 void qc_lincomb_dev(hipStream_t st, int n, const double *const *Fs, const double *c_dev, int m, double *out);
 
@@ -425,7 +427,8 @@ struct QcShellBlob {
 };
 int qc_shell_blob(qc_system *S, const QcShellBlob **out);
 
-// ---- eigensolvers (qc_linalg.hip, qc_eig_tridiag.hip).  dA: the symmetric matrix (left intact), dV0: start vectors, dV: sorted
+// ---- eigensolvers (qc_eig_jacobi.hip: rotations; qc_eig_refine.hip: refinement by the rule of qc_refine_rule.h; qc_eig_tridiag.hip:
+// tridiagonal start).  dA: the symmetric matrix (left intact), dV0: start vectors, dV: sorted
 // eigenvectors, dw: ascending eigenvalues; all on `st`.  QcEigWork: scratch of one eigensolve in flight, allocated once for a given n -
 // work, t1..t4: n*n each (callers may use them between eigensolves); x0 / tri: start vectors and work array of the tridiagonal path;
 // small: Rayleigh quotients, statistics, partner list, per-workgroup partials; ctl: four control words for callers without pass words.

@@ -1,6 +1,6 @@
 // qc_scf_small.hip - the Roothaan step of one spin for n <= 64 basis functions as ONE workgroup with every matrix in LDS.
 //
-// Replaces, for small molecules, the ~25-40 launches per SCF pass of the generic path (qc_api.cpp roothaan_enqueue + qc_linalg.hip):
+// Replaces, for small molecules, the ~25-40 launches per SCF pass of the generic path (qc_api.cpp roothaan_enqueue + qc_linalg.hip, qc_eig_refine.hip):
 // the body of the reference's loop between the Fock build and the convergence test (rhf.rs:70-88, uhf.rs:84-137), i.e.
 //   pre    e = F D S - S D F (rhf.rs:71), DIIS over the sample window (diis.rs:28-59), F' = X^T F X (rhf.rs:74)
 //   refine sorted_eigs(F') (rhf.rs:75, utils.rs:20-36) by Ogita-Aishima refinement from start vectors (previous pass / tridiagonal path)
@@ -18,6 +18,7 @@
 #include <atomic>
 
 #include "qc_internal.h"
+#include "qc_refine_rule.h"
 
 typedef double qcs_d4 __attribute__((ext_vector_type(4)));
 
@@ -163,8 +164,6 @@ __device__ __forceinline__ bool qcs_qr_solve(double (&col)[13], int lane, double
 }
 
 }  // namespace
-
-constexpr double QCS_REF_TAU = 1e-3, QCS_REF_TINY = 1e-13, QCS_REF_GFLOOR = 1e-8;      // as qc_linalg.hip (QC_REF_*)
 
 __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a) {
     extern __shared__ double lds[];
@@ -385,7 +384,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
     }
 
     if (a.phases & 2) {
-        // ---- eigenvectors of F' (B3) by refinement from V0: the passes of qc_eig_refine_async (qc_linalg.hip) back to back
+        // ---- eigenvectors of F' (B3) by refinement from V0: the passes of qc_eig_refine_async (qc_eig_refine.hip) back to back
         {
             double v[QCS_E], f[QCS_E];
             const bool loadA = !(a.phases & 1);                          // (uniform)
@@ -406,7 +405,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             __syncthreads();
             QCS_STAMP();
             const double *Sm = Xn, *XtX = B1;
-            // statistics and decisions (qc_refine_stats_kernel); everything reads the zero padding instead of testing bounds
+            // statistics and decisions by the rule of qc_refine_rule.h; everything reads the zero padding instead of testing bounds
             {
                 double part[2] = {0.0, 0.0};
                 double amax = 0.0;
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     const double sv = Sm[ic * ld + cc], r = ((in && dg) ? 1.0 : 0.0) - XtX[ic * ld + cc];
                     part[1] = fma(r, r, part[1]);
                     part[0] = dg ? part[0] : fma(sv, sv, part[0]);
-                    if (in && dg) { const double l = sv / (1.0 - r); lam[ic] = l; amax = fmax(amax, fabs(l)); }
+                    if (in && dg) { const double l = qc_ref_quotient(sv, r); lam[ic] = l; amax = fmax(amax, fabs(l)); }
                 }
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_down(amax, o, 64));
@@ -427,10 +426,10 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 if (tid == 0) { double c = 0.0; for (int k = 0; k < QCS_W; ++k) c = fmax(c, red[k]); scal[2] = c; }
                 __syncthreads();
             }
-            const double scale = scal[2], tiny = QCS_REF_TINY * scale, gfloor = QCS_REF_GFLOOR * scale;
+            const double scale = scal[2], tiny = QC_REF_TINY * scale, gfloor = QC_REF_GFLOOR * scale;
             {
                 double cmax = 0.0;
-                int big = 0, notlast = 0;                                // some regular pair has |a| > 0.1 g / > 1e-7 g (update size, without the division)
+                int big = 0, notlast = 0;                                // some regular pair has |a| > QC_REF_BIG g / > QC_REF_LAST g (update size, no division)
 #pragma unroll
                 for (int ii = 0; ii < 4; ++ii) {                         // one row per team of 16 lanes
                     const int i = (tid >> 4) + 16 * ii;
@@ -442,21 +441,21 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                         const double lj = lam[j];
                         const double r = -XtX[i * ld + j];
                         const double sij = 0.5 * (Sm[i * ld + j] + Sm[j * ld + i]);
-                        const double av = fabs(sij + 0.5 * (li_ + lj) * r), g = fabs(lj - li_);
-                        const bool valid = j != i && av > tiny;
-                        const bool strong = valid && av > QCS_REF_TAU * fmax(g, gfloor);
+                        const double av = fabs(QC_REF_COUPLING(sij, li_, lj, r)), g = fabs(lj - li_);
+                        const bool valid = j != i && qc_ref_coupled(av, tiny);       // the class tests as selects
+                        const bool strong = valid && qc_ref_strong(av, g, gfloor);
                         cnt += strong ? 1 : 0;
                         who = strong ? j : who;
                         const bool weak = valid && !strong;
-                        cmax = (weak && g <= gfloor) ? fmax(cmax, av) : cmax;
-                        const bool reg = weak && g > gfloor;
-                        big |= (reg && !(av <= 0.1 * g)) ? 1 : 0;
-                        notlast |= (reg && !(av <= 1e-7 * g)) ? 1 : 0;
+                        cmax = (weak && qc_ref_degenerate(g, gfloor)) ? fmax(cmax, av) : cmax;
+                        const bool reg = weak && qc_ref_regular(g, gfloor);
+                        big |= (reg && qc_ref_pair_big(av, g)) ? 1 : 0;
+                        notlast |= (reg && qc_ref_pair_notlast(av, g)) ? 1 : 0;
                     }
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o, 16); who = max(who, __shfl_xor(who, o, 16)); }
                     if ((tid & 15) == 0 && i < n) {
-                        partner[i] = cnt == 0 ? -1 : (cnt == 1 ? who : -2);
+                        partner[i] = qc_ref_partner(cnt, who);
                         if (cnt > 1) flg[4] = 1;
                         if (cnt == 1) atomicAdd(&flg[5], 1);
                     }
@@ -467,24 +466,24 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 if (notlast) flg[7] = 1;
                 __syncthreads();
                 if ((tid & 63) == 0) red[tid >> 6] = cmax;
-                if (tid < n) { const int pj = partner[tid]; if (pj >= 0 && partner[pj] != tid) flg[4] = 1; }     // a strong pair must be mutual
+                if (tid < n && qc_ref_not_mutual(partner, tid)) flg[4] = 1;
                 __syncthreads();
                 if (tid == 0) {
                     double ca = 0.0;
                     for (int k = 0; k < QCS_W; ++k) ca = fmax(ca, red[k]);
-                    const double orth = sqrt(scal[1]), scl = fmax(scale, 1e-300);
+                    const double orth = sqrt(scal[1]), scl = fmax(scale, QC_REF_SCALE_FLOOR);
                     const int multi = flg[4];
-                    if (flg[6] || !(orth <= 1e-3) || multi) flg[QC_EIG_STATE] = QC_EIG_ROTATE;                          // not perturbative: rotations needed
+                    if (QC_REF_ROTATE(flg[6], orth, multi)) flg[QC_EIG_STATE] = QC_EIG_ROTATE;
                     else {
-                        flg[QC_EIG_LAST] = (!flg[7] && orth <= 1e-7 && flg[5] == 0) ? 1 : 0;               // one more update finishes
-                        flg[QC_EIG_CLEAN] = (ca <= 1e-12 * scl) ? 1 : 0;                                    // no coupling left inside degenerate pairs
+                        flg[QC_EIG_LAST] = QC_REF_IS_LAST(flg[7], orth, flg[5]) ? 1 : 0;
+                        flg[QC_EIG_CLEAN] = QC_REF_IS_CLEAN(ca, scl) ? 1 : 0;
                     }
                 }
                 __syncthreads();
             }
             QCS_STAMP();
             if (flg[QC_EIG_STATE] != QC_EIG_RUNNING) break;
-            // M = I + E with exact rotations on the strong pairs (qc_refine_m), into B1 in place of X^T X
+            // M = I + E with exact rotations on the strong pairs, into B1 in place of X^T X
             {
                 double mv[QCS_E];
                 const double lj = lam[cc];
@@ -493,16 +492,14 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     const double li_ = lam[ic], xij = XtX[ic * ld + j];
                     const double sij = 0.5 * (Sm[ic * ld + j] + Sm[j * ld + ic]);
                     const double r = (ic == j ? 1.0 : 0.0) - xij;
-                    const double av = sij + 0.5 * (li_ + lj) * r, g = lj - li_;
+                    const double av = QC_REF_COUPLING(sij, li_, lj, r), g = lj - li_;
                     const int pi_ = partner[ic];
-                    double mm = (fabs(av) <= tiny || fabs(g) <= gfloor) ? 0.5 * r : (sij + lj * r) / g;         // regular / negligible / degenerate
-                    if (ic == j) mm = 1.0 + 0.5 * r;
+                    double mm = QC_REF_M_WEAK(sij, r, lj, av, g, tiny, gfloor);
+                    if (ic == j) mm = qc_ref_m_diag(r);
                     if (pi_ >= 0 && (pi_ == j || ic == j)) {             // this index rotates with its strong partner
-                        const double avp = ic == j ? 0.5 * (Sm[ic * ld + pi_] + Sm[pi_ * ld + ic]) - 0.5 * (li_ + lam[pi_]) * XtX[ic * ld + pi_] : av;
+                        const double avp = ic == j ? QC_REF_COUPLING(0.5 * (Sm[ic * ld + pi_] + Sm[pi_ * ld + ic]), li_, lam[pi_], -XtX[ic * ld + pi_]) : av;
                         const double gp = ic == j ? lam[pi_] - li_ : g;
-                        const double theta = gp / (2.0 * avp);
-                        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
-                        mm = ic == j ? 1.0 / sqrt(fma(t, t, 1.0)) + 0.5 * r : t / sqrt(fma(t, t, 1.0));
+                        mm = ic == j ? qc_ref_m_diag_rot(r, avp, gp) : qc_ref_m_rot(avp, gp);
                     }
                     mv[q] = mm;
                 }
@@ -519,7 +516,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 if (tid < n) {
                     const double wi = lam[tid];
                     int r = 0;
-                    for (int j = 0; j < n; ++j) r += (lam[j] < wi || (lam[j] == wi && j < tid)) ? 1 : 0;
+                    for (int j = 0; j < n; ++j) r += QC_REF_BEFORE(lam, j, wi, tid) ? 1 : 0;
                     rank_s[tid] = r;
                     a.w_out[r] = wi;
                 }

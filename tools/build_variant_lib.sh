@@ -6,7 +6,7 @@ set -e
 NAME=$1; FLAGS=$2; shift 2
 cd "$(dirname "$0")/../qchem-rs_amd/csrc"
 make -s -j8
-ALL="qc_system qc_api qc_fock qc_fock_bm qc_one_electron qc_linalg qc_eig_tridiag qc_peaks qc_scf_small gen/qc_fock_lab0 gen/qc_fock_lab1 gen/qc_fock_lab2 gen/qc_fock_lab3 gen/qc_fock_lab4 gen/qc_fock_lab5 gen/qc_fock_lab6 gen/qc_fock_low1 gen/qc_fock_mid1 gen/qc_fock_hi1"
+ALL=$(make -s --eval='print-objs: ; @echo $(OBJS)' print-objs | sed 's/\.o\b//g')       # the Makefile's list of translation units
 objs=""
 for tu in $ALL; do
   hit=0; for v in "$@"; do [ "$v" = "$tu" ] && hit=1; done
