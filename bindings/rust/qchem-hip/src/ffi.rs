@@ -78,6 +78,30 @@ pub struct QcPolarizability {
     pub ms_builds: f64,
 }
 
+/// qc_excitations (include/qchem_hip.h): in method (0 CIS, 1 TDHF), kind (0 singlets, 1 triplets), nroots (1..8), max_iterations
+/// (0: 100), tol (0: 1e-6); out excitation energies (Eh, ascending), residual norms, oscillator strengths, transition dipoles
+/// (x, y, z per state; both zero for triplets), counts, the flag of a reference TDHF refuses, and times.
+#[repr(C)]
+pub struct QcExcitations {
+    pub method: i32,
+    pub kind: i32,
+    pub nroots: i32,
+    pub max_iterations: i32,
+    pub tol: f64,
+    pub energies: [f64; 8],
+    pub residuals: [f64; 8],
+    pub oscillator: [f64; 8],
+    pub transition_dipole: [f64; 24],
+    pub nconverged: i32,
+    pub iterations: i32,
+    pub products: i32,
+    pub reference_unstable: i32,
+    pub ms_total: f64,
+    pub ms_tensor: f64,
+    pub ms_transform: f64,
+    pub ms_solve: f64,
+}
+
 pub const QC_OK: c_int = 0;
 pub const QC_NOT_CONVERGED: c_int = 1;
 pub const QC_DIIS_SINGULAR: c_int = 2;
@@ -145,6 +169,11 @@ extern "C" {
     /// Static dipole polarizability (bohr^3) by coupled-perturbed HF at the state's last orbitals; response: null or 3 x
     /// qc_scf_stability_dim(st, 0) doubles.  The state is left as it was.
     pub fn qc_scf_polarizability(st: *mut QcScfState, io: *mut QcPolarizability, response: *mut f64) -> c_int;
+    /// CIS / TDHF excited states of an RHF state from explicit A + B and A - B matrices; vectors: null, or nroots x dim (CIS) /
+    /// 2 x nroots x dim (TDHF: all R = X + Y, then all L = X - Y) doubles, dim = qc_scf_stability_dim(st, 0).  The state is left as it was.
+    pub fn qc_scf_excitations(st: *mut QcScfState, io: *mut QcExcitations, vectors: *mut f64) -> c_int;
+    /// A + B and A - B of kind 0 (singlets) or 1 (triplets), dim x dim doubles each, either pointer null.
+    pub fn qc_scf_excitation_matrices(st: *mut QcScfState, kind: c_int, apb: *mut f64, amb: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

@@ -134,6 +134,21 @@ pub fn dipole_moment(st: *mut ffi::QcScfState) -> Option<[f64; 3]> {
     }
 }
 
+/// The lowest `nroots` (1..8) excitation energies (Eh) and oscillator strengths of a state that has done at least one pass
+/// (`qc_scf_excitations`, default tolerance): `tdhf` false CIS, true TDHF; `triplets` false singlets, true triplets (oscillator strengths
+/// then zero).  None on any error, when the roots do not converge, or when TDHF refuses an unstable reference.  The state is left as it was.
+pub fn excited_states(st: *mut ffi::QcScfState, tdhf: bool, triplets: bool, nroots: usize) -> Option<(Vec<f64>, Vec<f64>)> {
+    if nroots == 0 || nroots > 8 { return None; }
+    let mut io = ffi::QcExcitations { method: tdhf as i32, kind: triplets as i32, nroots: nroots as i32, max_iterations: 0, tol: 0.0,
+                                      energies: [0.0; 8], residuals: [0.0; 8], oscillator: [0.0; 8], transition_dipole: [0.0; 24],
+                                      nconverged: 0, iterations: 0, products: 0, reference_unstable: 0, ms_total: 0.0, ms_tensor: 0.0,
+                                      ms_transform: 0.0, ms_solve: 0.0 };
+    match unsafe { ffi::qc_scf_excitations(st, &mut io, null_mut()) } {
+        ffi::QC_OK => Some((io.energies[..nroots].to_vec(), io.oscillator[..nroots].to_vec())),
+        _ => None,
+    }
+}
+
 /// Static dipole polarizability (bohr^3, row-major 3 x 3, symmetrised) of a state that has done at least one pass
 /// (`qc_scf_polarizability`, default tolerance).  None on any error or when the response equations do not converge.  The state is left
 /// as it was.

@@ -275,6 +275,50 @@ typedef struct {
 } qc_polarizability;
 int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response /* nullable: 3 x dim doubles on the host */);
 
+/* ---- excited states of an RHF state (after SCF, not in the reference): configuration interaction singles (CIS, the Tamm-Dancoff
+ * approximation) and time-dependent Hartree-Fock (TDHF, the random-phase approximation), singlets or triplets, at the state's last C and
+ * orbital energies.  With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij delta_ab (e_a - e_i), rows and columns
+ * laid out [i * v + a] as for qc_scf_stability (dim = qc_scf_stability_dim of kind 0):
+ *   singlets  A + B = Delta + 4 (ia|jb) - (ib|ja) - (ij|ab)        triplets  A + B = Delta - (ib|ja) - (ij|ab)
+ *   both      A - B = Delta + (ib|ja) - (ij|ab)                    A = 1/2 [(A + B) + (A - B)]
+ * (A + B) of kind k is the operator qc_scf_stability(kind k) applies by direct Fock builds.  Here both matrices are built explicitly: the
+ * AO tensor in HBM (as qc_scf_mp2), MFMA quarter transformations to (ia|jb) and (ij|ab), one assembly kernel that makes both matrices
+ * exactly symmetric; then every product of the iterative solver is one GEMM over all new trial vectors.  Needs about 8 (n^4 + o n^3) bytes
+ * for the tensor phase and 24 dim^2 bytes for the matrices: QC_ERR_UNSUPPORTED when the device cannot hold them.  No frozen core; nothing
+ * is cached between calls.
+ * CIS: A X = w X by a block Davidson iteration (subspace of at most 40 vectors); any reference is accepted, a negative root is a result.
+ * TDHF: (A - B)(A + B) R = w^2 R by the reduced-space algorithm of Stratmann, Scuseria and Frisch, J. Chem. Phys. 109, 8218 (1998), R = X + Y,
+ *   L = X - Y = (A + B) R / w.  It needs A + B and A - B positive definite: before it starts, the lowest root theta of each matrix is found to
+ *   its own residual rho, and if theta - rho <= 0 for either the call returns QC_NOT_CONVERGED with reference_unstable = 1, nconverged = 0
+ *   and no state (RHF -> UHF unstable references have no triplet TDHF states; their CIS triplets exist).
+ *   The check runs to tol with a budget of 100 rounds of its own, independent of max_iterations; should it end with rho >= theta > 0
+ *   all the same, the reference is reported unstable (the flag then says "not certified", which errs on the safe side).
+ * In:  method 0 CIS, 1 TDHF; kind 0 singlets, 1 triplets; nroots 1..8 and <= dim; tol: residual 2-norm every root must reach (0: 1e-6;
+ *      TDHF: both |(A+B) R - w L| and |(A-B) L - w R|, residuals[k] is the larger); max_iterations (0: 100).
+ * Out: excitation energies (Eh) ascending, residual norms; singlets: the transition dipole mu_k = sqrt 2 r . X_k (CIS) or sqrt 2 r . R_k (TDHF)
+ *      with r^q = C_occ^T M_q C_virt (length gauge, origin (0, 0, 0)) and the oscillator strength f_k = 2/3 w_k |mu_k|^2; triplets: both
+ *      exactly 0.  The sign of a vector, and with it the sign of mu_k, is arbitrary.  products: matrix-vector products (TDHF: with either
+ *      matrix, the two checks of the reference included); iterations: rounds of the solver; wall times of the call, the AO tensor, the
+ *      transformation with the assembly, and the solver (ms).
+ * vectors (nullable, host): CIS nroots x dim with |X_k| = 1; TDHF 2 x nroots x dim - all R_k first, then all L_k, with L_k . R_k = 1
+ *      (X^T X - Y^T Y = 1).
+ * QC_NOT_CONVERGED when the iterations run out (the outputs are filled with the best estimates).  QC_ERR_INVALID: a null io, a bad
+ * method, kind or nroots, a negative or NaN tol, a negative max_iterations, a state before its first qc_scf_iterate, dim = 0 - all checked
+ * before the device is touched.  QC_ERR_UNSUPPORTED: a UHF state, a sharded handle or one with a communicator, too little free memory.
+ * Bitwise reproducible from call to call and across fresh handles.  The state is left exactly as it was (no Fock build runs). */
+typedef struct {
+    int32_t method, kind, nroots, max_iterations;
+    double tol;
+    double energies[8], residuals[8];
+    double oscillator[8], transition_dipole[24];
+    int32_t nconverged, iterations, products, reference_unstable;
+    double ms_total, ms_tensor, ms_transform, ms_solve;
+} qc_excitations;
+int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors /* nullable, host */);
+/* The two matrices themselves, dim x dim doubles each on the host, either pointer nullable: for small systems and for tests.  Errors as
+ * qc_scf_excitations (kind 0 or 1). */
+int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *AmB);
+
 /* qc_scf_begin_rhf / qc_scf_begin_uhf with the caller's densities (host, n*n, in the convention of qc_scf_density: the RHF density carries
  * the factor 2) in place of the Hueckel guess: DIIS windows empty, first eigensolve cold.  Null densities are QC_ERR_INVALID (checked
  * before the device is touched). */

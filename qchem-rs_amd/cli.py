@@ -18,6 +18,11 @@ Three additions, all opt-in:
   * `--dipole` adds the dipole moment of the converged determinant (origin 0): `dipole moment (a.u.): x y z`, the same in Debye, and
     `|mu|`; `--polarizability` adds the static dipole polarizability (coupled-perturbed HF, bohr^3): three rows and the isotropic value;
     `--json` then carries "dipole" / "polarizability" objects.  Neither combines with `--follow`.
+  * `rhf --cis N` / `--tdhf N` (N = 1..8) add the lowest N CIS or TDHF excited states of the converged determinant, singlets or, with
+    `--triplets`, triplets: one line per state - index, energy in Eh and in eV, and for singlets the oscillator strength f; `--json` then
+    carries an "excitations" list, one object per flag given (CIS first).  States that do not converge, or a reference that TDHF refuses,
+    are reported on stderr and end the command with exit status 1 after everything else has been printed.  The flags do not exist on
+    `uhf` and do not combine with `--follow`.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -85,6 +90,10 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--stability", action="store_true", help="also print the lowest eigenvalue(s) of the orbital Hessian and whether the determinant is a minimum")
         s.add_argument("--dipole", action="store_true", help="also print the dipole moment of the converged determinant (a.u. and Debye)")
         s.add_argument("--polarizability", action="store_true", help="also print the static dipole polarizability (coupled-perturbed HF, bohr^3)")
+        if name == "rhf":
+            s.add_argument("--cis", type=int, default=0, metavar="N", help="also print the lowest N CIS excited states (1..8)")
+            s.add_argument("--tdhf", type=int, default=0, metavar="N", help="also print the lowest N TDHF (RPA) excited states (1..8)")
+            s.add_argument("--triplets", action="store_true", help="triplet instead of singlet excited states (requires --cis or --tdhf)")
         s.add_argument("--follow", action="store_true", help="follow instabilities downhill until the determinant is stable (at most 8 cycles)")
     return p
 
@@ -98,6 +107,14 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--frozen-core must not be negative")
     if args.follow and (args.mp2 or args.gradient or args.dipole or args.polarizability):
         p.error("--follow cannot be combined with --mp2, --gradient, --dipole or --polarizability")
+    if args.command == "rhf":
+        for flag, nstates in (("--cis", args.cis), ("--tdhf", args.tdhf)):
+            if nstates < 0 or nstates > 8:
+                p.error(flag + " takes 1 to 8 states")
+        if args.triplets and not (args.cis or args.tdhf):
+            p.error("--triplets requires --cis or --tdhf")
+        if args.follow and (args.cis or args.tdhf):
+            p.error("--follow cannot be combined with --cis or --tdhf")
     return args
 
 
@@ -147,6 +164,35 @@ def _print_polarizability(d: dict) -> None:
 def _properties(st, args):
     """(dipole, polarizability) JSON objects of the flags given, from the converged state"""
     return (_dipole_json(st.dipole()) if args.dipole else None, _polarizability_json(st.polarizability()) if args.polarizability else None)
+
+
+HARTREE_TO_EV = 27.211386245988
+EXCITATIONS_FAILED = 1            # exit status when excited states did not converge or TDHF refused the reference (the SCF's own is 101)
+
+
+def _excitations_json(r: "hf.ExcitationsOutput") -> dict:
+    return {"method": r.method, "kind": "triplets" if r.kind else "singlets", "energies": r.energies.tolist(),
+            "energies_ev": (r.energies * HARTREE_TO_EV).tolist(), "oscillator_strengths": r.oscillator.tolist(),
+            "transition_dipoles": r.transition_dipole.tolist(), "residuals": r.residuals.tolist(), "converged": r.converged,
+            "reference_unstable": r.reference_unstable, "iterations": r.iterations, "products": r.products,
+            "timings_ms": {"total": r.ms_total, "tensor": r.ms_tensor, "transform": r.ms_transform, "solve": r.ms_solve}}
+
+
+def _print_excitations(d: dict) -> None:
+    if d["reference_unstable"]:
+        print("%s %s: the reference is unstable (A + B or A - B is not positive definite), no states" % (d["method"], d["kind"]), file=sys.stderr)
+        return
+    for k, (e, ev, f) in enumerate(zip(d["energies"], d["energies_ev"], d["oscillator_strengths"])):
+        line = "%s %s state %d: %.8f Eh = %.6f eV" % (d["method"], d["kind"][:-1], k + 1, e, ev)
+        print(line if d["kind"] == "triplets" else line + ", f = %.8f" % f)
+    if not d["converged"]:
+        print("%s: the excited states did not converge" % d["method"], file=sys.stderr)
+
+
+def _excitations(st, args) -> list:
+    """the "excitations" JSON objects of the flags given (CIS first), from the converged state"""
+    kind = 1 if args.triplets else 0
+    return [_excitations_json(st.excitations(method=m, kind=kind, nroots=k)) for m, k in (("cis", args.cis), ("tdhf", args.tdhf)) if k]
 
 
 STABILITY_THRESHOLD = 1e-5        # eigenvalues above -threshold count as stable (exact zero modes come out as +-1e-9)
@@ -226,12 +272,14 @@ def run_rhf(args) -> int:
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
     mp2 = grad = stab = dip = pol = None
+    exc = []
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.stability or args.dipole or args.polarizability:
+    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
                                                              st.gradient() if args.gradient else None,
-                                                             _stability(st, False) if args.stability else None) + _properties(st, args))
-        out, (mp2, grad, stab, dip, pol) = res if res is not None else (None, (None,) * 5)
+                                                             _stability(st, False) if args.stability else None) + _properties(st, args)
+                                                            + (_excitations(st, args),))
+        out, (mp2, grad, stab, dip, pol, exc) = res if res is not None else (None, (None,) * 5 + ([],))
     elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
@@ -258,6 +306,8 @@ def run_rhf(args) -> int:
         _print_dipole(dip)
     if pol is not None:
         _print_polarizability(pol)
+    for e in exc:
+        _print_excitations(e)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -272,7 +322,11 @@ def run_rhf(args) -> int:
             doc["dipole"] = dip
         if pol is not None:
             doc["polarizability"] = pol
+        if exc:
+            doc["excitations"] = exc
         print(json.dumps(doc))
+    if any(not e["converged"] for e in exc):
+        return EXCITATIONS_FAILED
     return 0
 
 

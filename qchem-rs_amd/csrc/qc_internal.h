@@ -336,6 +336,14 @@ int qc_launch_eri_full(qc_system *S, double *d_out);
 // the intermediates live for the duration of the call.
 int qc_mp2_validate(int n, int nspin, const double *eps, const int32_t *nocc, int n_frozen);
 int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps, const int32_t *nocc, int n_frozen, qc_mp2_output *out);
+// the batched strided f64 MFMA GEMM of the quarter transformations, C[b] = A[b] B[b]: A[m,k] = A[b a_bs + m a_ms + k a_ks] (any strides),
+// B[k,j] = B[b b_bs + k ldb + j], C[m,j] = C[b c_bs + m ldc + j]; every edge is masked (M, N, K need not be multiples of the tile)
+void qc_mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A, int64_t a_ms, int64_t a_ks, int64_t a_bs,
+                 const double *B, int64_t ldb, int64_t b_bs, double *C, int64_t ldc, int64_t c_bs);
+// excited states (qc_excited.hip): CIS / TDHF of an RHF state from explicit A + B and A - B matrices built from MO integrals.  The
+// caller has checked io's inputs.  matrices: the two d x d matrices of `kind` copied to the host (either nullable).
+int qc_excitations_device(qc_system *S, int nocc, const double *dC, const double *dEps, qc_excitations *io, double *vectors);
+int qc_excitation_matrices_device(qc_system *S, int nocc, const double *dC, const double *dEps, int kind, double *ApB, double *AmB);
 // nuclear gradient (qc_grad.hip): terms3 = [core | overlap | two-electron] x 3 natoms (host) from device densities dP (RHF D, UHF [Da; Db])
 // and dW; ms[4] = phase times (transform, one-electron, two-electron, sum) or null.  w: W of an SCF state's orbitals (enqueued).
 int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *dW, double *terms3, double *ms);

@@ -134,7 +134,9 @@ __global__ __launch_bounds__(256) void qc_mp2_gemm_kernel(const Mp2Gemm g) {
         }
 }
 
-void mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A, int64_t a_ms, int64_t a_ks, int64_t a_bs,
+}  // namespace
+
+void qc_mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A, int64_t a_ms, int64_t a_ks, int64_t a_bs,
               const double *B, int64_t ldb, int64_t b_bs, double *C, int64_t ldc, int64_t c_bs) {
     if (batch <= 0 || M <= 0 || N <= 0 || K <= 0) return;
     Mp2Gemm g{M, N, K, (M + BM - 1) / BM, (N + BN - 1) / BN, A, a_ms, a_ks, a_bs, B, ldb, b_bs, C, ldc, c_bs};
@@ -143,6 +145,8 @@ void mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A, i
     if (vec) hipLaunchKernelGGL(qc_mp2_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(qc_mp2_gemm_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, g);
 }
+
+namespace {
 
 // ---- pair energies.  W[i,a,j,b] = (ia|jb) of one spin block, dims (o1, v1, o2, v2); one workgroup per pair (i,j).
 //   mode 0 (RHF):        os = sum_ab W^2 / D,  ss = sum_ab W (W - Wx) / D
@@ -260,18 +264,18 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
         if (o[s] == 0 || v[s] == 0) continue;
         const double *Cs = dC + s * nn;
         // (i nu|la si): A = C_occ^T (A[i,mu] = C[mu, nf + i]), B = I as n x n^3
-        mp2_gemm(st, 1, o[s], (int)n3, n, Cs + n_frozen, 1, n, 0, I.p, n3, 0, T1.p, n3, 0);
+        qc_mp2_gemm(st, 1, o[s], (int)n3, n, Cs + n_frozen, 1, n, 0, I.p, n3, 0, T1.p, n3, 0);
         // (i a|la si), batched over i: A = C_virt^T, B = T1[i] as n x n^2
-        mp2_gemm(st, o[s], v[s], (int)nn, n, Cs + nocc[s], 1, n, 0, T1.p, nn, n3, T2.p + t2_off[s], nn, (int64_t)v[s] * nn);
+        qc_mp2_gemm(st, o[s], v[s], (int)nn, n, Cs + nocc[s], 1, n, 0, T1.p, nn, n3, T2.p + t2_off[s], nn, (int64_t)v[s] * nn);
     }
     for (const auto &b : blks) {
         const int o1 = o[b.s1], v1 = v[b.s1], o2 = o[b.s2], v2 = v[b.s2];
         if (o1 == 0 || v1 == 0 || o2 == 0 || v2 == 0) continue;
         const double *C2 = dC + b.s2 * nn;
         // (i a|j si), batched over (i,a): A = C_occ^T of spin s2, B = T2[i,a] as n x n
-        mp2_gemm(st, o1 * v1, o2, n, n, C2 + n_frozen, 1, n, 0, T2.p + t2_off[b.s1], n, nn, T3.p, n, (int64_t)o2 * n);
+        qc_mp2_gemm(st, o1 * v1, o2, n, n, C2 + n_frozen, 1, n, 0, T2.p + t2_off[b.s1], n, nn, T3.p, n, (int64_t)o2 * n);
         // (i a|j b): A = T3 as (o1 v1 o2) x n, B = C_virt of spin s2 (n x v2, row stride n)
-        mp2_gemm(st, 1, o1 * v1 * o2, v2, n, T3.p, n, 1, 0, C2 + nocc[b.s2], n, 0, W.p + b.w_off, v2, 0);
+        qc_mp2_gemm(st, 1, o1 * v1 * o2, v2, n, T3.p, n, 1, 0, C2 + nocc[b.s2], n, 0, W.p + b.w_off, v2, 0);
     }
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipStreamSynchronize(st));

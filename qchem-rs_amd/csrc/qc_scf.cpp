@@ -846,6 +846,26 @@ int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *respo
     const int rc2 = keep.restore();
     return rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc);
 }
+// CIS / TDHF from MO integrals: like qc_scf_mp2 the calls read Cs / ws and run no Fock build, so nothing of the handle needs saving
+int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors) {
+    if (!st || !io || st->passes == 0) return QC_ERR_INVALID;
+    if (io->method < 0 || io->method > 1 || io->kind < 0 || io->kind > 1 || io->nroots < 1 || io->nroots > 8 || io->max_iterations < 0 || !(io->tol >= 0.0))
+        return QC_ERR_INVALID;
+    if (st->uhf) return QC_ERR_UNSUPPORTED;
+    qc_system *S = st->S;
+    const int dim = qc_stability_dim(S->nbasis, false, st->nocc);
+    if (dim <= 0 || io->nroots > dim) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    return qc_excitations_device(S, st->nocc[0], st->Cs.p, st->ws.p, io, vectors);
+}
+int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *AmB) {
+    if (!st || st->passes == 0 || kind < 0 || kind > 1) return QC_ERR_INVALID;
+    if (st->uhf) return QC_ERR_UNSUPPORTED;
+    qc_system *S = st->S;
+    if (qc_stability_dim(S->nbasis, false, st->nocc) <= 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    return qc_excitation_matrices_device(S, st->nocc[0], st->Cs.p, st->ws.p, kind, ApB, AmB);
+}
 int qc_scf_begin_rhf_from(qc_system *S, const double *D, qc_scf_state **out) {
     if (!S || !D || !out) return QC_ERR_INVALID;
     return scf_begin(S, false, 0, 0, out, D, nullptr);

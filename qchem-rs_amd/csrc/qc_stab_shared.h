@@ -1,8 +1,13 @@
-// qc_stab_shared.h - what the stability analysis (qc_stability.hip) and the response solver (qc_response.hip) share: the layout of a
-// vector, the Hessian-vector product sigma = (A + B) x as one direct Fock build, the fixed-order reductions and the subspace kernels.
-// Everything sits in an anonymous namespace: each of the two files compiles its own copy of the kernels from this one text.
+// qc_stab_shared.h - what the stability analysis (qc_stability.hip), the response solver (qc_response.hip) and the excited states
+// (qc_excited.hip) share: the layout of a vector, the Hessian-vector product sigma = (A + B) x as one direct Fock build, the fixed-order
+// reductions, the subspace kernels, the host eigensolver of the subspace matrix and the block Davidson loop over an abstract product.
+// Everything sits in an anonymous namespace: each of the files compiles its own copy of the kernels from this one text.
 #pragma once
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <numeric>
+#include <vector>
 
 #include "qc_internal.h"
 
@@ -190,5 +195,171 @@ struct StabSigma {
         return QC_OK;
     }
 };
+
+// eigenpairs of a small symmetric matrix on the host: cyclic Jacobi, ascending eigenvalues, vectors as the ROWS of Vr (Vr[k * m + i]).
+// The sweeps end once |off-diagonal|^2 <= rel_stop |diagonal|^2.  Rounding alone keeps that ratio near (m - 1) u^2 = 5e-31 at m = 40,
+// so the default runs all 100 sweeps on a full subspace (22 ms at m = 40) - the stability analysis keeps it, since its results are
+// pinned bit for bit; a caller that solves two such problems per round (TDHF) passes a ratio above the rounding floor.
+inline void host_sym_eig(int m, std::vector<double> A, std::vector<double> &w, std::vector<double> &Vr, double rel_stop = 1e-32) {
+    std::vector<double> V((size_t)m * m, 0.0);
+    for (int i = 0; i < m; ++i) V[(size_t)i * m + i] = 1.0;
+    for (int i = 0; i < m; ++i) for (int j = 0; j < i; ++j) A[(size_t)j * m + i] = A[(size_t)i * m + j];      // (the lower triangle counts)
+    for (int sweep = 0; sweep < 100; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) (i == j ? diag : off) += A[(size_t)i * m + j] * A[(size_t)i * m + j];
+        if (off <= rel_stop * diag || off == 0.0) break;
+        for (int p = 0; p < m - 1; ++p)
+            for (int q = p + 1; q < m; ++q) {
+                const double apq = A[(size_t)p * m + q];
+                if (apq == 0.0) continue;
+                const double tau = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2.0 * apq);
+                const double tn = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double c = 1.0 / std::sqrt(1.0 + tn * tn), sn = tn * c;
+                for (int k = 0; k < m; ++k) {
+                    const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
+                    A[(size_t)k * m + p] = c * akp - sn * akq; A[(size_t)k * m + q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < m; ++k) {
+                    const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
+                    A[(size_t)p * m + k] = c * apk - sn * aqk; A[(size_t)q * m + k] = sn * apk + c * aqk;
+                }
+                for (int k = 0; k < m; ++k) {
+                    const double vkp = V[(size_t)k * m + p], vkq = V[(size_t)k * m + q];
+                    V[(size_t)k * m + p] = c * vkp - sn * vkq; V[(size_t)k * m + q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    std::vector<int> idx(m);
+    std::iota(idx.begin(), idx.end(), 0);
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return A[(size_t)a * m + a] < A[(size_t)b * m + b]; });
+    w.resize(m); Vr.assign((size_t)m * m, 0.0);
+    for (int k = 0; k < m; ++k) {
+        w[k] = A[(size_t)idx[k] * m + idx[k]];
+        for (int i = 0; i < m; ++i) Vr[(size_t)k * m + i] = V[(size_t)i * m + idx[k]];
+    }
+}
+
+// Start vectors of a Davidson iteration for the lowest `nroots` roots of a symmetric operator with diagonal `de` (host), orthonormalised
+// into rows 0 .. *m_out - 1 of V (msub + 1 rows).  stage: msub + 1 rows of scratch; cnt, info: the counter and the 2 (msub + 1) info words
+// of the expand kernel.
+inline int qc_stab_start(hipStream_t st, int dim, int nroots, int msub, const std::vector<double> &de, double *V, double *stage, int *cnt, double *info,
+                         int *m_out) {
+    // Unit vectors on the smallest e_a - e_i (ties: lower index first); a subspace that can hold the whole space starts as
+    // the whole space.  Unit vectors carry the symmetry of one orbital pair, and a Krylov space never leaves the symmetries it starts
+    // with - so one more start vector has a fixed pseudo-random component on every orbital pair.
+    std::vector<int> order(dim);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return de[a] < de[b]; });
+    const bool whole = dim <= QC_STAB_MAXSUB;
+    const int nunit = whole ? dim : std::min(dim, 2 * nroots);
+    const int nstart = whole ? dim : nunit + 1;
+    {
+        std::vector<double> start((size_t)nstart * dim, 0.0);
+        for (int k = 0; k < nunit; ++k) start[(size_t)k * dim + order[k]] = 1.0;
+        if (!whole) {
+            uint32_t lcg = 12345u;
+            for (int e = 0; e < dim; ++e) { lcg = lcg * 1664525u + 1013904223u; start[(size_t)nunit * dim + e] = (double)(lcg >> 8) / 8388608.0 - 1.0; }
+        }
+        // (staged behind the subspace rows: Sg is not in use yet)
+        if (nstart > msub + 1) return QC_ERR_INVALID;
+        QC_HIP_CHECK(hipMemcpyAsync(stage, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int), st));
+        for (int k = 0; k < nstart; ++k)
+            hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, 0, msub, V, (const double *)nullptr, (const double *)nullptr,
+                               (const double *)nullptr, (const double *)nullptr, (const double *)(stage + (size_t)k * dim), (const double *)nullptr, 0.0, cnt, info + 2 * k);
+        QC_HIP_CHECK(hipStreamSynchronize(st));      // (the staged vectors have been read before the first sigma vector overwrites them)
+    }
+    QC_HIP_CHECK(hipMemcpy(m_out, cnt, sizeof(int), hipMemcpyDeviceToHost));
+    if (*m_out < nroots) return QC_ERR_INVALID;
+    return QC_OK;
+}
+
+struct StabDavidsonOut { double theta[QC_STAB_MAXROOTS], rnorm[QC_STAB_MAXROOTS]; int nconv = 0, iterations = 0; };
+
+// Block Davidson iteration for the lowest `nroots` eigenpairs of a symmetric operator of order `dim` (nroots <= dim, <= QC_STAB_MAXROOTS).
+// apply(V, Sg, k0, k1) writes the products of rows k0 .. k1 - 1 of V into the same rows of Sg (both device, rows of `dim` doubles) on the
+// handle's stream and returns a status; dDiag / de: the diagonal of the preconditioner on the device and on the host.  Ritz vectors
+// (nroots x dim) go to `vectors` (host) and `d_vectors` (device), both nullable.  eig_stop: the stop ratio of host_sym_eig for the
+// subspace matrix.  QC_OK, QC_NOT_CONVERGED (out is filled with the best estimates) or an error.
+template <class Apply>
+int qc_stab_davidson(qc_system *S, int dim, int nroots, double tol, int maxit, const double *dDiag, const std::vector<double> &de, Apply &&apply,
+                     StabDavidsonOut &out, double *vectors, double *d_vectors, double eig_stop = 1e-32) {
+    hipStream_t st = S->stream;
+    const int msub = std::min(dim, QC_STAB_MAXSUB);
+    DevBuf V, Sg, Wk, dM, dY, dTheta, dInfo;
+    QcDev<int> dCnt;
+    const size_t rows = (size_t)msub + 1;
+    if (V.alloc(rows * dim) != QC_OK || Sg.alloc(rows * dim) != QC_OK || Wk.alloc(2 * (size_t)QC_STAB_MAXROOTS * dim) != QC_OK ||
+        dM.alloc((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB) != QC_OK || dY.alloc((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB) != QC_OK ||
+        dTheta.alloc(QC_STAB_MAXROOTS) != QC_OK || dInfo.alloc(2 * (QC_STAB_MAXSUB + 1)) != QC_OK || dCnt.alloc(1) != QC_OK) return QC_ERR_HIP;
+
+    int m = 0;
+    int rc = qc_stab_start(st, dim, nroots, msub, de, V.p, Sg.p, dCnt.p, dInfo.p, &m);
+    if (rc != QC_OK) return rc;
+
+    std::vector<double> M((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB, 0.0), w, Y, theta(nroots, 0.0), rnorm(nroots, 0.0), info(2 * QC_STAB_MAXROOTS);
+    std::vector<double> Ysel((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB, 0.0);
+    int m_done = 0, it = 0, nconv = 0;
+    bool converged = false;
+    for (it = 1; it <= maxit; ++it) {
+        if ((rc = apply((const double *)V.p, Sg.p, m_done, m)) != QC_OK) return rc;
+        // new rows of the subspace matrix: M[k][j] = <V_j, Sg_k>, j <= k
+        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sg.p, m_done, QC_STAB_MAXSUB, dM.p);
+        QC_HIP_CHECK(hipMemcpyAsync(M.data() + (size_t)m_done * QC_STAB_MAXSUB, dM.p + (size_t)m_done * QC_STAB_MAXSUB,
+                                    (size_t)(m - m_done) * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        m_done = m;
+        std::vector<double> A((size_t)m * m);
+        for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = M[(size_t)i * QC_STAB_MAXSUB + j];
+        host_sym_eig(m, A, w, Y, eig_stop);
+        for (int r = 0; r < nroots; ++r) {
+            theta[r] = w[r];
+            for (int j = 0; j < QC_STAB_MAXSUB; ++j) Ysel[(size_t)r * QC_STAB_MAXSUB + j] = j < m ? Y[(size_t)r * m + j] : 0.0;
+        }
+        QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemcpyAsync(dTheta.p, theta.data(), nroots * sizeof(double), hipMemcpyHostToDevice, st));
+        // the subspace is full: collapse onto the Ritz vectors of the requested roots (their sigma vectors follow by linearity)
+        if (m + nroots > msub && m > nroots && m < dim) {
+            dim3 grid((dim + 255) / 256, nroots);
+            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
+            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim);
+            QC_HIP_CHECK(hipMemcpyAsync(V.p, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+            QC_HIP_CHECK(hipMemcpyAsync(Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+            m = m_done = nroots;
+            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sg.p, 0, QC_STAB_MAXSUB, dM.p);
+            QC_HIP_CHECK(hipMemcpyAsync(M.data(), dM.p, (size_t)m * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
+            std::fill(Ysel.begin(), Ysel.end(), 0.0);
+            for (int r = 0; r < nroots; ++r) Ysel[(size_t)r * QC_STAB_MAXSUB + r] = 1.0;
+            QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        // residual | preconditioner | orthogonalisation of every requested root, one launch each; the device counts the vectors it added
+        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
+        for (int r = 0; r < nroots; ++r)
+            hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, m, msub, V.p, (const double *)Sg.p,
+                               (const double *)(dY.p + (size_t)r * QC_STAB_MAXSUB), (const double *)(dTheta.p + r), dDiag,
+                               (const double *)nullptr, (const double *)nullptr, tol, dCnt.p, dInfo.p + 2 * r);
+        int added = 0;
+        QC_HIP_CHECK(hipMemcpyAsync(info.data(), dInfo.p, 2 * nroots * sizeof(double), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipMemcpyAsync(&added, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+        nconv = 0;
+        for (int r = 0; r < nroots; ++r) { rnorm[r] = std::sqrt(info[2 * r]); if (rnorm[r] <= tol) ++nconv; }
+        if (nconv == nroots) { converged = true; break; }
+        if (added == 0) break;                           // (nothing left to add: the residuals are as small as this arithmetic makes them)
+        m += added;
+    }
+    if (it > maxit) it = maxit;
+    for (int r = 0; r < QC_STAB_MAXROOTS; ++r) { out.theta[r] = r < nroots ? theta[r] : 0.0; out.rnorm[r] = r < nroots ? rnorm[r] : 0.0; }
+    out.nconv = nconv; out.iterations = it;
+    if (vectors || d_vectors) {
+        dim3 grid((dim + 255) / 256, nroots);
+        hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m_done, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
+        if (vectors) QC_HIP_CHECK(hipMemcpyAsync(vectors, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (d_vectors) QC_HIP_CHECK(hipMemcpyAsync(d_vectors, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+        QC_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    QC_HIP_CHECK(hipGetLastError());
+    return converged ? QC_OK : QC_NOT_CONVERGED;
+}
 
 }  // namespace

@@ -10,8 +10,9 @@
 // Trial vectors, sigma vectors and the correction vector live in HBM (msub + 1 rows of `dim` doubles each); the subspace matrix
 // (at most QC_STAB_MAXSUB rows) is diagonalised on the host.  Every dot product is a fixed-order reduction (a thread's elements in
 // index order, the 64 lanes of a wave by a shuffle tree, the waves in order) and the Fock build accumulates integers: a call is bitwise
-// reproducible.  The layout of a vector, the Hessian-vector product and the subspace kernels are in qc_stab_shared.h (shared with the
-// response solver, qc_response.hip); this file keeps the Davidson driver, the host eigenproblem and the rotation.
+// reproducible.  The layout of a vector, the Hessian-vector product, the subspace kernels, the host eigenproblem and the Davidson loop
+// itself are in qc_stab_shared.h (shared with the response solver, qc_response.hip, and the excited states, qc_excited.hip); this file
+// keeps the product handed to that loop and the rotation.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,50 +20,6 @@
 #include <vector>
 
 #include "qc_stab_shared.h"
-
-namespace {
-
-// eigenpairs of a small symmetric matrix on the host: cyclic Jacobi, ascending eigenvalues, vectors as the ROWS of Vr (Vr[k * m + i])
-void host_sym_eig(int m, std::vector<double> A, std::vector<double> &w, std::vector<double> &Vr) {
-    std::vector<double> V((size_t)m * m, 0.0);
-    for (int i = 0; i < m; ++i) V[(size_t)i * m + i] = 1.0;
-    for (int i = 0; i < m; ++i) for (int j = 0; j < i; ++j) A[(size_t)j * m + i] = A[(size_t)i * m + j];      // (the lower triangle counts)
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) (i == j ? diag : off) += A[(size_t)i * m + j] * A[(size_t)i * m + j];
-        if (off <= 1e-32 * diag || off == 0.0) break;
-        for (int p = 0; p < m - 1; ++p)
-            for (int q = p + 1; q < m; ++q) {
-                const double apq = A[(size_t)p * m + q];
-                if (apq == 0.0) continue;
-                const double tau = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2.0 * apq);
-                const double tn = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
-                const double c = 1.0 / std::sqrt(1.0 + tn * tn), sn = tn * c;
-                for (int k = 0; k < m; ++k) {
-                    const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
-                    A[(size_t)k * m + p] = c * akp - sn * akq; A[(size_t)k * m + q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < m; ++k) {
-                    const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
-                    A[(size_t)p * m + k] = c * apk - sn * aqk; A[(size_t)q * m + k] = sn * apk + c * aqk;
-                }
-                for (int k = 0; k < m; ++k) {
-                    const double vkp = V[(size_t)k * m + p], vkq = V[(size_t)k * m + q];
-                    V[(size_t)k * m + p] = c * vkp - sn * vkq; V[(size_t)k * m + q] = sn * vkp + c * vkq;
-                }
-            }
-    }
-    std::vector<int> idx(m);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return A[(size_t)a * m + a] < A[(size_t)b * m + b]; });
-    w.resize(m); Vr.assign((size_t)m * m, 0.0);
-    for (int k = 0; k < m; ++k) {
-        w[k] = A[(size_t)idx[k] * m + idx[k]];
-        for (int i = 0; i < m; ++i) Vr[(size_t)k * m + i] = V[(size_t)i * m + idx[k]];
-    }
-}
-
-}  // namespace
 
 int qc_stability_dim(int n, bool uhf, const int *nocc) { return StabLayout(n, uhf, nocc).dim; }
 
@@ -76,7 +33,6 @@ int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *d
     const double tol = io->tol > 0.0 ? io->tol : 1e-6;
     const int maxit = io->max_iterations > 0 ? io->max_iterations : 100;
     hipStream_t st = S->stream;
-    const int msub = std::min(dim, QC_STAB_MAXSUB);
 
     // diagonal e_a - e_i, on the device and on the host (start vectors)
     DevBuf dDe;
@@ -90,107 +46,21 @@ int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *d
     QC_HIP_CHECK(hipStreamSynchronize(st));
 
     StabSigma sigma(S, L, uhf, io->kind, dC, dDe.p);
-    DevBuf V, Sg, Wk, dM, dY, dTheta, dInfo;
-    QcDev<int> dCnt;
-    const size_t rows = (size_t)msub + 1;
-    if (sigma.alloc() != QC_OK || V.alloc(rows * dim) != QC_OK || Sg.alloc(rows * dim) != QC_OK || Wk.alloc(2 * (size_t)QC_STAB_MAXROOTS * dim) != QC_OK ||
-        dM.alloc((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB) != QC_OK || dY.alloc((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB) != QC_OK ||
-        dTheta.alloc(QC_STAB_MAXROOTS) != QC_OK || dInfo.alloc(2 * (QC_STAB_MAXSUB + 1)) != QC_OK || dCnt.alloc(1) != QC_OK) return QC_ERR_HIP;
-
-    // Start vectors: unit vectors on the smallest e_a - e_i (ties: lower index first); a subspace that can hold the whole space starts as
-    // the whole space.  Unit vectors carry the symmetry of one orbital pair, and a Krylov space never leaves the symmetries it starts
-    // with - so one more start vector has a fixed pseudo-random component on every orbital pair.
-    std::vector<int> order(dim);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return de[a] < de[b]; });
-    const bool whole = dim <= QC_STAB_MAXSUB;
-    const int nunit = whole ? dim : std::min(dim, 2 * nroots);
-    const int nstart = whole ? dim : nunit + 1;
-    {
-        std::vector<double> start((size_t)nstart * dim, 0.0);
-        for (int k = 0; k < nunit; ++k) start[(size_t)k * dim + order[k]] = 1.0;
-        if (!whole) {
-            uint32_t lcg = 12345u;
-            for (int e = 0; e < dim; ++e) { lcg = lcg * 1664525u + 1013904223u; start[(size_t)nunit * dim + e] = (double)(lcg >> 8) / 8388608.0 - 1.0; }
+    if (sigma.alloc() != QC_OK) return QC_ERR_HIP;
+    StabDavidsonOut out;
+    const int rc = qc_stab_davidson(S, dim, nroots, tol, maxit, dDe.p, de, [&](const double *V, double *Sg, int k0, int k1) {
+        for (int k = k0; k < k1; ++k) {
+            const int r = sigma.apply(V + (size_t)k * dim, Sg + (size_t)k * dim);
+            if (r != QC_OK) return r;
         }
-        // (staged behind the subspace rows: Sg is not in use yet)
-        if (nstart > (int)rows) return QC_ERR_INVALID;
-        QC_HIP_CHECK(hipMemcpyAsync(Sg.p, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
-        for (int k = 0; k < nstart; ++k)
-            hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, 0, msub, V.p, (const double *)nullptr, (const double *)nullptr,
-                               (const double *)nullptr, (const double *)nullptr, (const double *)(Sg.p + (size_t)k * dim), (const double *)nullptr, 0.0, dCnt.p, dInfo.p + 2 * k);
-        QC_HIP_CHECK(hipStreamSynchronize(st));      // (the staged vectors have been read before the first sigma vector overwrites them)
-    }
-    int m = 0;
-    QC_HIP_CHECK(hipMemcpy(&m, dCnt.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (m < nroots) return QC_ERR_INVALID;
-
-    std::vector<double> M((size_t)QC_STAB_MAXSUB * QC_STAB_MAXSUB, 0.0), w, Y, theta(nroots, 0.0), rnorm(nroots, 0.0), info(2 * QC_STAB_MAXROOTS);
-    std::vector<double> Ysel((size_t)QC_STAB_MAXROOTS * QC_STAB_MAXSUB, 0.0);
-    int m_done = 0, it = 0, nconv = 0, rc = QC_OK;
-    bool converged = false;
-    for (it = 1; it <= maxit; ++it) {
-        for (int k = m_done; k < m; ++k)
-            if ((rc = sigma.apply(V.p + (size_t)k * dim, Sg.p + (size_t)k * dim)) != QC_OK) return rc;
-        // new rows of the subspace matrix: M[k][j] = <V_j, Sg_k>, j <= k
-        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sg.p, m_done, QC_STAB_MAXSUB, dM.p);
-        QC_HIP_CHECK(hipMemcpyAsync(M.data() + (size_t)m_done * QC_STAB_MAXSUB, dM.p + (size_t)m_done * QC_STAB_MAXSUB,
-                                    (size_t)(m - m_done) * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
-        m_done = m;
-        std::vector<double> A((size_t)m * m);
-        for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = M[(size_t)i * QC_STAB_MAXSUB + j];
-        host_sym_eig(m, A, w, Y);
-        for (int r = 0; r < nroots; ++r) {
-            theta[r] = w[r];
-            for (int j = 0; j < QC_STAB_MAXSUB; ++j) Ysel[(size_t)r * QC_STAB_MAXSUB + j] = j < m ? Y[(size_t)r * m + j] : 0.0;
-        }
-        QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        QC_HIP_CHECK(hipMemcpyAsync(dTheta.p, theta.data(), nroots * sizeof(double), hipMemcpyHostToDevice, st));
-        // the subspace is full: collapse onto the Ritz vectors of the requested roots (their sigma vectors follow by linearity)
-        if (m + nroots > msub && m > nroots && m < dim) {
-            dim3 grid((dim + 255) / 256, nroots);
-            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
-            hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, QC_STAB_MAXSUB, dY.p, Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim);
-            QC_HIP_CHECK(hipMemcpyAsync(V.p, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-            QC_HIP_CHECK(hipMemcpyAsync(Sg.p, Wk.p + (size_t)QC_STAB_MAXROOTS * dim, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-            m = m_done = nroots;
-            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sg.p, 0, QC_STAB_MAXSUB, dM.p);
-            QC_HIP_CHECK(hipMemcpyAsync(M.data(), dM.p, (size_t)m * QC_STAB_MAXSUB * sizeof(double), hipMemcpyDeviceToHost, st));
-            std::fill(Ysel.begin(), Ysel.end(), 0.0);
-            for (int r = 0; r < nroots; ++r) Ysel[(size_t)r * QC_STAB_MAXSUB + r] = 1.0;
-            QC_HIP_CHECK(hipMemcpyAsync(dY.p, Ysel.data(), Ysel.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        // residual | preconditioner | orthogonalisation of every requested root, one launch each; the device counts the vectors it added
-        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
-        for (int r = 0; r < nroots; ++r)
-            hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, m, msub, V.p, (const double *)Sg.p,
-                               (const double *)(dY.p + (size_t)r * QC_STAB_MAXSUB), (const double *)(dTheta.p + r), (const double *)dDe.p,
-                               (const double *)nullptr, (const double *)nullptr, tol, dCnt.p, dInfo.p + 2 * r);
-        int added = 0;
-        QC_HIP_CHECK(hipMemcpyAsync(info.data(), dInfo.p, 2 * nroots * sizeof(double), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipMemcpyAsync(&added, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
-        nconv = 0;
-        for (int r = 0; r < nroots; ++r) { rnorm[r] = std::sqrt(info[2 * r]); if (rnorm[r] <= tol) ++nconv; }
-        if (nconv == nroots) { converged = true; break; }
-        if (added == 0) break;                           // (nothing left to add: the residuals are as small as this arithmetic makes them)
-        m += added;
-    }
-    if (it > maxit) it = maxit;
-    for (int r = 0; r < QC_STAB_MAXROOTS; ++r) { io->eigenvalues[r] = r < nroots ? theta[r] : 0.0; io->residuals[r] = r < nroots ? rnorm[r] : 0.0; }
-    io->nconverged = nconv; io->iterations = it; io->builds = sigma.builds;
-    if (vectors) {
-        dim3 grid((dim + 255) / 256, nroots);
-        hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m_done, QC_STAB_MAXSUB, dY.p, V.p, Wk.p);
-        QC_HIP_CHECK(hipMemcpyAsync(vectors, Wk.p, (size_t)nroots * dim * sizeof(double), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    QC_HIP_CHECK(hipGetLastError());
+        return (int)QC_OK;
+    }, out, vectors, nullptr);
+    if (rc < 0) return rc;
+    for (int r = 0; r < QC_STAB_MAXROOTS; ++r) { io->eigenvalues[r] = r < nroots ? out.theta[r] : 0.0; io->residuals[r] = r < nroots ? out.rnorm[r] : 0.0; }
+    io->nconverged = out.nconv; io->iterations = out.iterations; io->builds = sigma.builds;
     io->ms_builds = sigma.ms_builds;
     io->ms_total = qc_now_ms() - t_begin;
-    return converged ? QC_OK : QC_NOT_CONVERGED;
+    return rc;
 }
 
 // ---- rotation along a vector.  In the MO basis (occupied first) kappa = [[0, -x], [x^T, 0]] with x the o x v block, so kappa_ai = x_ia.

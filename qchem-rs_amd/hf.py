@@ -46,7 +46,11 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_scf_set_stop_rule", "qc_scf_counters", "qc_debug_ket_entry", "qc_dispatch_lanes", "qc_freeze_assignment",
            "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
            "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from",
-           "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability"]
+           "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability",
+           "qc_scf_excitations", "qc_scf_excitation_matrices"]
+
+
+EXCITATION_METHODS = {"cis": 0, "tdhf": 1}
 
 
 class QcError(RuntimeError):
@@ -128,6 +132,38 @@ class PolarizabilityOutput:
     ms_builds: float
     asymmetry: float = 0.0
     response: Optional[np.ndarray] = None
+
+
+class _Excitations(C.Structure):
+    _fields_ = [("method", C.c_int32), ("kind", C.c_int32), ("nroots", C.c_int32), ("max_iterations", C.c_int32), ("tol", C.c_double),
+                ("energies", C.c_double * 8), ("residuals", C.c_double * 8), ("oscillator", C.c_double * 8), ("transition_dipole", C.c_double * 24),
+                ("nconverged", C.c_int32), ("iterations", C.c_int32), ("products", C.c_int32), ("reference_unstable", C.c_int32),
+                ("ms_total", C.c_double), ("ms_tensor", C.c_double), ("ms_transform", C.c_double), ("ms_solve", C.c_double)]
+
+
+@dataclass
+class ExcitationsOutput:
+    """qc_excitations: excitation energies (Eh, ascending) of the CIS or TDHF states of an RHF determinant with their residual norms,
+    oscillator strengths and transition dipoles (nroots, 3) - both exactly zero for triplets; the sign of a vector and of its transition
+    dipole is arbitrary.  converged: every root reached the tolerance.  reference_unstable: TDHF was refused because A + B or A - B is not
+    positive definite (then converged is False and no state is returned).  vectors, when asked for: CIS (nroots, dim) with |X| = 1;
+    TDHF (2, nroots, dim) - R = X + Y, then L = X - Y, with L_k . R_k = 1."""
+    method: str
+    kind: int
+    energies: np.ndarray
+    residuals: np.ndarray
+    oscillator: np.ndarray
+    transition_dipole: np.ndarray
+    converged: bool
+    reference_unstable: bool
+    nconverged: int
+    iterations: int
+    products: int
+    ms_total: float
+    ms_tensor: float
+    ms_transform: float
+    ms_solve: float
+    vectors: Optional[np.ndarray] = None
 
 
 class WorkStats(C.Structure):
@@ -217,6 +253,8 @@ def lib():
         L.qc_dipole_matrices_gpu.argtypes = [vp, vp, vp]
         L.qc_scf_dipole.argtypes = [vp, vp, vp, vp]
         L.qc_scf_polarizability.argtypes = [vp, C.POINTER(_Polarizability), vp]
+        L.qc_scf_excitations.argtypes = [vp, C.POINTER(_Excitations), vp]
+        L.qc_scf_excitation_matrices.argtypes = [vp, C.c_int, vp, vp]
         _lib = L
     return _lib
 
@@ -521,6 +559,32 @@ class ScfStepper:
         alpha = np.array(io.alpha).reshape(3, 3)
         return PolarizabilityOutput(alpha, float(np.trace(alpha)) / 3.0, np.array(io.residuals), rc == QC_OK, int(io.iterations), int(io.builds),
                                     io.ms_total, io.ms_builds, io.asymmetry, U)
+
+    def excitations(self, method: str = "cis", kind: int = 0, nroots: int = 1, tol: float = 0.0, max_iterations: int = 0,
+                    vectors: bool = False) -> "ExcitationsOutput":
+        """CIS or TDHF excited states of an RHF state at its last orbitals (qc_scf_excitations); the state is left as it was.
+        method "cis" | "tdhf"; kind 0 singlets, 1 triplets; nroots 1..8; tol 0: 1e-6; max_iterations 0: 100."""
+        if method not in EXCITATION_METHODS:
+            raise QcError("excitations: method must be 'cis' or 'tdhf'")
+        code, nroots = EXCITATION_METHODS[method], int(nroots)
+        io = _Excitations(method=code, kind=int(kind), nroots=nroots, max_iterations=int(max_iterations), tol=float(tol))
+        X = None
+        if vectors:
+            dim = self.stability_dim(0)
+            X = np.zeros((2, nroots, dim) if code == 1 else (nroots, dim))
+        rc = _check(lib().qc_scf_excitations(self._st, C.byref(io), None if X is None else X.ctypes.data_as(C.c_void_p)), "qc_scf_excitations")
+        return ExcitationsOutput(method, int(kind), np.array(io.energies[:nroots]), np.array(io.residuals[:nroots]), np.array(io.oscillator[:nroots]),
+                                 np.array(io.transition_dipole[:3 * nroots]).reshape(nroots, 3), rc == QC_OK, bool(io.reference_unstable),
+                                 int(io.nconverged), int(io.iterations), int(io.products), io.ms_total, io.ms_tensor, io.ms_transform, io.ms_solve, X)
+
+    def excitation_matrices(self, kind: int = 0):
+        """(A + B, A - B) of an RHF state, (dim, dim) each, rows and columns [i * v + a] (qc_scf_excitation_matrices): kind 0 singlets,
+        1 triplets.  Both exactly symmetric."""
+        dim = self.stability_dim(0)
+        P, M = np.zeros((dim, dim)), np.zeros((dim, dim))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(lib().qc_scf_excitation_matrices(self._st, int(kind), p(P), p(M)), "qc_scf_excitation_matrices")
+        return P, M
 
     def rotated_density(self, x, angle: float = 0.0, kind: int = 0):
         """(D_alpha, D_beta, electronic energy) of the determinant rotated along x by `angle` radians (qc_scf_rotated_density);
