@@ -9,24 +9,15 @@
 // of order d = o v, a workgroup per occupied pair i >= j and 32 x 32 tile of (a, b): it writes an element of block (i, j) and its
 // mirror image in block (j, i) from the same value, so both matrices are exactly symmetric although the GEMM chain rounds
 // W[i,a,j,b] and W[j,b,i,a] differently.  After that every product of the iterative solvers is one qc_gemm over all new trial vectors:
-//   CIS   block Davidson on A (the loop of the stability analysis, qc_stab_shared.h)
+//   CIS   block Davidson on A (the loop of the stability analysis, qc_stab_davidson in qc_subspace.h)
 //   TDHF  the reduced-space algorithm of Stratmann, Scuseria and Frisch, J. Chem. Phys. 109, 8218 (1998), with P = A + B, M = A - B:
-//         one orthonormal basis b, M+ = b^T P b, M- = b^T M b, H = (M-)^1/2 M+ (M-)^1/2, H T = w^2 T,
+//         one orthonormal basis b with two sigma blocks (QcSubspace), M+ = b^T P b, M- = b^T M b, H = (M-)^1/2 M+ (M-)^1/2, H T = w^2 T,
 //         R~ = (M-)^1/2 T w^-1/2, L~ = M+ R~ / w, R = b R~ = X + Y, L = b L~ = X - Y, L . R = 1,
 //         residuals W_R = P R - w L and W_L = M L - w R.
 // Every sum outside the GEMMs is a fixed-order reduction and no kernel uses atomics: a call is bitwise reproducible.
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "qc_stab_shared.h"
+#include "qc_subspace.h"
 
 namespace {
-
-// stop ratio of the host Jacobi eigensolves of the subspace problems: off-diagonal norm <= 3e-14 of the diagonal's - above the rounding
-// floor of a 40 x 40 problem (where the default never stops before its 100th sweep), far below what the residuals resolve
-constexpr double kJacobiStop = 1e-27;
 
 constexpr int XT = 32;            // tile of the assembly kernel: XT x XT elements of (a, b), 256 threads, four rows each
 constexpr int XT_LD = XT + 1;     // LDS row of 33 doubles: a column read by the 32 lanes of a half-wave strides 66 dwords, and
@@ -156,27 +147,23 @@ int exc_build_matrices(qc_system *S, int nocc, const double *dC, const double *d
     QC_HIP_CHECK(hipStreamSynchronize(st));
     const double t1 = qc_now_ms();
     // 2. quarter transformations.  (i nu|la si) is shared; the tensor and every intermediate are freed as soon as nothing reads them.
-    const double *Co = dC, *Cv = dC + o;                                   // A[i,mu] = C[mu, i]: row stride 1, k stride n
     if (T1.alloc(o * n3) != QC_OK) return QC_ERR_HIP;
-    qc_mp2_gemm(st, 1, o, (int)n3, n, Co, 1, n, 0, I.p, n3, 0, T1.p, n3, 0);
+    qc_quarter_first(st, n, dC, 0, o, I.p, T1.p);
     QC_HIP_CHECK(hipStreamSynchronize(st));
     I.reset();
     if (T2.alloc(d * nn) != QC_OK || U.alloc((int64_t)o * o * nn) != QC_OK) return QC_ERR_HIP;
-    // (i a|la si) and (i j|la si), batched over i: A = C_virt^T / C_occ^T, B = T1[i] as n x n^2
-    qc_mp2_gemm(st, o, v, (int)nn, n, Cv, 1, n, 0, T1.p, nn, n3, T2.p, nn, (int64_t)v * nn);
-    qc_mp2_gemm(st, o, o, (int)nn, n, Co, 1, n, 0, T1.p, nn, n3, U.p, nn, (int64_t)o * nn);
+    qc_quarter_second(st, n, o, dC, o, v, T1.p, T2.p);                    // (i a|la si)
+    qc_quarter_second(st, n, o, dC, 0, o, T1.p, U.p);                     // (i j|la si)
     QC_HIP_CHECK(hipStreamSynchronize(st));
     T1.reset();
     if (T3.alloc(d * o * n) != QC_OK || Y.alloc((int64_t)o * o * v * n) != QC_OK) return QC_ERR_HIP;
-    // (i a|j si), batched over (i,a): A = C_occ^T, B = T2[i,a] as n x n;  (i j|a si), batched over (i,j): A = C_virt^T, B = U[i,j] as n x n
-    qc_mp2_gemm(st, (int)d, o, n, n, Co, 1, n, 0, T2.p, n, nn, T3.p, n, (int64_t)o * n);
-    qc_mp2_gemm(st, o * o, v, n, n, Cv, 1, n, 0, U.p, n, nn, Y.p, n, (int64_t)v * n);
+    qc_quarter_third(st, n, (int)d, dC, 0, o, T2.p, T3.p);                // (i a|j si)
+    qc_quarter_third(st, n, o * o, dC, o, v, U.p, Y.p);                   // (i j|a si)
     QC_HIP_CHECK(hipStreamSynchronize(st));
     T2.reset(); U.reset();
     if (W.alloc(d * d) != QC_OK || Vv.alloc((int64_t)o * o * v * v) != QC_OK) return QC_ERR_HIP;
-    // (i a|j b) and (i j|a b): A = T3 as (o v o) x n / Y as (o o v) x n, B = C_virt (n x v, row stride n)
-    qc_mp2_gemm(st, 1, (int)(d * o), v, n, T3.p, n, 1, 0, Cv, n, 0, W.p, v, 0);
-    qc_mp2_gemm(st, 1, o * o * v, v, n, Y.p, n, 1, 0, Cv, n, 0, Vv.p, v, 0);
+    qc_quarter_last(st, n, (int)(d * o), dC, o, v, T3.p, W.p);            // (i a|j b)
+    qc_quarter_last(st, n, o * o * v, dC, o, v, Y.p, Vv.p);               // (i j|a b)
     QC_HIP_CHECK(hipStreamSynchronize(st));
     T3.reset(); Y.reset();
     // 3. assembly
@@ -220,11 +207,8 @@ int exc_transition_dipoles(qc_system *S, int o, int v, const double *dC, const d
     const double origin[3] = {0.0, 0.0, 0.0};
     int rc = qc_dipole_device(S, origin, dM3.p);
     if (rc != QC_OK) return rc;
-    for (int q = 0; q < 3; ++q) {
-        qc_gemm(st, n, v, n, 1.0, dM3.p + q * nn, n, false, dC + o, n, false, 0.0, Pb.p, v);                  // M C_virt
-        qc_gemm(st, o, v, n, 1.0, dC, n, true, Pb.p, v, false, 0.0, Rh.p + (size_t)q * d, v);                  // C_occ^T (.)
-    }
-    hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(3, nroots), dim3(256), 0, st, d, Rh.p, dX, 0, 3, dOut.p);     // out[k * 3 + q] = <r^q, x_k>
+    for (int q = 0; q < 3; ++q) qc_ao_to_ov(st, n, o, v, dC, dM3.p + q * nn, Pb.p, Rh.p + (size_t)q * d);
+    qc_stab_dots(st, d, Rh.p, 3, dX, 0, nroots, 3, dOut.p);                                                    // out[k * 3 + q] = <r^q, x_k>
     double h[3 * QC_STAB_MAXROOTS];
     QC_HIP_CHECK(hipMemcpyAsync(h, dOut.p, (size_t)3 * nroots * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipStreamSynchronize(st));
@@ -232,32 +216,7 @@ int exc_transition_dipoles(qc_system *S, int o, int v, const double *dC, const d
     return QC_OK;
 }
 
-// ---- TDHF: the reduced generalised problem on the host.  Mp, Mm: m x m (row-major, symmetric).  Out: omega (ascending), Rt, Lt (rows of m,
-// nroots each).  false: M- or H is not positive definite in this subspace.
-bool tdhf_reduced(int m, const std::vector<double> &Mp, const std::vector<double> &Mm, int nroots, double *omega, std::vector<double> &Rt,
-                  std::vector<double> &Lt) {
-    std::vector<double> s, U, w2, T;
-    host_sym_eig(m, Mm, s, U, kJacobiStop);                        // rows of U: eigenvectors of M-
-    if (!(s[0] > 0.0)) return false;
-    std::vector<double> Sh((size_t)m * m, 0.0), X((size_t)m * m, 0.0), H((size_t)m * m, 0.0);
-    for (int k = 0; k < m; ++k) {
-        const double r = std::sqrt(s[k]);
-        for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) Sh[(size_t)i * m + j] += r * U[(size_t)k * m + i] * U[(size_t)k * m + j];
-    }
-    for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) { double t = 0.0; for (int k = 0; k < m; ++k) t += Mp[(size_t)i * m + k] * Sh[(size_t)k * m + j]; X[(size_t)i * m + j] = t; }
-    for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) { double t = 0.0; for (int k = 0; k < m; ++k) t += Sh[(size_t)i * m + k] * X[(size_t)k * m + j]; H[(size_t)i * m + j] = H[(size_t)j * m + i] = t; }
-    host_sym_eig(m, H, w2, T, kJacobiStop);
-    if (!(w2[0] > 0.0)) return false;
-    Rt.assign((size_t)nroots * m, 0.0); Lt.assign((size_t)nroots * m, 0.0);
-    for (int r = 0; r < nroots; ++r) {
-        const double w = std::sqrt(w2[r]), is = 1.0 / std::sqrt(w);
-        omega[r] = w;
-        for (int i = 0; i < m; ++i) { double t = 0.0; for (int k = 0; k < m; ++k) t += Sh[(size_t)i * m + k] * T[(size_t)r * m + k]; Rt[(size_t)r * m + i] = t * is; }
-        for (int i = 0; i < m; ++i) { double t = 0.0; for (int k = 0; k < m; ++k) t += Mp[(size_t)i * m + k] * Rt[(size_t)r * m + k]; Lt[(size_t)r * m + i] = t / w; }
-    }
-    return true;
-}
-
+// ---- TDHF (the reduced generalised problem on the host: tdhf_reduced, qc_subspace_host.h)
 struct TdhfOut { double omega[QC_STAB_MAXROOTS], rnorm[QC_STAB_MAXROOTS]; int nconv = 0, iterations = 0, products = 0; };
 
 // Lowest nroots positive roots of M P R = w^2 R.  dR, dL (device, nroots x dim each): R = X + Y and L = X - Y of the last estimate.
@@ -265,54 +224,40 @@ int tdhf_solve(qc_system *S, int dim, int nroots, double tol, int maxit, const d
                const std::vector<double> &diag, TdhfOut &out, double *dR, double *dL) {
     constexpr int LD = QC_STAB_MAXSUB, NR = QC_STAB_MAXROOTS;
     hipStream_t st = S->stream;
-    const int msub = std::min(dim, LD);
-    const size_t rows = (size_t)msub + 1;
-    DevBuf V, Sp, Sm, Wk, T, dMp, dMm, dRt, dLt, dW, dInfo, dNorm;
-    QcDev<int> dCnt;
-    if (V.alloc(rows * dim) != QC_OK || Sp.alloc(rows * dim) != QC_OK || Sm.alloc(rows * dim) != QC_OK || Wk.alloc(3 * (size_t)LD * dim) != QC_OK ||
-        T.alloc((size_t)2 * NR * dim) != QC_OK || dMp.alloc((size_t)LD * LD) != QC_OK || dMm.alloc((size_t)LD * LD) != QC_OK ||
-        dRt.alloc((size_t)LD * LD) != QC_OK || dLt.alloc((size_t)NR * LD) != QC_OK || dW.alloc(NR) != QC_OK || dInfo.alloc(2 * (LD + 1)) != QC_OK ||
-        dNorm.alloc(2 * NR) != QC_OK || dCnt.alloc(1) != QC_OK) return QC_ERR_HIP;
-    int m = 0;
-    int rc = qc_stab_start(st, dim, nroots, msub, diag, V.p, Sp.p, dCnt.p, dInfo.p, &m);
+    // sigma block 0: P b, block 1: M b; the coefficient rows of the subspace hold R~ (and the Z of a restart), dLt holds L~
+    QcSubspace sub;
+    DevBuf T, dLt, dW, dNorm;
+    if (sub.alloc(st, dim, 2, LD) != QC_OK || T.alloc((size_t)2 * NR * dim) != QC_OK || dLt.alloc((size_t)NR * LD) != QC_OK || dW.alloc(NR) != QC_OK ||
+        dNorm.alloc(2 * NR) != QC_OK) return QC_ERR_HIP;
+    int rc = qc_stab_start(sub, nroots, diag);
     if (rc != QC_OK) return rc;
 
-    std::vector<double> Mp((size_t)LD * LD, 0.0), Mm((size_t)LD * LD, 0.0), Rt, Lt, Rsel((size_t)NR * LD, 0.0), Lsel((size_t)NR * LD, 0.0), Z((size_t)LD * LD, 0.0);
+    std::vector<double> Rt, Lt, Rsel((size_t)NR * LD, 0.0), Lsel((size_t)NR * LD, 0.0), Z((size_t)LD * LD, 0.0);
     std::vector<double> Rprev((size_t)NR * LD, 0.0), Lprev((size_t)NR * LD, 0.0);      // the estimates of the round before, in the coordinates of b
-    bool have_prev = false;
     double omega[NR] = {0}, rnorm[NR] = {0}, norm2[2 * NR];
-    int m_done = 0, it = 0, nconv = 0;
-    bool converged = false;
+    int it = 0, nconv = 0; bool converged = false, have_prev = false;
     for (int r = 0; r < NR; ++r) out.omega[r] = out.rnorm[r] = 0.0;
     for (it = 1; it <= maxit; ++it) {
         // sigma+ = P b and sigma- = M b of the new rows, one GEMM each
-        if (m > m_done) {
-            qc_gemm(st, m - m_done, dim, dim, 1.0, V.p + (size_t)m_done * dim, dim, false, P, dim, false, 0.0, Sp.p + (size_t)m_done * dim, dim);
-            qc_gemm(st, m - m_done, dim, dim, 1.0, V.p + (size_t)m_done * dim, dim, false, Mx, dim, false, 0.0, Sm.p + (size_t)m_done * dim, dim);
-            out.products += 2 * (m - m_done);
-            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sp.p, m_done, LD, dMp.p);
-            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sm.p, m_done, LD, dMm.p);
-            QC_HIP_CHECK(hipMemcpyAsync(Mp.data() + (size_t)m_done * LD, dMp.p + (size_t)m_done * LD, (size_t)(m - m_done) * LD * sizeof(double), hipMemcpyDeviceToHost, st));
-            QC_HIP_CHECK(hipMemcpyAsync(Mm.data() + (size_t)m_done * LD, dMm.p + (size_t)m_done * LD, (size_t)(m - m_done) * LD * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (sub.m > sub.m_done) {
+            const int k0 = sub.m_done, nk = sub.m - sub.m_done;
+            qc_gemm(st, nk, dim, dim, 1.0, sub.V.p + (size_t)k0 * dim, dim, false, P, dim, false, 0.0, sub.Sg[0].p + (size_t)k0 * dim, dim);
+            qc_gemm(st, nk, dim, dim, 1.0, sub.V.p + (size_t)k0 * dim, dim, false, Mx, dim, false, 0.0, sub.Sg[1].p + (size_t)k0 * dim, dim);
+            out.products += 2 * nk;
         }
-        QC_HIP_CHECK(hipStreamSynchronize(st));
-        m_done = m;
-        std::vector<double> Ap((size_t)m * m), Am((size_t)m * m);
-        for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) {
-            Ap[(size_t)i * m + j] = Ap[(size_t)j * m + i] = Mp[(size_t)i * LD + j];
-            Am[(size_t)i * m + j] = Am[(size_t)j * m + i] = Mm[(size_t)i * LD + j];
-        }
-        if (!tdhf_reduced(m, Ap, Am, nroots, omega, Rt, Lt)) break;      // (cannot happen at a reference certified stable; the last estimates stand)
+        if ((rc = sub.project()) != QC_OK) return rc;
+        const int m = sub.m;
+        if (!tdhf_reduced(m, sub.reduced(0), sub.reduced(1), nroots, omega, Rt, Lt)) break;      // (cannot happen at a reference certified stable; the last estimates stand)
         std::fill(Rsel.begin(), Rsel.end(), 0.0); std::fill(Lsel.begin(), Lsel.end(), 0.0);
         for (int r = 0; r < nroots; ++r) for (int j = 0; j < m; ++j) { Rsel[(size_t)r * LD + j] = Rt[(size_t)r * m + j]; Lsel[(size_t)r * LD + j] = Lt[(size_t)r * m + j]; }
-        QC_HIP_CHECK(hipMemcpyAsync(dRt.p, Rsel.data(), Rsel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemcpyAsync(sub.coef.p, Rsel.data(), Rsel.size() * sizeof(double), hipMemcpyHostToDevice, st));
         QC_HIP_CHECK(hipMemcpyAsync(dLt.p, Lsel.data(), Lsel.size() * sizeof(double), hipMemcpyHostToDevice, st));
         QC_HIP_CHECK(hipMemcpyAsync(dW.p, omega, nroots * sizeof(double), hipMemcpyHostToDevice, st));
         // R = b R~ and L = b L~ of this estimate, both residuals and their preconditioned images
-        dim3 grid((dim + 255) / 256, nroots);
-        hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, LD, dRt.p, V.p, dR);
-        hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, LD, dLt.p, V.p, dL);
-        hipLaunchKernelGGL(qc_tdhf_residual_kernel, dim3(2 * nroots), dim3(1024), 0, st, dim, m, LD, V.p, Sp.p, Sm.p, dRt.p, dLt.p, dW.p, dDiag, T.p, dNorm.p);
+        sub.combine(sub.coef.p, nroots, 0, dR);
+        sub.combine(dLt.p, nroots, 0, dL);
+        hipLaunchKernelGGL(qc_tdhf_residual_kernel, dim3(2 * nroots), dim3(1024), 0, st, dim, m, LD, sub.V.p, sub.Sg[0].p, sub.Sg[1].p, sub.coef.p, dLt.p, dW.p,
+                           dDiag, T.p, dNorm.p);
         QC_HIP_CHECK(hipMemcpyAsync(norm2, dNorm.p, 2 * nroots * sizeof(double), hipMemcpyDeviceToHost, st));
         QC_HIP_CHECK(hipStreamSynchronize(st));
         nconv = 0;
@@ -327,71 +272,33 @@ int tdhf_solve(qc_system *S, int dim, int nroots, double tol, int maxit, const d
         // space (b is orthonormal).  sigma+ and sigma- follow by linearity; the reduced problem of the smaller space has the same roots.
         const int nadd = 2 * (nroots - nconv);
         bool collapsed = false;
-        if (dim > msub && m + nadd > msub && m > 2 * nroots) {
+        if (dim > sub.msub && m + nadd > sub.msub && m > 2 * nroots) {
             std::fill(Z.begin(), Z.end(), 0.0);
             int k = 0;
-            auto take = [&](const double *src) {
-                double *z = &Z[(size_t)k * LD];
-                double before = 0.0, after = 0.0;
-                for (int j = 0; j < m; ++j) { z[j] = src[j]; before += z[j] * z[j]; }
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int r = 0; r < k; ++r) {
-                        double dd = 0.0;
-                        for (int j = 0; j < m; ++j) dd += z[j] * Z[(size_t)r * LD + j];
-                        for (int j = 0; j < m; ++j) z[j] -= dd * Z[(size_t)r * LD + j];
-                    }
-                for (int j = 0; j < m; ++j) after += z[j] * z[j];
-                if (!(after > QC_STAB_KEEP * QC_STAB_KEEP * before)) { std::fill(z, z + LD, 0.0); return; }
-                const double inv = 1.0 / std::sqrt(after);
-                for (int j = 0; j < m; ++j) z[j] *= inv;
-                ++k;
-            };
-            for (int q = 0; q < 2 * nroots; ++q) take((q & 1) ? &Lsel[(size_t)(q >> 1) * LD] : &Rsel[(size_t)(q >> 1) * LD]);
+            for (int q = 0; q < 2 * nroots; ++q)
+                if (qc_orthonormalize_row(Z.data(), LD, m, k, (q & 1) ? &Lsel[(size_t)(q >> 1) * LD] : &Rsel[(size_t)(q >> 1) * LD])) ++k;
             if (have_prev)
                 for (int side = 0; side < 2; ++side)
                     for (int r = 0; r < nroots; ++r)
-                        if (rnorm[r] > tol && k + nadd < msub) take(side ? &Lprev[(size_t)r * LD] : &Rprev[(size_t)r * LD]);
-            QC_HIP_CHECK(hipMemcpyAsync(dRt.p, Z.data(), Z.size() * sizeof(double), hipMemcpyHostToDevice, st));
-            dim3 gk((dim + 255) / 256, k);
-            const size_t blk = (size_t)LD * dim;
-            hipLaunchKernelGGL(qc_stab_lincomb_kernel, gk, dim3(256), 0, st, dim, m, LD, dRt.p, V.p, Wk.p);
-            hipLaunchKernelGGL(qc_stab_lincomb_kernel, gk, dim3(256), 0, st, dim, m, LD, dRt.p, Sp.p, Wk.p + blk);
-            hipLaunchKernelGGL(qc_stab_lincomb_kernel, gk, dim3(256), 0, st, dim, m, LD, dRt.p, Sm.p, Wk.p + 2 * blk);
-            QC_HIP_CHECK(hipMemcpyAsync(V.p, Wk.p, (size_t)k * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-            QC_HIP_CHECK(hipMemcpyAsync(Sp.p, Wk.p + blk, (size_t)k * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-            QC_HIP_CHECK(hipMemcpyAsync(Sm.p, Wk.p + 2 * blk, (size_t)k * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+                        if (rnorm[r] > tol && k + nadd < sub.msub && qc_orthonormalize_row(Z.data(), LD, m, k, side ? &Lprev[(size_t)r * LD] : &Rprev[(size_t)r * LD])) ++k;
+            if ((rc = sub.collapse(Z.data(), k)) != QC_OK) return rc;
             // this round's estimates in the coordinates of the new basis: they are the "round before" of the next restart
-            std::fill(Rprev.begin(), Rprev.end(), 0.0); std::fill(Lprev.begin(), Lprev.end(), 0.0);
-            for (int r = 0; r < nroots; ++r)
-                for (int i = 0; i < k; ++i) {
-                    double a = 0.0, b = 0.0;
-                    for (int j = 0; j < m; ++j) { a += Z[(size_t)i * LD + j] * Rsel[(size_t)r * LD + j]; b += Z[(size_t)i * LD + j] * Lsel[(size_t)r * LD + j]; }
-                    Rprev[(size_t)r * LD + i] = a; Lprev[(size_t)r * LD + i] = b;
-                }
-            m = m_done = k;
-            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sp.p, 0, LD, dMp.p);
-            hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sm.p, 0, LD, dMm.p);
-            QC_HIP_CHECK(hipMemcpyAsync(Mp.data(), dMp.p, (size_t)m * LD * sizeof(double), hipMemcpyDeviceToHost, st));
-            QC_HIP_CHECK(hipMemcpyAsync(Mm.data(), dMm.p, (size_t)m * LD * sizeof(double), hipMemcpyDeviceToHost, st));
+            qc_rows_in_basis(Z.data(), LD, m, k, Rsel.data(), NR, Rprev.data());
+            qc_rows_in_basis(Z.data(), LD, m, k, Lsel.data(), NR, Lprev.data());
             QC_HIP_CHECK(hipStreamSynchronize(st));          // (Z is read by the enqueued copy; the next round overwrites it)
             collapsed = true;
         }
         if (!collapsed) { Rprev = Rsel; Lprev = Lsel; }
         have_prev = true;
         // new directions: the preconditioned residuals of every root that has not converged, orthogonalised into b (at most two per root)
-        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
         for (int r = 0; r < nroots; ++r) {
             if (rnorm[r] <= tol) continue;
-            for (int side = 0; side < 2; ++side)
-                hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, m, msub, V.p, (const double *)nullptr, (const double *)nullptr,
-                                   (const double *)nullptr, (const double *)nullptr, (const double *)(T.p + (size_t)(2 * r + side) * dim), (const double *)nullptr,
-                                   0.0, dCnt.p, dInfo.p + 2 * (2 * r + side));
+            for (int side = 0; side < 2; ++side) sub.seed(T.p + (size_t)(2 * r + side) * dim, 2 * r + side);
         }
         int added = 0;
-        QC_HIP_CHECK(hipMemcpyAsync(&added, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
+        if ((rc = sub.added(&added)) != QC_OK) return rc;
         if (added == 0) break;                               // (nothing left to add: the residuals are as small as this arithmetic makes them)
-        m += added;
+        sub.m += added;
     }
     if (it > maxit) it = maxit;
     out.nconv = nconv; out.iterations = it;

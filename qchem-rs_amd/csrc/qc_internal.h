@@ -340,6 +340,12 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
 // B[k,j] = B[b b_bs + k ldb + j], C[m,j] = C[b c_bs + m ldc + j]; every edge is masked (M, N, K need not be multiples of the tile)
 void qc_mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A, int64_t a_ms, int64_t a_ks, int64_t a_bs,
                  const double *B, int64_t ldb, int64_t b_bs, double *C, int64_t ldc, int64_t c_bs);
+// the four contraction shapes of a quarter-transformation chain, one qc_mp2_gemm call each, against `m` columns of C (n x n, columns = MOs) from column c0; dense, slowest index
+// first.  first: (mu x n^3) -> (m x n^3); second, batched over the first index: (batch x mu x n^2) -> (batch x m x n^2); third, over the first two: (batch x mu x n) -> (batch x m x n); last: (rows x mu) -> (rows x m)
+void qc_quarter_first(hipStream_t st, int n, const double *C, int c0, int m, const double *In, double *Out);
+void qc_quarter_second(hipStream_t st, int n, int batch, const double *C, int c0, int m, const double *In, double *Out);
+void qc_quarter_third(hipStream_t st, int n, int batch, const double *C, int c0, int m, const double *In, double *Out);
+void qc_quarter_last(hipStream_t st, int n, int rows, const double *C, int c0, int m, const double *In, double *Out);
 // excited states (qc_excited.hip): CIS / TDHF of an RHF state from explicit A + B and A - B matrices built from MO integrals.  The
 // caller has checked io's inputs.  matrices: the two d x d matrices of `kind` copied to the host (either nullable).
 int qc_excitations_device(qc_system *S, int nocc, const double *dC, const double *dEps, qc_excitations *io, double *vectors);

@@ -146,6 +146,20 @@ void qc_mp2_gemm(hipStream_t st, int batch, int M, int N, int K, const double *A
     else hipLaunchKernelGGL(qc_mp2_gemm_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, g);
 }
 
+// ---- the four quarter transformations: one index of the operand against `m` columns of C from column c0 (A[i,mu] = C[mu, c0 + i]: row stride 1, k stride n)
+void qc_quarter_first(hipStream_t st, int n, const double *C, int c0, int m, const double *In, double *Out) {
+    const int64_t n3 = (int64_t)n * n * n;
+    qc_mp2_gemm(st, 1, m, (int)n3, n, C + c0, 1, n, 0, In, n3, 0, Out, n3, 0);
+}
+void qc_quarter_second(hipStream_t st, int n, int batch, const double *C, int c0, int m, const double *In, double *Out) {
+    const int64_t nn = (int64_t)n * n;
+    qc_mp2_gemm(st, batch, m, (int)nn, n, C + c0, 1, n, 0, In, nn, nn * n, Out, nn, (int64_t)m * nn);
+}
+void qc_quarter_third(hipStream_t st, int n, int batch, const double *C, int c0, int m, const double *In, double *Out) {
+    qc_mp2_gemm(st, batch, m, n, n, C + c0, 1, n, 0, In, n, (int64_t)n * n, Out, n, (int64_t)m * n);
+}
+void qc_quarter_last(hipStream_t st, int n, int rows, const double *C, int c0, int m, const double *In, double *Out) { qc_mp2_gemm(st, 1, rows, m, n, In, n, 1, 0, C + c0, n, 0, Out, m, 0); }
+
 namespace {
 
 // ---- pair energies.  W[i,a,j,b] = (ia|jb) of one spin block, dims (o1, v1, o2, v2); one workgroup per pair (i,j).
@@ -263,19 +277,15 @@ int qc_mp2_device(qc_system *S, int nspin, const double *dC, const double *dEps,
     for (int s = 0; s < nspin; ++s) {
         if (o[s] == 0 || v[s] == 0) continue;
         const double *Cs = dC + s * nn;
-        // (i nu|la si): A = C_occ^T (A[i,mu] = C[mu, nf + i]), B = I as n x n^3
-        qc_mp2_gemm(st, 1, o[s], (int)n3, n, Cs + n_frozen, 1, n, 0, I.p, n3, 0, T1.p, n3, 0);
-        // (i a|la si), batched over i: A = C_virt^T, B = T1[i] as n x n^2
-        qc_mp2_gemm(st, o[s], v[s], (int)nn, n, Cs + nocc[s], 1, n, 0, T1.p, nn, n3, T2.p + t2_off[s], nn, (int64_t)v[s] * nn);
+        qc_quarter_first(st, n, Cs, n_frozen, o[s], I.p, T1.p);                               // (i nu|la si)
+        qc_quarter_second(st, n, o[s], Cs, nocc[s], v[s], T1.p, T2.p + t2_off[s]);            // (i a|la si)
     }
     for (const auto &b : blks) {
         const int o1 = o[b.s1], v1 = v[b.s1], o2 = o[b.s2], v2 = v[b.s2];
         if (o1 == 0 || v1 == 0 || o2 == 0 || v2 == 0) continue;
         const double *C2 = dC + b.s2 * nn;
-        // (i a|j si), batched over (i,a): A = C_occ^T of spin s2, B = T2[i,a] as n x n
-        qc_mp2_gemm(st, o1 * v1, o2, n, n, C2 + n_frozen, 1, n, 0, T2.p + t2_off[b.s1], n, nn, T3.p, n, (int64_t)o2 * n);
-        // (i a|j b): A = T3 as (o1 v1 o2) x n, B = C_virt of spin s2 (n x v2, row stride n)
-        qc_mp2_gemm(st, 1, o1 * v1 * o2, v2, n, T3.p, n, 1, 0, C2 + nocc[b.s2], n, 0, W.p + b.w_off, v2, 0);
+        qc_quarter_third(st, n, o1 * v1, C2, n_frozen, o2, T2.p + t2_off[b.s1], T3.p);        // (i a|j si), spin s2 on the third index
+        qc_quarter_last(st, n, o1 * v1 * o2, C2, nocc[b.s2], v2, T3.p, W.p + b.w_off);        // (i a|j b)
     }
     QC_HIP_CHECK(hipGetLastError());
     QC_HIP_CHECK(hipStreamSynchronize(st));

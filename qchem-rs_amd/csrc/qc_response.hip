@@ -4,17 +4,13 @@
 // For a static, real perturbation the first-order orbital rotations U^q solve (A + B) U^q = r^q with r^q = C_occ^T M_q C_virt per spin
 // block (M_q: dipole matrix of direction q; vectors laid out x[i * v + a] as in qc_stability.hip), and
 //   alpha_pq = c r^p . U^q,   c = 4 for an RHF state (singlet operator), c = 2 for a UHF state (internal operator, vector [x^a; x^b]).
-// (A + B) x is the Hessian-vector product of the stability analysis - one direct Fock build of the symmetric pseudo-density, qc_stab_shared.h.
-// The three systems share one orthonormal subspace V (reduced-space iteration): per round one build per new vector, the projected
+// (A + B) x is the Hessian-vector product of the stability analysis - one direct Fock build of the symmetric pseudo-density, StabSigma in qc_subspace.h.
+// The three systems share one orthonormal subspace (QcSubspace, qc_subspace.h; reduced-space iteration): per round one build per new vector, the projected
 // matrix V^T (A + B) V and V^T r by fixed-order dot products, the small systems solved on the host, and per right-hand side one launch that
 // forms the residual, preconditions it with 1 / (e_a - e_i) and orthogonalises it into V.  A Galerkin solve needs the projected matrix
 // to be non-singular, not (A + B) to be positive definite: at a saddle the iteration works as long as no projected matrix is singular.
 // Every sum is a fixed-order reduction and the Fock build accumulates integers: a call is bitwise reproducible.
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "qc_stab_shared.h"
+#include "qc_subspace.h"
 
 namespace {
 
@@ -38,37 +34,6 @@ __global__ void qc_cphf_precond_kernel(int dim, const double *__restrict__ de, c
     double d = de[e];
     if (fabs(d) < QC_STAB_DENOM_FLOOR) d = d < 0.0 ? -QC_STAB_DENOM_FLOOR : QC_STAB_DENOM_FLOOR;
     x[e] = r[e] / d;
-}
-
-// A y = b for nrhs right-hand sides (b, y: nrhs rows of m) by LU with partial pivoting; false: a pivot vanished against the matrix
-bool host_lu_solve(int m, std::vector<double> A, int nrhs, const double *b, double *y) {
-    std::vector<int> piv(m);
-    double amax = 0.0;
-    for (double a : A) amax = std::max(amax, std::fabs(a));
-    for (int k = 0; k < m; ++k) {
-        int p = k;
-        for (int i = k + 1; i < m; ++i) if (std::fabs(A[(size_t)i * m + k]) > std::fabs(A[(size_t)p * m + k])) p = i;
-        if (!(std::fabs(A[(size_t)p * m + k]) > 1e-14 * amax)) return false;
-        piv[k] = p;
-        if (p != k) for (int j = 0; j < m; ++j) std::swap(A[(size_t)k * m + j], A[(size_t)p * m + j]);
-        for (int i = k + 1; i < m; ++i) {
-            const double l = A[(size_t)i * m + k] / A[(size_t)k * m + k];
-            A[(size_t)i * m + k] = l;
-            for (int j = k + 1; j < m; ++j) A[(size_t)i * m + j] -= l * A[(size_t)k * m + j];
-        }
-    }
-    for (int q = 0; q < nrhs; ++q) {
-        double *x = y + (size_t)q * m;
-        for (int i = 0; i < m; ++i) x[i] = b[(size_t)q * m + i];
-        for (int k = 0; k < m; ++k) if (piv[k] != k) std::swap(x[k], x[piv[k]]);      // (whole rows were swapped: all of P first, then L)
-        for (int k = 0; k < m; ++k)
-            for (int i = k + 1; i < m; ++i) x[i] -= A[(size_t)i * m + k] * x[k];
-        for (int i = m - 1; i >= 0; --i) {
-            for (int j = i + 1; j < m; ++j) x[i] -= A[(size_t)i * m + j] * x[j];
-            x[i] /= A[(size_t)i * m + i];
-        }
-    }
-    return true;
 }
 
 }  // namespace
@@ -98,154 +63,97 @@ int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const doub
     io->asymmetry = 0.0; io->nconverged = NR; io->iterations = 0; io->builds = 0; io->ms_builds = 0.0; io->ms_total = 0.0;
     if (response) std::fill(response, response + (size_t)NR * dim, 0.0);
     if (dim == 0) { io->ms_total = qc_now_ms() - t_begin; return QC_OK; }
-    const int msub = std::min(dim, QC_STAB_MAXSUB);
-    const size_t rows = (size_t)msub + 1;
-
-    DevBuf dDe, dM3, Rh, V, Sg, Wk, dA, dB, dY, dInfo, dOut;
-    QcDev<int> dCnt;
+    DevBuf dDe, dM3, Rh, dB, dOut;
+    QcSubspace sub;
     StabSigma sigma(S, L, uhf, 0, dC, nullptr);
-    if (dDe.alloc(dim) != QC_OK || dM3.alloc(3 * nn) != QC_OK || Rh.alloc((size_t)NR * dim) != QC_OK || V.alloc(rows * dim) != QC_OK ||
-        Sg.alloc(rows * dim) != QC_OK || Wk.alloc(2 * (size_t)NR * dim) != QC_OK || dA.alloc((size_t)LD * LD) != QC_OK || dB.alloc((size_t)NR * LD) != QC_OK ||
-        dY.alloc((size_t)NR * LD) != QC_OK || dInfo.alloc(2 * NR) != QC_OK || dOut.alloc(NR * NR) != QC_OK || dCnt.alloc(1) != QC_OK || sigma.alloc() != QC_OK)
-        return QC_ERR_HIP;
+    if (dDe.alloc(dim) != QC_OK || dM3.alloc(3 * nn) != QC_OK || Rh.alloc((size_t)NR * dim) != QC_OK || sub.alloc(st, dim, 1, NR) != QC_OK ||
+        dB.alloc((size_t)NR * LD) != QC_OK || dOut.alloc(NR * NR) != QC_OK || sigma.alloc() != QC_OK) return QC_ERR_HIP;
     sigma.dDe = dDe.p;
-    for (int b = 0; b < L.nblk; ++b) {
-        const int ov = L.o[b] * L.v[b];
-        if (ov > 0) hipLaunchKernelGGL(qc_stab_delta_kernel, dim3((ov + 255) / 256), dim3(256), 0, st, L.o[b], L.v[b], dEps + (size_t)b * n, dDe.p + L.off[b]);
-    }
+    qc_stab_fill_delta(st, L, n, dEps, dDe.p);
 
     // right-hand sides r^q = C_occ^T M_q C_virt per block (origin 0: occupied and virtual orbitals are orthogonal), and their squared norms
     const double origin[3] = {0.0, 0.0, 0.0};
     int rc = qc_dipole_device(S, origin, dM3.p);
     if (rc != QC_OK) return rc;
     for (int q = 0; q < NR; ++q)
-        for (int b = 0; b < L.nblk; ++b) {
-            if (L.o[b] == 0 || L.v[b] == 0) continue;
-            const double *Cb = dC + b * nn;
-            qc_gemm(st, n, L.v[b], n, 1.0, dM3.p + q * nn, n, false, Cb + L.o[b], n, false, 0.0, sigma.P.p, L.v[b]);                       // M C_virt
-            qc_gemm(st, L.o[b], L.v[b], n, 1.0, Cb, n, true, sigma.P.p, L.v[b], false, 0.0, Rh.p + (size_t)q * dim + L.off[b], L.v[b]);    // C_occ^T (.)
-        }
-    hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(NR, NR), dim3(256), 0, st, dim, Rh.p, Rh.p, 0, NR, dOut.p);
+        for (int b = 0; b < L.nblk; ++b)
+            if (L.o[b] > 0 && L.v[b] > 0) qc_ao_to_ov(st, n, L.o[b], L.v[b], dC + b * nn, dM3.p + q * nn, sigma.P.p, Rh.p + (size_t)q * dim + L.off[b]);
+    qc_stab_dots(st, dim, Rh.p, NR, Rh.p, 0, NR, NR, dOut.p);
     double rr[NR * NR];
     QC_HIP_CHECK(hipMemcpyAsync(rr, dOut.p, sizeof(rr), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipStreamSynchronize(st));
-    bool active[NR];
-    int nactive = 0;
+    bool active[NR]; int nactive = 0;
     for (int q = 0; q < NR; ++q) { active[q] = rr[q * NR + q] > 0.0; nactive += active[q] ? 1 : 0; }
 
-    // start vectors: the preconditioned right-hand sides, orthonormalised (staged in Wk)
-    QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
+    // start vectors: the preconditioned right-hand sides, orthonormalised (staged in the work rows)
     for (int q = 0; q < NR; ++q) {
         if (!active[q]) continue;
-        hipLaunchKernelGGL(qc_cphf_precond_kernel, dim3((dim + 255) / 256), dim3(256), 0, st, dim, dDe.p, Rh.p + (size_t)q * dim, Wk.p + (size_t)q * dim);
-        hipLaunchKernelGGL(qc_stab_expand_kernel<false>, dim3(1), dim3(1024), 0, st, dim, 0, msub, V.p, (const double *)nullptr, (const double *)nullptr,
-                           (const double *)nullptr, (const double *)nullptr, (const double *)(Wk.p + (size_t)q * dim), (const double *)nullptr, 0.0,
-                           dCnt.p, dInfo.p + 2 * q);
+        hipLaunchKernelGGL(qc_cphf_precond_kernel, dim3((dim + 255) / 256), dim3(256), 0, st, dim, dDe.p, Rh.p + (size_t)q * dim, sub.Wk.p + (size_t)q * dim);
+        sub.seed(sub.Wk.p + (size_t)q * dim, q);
     }
-    int m = 0;
-    QC_HIP_CHECK(hipMemcpyAsync(&m, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    QC_HIP_CHECK(hipStreamSynchronize(st));
+    if ((rc = sub.added(&sub.m)) != QC_OK) return rc;
 
-    // (Z, Yn: the collapse's coefficient arrays; they are sources of enqueued copies and live as long as the stream may read them)
-    std::vector<double> M((size_t)LD * LD, 0.0), B((size_t)NR * LD, 0.0), Y((size_t)NR * LD, 0.0), info(2 * NR, 0.0);
-    std::vector<double> Z((size_t)NR * LD, 0.0), Yn((size_t)NR * LD, 0.0);
+    // (Z: the collapse's coefficient array; Y and Z are sources of enqueued copies and live as long as the stream may read them)
+    std::vector<double> B((size_t)NR * LD, 0.0), Y((size_t)NR * LD, 0.0), info(2 * NR, 0.0), Z((size_t)NR * LD, 0.0), Yn((size_t)NR * LD, 0.0);
     // the residual norms always belong to the estimate that is returned: before the first solve that is U = 0, whose residual is r itself
     double rnorm[NR];
     for (int q = 0; q < NR; ++q) rnorm[q] = active[q] ? std::sqrt(rr[q * NR + q]) : 0.0;
-    int m_done = 0, it = 0, nconv = NR - nactive;
-    bool converged = nactive == 0;
-    for (it = 1; m > 0 && !converged && it <= maxit; ++it) {
-        for (int k = m_done; k < m; ++k)
-            if ((rc = sigma.apply(V.p + (size_t)k * dim, Sg.p + (size_t)k * dim)) != QC_OK) return rc;
-        // new rows of the projected matrix, M[k][j] = <V_j, Sg_k>, j <= k, and the new entries of V^T r, B[q][j] = <V_j, r^q>
-        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m - m_done), dim3(256), 0, st, dim, V.p, Sg.p, m_done, LD, dA.p);
-        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m - m_done, NR), dim3(256), 0, st, dim, V.p + (size_t)m_done * dim, Rh.p, 0, LD, dB.p + m_done);
-        QC_HIP_CHECK(hipMemcpyAsync(M.data() + (size_t)m_done * LD, dA.p + (size_t)m_done * LD, (size_t)(m - m_done) * LD * sizeof(double), hipMemcpyDeviceToHost, st));
+    int it = 0, nconv = NR - nactive; bool converged = nactive == 0;
+    for (it = 1; sub.m > 0 && !converged && it <= maxit; ++it) {
+        for (int k = sub.m_done; k < sub.m; ++k)
+            if ((rc = sigma.apply(sub.V.p + (size_t)k * dim, sub.Sg[0].p + (size_t)k * dim)) != QC_OK) return rc;
+        // new entries of V^T r, B[q][j] = <V_j, r^q>, then the new rows of the projected matrix (B's launch and copy stood behind the matrix's: nothing in common; the one wait is still project()'s)
+        qc_stab_dots(st, dim, sub.V.p + (size_t)sub.m_done * dim, sub.m - sub.m_done, Rh.p, 0, NR, LD, dB.p + sub.m_done);
         QC_HIP_CHECK(hipMemcpyAsync(B.data(), dB.p, B.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
-        m_done = m;
-        std::vector<double> A((size_t)m * m), b((size_t)NR * m, 0.0), y((size_t)NR * m, 0.0);
-        for (int i = 0; i < m; ++i) for (int j = 0; j <= i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = M[(size_t)i * LD + j];
+        if ((rc = sub.project()) != QC_OK) return rc;
+        const int m = sub.m;
+        std::vector<double> b((size_t)NR * m, 0.0), y((size_t)NR * m, 0.0);
         for (int q = 0; q < NR; ++q) if (active[q]) for (int j = 0; j < m; ++j) b[(size_t)q * m + j] = B[(size_t)q * LD + j];
-        if (!host_lu_solve(m, A, NR, b.data(), y.data())) break;   // (a singular projected system: the last estimates and their residuals stand)
+        if (!host_lu_solve(m, sub.reduced(0), NR, b.data(), y.data())) break;   // (a singular projected system: the last estimates and their residuals stand)
         std::fill(Y.begin(), Y.end(), 0.0);
         for (int q = 0; q < NR; ++q) for (int j = 0; j < m; ++j) Y[(size_t)q * LD + j] = y[(size_t)q * m + j];
-        QC_HIP_CHECK(hipMemcpyAsync(dY.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        QC_HIP_CHECK(hipMemcpyAsync(sub.coef.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
         // the subspace is full: collapse onto the current solutions, orthonormalised in coefficient space (V is orthonormal); their sigma
         // vectors follow by linearity, and the Galerkin solutions in the smaller space are the same vectors.  Only a space larger than the
         // subspace collapses: with dim <= QC_STAB_MAXSUB the basis grows until it spans the whole space, where the solve is exact
         // (at most dim builds).
-        if (dim > msub && m + nactive > msub && m > nactive) {
+        if (dim > sub.msub && m + nactive > sub.msub && m > nactive) {
             std::fill(Z.begin(), Z.end(), 0.0);
             int k = 0;
-            for (int q = 0; q < NR; ++q) {
-                if (!active[q]) continue;
-                double *z = &Z[(size_t)k * LD];
-                double before = 0.0, after = 0.0;
-                for (int j = 0; j < m; ++j) { z[j] = Y[(size_t)q * LD + j]; before += z[j] * z[j]; }
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int r = 0; r < k; ++r) {
-                        double d = 0.0;
-                        for (int j = 0; j < m; ++j) d += z[j] * Z[(size_t)r * LD + j];
-                        for (int j = 0; j < m; ++j) z[j] -= d * Z[(size_t)r * LD + j];
-                    }
-                for (int j = 0; j < m; ++j) after += z[j] * z[j];
-                if (!(after > QC_STAB_KEEP * QC_STAB_KEEP * before)) { std::fill(z, z + LD, 0.0); continue; }
-                const double inv = 1.0 / std::sqrt(after);
-                for (int j = 0; j < m; ++j) z[j] *= inv;
-                ++k;
-            }
+            for (int q = 0; q < NR; ++q)
+                if (active[q] && qc_orthonormalize_row(Z.data(), LD, m, k, &Y[(size_t)q * LD])) ++k;
             if (k > 0) {
-                QC_HIP_CHECK(hipMemcpyAsync(dY.p, Z.data(), Z.size() * sizeof(double), hipMemcpyHostToDevice, st));
-                dim3 grid((dim + 255) / 256, k);
-                hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, LD, dY.p, V.p, Wk.p);
-                hipLaunchKernelGGL(qc_stab_lincomb_kernel, grid, dim3(256), 0, st, dim, m, LD, dY.p, Sg.p, Wk.p + (size_t)NR * dim);
-                QC_HIP_CHECK(hipMemcpyAsync(V.p, Wk.p, (size_t)k * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-                QC_HIP_CHECK(hipMemcpyAsync(Sg.p, Wk.p + (size_t)NR * dim, (size_t)k * dim * sizeof(double), hipMemcpyDeviceToDevice, st));
-                // coefficients of the solutions in the new basis, and its projected matrix and right-hand sides
-                std::fill(Yn.begin(), Yn.end(), 0.0);
-                for (int q = 0; q < NR; ++q)
-                    for (int r = 0; r < k; ++r) {
-                        double d = 0.0;
-                        for (int j = 0; j < m; ++j) d += Z[(size_t)r * LD + j] * Y[(size_t)q * LD + j];
-                        Yn[(size_t)q * LD + r] = d;
-                    }
+                if ((rc = sub.collapse(Z.data(), k)) != QC_OK) return rc;
+                // the solutions' coefficients and V^T r in the new basis (V^T r's launch stood before the matrix's copy to the host, which collapse() enqueues: nothing in common)
+                qc_rows_in_basis(Z.data(), LD, m, k, Y.data(), NR, Yn.data());
                 Y.swap(Yn);
-                m = m_done = k;
-                hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, m), dim3(256), 0, st, dim, V.p, Sg.p, 0, LD, dA.p);
-                hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(m, NR), dim3(256), 0, st, dim, V.p, Rh.p, 0, LD, dB.p);
-                QC_HIP_CHECK(hipMemcpyAsync(M.data(), dA.p, (size_t)m * LD * sizeof(double), hipMemcpyDeviceToHost, st));
-                QC_HIP_CHECK(hipMemcpyAsync(dY.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
+                qc_stab_dots(st, dim, sub.V.p, k, Rh.p, 0, NR, LD, dB.p);
+                QC_HIP_CHECK(hipMemcpyAsync(sub.coef.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
             }
         }
         // residual | preconditioner | orthogonalisation of every right-hand side, one launch each; the device counts the vectors it added
-        QC_HIP_CHECK(hipMemsetAsync(dCnt.p, 0, sizeof(int), st));
         for (int q = 0; q < NR; ++q)
-            if (active[q])
-                hipLaunchKernelGGL(qc_stab_expand_kernel<true>, dim3(1), dim3(1024), 0, st, dim, m, msub, V.p, (const double *)Sg.p,
-                                   (const double *)(dY.p + (size_t)q * LD), (const double *)nullptr, (const double *)dDe.p, (const double *)nullptr,
-                                   (const double *)(Rh.p + (size_t)q * dim), tol, dCnt.p, dInfo.p + 2 * q);
+            if (active[q]) sub.expand_residual(sub.coef.p + (size_t)q * LD, nullptr, dDe.p, Rh.p + (size_t)q * dim, tol, q);
         int added = 0;
-        QC_HIP_CHECK(hipMemcpyAsync(info.data(), dInfo.p, 2 * NR * sizeof(double), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipMemcpyAsync(&added, dCnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        QC_HIP_CHECK(hipStreamSynchronize(st));
+        QC_HIP_CHECK(hipMemcpyAsync(info.data(), sub.info.p, 2 * NR * sizeof(double), hipMemcpyDeviceToHost, st));
+        if ((rc = sub.added(&added)) != QC_OK) return rc;
         nconv = 0;
         for (int q = 0; q < NR; ++q) { rnorm[q] = active[q] ? std::sqrt(info[2 * q]) : 0.0; if (rnorm[q] <= tol) ++nconv; }
         if (nconv == NR) { converged = true; break; }
         if (added == 0) break;                           // (nothing left to add: the residuals are as small as this arithmetic makes them)
-        m += added;
+        sub.m += added;
     }
     if (it > maxit) it = maxit;
-    if (nactive == 0 || m == 0) it = 0;
+    if (nactive == 0 || sub.m == 0) it = 0;
 
     // U^q = sum_j y^q_j V_j, alpha_pq = c <r^p, U^q> by the fixed-order dot products; symmetrised on the host
-    if (m_done > 0) {
-        QC_HIP_CHECK(hipMemcpyAsync(dY.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(qc_stab_lincomb_kernel, dim3((dim + 255) / 256, NR), dim3(256), 0, st, dim, m_done, LD, dY.p, V.p, Wk.p);
-        hipLaunchKernelGGL(qc_stab_dots_kernel, dim3(NR, NR), dim3(256), 0, st, dim, Rh.p, Wk.p, 0, NR, dOut.p);       // out[q * 3 + p] = <r^p, U^q>
+    if (sub.m_done > 0) {
+        QC_HIP_CHECK(hipMemcpyAsync(sub.coef.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        sub.combine(sub.coef.p, NR, 0, sub.Wk.p);
+        qc_stab_dots(st, dim, Rh.p, NR, sub.Wk.p, 0, NR, NR, dOut.p);       // out[q * 3 + p] = <r^p, U^q>
         double ru[NR * NR];
         QC_HIP_CHECK(hipMemcpyAsync(ru, dOut.p, sizeof(ru), hipMemcpyDeviceToHost, st));
-        if (response) QC_HIP_CHECK(hipMemcpyAsync(response, Wk.p, (size_t)NR * dim * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (response) QC_HIP_CHECK(hipMemcpyAsync(response, sub.Wk.p, (size_t)NR * dim * sizeof(double), hipMemcpyDeviceToHost, st));
         QC_HIP_CHECK(hipStreamSynchronize(st));
         for (int p = 0; p < NR; ++p)
             for (int q = 0; q < NR; ++q) {

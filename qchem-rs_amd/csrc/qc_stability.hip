@@ -10,16 +10,84 @@
 // Trial vectors, sigma vectors and the correction vector live in HBM (msub + 1 rows of `dim` doubles each); the subspace matrix
 // (at most QC_STAB_MAXSUB rows) is diagonalised on the host.  Every dot product is a fixed-order reduction (a thread's elements in
 // index order, the 64 lanes of a wave by a shuffle tree, the waves in order) and the Fock build accumulates integers: a call is bitwise
-// reproducible.  The layout of a vector, the Hessian-vector product, the subspace kernels, the host eigenproblem and the Davidson loop
-// itself are in qc_stab_shared.h (shared with the response solver, qc_response.hip, and the excited states, qc_excited.hip); this file
-// keeps the product handed to that loop and the rotation.
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <numeric>
-#include <vector>
+// reproducible.  The subspace, its kernels and the Davidson loop are in qc_subspace.h / qc_subspace.hip (shared with qc_response.hip and qc_excited.hip);
+// this file defines the Hessian-vector product declared there (StabSigma, its kernels, qc_ao_to_ov), the product handed to that loop and the rotation.
+#include "qc_subspace.h"
 
-#include "qc_stab_shared.h"
+namespace {
+
+// de[i * v + a] = eps[o + a] - eps[i]
+__global__ void qc_stab_delta_kernel(int o, int v, const double *__restrict__ eps, double *__restrict__ de) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < o * v) de[e] = eps[o + e % v] - eps[e / v];
+}
+
+// pseudo-density: D = s (Q + Q^T) with Q = C_occ x C_virt^T; Dneg (nullable) = -D
+__global__ void qc_stab_symmetrize_kernel(int n, double s, const double *__restrict__ Q, double *__restrict__ D, double *__restrict__ Dneg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n) return;
+    const int r = e / n, c = e % n;
+    const double d = s * (Q[e] + Q[(size_t)c * n + r]);
+    D[e] = d;
+    if (Dneg) Dneg[e] = -d;
+}
+
+// sigma = de * x + R, R = the occupied-virtual block of the two-electron matrix
+__global__ void qc_stab_sigma_kernel(int dim, const double *__restrict__ de, const double *__restrict__ x, const double *__restrict__ R,
+                                     double *__restrict__ sg) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < dim) sg[e] = fma(de[e], x[e], R[e]);
+}
+
+}  // namespace
+
+void qc_stab_fill_delta(hipStream_t st, const StabLayout &L, int n, const double *dEps, double *dDe) {
+    for (int b = 0; b < L.nblk; ++b)
+        if (L.o[b] * L.v[b] > 0) hipLaunchKernelGGL(qc_stab_delta_kernel, dim3((L.o[b] * L.v[b] + 255) / 256), dim3(256), 0, st, L.o[b], L.v[b], dEps + (size_t)b * n, dDe + L.off[b]);
+}
+
+void qc_ao_to_ov(hipStream_t st, int n, int o, int v, const double *C, const double *M_ao, double *scratch, double *out) {
+    qc_gemm(st, n, v, n, 1.0, M_ao, n, false, C + o, n, false, 0.0, scratch, v);      // M C_virt
+    qc_gemm(st, o, v, n, 1.0, C, n, true, scratch, v, false, 0.0, out, v);            // C_occ^T (.)
+}
+
+int StabSigma::alloc() {
+    const size_t n = S->nbasis, nn = n * n;
+    return P.alloc(nn) != QC_OK || Q.alloc(nn) != QC_OK || D1.alloc(2 * nn) != QC_OK || G.alloc(2 * nn) != QC_OK || R.alloc(std::max<size_t>(L.dim, 1)) != QC_OK ? QC_ERR_HIP : QC_OK;
+}
+
+int StabSigma::apply(const double *dx, double *dsg) {
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    hipStream_t st = S->stream;
+    const bool triplet = !uhf && kind == 1, rhf_build = !uhf && kind == 0;
+    for (int b = 0; b < L.nblk; ++b) {
+        const double *Cb = dC + b * nn;
+        double *Db = D1.p + b * nn;
+        if (L.o[b] == 0 || L.v[b] == 0) { QC_HIP_CHECK(hipMemsetAsync(Db, 0, nn * sizeof(double), st)); continue; }
+        qc_gemm(st, n, L.v[b], L.o[b], 1.0, Cb, n, false, dx + L.off[b], L.v[b], false, 0.0, P.p, L.v[b]);          // C_occ x
+        qc_gemm(st, n, n, L.v[b], 1.0, P.p, L.v[b], false, Cb + L.o[b], n, true, 0.0, Q.p, n);                       // (.) C_virt^T
+        hipLaunchKernelGGL(qc_stab_symmetrize_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, n, rhf_build ? 2.0 : 1.0, Q.p, Db,
+                           triplet ? D1.p + nn : nullptr);
+    }
+    const double t0 = qc_now_ms();
+    int rc = rhf_build ? qc_fock_build_device(S, D1.p, nullptr, G.p, nullptr, false)
+                       : qc_fock_build_device(S, D1.p, D1.p + nn, G.p, G.p + nn, true);
+    if (rc != QC_OK) return rc;
+    QC_HIP_CHECK(hipStreamSynchronize(st));
+    if ((rc = qc_join_check(S)) != QC_OK) return rc;
+    qc_gate_quiet(S);
+    ms_builds += qc_now_ms() - t0; builds += 1;
+    for (int b = 0; b < L.nblk; ++b) {
+        if (L.o[b] == 0 || L.v[b] == 0) continue;
+        qc_ao_to_ov(st, n, L.o[b], L.v[b], dC + b * nn, G.p + b * nn, P.p, R.p + L.off[b]);                           // C_occ^T G C_virt
+        const int ov = L.o[b] * L.v[b];
+        hipLaunchKernelGGL(qc_stab_sigma_kernel, dim3((ov + 255) / 256), dim3(256), 0, st, ov, dDe + L.off[b], dx + L.off[b], R.p + L.off[b],
+                           dsg + L.off[b]);
+    }
+    QC_HIP_CHECK(hipGetLastError());
+    return QC_OK;
+}
 
 int qc_stability_dim(int n, bool uhf, const int *nocc) { return StabLayout(n, uhf, nocc).dim; }
 
@@ -37,10 +105,7 @@ int qc_stability_device(qc_system *S, bool uhf, const int *nocc, const double *d
     // diagonal e_a - e_i, on the device and on the host (start vectors)
     DevBuf dDe;
     if (dDe.alloc(dim) != QC_OK) return QC_ERR_HIP;
-    for (int b = 0; b < L.nblk; ++b) {
-        const int ov = L.o[b] * L.v[b];
-        if (ov > 0) hipLaunchKernelGGL(qc_stab_delta_kernel, dim3((ov + 255) / 256), dim3(256), 0, st, L.o[b], L.v[b], dEps + (size_t)b * n, dDe.p + L.off[b]);
-    }
+    qc_stab_fill_delta(st, L, n, dEps, dDe.p);
     std::vector<double> de(dim);
     QC_HIP_CHECK(hipMemcpyAsync(de.data(), dDe.p, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipStreamSynchronize(st));
