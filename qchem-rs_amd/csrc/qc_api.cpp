@@ -68,6 +68,14 @@ int sym_eig_host(qc_system *S, int n, const double *A, const double *V0, double 
     return flag ? QC_EIG_NOT_CONVERGED : QC_OK;
 }
 
+// the handle's work lists as those of shard (rank, nranks) for the life of this object; its own shard's lists are back when it ends
+struct ShardScope {
+    qc_system *S; int rank0, nranks0;
+    ShardScope(qc_system *S_, int rank, int nranks) : S(S_), rank0(S_->rank), nranks0(S_->nranks) { set(rank, nranks); }
+    ~ShardScope() { set(rank0, nranks0); }
+    void set(int rank, int nranks) { S->rank = rank; S->nranks = nranks; qc_build_shards(S); }
+};
+
 }  // namespace
 
 void qc_system_free(qc_system *S) {
@@ -361,38 +369,28 @@ int qc_rccl_info(char *buf, size_t len) {
 
 int qc_plan_shard(qc_system *S, int rank, int nranks, int64_t *nquartets, double *flops) {
     if (!S || nranks <= 0 || rank < 0 || rank >= nranks) return QC_ERR_INVALID;
-    const int r0 = S->rank, n0 = S->nranks;
-    S->rank = rank; S->nranks = nranks;
-    qc_build_shards(S);
+    ShardScope as(S, rank, nranks);
     int64_t nq = 0; double fl = 0.0;
     for (const auto &c : S->classes) { nq += (int64_t)c.shard.size(); fl += c.flops_alg; }
     if (nquartets) *nquartets = nq;
     if (flops) *flops = fl;
-    S->rank = r0; S->nranks = n0;
-    qc_build_shards(S);
     return QC_OK;
 }
 
 // list the quartets of a shard as (shell A, B, C, D) so a host-side checker can digest exactly the same units
 int qc_plan_shard_quartets(qc_system *S, int rank, int nranks, int32_t *abcd /* 4 * nquartets or NULL */, int64_t capacity) {
     if (!S || nranks <= 0 || rank < 0 || rank >= nranks) return QC_ERR_INVALID;
-    const int r0 = S->rank, n0 = S->nranks;
-    S->rank = rank; S->nranks = nranks;
-    qc_build_shards(S);                                   // exactly the lists the device would be given
+    ShardScope as(S, rank, nranks);                       // exactly the lists the device would be given
     int64_t k = 0;
-    bool overflow = false;
     for (const auto &c : S->classes)
         for (const auto &t : c.shard) {
             if (abcd) {
-                if (k >= capacity) { overflow = true; break; }
+                if (k >= capacity) return QC_ERR_INVALID;
                 abcd[4 * k + 0] = S->pairA[t.bra]; abcd[4 * k + 1] = S->pairB[t.bra];
                 abcd[4 * k + 2] = S->pairA[t.ket]; abcd[4 * k + 3] = S->pairB[t.ket];
             }
             ++k;
         }
-    S->rank = r0; S->nranks = n0;
-    qc_build_shards(S);
-    if (overflow) return QC_ERR_INVALID;
     return (int)k;
 }
 

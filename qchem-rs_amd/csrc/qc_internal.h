@@ -245,6 +245,16 @@ struct QcTimeline {
     int pass = 0;
 };
 
+// A/B switches of the work-list planner (qc_plan.cpp; what each one does: DESIGN.md 2), with their defaults.  Read from the environment
+// once per handle, at the start of qc_build_model: the classes and every later re-shard of the handle use the same values, a test
+// that sets a variable before it creates a System is served, and no getenv runs inside a per-quartet or per-bundle loop.
+struct QcPlanSwitches {
+    bool no_bm_pp = false, no_bm_ps4 = false, no_t1_merge = false, no_bm_merge = false;
+    long bm_pp_min = 8192, mfma4_max = 1024, bm_merge_max = 262144;
+    int bm_pq = 32, bm_pp_pq = 96, bm_unit = 8, bm_pp_unit = 8, bm_gain = 0, bra_run = 0;
+    static QcPlanSwitches from_env();
+};
+
 struct qc_system {
     int natoms = 0, nshells = 0, nbasis = 0, nelec = 0;
     std::vector<int> Z;
@@ -257,6 +267,7 @@ struct qc_system {
     std::vector<double> pspack;                 // ps pairs, 8 doubles per primitive: [q, Q(3), E_0[x,y,z], E_1] (see qc_fock_bm.hip)
     std::vector<double> pairdataT;              // same blocks with the expansion stored [ab][h] (bra side of the bra-major kernels)
     std::vector<QcClass> classes;
+    QcPlanSwitches plan;
     double grad_ms[4] = {0, 0, 0, 0};         // phase times of the last gradient call (qc_gradient_timings)
     std::vector<double> pairQ;                  // Schwarz factor sqrt(max_ab (ab|ab)) of each stored pair (empty until the device pass has run)
     double imax = 0.0;                          // max pairQ^2: bound on every |(ij|kl)|
@@ -291,8 +302,9 @@ struct qc_system {
     std::string last_error;
 };
 
-// ---- host model (qc_system.cpp)
+// ---- host model (qc_system.cpp) and work-list planner (qc_plan.cpp)
 void qc_build_model(qc_system *S);
+void qc_build_classes(qc_system *S, QcLap &lap);     // the launch classes with their task lists, has_fkets, merge_t1 / merge_bm
 // (meta_only: the classes' LDS / slot sizes only, from the whole task lists - what the Schwarz pass of the device set-up needs before the
 // screened lists can exist; the lists are then built once, behind that pass, or on demand: qc_ensure_lists)
 void qc_build_shards(qc_system *S, bool meta_only = false);

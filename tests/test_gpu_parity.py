@@ -1095,7 +1095,7 @@ def _column_classes(s, n):
 
 def _valu_fket_quartets(classes):
     """Quartets of the d.d / f.p-ket column classes (LCD = 4) with a d.p ... f.f bra (LAB >= 3) in their 32-lane VALU form (LGC = 5) -
-    the lists longer than QC_MFMA4_MAX (qc_system.cpp); shorter ones run as matrix-core tiles in the 64-lane instance (LGC = 6)."""
+    the lists longer than QC_MFMA4_MAX (qc_plan.cpp); shorter ones run as matrix-core tiles in the 64-lane instance (LGC = 6)."""
     return [k for c, k in classes.items() if not c >> 12 and (c >> 8) & 15 >= 3 and (c >> 4) & 15 == 4 and c & 15 == 5]
 
 
