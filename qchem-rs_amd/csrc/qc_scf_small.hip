@@ -165,6 +165,11 @@ __device__ __forceinline__ bool qcs_qr_solve(double (&col)[13], int lane, double
 
 }  // namespace
 
+// Block plan (a block is free once the barrier behind its last reader has passed):
+//   pre     B0: F, (F D) S, F_diis, then V0    B1: D, F X    B2: S, then X = S^-1/2    B3: F D, (flat e), F' = X^T F_diis X
+//   refine  B0 / B2: the vectors and their update in turn (X^T A X where the update will go)    B3: F'
+//           B1: A X, X^T X, I + E, at the end X = S^-1/2 for post
+//   post    B1: X = S^-1/2    C = X C' in whichever of B0 / B2 C' is not in    B3: the density
 __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a) {
     extern __shared__ double lds[];
     constexpr int ld = QCS_LD, BUF = QCS_BUF;
@@ -188,12 +193,23 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
     // element loops: all of a thread's loads are requested before the first use; out-of-range elements read element 0 and are not stored
 #define QCS_EACH(q, i) _Pragma("unroll") for (int q = 0, i = rr; q < QCS_E; ++q, i += QCS_W)
 #define QCS_IN(i) (cok && (i) < n)
-#define QCS_GX(i) (QCS_IN(i) ? (i) * n + cc : 0)
+#define QCS_GX(i) (gx[q])                                                // (inside QCS_EACH(q, i) only)
+    // the sixteen offsets are formed once: re-formed at every load (two tests, a multiplication and a select each) they cost the phases
+    // that stream matrices from L2 more than the loads themselves
+    unsigned gx[QCS_E];
+    QCS_EACH(q, i) gx[q] = QCS_IN(i) ? (unsigned)(i * n + cc) : 0u;
 
-    // the padding of the four blocks (and the small arrays) is zero for the whole kernel: products run over 64 x 64 without bounds tests
-    for (int x = tid; x < 4 * BUF + 64; x += QCS_T) lds[x] = 0.0;
-    if (tid < 64) partner[tid] = -1;
-    __syncthreads();
+    // The padding of the four blocks (rows and columns >= n) and lam are zero for the whole kernel: products run over 64 x 64 without
+    // bounds tests, and nothing ever stores there.  The interior is not zeroed: every element of it is written before it is read.  Runs
+    // once, in whichever phase comes first, between that phase's requests to L2 and its stores to LDS (the barrier after those covers it).
+    auto zero_padding = [&]() {
+        for (int b = 0; b < 4; ++b) {
+            double *Bk = lds + b * BUF;
+            for (int x = n * ld + tid; x < BUF; x += QCS_T) Bk[x] = 0.0;                         // rows n .. 63
+            if (cok) for (int c = n + rr; c < ld; c += QCS_W) Bk[cc * ld + c] = 0.0;             // columns n .. 65 of row cc < n
+        }
+        if (tid < 64) { lam[tid] = 0.0; partner[tid] = -1; }
+    };
 
     if (a.phases & 1) {
         // ---- e = F D S - S D F
@@ -206,7 +222,10 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 f[q] = fsrc[x]; d[q] = a.D[x]; s[q] = a.S[x];
                 g[q] = haveF ? 0.0 : a.G[x];
             }
-            if (tid < a.maxlen * a.maxlen) Bl[tid] = a.Bmat[tid];
+            const bool hasB = tid < a.maxlen * a.maxlen;
+            const double bl = a.Bmat[hasB ? tid : 0];
+            zero_padding();
+            if (hasB) Bl[tid] = bl;
             QCS_EACH(q, i)
                 if (QCS_IN(i)) {
                     double fv = f[q];
@@ -374,9 +393,17 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
         }
         __syncthreads();
         QCS_STAMP();
+        // the refinement's start vectors are requested ahead of the product that hides them and go to B0 once that product has read it
+        const bool refine = (a.phases & 2) != 0;                         // (uniform)
+        double v0[QCS_E];
+        QCS_EACH(q, i) v0[q] = refine ? a.V0[QCS_GX(i)] : 0.0;
         qcs_gemm<false, false>(B0, B2, B1, n, n, 1.0);                   // F X
         __syncthreads();
         QCS_STAMP();
+        if (refine) {
+            QCS_EACH(q, i) if (QCS_IN(i)) B0[i * ld + cc] = v0[q];
+            if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
+        }
         qcs_gemm<true, false>(B2, B1, B3, n, n, 1.0);                    // X^T (F X)
         __syncthreads();
         QCS_STAMP();
@@ -385,16 +412,19 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
 
     if (a.phases & 2) {
         // ---- eigenvectors of F' (B3) by refinement from V0: the passes of qc_eig_refine_async (qc_eig_refine.hip) back to back
-        {
+        // (after `pre` in the same launch everything is in place: V0 in B0, F' in B3, the flags cleared, and X = S^-1/2 still in B2)
+        const bool post = (a.phases & 4) != 0;                           // (uniform)
+        double xpost[QCS_E];                                             // X of this thread's elements for `post`, held across the refinement
+        if (!(a.phases & 1)) {
             double v[QCS_E], f[QCS_E];
-            const bool loadA = !(a.phases & 1);                          // (uniform)
-            const double *__restrict__ fsrc = loadA ? a.Fp : a.V0;
-            QCS_EACH(q, i) { const int x = QCS_GX(i); v[q] = a.V0[x]; f[q] = fsrc[x]; }
-            QCS_EACH(q, i) if (QCS_IN(i)) { B0[i * ld + cc] = v[q]; if (loadA) B3[i * ld + cc] = f[q]; }
-        }
-        if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
-        __syncthreads();
+            QCS_EACH(q, i) { const int x = QCS_GX(i); v[q] = a.V0[x]; f[q] = a.Fp[x]; xpost[q] = post ? a.X[x] : 0.0; }
+            zero_padding();
+            QCS_EACH(q, i) if (QCS_IN(i)) { B0[i * ld + cc] = v[q]; B3[i * ld + cc] = f[q]; }
+            if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
+            __syncthreads();
+        } else QCS_EACH(q, i) xpost[q] = B2[min(i, 63) * ld + cc];
         QCS_STAMP();
+        int state = QC_EIG_RUNNING, last = 0, clean = 0;                 // (uniform) the decisions of a pass: every thread takes them, thread 0 files them in flg
         double *X = B0, *Xn = B2;
         for (int pass = 0; pass < a.npass; ++pass) {
             qcs_gemm<false, false>(B3, X, B1, n, n, 1.0);                // A X
@@ -406,27 +436,34 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             QCS_STAMP();
             const double *Sm = Xn, *XtX = B1;
             // statistics and decisions by the rule of qc_refine_rule.h; everything reads the zero padding instead of testing bounds
+            // Two barriers: wave results go to red (slot 1 ||R||^2, 2 max |lam|, 3 max coupling left in degenerate pairs) and every thread
+            // combines them for itself, waves in ascending order - no thread waits for a single one.
+            const int wave = qcs_wave(), lane = tid & 63;
             {
-                double part[2] = {0.0, 0.0};
-                double amax = 0.0;
+                double rsum = 0.0;
                 QCS_EACH(q, i) {
                     const int ic = min(i, 63);
-                    const bool in = QCS_IN(i), dg = ic == cc;
-                    const double sv = Sm[ic * ld + cc], r = ((in && dg) ? 1.0 : 0.0) - XtX[ic * ld + cc];
-                    part[1] = fma(r, r, part[1]);
-                    part[0] = dg ? part[0] : fma(sv, sv, part[0]);
-                    if (in && dg) { const double l = qc_ref_quotient(sv, r); lam[ic] = l; amax = fmax(amax, fabs(l)); }
+                    const double r = ((QCS_IN(i) && ic == cc) ? 1.0 : 0.0) - XtX[ic * ld + cc];
+                    rsum = fma(r, r, rsum);
                 }
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_down(amax, o, 64));
-                qcs_block_sums<2>(part, 2, red, scal);                   // scal[0] = ||off S||^2, scal[1] = ||R||^2
-                if ((tid & 63) == 0) red[tid >> 6] = amax;
+                for (int o = 32; o > 0; o >>= 1) rsum += __shfl_down(rsum, o, 64);
+                if (lane == 0) red[wave * 12 + 1] = rsum;
+                if (wave == 0) {                                         // the Rayleigh quotients: one division per lane (a maximum has no order)
+                    double amax = 0.0;
+                    if (cok) { const double l = qc_ref_quotient(Sm[cc * ld + cc], 1.0 - XtX[cc * ld + cc]); lam[cc] = l; amax = fmax(amax, fabs(l)); }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_down(amax, o, 64));
+                    if (lane == 0) red[2] = amax;
+                }
                 if (tid == 0) { flg[4] = 0; flg[5] = 0; flg[6] = 0; flg[7] = 0; }      // multi, nstrong, big update, not the last update
                 __syncthreads();
-                if (tid == 0) { double c = 0.0; for (int k = 0; k < QCS_W; ++k) c = fmax(c, red[k]); scal[2] = c; }
-                __syncthreads();
             }
-            const double scale = scal[2], tiny = QC_REF_TINY * scale, gfloor = QC_REF_GFLOOR * scale;
+            double rr2 = 0.0;                                            // ||R||^2
+#pragma unroll
+            for (int k = 0; k < QCS_W; ++k) rr2 += red[k * 12 + 1];
+            const double scale = red[2];                                 // max |lam|
+            const double tiny = QC_REF_TINY * scale, gfloor = QC_REF_GFLOOR * scale;
             {
                 double cmax = 0.0;
                 int big = 0, notlast = 0;                                // some regular pair has |a| > QC_REF_BIG g / > QC_REF_LAST g (update size, no division)
@@ -464,25 +501,28 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 for (int o = 32; o > 0; o >>= 1) cmax = fmax(cmax, __shfl_down(cmax, o, 64));
                 if (big) flg[6] = 1;
                 if (notlast) flg[7] = 1;
+                if (lane == 0) red[wave * 12 + 3] = cmax;
                 __syncthreads();
-                if ((tid & 63) == 0) red[tid >> 6] = cmax;
-                if (tid < n && qc_ref_not_mutual(partner, tid)) flg[4] = 1;
-                __syncthreads();
-                if (tid == 0) {
-                    double ca = 0.0;
-                    for (int k = 0; k < QCS_W; ++k) ca = fmax(ca, red[k]);
-                    const double orth = sqrt(scal[1]), scl = fmax(scale, QC_REF_SCALE_FLOOR);
-                    const int multi = flg[4];
-                    if (QC_REF_ROTATE(flg[6], orth, multi)) flg[QC_EIG_STATE] = QC_EIG_ROTATE;
-                    else {
-                        flg[QC_EIG_LAST] = QC_REF_IS_LAST(flg[7], orth, flg[5]) ? 1 : 0;
-                        flg[QC_EIG_CLEAN] = QC_REF_IS_CLEAN(ca, scl) ? 1 : 0;
-                    }
+                // (n <= 64: the lanes of every wave cover the indices, so each wave finds the non-mutual pairs for itself)
+                const bool notmutual = lane < n && qc_ref_not_mutual(partner, lane);
+                const int multi = (flg[4] != 0 || __ballot(notmutual) != 0) ? 1 : 0;
+                double ca = 0.0;
+#pragma unroll
+                for (int k = 0; k < QCS_W; ++k) ca = fmax(ca, red[k * 12 + 3]);
+                const double orth = sqrt(rr2), scl = fmax(scale, QC_REF_SCALE_FLOOR);
+                if (QC_REF_ROTATE(flg[6], orth, multi)) state = QC_EIG_ROTATE;
+                else {
+                    last = QC_REF_IS_LAST(flg[7], orth, flg[5]) ? 1 : 0;
+                    clean = QC_REF_IS_CLEAN(ca, scl) ? 1 : 0;
                 }
-                __syncthreads();
+                if (tid == 0) {
+                    if (state == QC_EIG_ROTATE) flg[QC_EIG_STATE] = QC_EIG_ROTATE;
+                    else { flg[QC_EIG_LAST] = last; flg[QC_EIG_CLEAN] = clean; }
+                }
+                state = __builtin_amdgcn_readfirstlane(state); last = __builtin_amdgcn_readfirstlane(last); clean = __builtin_amdgcn_readfirstlane(clean);
             }
             QCS_STAMP();
-            if (flg[QC_EIG_STATE] != QC_EIG_RUNNING) break;
+            if (state != QC_EIG_RUNNING) break;
             // M = I + E with exact rotations on the strong pairs, into B1 in place of X^T X
             {
                 double mv[QCS_E];
@@ -512,35 +552,33 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             __syncthreads();
             QCS_STAMP();
             if (tid == 0) flg[QC_EIG_PASSES] += 1;                                   // passes used
-            if (flg[QC_EIG_LAST] && flg[QC_EIG_CLEAN]) {                                      // final vectors: ascending eigenvalues, columns alongside
-                if (tid < n) {
-                    const double wi = lam[tid];
+            if (last && clean) {                                         // final vectors: ascending eigenvalues, columns alongside
+                {   // the rank of index tid / 4 is a count: four threads take sixteen candidates each
+                    const int idx = tid >> 2, j0 = 16 * (tid & 3);
+                    const double wi = lam[idx];
                     int r = 0;
-                    for (int j = 0; j < n; ++j) r += QC_REF_BEFORE(lam, j, wi, tid) ? 1 : 0;
-                    rank_s[tid] = r;
-                    a.w_out[r] = wi;
+                    for (int j = j0; j < j0 + 16; ++j) r += (j < n && QC_REF_BEFORE(lam, j, wi, idx)) ? 1 : 0;
+                    r += __shfl_xor(r, 1, 64);
+                    r += __shfl_xor(r, 2, 64);
+                    if ((tid & 3) == 0 && idx < n) { rank_s[idx] = r; a.w_out[r] = wi; }
                 }
                 __syncthreads();
                 const int rc = cok ? rank_s[cc] : 0;
                 QCS_EACH(q, i) if (QCS_IN(i)) X[i * ld + rc] = Xn[i * ld + cc];
-                if (tid == 0) flg[QC_EIG_STATE] = QC_EIG_DONE;
-                __syncthreads();
+                state = QC_EIG_DONE;
                 break;
             }
-            if (flg[QC_EIG_LAST] || pass == a.npass - 1) {                         // coupling inside a degenerate cluster, or passes exhausted
-                __syncthreads();
-                if (tid == 0) flg[QC_EIG_STATE] = QC_EIG_ROTATE;
-                __syncthreads();
-                break;
-            }
+            if (last || pass == a.npass - 1) { state = QC_EIG_ROTATE; break; }      // coupling inside a degenerate cluster, or passes exhausted
             double *t = X; X = Xn; Xn = t;
-            __syncthreads();
         }
+        ok = state == QC_EIG_DONE;
+        if (tid == 0) flg[QC_EIG_STATE] = state;
+        __syncthreads();
         if (tid < QC_CTL_EIG_STRIDE) a.ctl[tid] = flg[tid];
-        ok = flg[QC_EIG_STATE] == QC_EIG_DONE;
         if (ok) {
             QCS_EACH(q, i) if (QCS_IN(i)) a.Cp_out[i * n + cc] = X[i * ld + cc];
             Cpv = X;
+            if (post) QCS_EACH(q, i) if (QCS_IN(i)) B1[i * ld + cc] = xpost[q];   // X = S^-1/2 for C = X C' (B1 is free once the last update is formed)
         }
         __syncthreads();
         QCS_STAMP();
@@ -550,19 +588,18 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
         // ---- C = X C', D = dfac C_occ C_occ^T, energy, rms
         double h[QCS_E], g[QCS_E];                                       // H and G of this thread's elements: requested now, used at the end
         double dold = 0.0;
-        {
+        if (!(a.phases & 2)) {                                           // (after the refinement in the same launch X is in B1 already)
             double xv[QCS_E], cp[QCS_E];
-            const bool loadC = !(a.phases & 2);                          // (uniform)
-            const double *__restrict__ csrc = loadC ? a.Cp_in : a.X;
-            QCS_EACH(q, i) {
-                const int x = QCS_GX(i);
-                xv[q] = a.X[x]; cp[q] = csrc[x];
-                h[q] = a.H[x]; g[q] = a.G[x];
-            }
+            QCS_EACH(q, i) { const int x = QCS_GX(i); xv[q] = a.X[x]; cp[q] = a.Cp_in[x]; }
+            QCS_EACH(q, i) { const int x = QCS_GX(i); h[q] = a.H[x]; g[q] = a.G[x]; }
             dold = a.Dold[tid < n ? tid * n + tid : 0];
-            QCS_EACH(q, i) if (QCS_IN(i)) { B1[i * ld + cc] = xv[q]; if (loadC) B0[i * ld + cc] = cp[q]; }
+            zero_padding();
+            QCS_EACH(q, i) if (QCS_IN(i)) { B1[i * ld + cc] = xv[q]; B0[i * ld + cc] = cp[q]; }
+            __syncthreads();
+        } else {
+            QCS_EACH(q, i) { const int x = QCS_GX(i); h[q] = a.H[x]; g[q] = a.G[x]; }
+            dold = a.Dold[tid < n ? tid * n + tid : 0];
         }
-        __syncthreads();
         QCS_STAMP();
         double *const Cm = Cpv == B2 ? B0 : B2;                          // (the block the eigenvectors are not in)
         qcs_gemm<false, false>(B1, Cpv, Cm, n, n, 1.0);                  // C
