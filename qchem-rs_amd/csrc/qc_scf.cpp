@@ -155,105 +155,42 @@ EigRoute eig_route(const ScfWork &W, int spin, int n) {
     return W.have_prev[spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold;
 }
 
-// One spin's Roothaan step, enqueued without any host synchronisation: F = H + G; e = FDS - SDF; DIIS; F' = X^T F X;
-// eigenvectors (eig_route); C = X C'   (rhf.rs:70-76).  New vectors go to CpNew[spin], C to dC.
-// (`st`, `b`: the stream the step is enqueued on and its set of work buffers - the two spins of a UHF pass are independent until their
-// scalars meet and run side by side, scf_iterate)
-int roothaan_enqueue(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG, const double *dD, double *dw_out, double *dC, int spin,
-                     double *dE, double *dF, bool have_F, hipStream_t st, int b) {
-    const int n = S->nbasis;
-    QcEigWork &E = W.eig[b];
-    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin, *const notconv = W.ctl.p + QC_CTL_NOTCONV;
-    if (!have_F) qc_axpby(st, n, 1.0, W.H.p, 1.0, dG, dF);                               // F (else written by the build's closing kernel)
-    qc_gemm(st, n, n, n, 1.0, dF, n, false, dD, n, false, 0.0, E.t2.p, n);                  // F D
-    qc_gemm(st, n, n, n, 1.0, E.t2.p, n, false, W.S.p, n, false, 0.0, W.Fp[b].p, n);        // F D S
-    qc_sub_transpose(st, n, W.Fp[b].p, dE);                                                 // e = FDS - (FDS)^T = FDS - SDF
-    int rc = diis.extrapolate(st, W.Fd[b].p, W.ctl.p + QC_CTL_DIIS);
-    if (rc != QC_OK) return rc;
-    qc_gemm(st, n, n, n, 1.0, W.Fd[b].p, n, false, W.X.p, n, false, 0.0, E.t1.p, n);        // F X
-    qc_gemm(st, n, n, n, 1.0, W.X.p, n, true, E.t1.p, n, false, 0.0, Fps, n);               // X^T (F X)
-    const EigRoute route = eig_route(W, spin, n);
-    W.cold[spin] = route == EigRoute::Tridiag;
-    switch (route) {
-    case EigRoute::Refine: rc = qc_eig_refine_async(st, n, Fps, CpPrev, CpNew, dw_out, E, ctl, W.npass[spin]); break;
-    // (three refinement passes are enqueued: two finish most starts - the third is then five empty launches - but near-degenerate
-    // clusters of a nearly converged benzene need it, and running out of passes costs a Jacobi eigensolve)
-    case EigRoute::Tridiag: rc = qc_eig_cold_async(st, n, Fps, CpNew, dw_out, E, ctl, 3); break;
-    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
-    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); break;     // sorted_eigs (rhf.rs:75)
+// Times of the passes.  Events of a pass (start | build done | pass done), two sets used alternately: a pass whose end the host saw through
+// the pinned sequence word reads none of them before it returns - the last event may still be in flight, and asking costs host time
+// between two passes.  The next pass asks (flush), after its own build has been issued.
+struct PassTiming {
+    struct Build { bool tuned; unsigned gen; };   // the build contained a tuner run; it ran under this stream assignment (qc_system::assign_gen)
+    hipEvent_t evs[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    int cur = 0, pending_set = 0;
+    bool pending = false;                      // the pass of set `pending_set` has ended and its event times have not been read yet
+    Build cur_build = {false, 0}, pend_build = {false, 0};
+    double ms_fock = 0, ms_linalg = 0, ms_tuner = 0;
+    int64_t builds_timed = 0;
+    ~PassTiming() { for (auto &set : evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e); }
+    int create() {
+        for (auto &set : evs) for (hipEvent_t &e : set) QC_HIP_CHECK(hipEventCreate(&e));
+        return QC_OK;
     }
-    if (rc != QC_OK) return rc;
-    qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, CpNew, n, false, 0.0, dC, n);   // C = X C'
-    return QC_OK;
-}
-
-// The same step for n <= QC_SMALL_MAXN, density / energy / rms of rhf.rs:78-88 included: one launch when the eigensolve is a refinement from
-// the previous vectors, pre | tridiagonal start | refine + post when it starts cold, pre | Jacobi kernel | post for the rotation-only runs.
-struct SmallTail { int nocc; double dfac; double *Dn; const double *Dold; double *scal_out; int *ctl_all, *ctl_out; double *fxs_out; unsigned *seq_out = nullptr; unsigned seq = 0; };
-int roothaan_small(qc_system *S, ScfWork &W, DeviceDiis &diis, const double *dG, const double *dD, double *dw_out, double *dC, int spin,
-                   double *dE, double *dF, bool have_F, const SmallTail &tl, hipStream_t st_in = nullptr, int b = 0) {
-    const int n = S->nbasis;
-    hipStream_t st = st_in ? st_in : S->stream;               // (`st_in`, `b`: the beta step of a spin-parallel pass - side stream, second set of work buffers)
-    QcSmallArgs a{};
-    a.n = n;
-    a.F = have_F ? dF : nullptr; a.F_out = dF;
-    a.D = dD; a.S = W.S.p; a.X = W.X.p; a.H = W.H.p; a.G = dG;
-    a.E_out = dE;
-    a.m = (int)diis.slots.size(); a.minlen = diis.minlen; a.maxlen = diis.maxlen;
-    a.dots_generic = W.rotations_only ? 1 : 0;
-    for (int j = 0; j < a.m; ++j) { a.slot[j] = diis.slots[j]; a.errs[j] = diis.pool[2 * diis.slots[j]].p; a.focks[j] = diis.pool[2 * diis.slots[j] + 1].p; }
-    a.Bmat = diis.d_B.p; a.c_out = diis.d_c.p; a.diis_flag = W.ctl.p + QC_CTL_DIIS;
-    a.Fp = W.Fps[spin].p;
-    a.ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * spin;
-    a.Cp_out = W.CpNew[spin].p; a.w_out = dw_out; a.C_out = dC; a.Dn = tl.Dn; a.Dold = tl.Dold; a.nocc = tl.nocc; a.dfac = tl.dfac;
-    a.scal_out = tl.scal_out; a.ctl_all = tl.ctl_all; a.ctl_out = tl.ctl_out; a.fxs_out = tl.fxs_out; a.imax = S->imax;
-    a.seq_out = tl.seq_out; a.seq = tl.seq;
-    a.tl = S->tl.cur ? S->tl.cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
-    QcEigWork &E = W.eig[b];
-    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const notconv = W.ctl.p + QC_CTL_NOTCONV;
-    const EigRoute route = eig_route(W, spin, n);
-    W.cold[spin] = route == EigRoute::Tridiag;
-    int rc = QC_OK;
-    if (route != EigRoute::Refine) {
-        QcSmallArgs pre = a;
-        pre.phases = 1; pre.ctl_all = nullptr; pre.seq_out = nullptr;
-        if (a.tl) a.tl += QC_TL_W;                              // (the second launch of the pass has its own slot)
-        if ((rc = qc_scf_small_launch(st, pre)) != QC_OK) return rc;
+    hipEvent_t *begin_pass() { cur ^= 1; return evs[cur]; }
+    // (`t_start`: the host's clock before the build was issued - the time of a build with a tuner run in it is the tuner's)
+    void build_issued(bool tuned, double t_start, unsigned gen) { cur_build = {tuned, gen}; if (tuned) ms_tuner += qc_now_ms() - t_start; }
+    void pass_seen() { pending = true; pending_set = cur; pend_build = cur_build; }
+    void repeat_seen() { float ms = 0; (void)hipEventElapsedTime(&ms, evs[cur][1], evs[cur][2]); ms_linalg += ms; }
+    // (`tuner`: the handle whose stream tuner takes the build time as a sample, null for builds it does not assign)
+    void flush(qc_system *tuner) {
+        if (!pending) return;
+        pending = false;
+        hipEvent_t *e = evs[pending_set];
+        float ms_f = 0, ms_l = 0;
+        if (hipEventSynchronize(e[2]) != hipSuccess) return;
+        const bool have_f = hipEventElapsedTime(&ms_f, e[0], e[1]) == hipSuccess;
+        if (hipEventElapsedTime(&ms_l, e[1], e[2]) == hipSuccess) ms_linalg += ms_l;
+        // (a build that contained a tuner run is not a sample of the build time: neither for the totals nor for the tuner's online choice)
+        if (!have_f || pend_build.tuned) return;
+        ms_fock += ms_f; builds_timed += 1;
+        if (tuner) qc_fock_feedback(tuner, ms_f, pend_build.gen);
     }
-    switch (route) {
-    case EigRoute::Refine: a.phases = 7; a.V0 = CpPrev; a.npass = W.npass[spin]; break;
-    case EigRoute::Tridiag: rc = qc_eig_tridiag_start(st, n, Fps, E); a.phases = 6; a.V0 = E.x0.p; a.npass = 3; break;
-    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); a.phases = 4; a.Cp_in = CpNew; break;
-    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); a.phases = 4; a.Cp_in = CpNew; break;
-    }
-    if (rc != QC_OK) return rc;
-    return qc_scf_small_launch(st, a);
-}
-
-// The rare repeat of a spin's eigensolve when the route that reports through the control words asked for rotations (QC_EIG_ROTATE).
-// After Tridiag (the start was not good enough): the Jacobi routes.  After Refine (not perturbative after all): the synchronous forms
-// of Tridiag (its own fallback: the Jacobi kernels) or, for the rotation-only runs, of Refine (rotations in the basis of the previous vectors).
-int roothaan_redo_eig(qc_system *S, ScfWork &W, double *dw_out, double *dC, int spin) {
-    const int n = S->nbasis;
-    hipStream_t st = S->stream;
-    QcEigWork &E = W.eig[0];
-    double *const Fps = W.Fps[spin].p, *const CpPrev = W.CpPrev[spin].p, *const CpNew = W.CpNew[spin].p;
-    int *const notconv = W.ctl.p + QC_CTL_NOTCONV;
-    const EigRoute again = W.cold[spin] ? (W.have_prev[spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold)
-                                        : (W.rotations_only ? EigRoute::Refine : EigRoute::Tridiag);
-    int rc = QC_OK;
-    switch (again) {
-    case EigRoute::JacobiWarm: rc = qc_eig_device_warm(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
-    case EigRoute::JacobiCold: rc = qc_eig_device(st, n, Fps, CpNew, dw_out, E, notconv); break;
-    case EigRoute::Refine: rc = qc_eig_device_refine(st, n, Fps, CpPrev, CpNew, dw_out, E, notconv); break;
-    case EigRoute::Tridiag: rc = qc_eig_cold_sync(st, n, Fps, CpNew, dw_out, E, W.ctl.p + QC_CTL_SETUP, notconv); break;
-    }
-    if (rc != QC_OK) return rc;
-    qc_gemm(st, n, n, n, 1.0, W.X.p, n, false, CpNew, n, false, 0.0, dC, n);
-    return QC_OK;
-}
+};
 
 }  // namespace
 
@@ -265,31 +202,23 @@ struct qc_scf_state {
     int nocc[2] = {0, 0};
     ScfWork W;
     DevBuf D[2], Dn[2], G, Cs, ws;             // densities are double-buffered per spin: D <-> Dn swap when a pass is accepted
-    int64_t builds_timed = 0, passes = 0, redos = 0;
+    int64_t passes = 0, redos = 0;
     bool spin_parallel = getenv("QC_NO_SPIN_PARALLEL") == nullptr;      // (A/B switch, read per SCF state)
     double warm_rms_env = getenv("QC_EIG_WARM_RMS") ? atof(getenv("QC_EIG_WARM_RMS")) : 0.0;   // (read per SCF state: tests reach the repeat branch with it)
-    double ms_tuner = 0;
-    bool cur_build_tuned = false, pend_build_tuned = false;   // the build of the current / the pending timing set contained a tuner run
-    unsigned cur_build_gen = 0, pend_build_gen = 0;           // ... and ran under this stream assignment (qc_system::assign_gen)
     DevBuf T4, TK, Dtot;                       // stored mode: RHF T = I - I^x / 2; UHF I and its exchange-permuted copy
     bool stored = false;
     int twin = -1;                             // UHF spin-twin decision, taken at the first build
-    double ms_tensor = 0;
+    double ms_tensor = 0, ms_setup = 0;
     DeviceDiis *diis[2] = {nullptr, nullptr};
-    // timing events of a pass (start | build done | pass done), two sets used alternately: a pass whose end the host saw through the pinned
-    // sequence word reads none of them before it returns - the next pass does, after its own build has been issued
-    hipEvent_t evs[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    int ev_cur = 0, pending_set = 0;
-    double ms_fock = 0, ms_linalg = 0, ms_setup = 0;
+    PassTiming tm;
     unsigned pass_seq = 0;                     // sequence number of the last pass whose end the host saw through the pinned word
     bool event_wait = getenv("QC_EVENT_WAIT") != nullptr;      // (A/B switch, read per SCF state: the stream's event instead)
-    bool timing_pending = false;               // ... and whose event times (set `pending_set`) have not been read yet
     ~qc_scf_state() {
         if (S && S->prep.owner == this) { S->prep.prepared = false; S->prep.owner = nullptr; }
         delete diis[0]; delete diis[1];
         if (S && S->stream) { (void)hipStreamSynchronize(S->stream); qc_gate_quiet(S); qc_tl_dump(S); }
-        for (auto &set : evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
     }
+    qc_system *tuner() const { return !stored && !S->comm ? S : nullptr; }   // (for PassTiming::flush)
 };
 static void scf_state_delete(qc_scf_state *st) {
     if (!st) return;
@@ -297,6 +226,190 @@ static void scf_state_delete(qc_scf_state *st) {
     delete st;
     if (S && --S->live_states == 0 && S->zombie) qc_system_free(S);
 }
+
+namespace {
+
+// The shape of a pass, decided once before anything is enqueued.
+struct PassPlan {
+    bool fused;                // the one-workgroup kernels (qc_scf_small.hip) instead of the generic launch sequence
+    // UHF: the two spins' steps are independent (uhf.rs:84-135 runs them one after the other) - the beta step goes to a side stream on
+    // another dispatch pipe, with the second set of work buffers, behind an event of the build's closing kernel, and meets the handle's
+    // stream again before the scalars (device-side join).  Same kernels, same arithmetic, per spin: results are bit for bit those of the
+    // serial order (QC_NO_SPIN_PARALLEL).  On the one-workgroup path the kernel that joins the streams on the device also hands the control
+    // words over and stores the sequence word (qc_spin_join_end); not with a communicator.
+    bool side_by_side;
+    // Multi-rank runs take every decision (convergence, DIIS failure, eigensolve mode, repeat) from the SAME numbers on every
+    // rank: the pass scalars go to device memory, are all-reduced as bit patterns (max) together with their complements - so a
+    // rank whose copy differs is noticed (max(x) != ~max(~x)) - and only then reach the host.  The replicated linear algebra is
+    // deterministic and starts from bit-identical G (integer all-reduce), so the copies agree; this makes a divergence an
+    // error on all ranks in the same pass instead of a hang in the next all-reduce.
+    bool multi;
+    bool clear_sync_slot;      // multi-rank RHF: the unused spin slot of d_sync is cleared in every pass
+    // Single-rank runs on the one-workgroup path: the kernel that ends the pass stores the pass's sequence number into pinned memory
+    // after the scalars and control words, and the host polls THAT instead of the event behind it (a few microseconds earlier per pass).
+    bool seq_wait;
+    unsigned *h_seq; unsigned seq;
+    // (RHF, direct fixed-point builds on the one-workgroup path: the kernel that forms the new density also leaves the next build's fixed-point unit)
+    bool scale_in_kernel;
+    double *scal_out;          // where the kernels put energy and rms: pinned host memory, or (multi-rank) d_sync
+    int *ctl_out, *h_ctl;      // ... and the control words; where the host reads them
+};
+PassPlan plan_pass(const qc_scf_state *st) {
+    const qc_system *S = st->S;
+    const ScfWork &W = st->W;
+    PassPlan p{};
+    p.fused = W.small_fused;
+    p.multi = S->comm != nullptr;
+    p.side_by_side = st->uhf && st->spin_parallel && S->lanes.nlanes >= 2 && !S->join.by_events && !(p.fused && p.multi);
+    p.clear_sync_slot = p.multi && !st->uhf;
+    p.seq_wait = p.fused && !p.multi && !st->event_wait;
+    p.h_seq = reinterpret_cast<unsigned *>(W.h_scal + 2 * QC_SYNC_WORDS); p.seq = st->pass_seq + 1;
+    p.scale_in_kernel = p.fused && !st->uhf && !st->stored && S->accum_fx;
+    p.h_ctl = reinterpret_cast<int *>(W.h_scal + 4);
+    p.scal_out = p.multi ? reinterpret_cast<double *>(W.d_sync.p) : W.h_scal;
+    p.ctl_out = p.multi ? reinterpret_cast<int *>(W.d_sync.p + 4) : p.h_ctl;
+    return p;
+}
+
+// What one spin's part of a pass works on, built once per pass.
+struct SpinStep {
+    int spin;
+    hipStream_t st; int b;     // the stream the step is enqueued on and its set of work buffers (side by side: beta on the side stream, set 1)
+    int nocc; double dfac;     // D = dfac * C_occ C_occ^T
+    const double *G, *D;       // this pass's G and the density it was built from
+    double *Dn, *w, *C;        // new density, orbital energies, C
+    double *E, *F;             // this pass's DIIS sample buffers (error, Fock matrix)
+    DeviceDiis *diis;
+    bool dens_done;            // Dn was formed on the side stream already (generic sequence, side by side)
+    double *scal_out;          // the spin's two pass scalars
+};
+// (claims the spin's DIIS sample slot of the pass)
+SpinStep spin_step(qc_scf_state *st, const PassPlan &plan, int s) {
+    const size_t n = st->S->nbasis, nn = n * n;
+    SpinStep p{};
+    p.spin = s; p.st = st->S->stream; p.b = 0;
+    p.nocc = st->nocc[s]; p.dfac = st->uhf ? 1.0 : 2.0;
+    p.G = st->G.p + s * nn; p.D = st->D[s].p; p.Dn = st->Dn[s].p; p.w = st->ws.p + s * n; p.C = st->Cs.p + s * nn;
+    p.diis = st->diis[s]; p.scal_out = plan.scal_out + 2 * s;
+    p.diis->next_sample(&p.E, &p.F);
+    return p;
+}
+
+// enqueues the eigensolve of the spin's F' (W.Fps) by `route`: vectors to W.CpNew, eigenvalues to p.w.  (`again`: the repeat of a
+// pass's eigensolve - Refine and Tridiag in their synchronous forms, which report through QC_CTL_NOTCONV like the Jacobi routes)
+int eig_enqueue(ScfWork &W, const SpinStep &p, EigRoute route, bool again) {
+    const int n = W.n;
+    QcEigWork &E = W.eig[p.b];
+    double *const Fps = W.Fps[p.spin].p, *const CpPrev = W.CpPrev[p.spin].p, *const CpNew = W.CpNew[p.spin].p;
+    int *const ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * p.spin, *const notconv = W.ctl.p + QC_CTL_NOTCONV;
+    switch (route) {
+    case EigRoute::Refine:
+        return again ? qc_eig_device_refine(p.st, n, Fps, CpPrev, CpNew, p.w, E, notconv)
+                     : qc_eig_refine_async(p.st, n, Fps, CpPrev, CpNew, p.w, E, ctl, W.npass[p.spin]);
+    // (three refinement passes are enqueued: two finish most starts - the third is then five empty launches - but near-degenerate
+    // clusters of a nearly converged benzene need it, and running out of passes costs a Jacobi eigensolve)
+    case EigRoute::Tridiag:
+        return again ? qc_eig_cold_sync(p.st, n, Fps, CpNew, p.w, E, W.ctl.p + QC_CTL_SETUP, notconv)
+                     : qc_eig_cold_async(p.st, n, Fps, CpNew, p.w, E, ctl, 3);
+    case EigRoute::JacobiWarm: return qc_eig_device_warm(p.st, n, Fps, CpPrev, CpNew, p.w, E, notconv);
+    case EigRoute::JacobiCold: return qc_eig_device(p.st, n, Fps, CpNew, p.w, E, notconv);     // sorted_eigs (rhf.rs:75)
+    }
+    return QC_ERR_INVALID;
+}
+// ... followed by C = X C'
+int eig_and_coefficients(ScfWork &W, const SpinStep &p, EigRoute route, bool again) {
+    const int n = W.n;
+    const int rc = eig_enqueue(W, p, route, again);
+    if (rc != QC_OK) return rc;
+    qc_gemm(p.st, n, n, n, 1.0, W.X.p, n, false, W.CpNew[p.spin].p, n, false, 0.0, p.C, n);   // C = X C'
+    return QC_OK;
+}
+
+// One spin's Roothaan step, enqueued without any host synchronisation: F = H + G; e = FDS - SDF; DIIS; F' = X^T F X;
+// eigenvectors (eig_route); C = X C'   (rhf.rs:70-76).  New vectors go to CpNew[spin], C to p.C.
+int roothaan_enqueue(ScfWork &W, const SpinStep &p, bool have_F) {
+    const int n = W.n, b = p.b;
+    hipStream_t st = p.st;
+    QcEigWork &E = W.eig[b];
+    if (!have_F) qc_axpby(st, n, 1.0, W.H.p, 1.0, p.G, p.F);                                // F (else written by the build's closing kernel)
+    qc_gemm(st, n, n, n, 1.0, p.F, n, false, p.D, n, false, 0.0, E.t2.p, n);                // F D
+    qc_gemm(st, n, n, n, 1.0, E.t2.p, n, false, W.S.p, n, false, 0.0, W.Fp[b].p, n);        // F D S
+    qc_sub_transpose(st, n, W.Fp[b].p, p.E);                                                // e = FDS - (FDS)^T = FDS - SDF
+    const int rc = p.diis->extrapolate(st, W.Fd[b].p, W.ctl.p + QC_CTL_DIIS);
+    if (rc != QC_OK) return rc;
+    qc_gemm(st, n, n, n, 1.0, W.Fd[b].p, n, false, W.X.p, n, false, 0.0, E.t1.p, n);        // F X
+    qc_gemm(st, n, n, n, 1.0, W.X.p, n, true, E.t1.p, n, false, 0.0, W.Fps[p.spin].p, n);   // X^T (F X)
+    const EigRoute route = eig_route(W, p.spin, n);
+    W.cold[p.spin] = route == EigRoute::Tridiag;
+    return eig_and_coefficients(W, p, route, false);
+}
+
+// The same step for n <= QC_SMALL_MAXN, density / energy / rms of rhf.rs:78-88 included: one launch when the eigensolve is a refinement from
+// the previous vectors, pre | tridiagonal start | refine + post when it starts cold, pre | Jacobi kernel | post for the rotation-only runs.
+// (`ends_pass`: this spin's last launch also hands the control words over, clears them and - plan.seq_wait - stores the sequence word)
+int roothaan_small(qc_system *S, ScfWork &W, const PassPlan &plan, const SpinStep &p, bool have_F, bool ends_pass) {
+    const int n = W.n;
+    const DeviceDiis &diis = *p.diis;
+    QcSmallArgs a{};
+    a.n = n;
+    a.F = have_F ? p.F : nullptr; a.F_out = p.F;
+    a.D = p.D; a.S = W.S.p; a.X = W.X.p; a.H = W.H.p; a.G = p.G;
+    a.E_out = p.E;
+    a.m = (int)diis.slots.size(); a.minlen = diis.minlen; a.maxlen = diis.maxlen;
+    a.dots_generic = W.rotations_only ? 1 : 0;
+    for (int j = 0; j < a.m; ++j) { a.slot[j] = diis.slots[j]; a.errs[j] = diis.pool[2 * diis.slots[j]].p; a.focks[j] = diis.pool[2 * diis.slots[j] + 1].p; }
+    a.Bmat = diis.d_B.p; a.c_out = diis.d_c.p; a.diis_flag = W.ctl.p + QC_CTL_DIIS;
+    a.Fp = W.Fps[p.spin].p;
+    a.ctl = W.ctl.p + QC_CTL_EIG + QC_CTL_EIG_STRIDE * p.spin;
+    a.Cp_out = W.CpNew[p.spin].p; a.w_out = p.w; a.C_out = p.C; a.Dn = p.Dn; a.Dold = p.D; a.nocc = p.nocc; a.dfac = p.dfac;
+    a.scal_out = p.scal_out; a.ctl_all = ends_pass ? W.ctl.p : nullptr; a.ctl_out = plan.ctl_out; a.imax = S->imax;
+    a.fxs_out = plan.scale_in_kernel ? S->dev.d_fxs.p : nullptr;
+    if (ends_pass && plan.seq_wait) { a.seq_out = plan.h_seq; a.seq = plan.seq; }
+    a.tl = S->tl.cur ? S->tl.cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
+    const EigRoute route = eig_route(W, p.spin, n);
+    W.cold[p.spin] = route == EigRoute::Tridiag;
+    int rc = QC_OK;
+    if (route != EigRoute::Refine) {
+        QcSmallArgs pre = a;
+        pre.phases = 1; pre.ctl_all = nullptr; pre.seq_out = nullptr;
+        if (a.tl) a.tl += QC_TL_W;                              // (the second launch of the pass has its own slot)
+        if ((rc = qc_scf_small_launch(p.st, pre)) != QC_OK) return rc;
+    }
+    switch (route) {
+    case EigRoute::Refine: a.phases = 7; a.V0 = W.CpPrev[p.spin].p; a.npass = W.npass[p.spin]; break;
+    case EigRoute::Tridiag: rc = qc_eig_tridiag_start(p.st, n, a.Fp, W.eig[p.b]); a.phases = 6; a.V0 = W.eig[p.b].x0.p; a.npass = 3; break;
+    case EigRoute::JacobiWarm:
+    case EigRoute::JacobiCold: rc = eig_enqueue(W, p, route, false); a.phases = 4; a.Cp_in = a.Cp_out; break;
+    }
+    if (rc != QC_OK) return rc;
+    return qc_scf_small_launch(p.st, a);
+}
+
+// The rare repeat of a spin's eigensolve when the route that reports through the control words asked for rotations (QC_EIG_ROTATE).
+// After Tridiag (the start was not good enough): the Jacobi routes.  After Refine (not perturbative after all): the synchronous forms
+// of Tridiag (its own fallback: the Jacobi kernels) or, for the rotation-only runs, of Refine (rotations in the basis of the previous vectors).
+// On the handle's stream with the first set of work buffers, whichever the spin's step used.
+int roothaan_redo_eig(qc_system *S, ScfWork &W, const SpinStep &p) {
+    SpinStep r = p;
+    r.st = S->stream; r.b = 0;
+    const EigRoute again = W.cold[p.spin] ? (W.have_prev[p.spin] ? EigRoute::JacobiWarm : EigRoute::JacobiCold)
+                                          : (W.rotations_only ? EigRoute::Refine : EigRoute::Tridiag);
+    return eig_and_coefficients(W, r, again, true);
+}
+
+// enqueues, on the handle's stream: the spin's new density - unless the side stream formed it, once: a repeat of the eigensolve forms it
+// again, here - and its energy and rms straight into the plan's scalars; `hand_over`: the kernel also hands over and clears the control words
+int density_and_scalars(qc_system *S, ScfWork &W, const PassPlan &plan, SpinStep &p, bool hand_over) {
+    const int n = W.n;
+    hipStream_t sm = S->stream;
+    if (p.dens_done) p.dens_done = false;
+    else if (p.nocc > 0) qc_gemm(sm, n, n, p.nocc, p.dfac, p.C, n, false, p.C, n, true, 0.0, p.Dn, n);
+    else QC_HIP_CHECK(hipMemsetAsync(p.Dn, 0, (size_t)n * n * sizeof(double), sm));
+    qc_energy_rms(sm, n, p.Dn, p.D, W.H.p, p.G, p.scal_out, hand_over ? W.ctl.p : nullptr, plan.ctl_out);
+    return QC_OK;
+}
+
+}  // namespace
 
 // (hDa / hDb non-null: the caller's densities, host, in place of the Hueckel guess - qc_scf_begin_*_from)
 static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out, const double *hDa = nullptr, const double *hDb = nullptr) {
@@ -369,7 +482,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
         st->diis[s] = uhf ? new DeviceDiis(2, 8, n) : new DeviceDiis(4, 6, n);
         if ((rc = st->diis[s]->init()) != QC_OK) return rc;
     }
-    for (auto &set : st->evs) for (hipEvent_t &e : set) QC_HIP_CHECK(hipEventCreate(&e));
+    if ((rc = st->tm.create()) != QC_OK) return rc;
     int eig_flag = 0;                                                     // the eigensolves of X and of the Hueckel guess
     QC_HIP_CHECK(hipMemcpyAsync(&eig_flag, st->W.ctl.p + QC_CTL_NOTCONV, sizeof(int), hipMemcpyDeviceToHost, S->stream));
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
@@ -379,263 +492,195 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     return QC_OK;
 }
 
-// (a pass whose end the host saw through the pinned sequence word has not read its event times yet: the last event may still have been
-// in flight, and asking costs host time between two passes.  The next pass asks once its own build is out.)
-static void scf_flush_timing(qc_scf_state *st) {
-    if (!st->timing_pending) return;
-    st->timing_pending = false;
-    hipEvent_t *e = st->evs[st->pending_set];
-    float ms_f = 0, ms_l = 0;
-    if (hipEventSynchronize(e[2]) != hipSuccess) return;
-    const bool have_f = hipEventElapsedTime(&ms_f, e[0], e[1]) == hipSuccess;
-    if (hipEventElapsedTime(&ms_l, e[1], e[2]) == hipSuccess) st->ms_linalg += ms_l;
-    if (!have_f) return;
-    // (a build that contained a tuner run is not a sample of the build time: neither for the totals nor for the tuner's online choice)
-    if (st->pend_build_tuned) return;
-    st->ms_fock += ms_f; st->builds_timed += 1;
-    if (!st->stored && !st->S->comm) qc_fock_feedback(st->S, ms_f, st->pend_build_gen);
-}
-
-// Wait for an event by polling (what hipStreamSynchronize does too): a parked thread's wake-up latency is longer
-// than a whole SCF pass of a small molecule.  Not for ever: a kernel that never finishes is an error of the call, not a host core
-// pinned for good (QC_HOST_WAIT_LIMIT_S, default 120 s; the device-side waits give up earlier and say why).
-static double host_wait_limit_ms() {
-    static const double lim = getenv("QC_HOST_WAIT_LIMIT_S") ? atof(getenv("QC_HOST_WAIT_LIMIT_S")) * 1e3 : 120e3;
-    return lim;
-}
-static hipError_t wait_event(hipEvent_t ev) {
-    hipError_t e;
+// Wait for the end of a pass by polling (what hipStreamSynchronize does too): a parked thread's wake-up latency is longer than a whole
+// SCF pass of a small molecule.  `h_seq` non-null: for the pass's sequence word `want` in pinned memory, with the event behind the pass
+// as the witness of a failure (a failed launch or a fault never stores the word: the event knows); null: for the event alone.
+// Not for ever: a kernel that never finishes is an error of the call, not a host core pinned for good (QC_HOST_WAIT_LIMIT_S, default
+// 120 s; the device-side waits give up earlier and say why).
+static int wait_pass(hipEvent_t ev, const unsigned *h_seq = nullptr, unsigned want = 0) {
+    static const double limit_ms = getenv("QC_HOST_WAIT_LIMIT_S") ? atof(getenv("QC_HOST_WAIT_LIMIT_S")) * 1e3 : 120e3;
     unsigned spins = 0;
     double t0 = 0.0;
-    while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
-        if ((++spins & 0x3fff) == 0) {
+    for (;;) {
+        if (h_seq && __atomic_load_n(h_seq, __ATOMIC_ACQUIRE) == want) return QC_OK;
+        const bool look = (++spins & 0xfff) == 0;               // (now and then: the clock, and next to the word the event)
+        if (h_seq && !look) continue;
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipErrorNotReady) {
+            if (!look) continue;
             const double t = qc_now_ms();
             if (t0 == 0.0) t0 = t;
-            else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return hipErrorLaunchTimeOut; }
+            else if (t - t0 > limit_ms) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", limit_ms * 1e-3); return QC_ERR_HIP; }
+            continue;
         }
+        if (!h_seq && e == hipSuccess) return QC_OK;
+        if (!h_seq) { fprintf(stderr, "qchem_hip: the wait for the end of an SCF pass failed: %s\n", hipGetErrorString(e)); return QC_ERR_HIP; }
+        if (e != hipSuccess || __atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != want) { fprintf(stderr, "qchem_hip: the pass ended without its sequence word (%s)\n", hipGetErrorString(e)); return QC_ERR_HIP; }
     }
-    return e;
 }
 
-// one pass of the loop body.  RHF: rhf.rs:67-88.  UHF: uhf.rs:81-137 (returns the reference's `density_rms`,
-// i.e. (rms_a + rms_b) / 2, and the energy expression of uhf.rs:145-153 evaluated every pass).
-// The whole pass is enqueued without looking at the device; one synchronisation at its end returns the energy, the rms
-// and the control words (DIIS failure, eigen-refinement outcome).  Launch latency of ~50 small kernels then overlaps with
-// their execution instead of adding to it.
-static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
+// ---- one pass of the loop body, step by step (scf_iterate)
+
+// enqueues G of every spin from the *old* densities, behind the pass's first event; direct builds also write F = H + G where they can (*have_F)
+static int build_G(qc_scf_state *st, hipEvent_t ev0, const SpinStep *sp, bool *have_F) {
     qc_system *S = st->S;
     ScfWork &W = st->W;
     const int n = S->nbasis;
-    const size_t nn = (size_t)n * n;
     hipStream_t sm = S->stream;
-    const int nspin = st->uhf ? 2 : 1;
+    double *const dG = st->G.p, *const dGb = dG + (size_t)n * n;
     int rc;
-    const double th0 = qc_now_ms();
-    qc_stamp("enter pass");
-    if ((rc = qc_tl_begin_pass(S)) != QC_OK) return rc;
-    st->ev_cur ^= 1;
-    hipEvent_t *const ev = st->evs[st->ev_cur];
-    hipEvent_t const ev0 = ev[0], ev1 = ev[1], ev2 = ev[2];
-    double *const dG = st->G.p;
-    double *dE[2] = {nullptr, nullptr}, *dF[2] = {nullptr, nullptr};       // this pass's DIIS sample buffers (error, Fock matrix) per spin
-    for (int s = 0; s < nspin; ++s) st->diis[s]->next_sample(&dE[s], &dF[s]);
-    bool have_F = false;
-    // G of every spin from the *old* densities
+    QC_HIP_CHECK(hipEventRecord(ev0, sm));
     if (st->stored) {
-        QC_HIP_CHECK(hipEventRecord(ev0, sm));
         if (st->uhf) {   // uhf.rs:216-226: G_s = <I, D_s + D_s'> - <I^x, D_s>
             qc_axpby(sm, n, 1.0, st->D[0].p, 1.0, st->D[1].p, st->Dtot.p);
             qc_axpby(sm, n, -1.0, st->D[0].p, 0.0, nullptr, W.eig[0].t1.p);
             if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.eig[0].t1.p, dG)) != QC_OK) return rc;
             qc_axpby(sm, n, -1.0, st->D[1].p, 0.0, nullptr, W.eig[0].t1.p);
-            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.eig[0].t1.p, dG + nn)) != QC_OK) return rc;
+            if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->Dtot.p, st->TK.p, W.eig[0].t1.p, dGb)) != QC_OK) return rc;
         } else {
             if ((rc = qc_tensor_gemv(sm, n, st->T4.p, st->D[0].p, nullptr, nullptr, dG)) != QC_OK) return rc;   // rhf.rs:152-167
         }
-        st->cur_build_tuned = false; st->cur_build_gen = S->assign.gen;
-    } else {
-        QC_HIP_CHECK(hipEventRecord(ev0, sm));
-        qc_stamp("ev0");
-        const int tunes0 = S->assign.tune_count;
-        const double tt0 = qc_now_ms();
-        if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dG + nn : nullptr, st->uhf,
-                                       &st->twin, W.H.p, dF[0], dF[1], &have_F, st)) != QC_OK) return rc;
-        st->cur_build_tuned = S->assign.tune_count != tunes0;
-        if (st->cur_build_tuned) st->ms_tuner += qc_now_ms() - tt0;
-        st->cur_build_gen = S->assign.gen;
-    }
-    qc_stamp("build out");
-    scf_flush_timing(st);                                                 // (the previous pass's times, now that this pass's build is out)
-    QC_HIP_CHECK(hipEventRecord(ev1, sm));
-    qc_stamp("flush timing, ev1");
-    // UHF: the two spins' steps are independent (uhf.rs:84-135 runs them one after the other) - the beta step goes to a side stream on
-    // another dispatch pipe, behind an event of the build's closing kernel, and meets the handle's stream again before the scalars
-    // (device-side join).  Same kernels, same arithmetic, per spin: results are bit for bit those of the serial order (QC_NO_SPIN_PARALLEL).
-    const bool spin_par = st->uhf && !W.small_fused && st->spin_parallel && S->lanes.nlanes >= 2 && !S->join.by_events;
-    if (!W.small_fused) {
-        hipStream_t side = spin_par ? qc_spin_fork(S) : nullptr;
-        if (spin_par && !side) return QC_ERR_HIP;
-        for (int s = 0; s < nspin; ++s) {                                 // (the control words were cleared by the previous pass)
-            const bool on_side = spin_par && s == 1;
-            if ((rc = roothaan_enqueue(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F,
-                                       on_side ? side : sm, on_side ? 1 : 0)) != QC_OK) return rc;
-            if (on_side) {    // the beta density on the side stream as well; then the streams meet
-                if (st->nocc[s] > 0) qc_gemm(side, n, n, st->nocc[s], 1.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
-                else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), side));
-            }
-        }
-        if (spin_par && (rc = qc_spin_join(S)) != QC_OK) return rc;
-    }
-    int *h_ctl = reinterpret_cast<int *>(W.h_scal + 4);
-    // Multi-rank runs take every decision (convergence, DIIS failure, eigensolve mode, repeat) from the SAME numbers on every
-    // rank: the pass scalars go to device memory, are all-reduced as bit patterns (max) together with their complements - so a
-    // rank whose copy differs is noticed (max(x) != ~max(~x)) - and only then reach the host.  The replicated linear algebra is
-    // deterministic and starts from bit-identical G (integer all-reduce), so the copies agree; this makes a divergence an
-    // error on all ranks in the same pass instead of a hang in the next all-reduce.
-    const bool multi = S->comm != nullptr;
-    double *scal_out = multi ? reinterpret_cast<double *>(W.d_sync.p) : W.h_scal;
-    int *ctl_out = multi ? reinterpret_cast<int *>(W.d_sync.p + 4) : h_ctl;
-    bool dens_done[2] = {false, spin_par};                               // (the beta density of a spin-parallel pass was formed on the side stream)
-    auto density_and_scalars = [&](int s, bool hand_over) -> int {
-        if (dens_done[s]) dens_done[s] = false;                          // (once: a repeat of the eigensolve forms it again, here)
-        else if (st->nocc[s] > 0) qc_gemm(sm, n, n, st->nocc[s], st->uhf ? 1.0 : 2.0, st->Cs.p + s * nn, n, false, st->Cs.p + s * nn, n, true, 0.0, st->Dn[s].p, n);
-        else QC_HIP_CHECK(hipMemsetAsync(st->Dn[s].p, 0, nn * sizeof(double), sm));
-        // energy and rms straight into pinned host memory; the last spin's kernel also hands over and clears the control words
-        qc_energy_rms(sm, n, st->Dn[s].p, st->D[s].p, W.H.p, dG + s * nn, scal_out + 2 * s, hand_over ? W.ctl.p : nullptr, ctl_out);
+        st->tm.build_issued(false, 0.0, S->assign.gen);
         return QC_OK;
-    };
-    auto publish_scalars = [&]() -> int {
-        if (!multi) return QC_OK;
-        qc_sync_pack(sm, W.d_sync.p, QC_SYNC_WORDS);
-        if (qc_rccl().AllReduce(W.d_sync.p, W.d_sync.p, 2 * QC_SYNC_WORDS, ncclUint64, ncclMax, (ncclComm_t)S->comm, sm) != ncclSuccess) return QC_ERR_RCCL;
-        QC_HIP_CHECK(hipMemcpyAsync(W.h_scal, W.d_sync.p, 2 * QC_SYNC_WORDS * sizeof(double), hipMemcpyDeviceToHost, sm));
-        return QC_OK;
-    };
-    auto ranks_agree = [&]() -> bool {
-        if (!multi) return true;
-        const unsigned long long *w = reinterpret_cast<const unsigned long long *>(W.h_scal);
-        for (int i = 0; i < QC_SYNC_WORDS; ++i) if (w[QC_SYNC_WORDS + i] != ~w[i]) return false;
-        return true;
-    };
-    if (multi && nspin == 1) QC_HIP_CHECK(hipMemsetAsync(W.d_sync.p + 2, 0, 2 * sizeof(double), sm));       // unused spin slot
-    bool scale_in_kernel = false;
-    // Single-rank runs on the one-workgroup path: the kernel that ends the pass stores the pass's sequence number into pinned memory
-    // after the scalars and control words, and the host polls THAT instead of the event behind it (a few microseconds earlier per pass).
-    unsigned *h_seq = reinterpret_cast<unsigned *>(W.h_scal + 2 * QC_SYNC_WORDS);
-    const bool seq_wait = W.small_fused && !multi && !st->event_wait;
-    // UHF on the one-workgroup path: the two spins' kernels side by side as well - beta on a side stream of another dispatch pipe behind an
-    // event of the build's closing kernel, with the second set of work buffers; the kernel that joins the streams on the device also hands
-    // the control words over and stores the sequence word (qc_spin_join_end).  Same kernels per spin: bit for bit the serial order.
-    const bool small_par = W.small_fused && st->uhf && st->spin_parallel && S->lanes.nlanes >= 2 && !S->join.by_events && !multi;
-    if (small_par) {
-        hipStream_t side = qc_spin_fork(S);
-        if (!side) return QC_ERR_HIP;
-        for (int s = 0; s < nspin; ++s) {
-            SmallTail tl{st->nocc[s], 1.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, nullptr, ctl_out, nullptr};
-            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl,
-                                     s == 1 ? side : nullptr, s)) != QC_OK) return rc;
+    }
+    qc_stamp("ev0");
+    const int tunes0 = S->assign.tune_count;
+    const double tt0 = qc_now_ms();
+    if ((rc = qc_fock_build_device(S, st->D[0].p, st->uhf ? st->D[1].p : nullptr, dG, st->uhf ? dGb : nullptr, st->uhf,
+                                   &st->twin, W.H.p, sp[0].F, st->uhf ? sp[1].F : nullptr, have_F, st)) != QC_OK) return rc;
+    st->tm.build_issued(S->assign.tune_count != tunes0, tt0, S->assign.gen);
+    return QC_OK;
+}
+
+// enqueues every spin's Roothaan step - on the stream and with the work buffers the plan gives it - and the join the plan names; on
+// the generic sequence then the densities and scalars, which the one-workgroup kernels form themselves
+static int issue_spins(qc_scf_state *st, const PassPlan &plan, SpinStep *sp, bool have_F) {
+    qc_system *S = st->S;
+    ScfWork &W = st->W;
+    const int n = S->nbasis, nspin = st->uhf ? 2 : 1;
+    int rc;
+    if (plan.clear_sync_slot && plan.fused) QC_HIP_CHECK(hipMemsetAsync(W.d_sync.p + 2, 0, 2 * sizeof(double), S->stream));       // unused spin slot
+    hipStream_t side = plan.side_by_side ? qc_spin_fork(S) : nullptr;
+    if (plan.side_by_side && !side) return QC_ERR_HIP;
+    for (int s = 0; s < nspin; ++s) {                                     // (the control words were cleared by the previous pass)
+        SpinStep &p = sp[s];
+        const bool on_side = plan.side_by_side && s == 1;
+        if (on_side) { p.st = side; p.b = 1; }
+        // (the kernel that hands over and clears the control words: the last spin's kernel when the spins run one after the other)
+        if (plan.fused) rc = roothaan_small(S, W, plan, p, have_F, !plan.side_by_side && s == nspin - 1);
+        else rc = roothaan_enqueue(W, p, have_F);
+        if (rc != QC_OK) return rc;
+        if (on_side && !plan.fused) {    // the beta density on the side stream as well; then the streams meet
+            if (p.nocc > 0) qc_gemm(side, n, n, p.nocc, 1.0, p.C, n, false, p.C, n, true, 0.0, p.Dn, n);
+            else QC_HIP_CHECK(hipMemsetAsync(p.Dn, 0, (size_t)n * n * sizeof(double), side));
+            p.dens_done = true;                                           // (the density step below skips it, once)
         }
-        if ((rc = qc_spin_join_end(S, W.ctl.p, ctl_out, seq_wait ? h_seq : nullptr, st->pass_seq + 1)) != QC_OK) return rc;
-    } else if (W.small_fused) {
-        for (int s = 0; s < nspin; ++s) {
-            // (RHF, direct fixed-point builds: the kernel that forms the new density also leaves the next build's fixed-point unit)
-            const bool scale_here = !st->uhf && !st->stored && S->accum_fx;
-            scale_in_kernel = scale_here;
-            SmallTail tl{st->nocc[s], st->uhf ? 1.0 : 2.0, st->Dn[s].p, st->D[s].p, scal_out + 2 * s, s == nspin - 1 ? W.ctl.p : nullptr, ctl_out,
-                         scale_here ? S->dev.d_fxs.p : nullptr};
-            if (seq_wait && s == nspin - 1) { tl.seq_out = h_seq; tl.seq = st->pass_seq + 1; }
-            if ((rc = roothaan_small(S, W, *st->diis[s], dG + s * nn, st->D[s].p, st->ws.p + s * n, st->Cs.p + s * nn, s, dE[s], dF[s], have_F, tl)) != QC_OK) return rc;
-        }
-    } else
-        for (int s = 0; s < nspin; ++s) if ((rc = density_and_scalars(s, s == nspin - 1)) != QC_OK) return rc;
-    if ((rc = publish_scalars()) != QC_OK) return rc;
-    // the next pass's build starts from Dn: its density-only preliminaries run while the host turns around
-    auto prepare_next = [&]() -> int { return st->stored ? QC_OK : qc_fock_prepare_device(S, st->Dn[0].p, st->uhf ? st->Dn[1].p : nullptr, st->uhf, st, scale_in_kernel); };
-    if ((rc = prepare_next()) != QC_OK) return rc;
-    qc_stamp("roothaan out");
-    QC_HIP_CHECK(hipEventRecord(ev2, sm));
-    qc_stamp("ev2");
-    const double th1 = qc_now_ms();
-    if (seq_wait) {
-        const unsigned want = st->pass_seq + 1;
-        unsigned spins = 0;
-        double t0 = 0.0;
-        while (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != want) {
-            if ((++spins & 0xfff) == 0) {                   // (a failed launch or a fault never stores the word: the event knows)
-                const hipError_t e = hipEventQuery(ev2);
-                if (e == hipErrorNotReady) {
-                    const double t = qc_now_ms();
-                    if (t0 == 0.0) t0 = t;
-                    else if (t - t0 > host_wait_limit_ms()) { fprintf(stderr, "qchem_hip: an SCF pass did not finish within %.0f s\n", host_wait_limit_ms() * 1e-3); return QC_ERR_HIP; }
-                    continue;
-                }
-                if (e != hipSuccess || __atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != want) { fprintf(stderr, "qchem_hip: the pass ended without its sequence word (%s)\n", hipGetErrorString(e)); return QC_ERR_HIP; }
-            }
-        }
-        st->pass_seq = want;
-        // The word says that the pass's last kernel is through.  If the preliminaries of the next build were put behind it (UHF: density
-        // sum and fixed-point unit; a memset after a mode change), the next build's side streams - which start without a fork event -
-        // must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there: the kernel
-        // leaves the fixed-point unit itself and the fold left the planes clean.)
-        if (!st->stored && S->prep.enqueued) QC_HIP_CHECK(wait_event(ev2));
-    } else QC_HIP_CHECK(wait_event(ev2));
-    const double th2 = qc_now_ms();
-    qc_stamp("pass seen");
+    }
+    if (plan.side_by_side && (rc = plan.fused ? qc_spin_join_end(S, W.ctl.p, plan.ctl_out, plan.seq_wait ? plan.h_seq : nullptr, plan.seq)
+                                              : qc_spin_join(S)) != QC_OK) return rc;
+    if (plan.fused) return QC_OK;
+    if (plan.clear_sync_slot) QC_HIP_CHECK(hipMemsetAsync(W.d_sync.p + 2, 0, 2 * sizeof(double), S->stream));                     // unused spin slot
+    // energy and rms straight into pinned host memory; the last spin's kernel also hands over and clears the control words
+    for (int s = 0; s < nspin; ++s) if ((rc = density_and_scalars(S, W, plan, sp[s], s == nspin - 1)) != QC_OK) return rc;
+    return QC_OK;
+}
+
+// enqueues (multi-rank) the scalars' way to the host: complements, all-reduce, copy; then what the next pass's build can do with the new
+// densities alone - it starts from Dn, and its density-only preliminaries run while the host turns around
+// (`scale_done`: the kernel that formed the density left the build's fixed-point unit as well)
+static int publish_and_prepare(qc_scf_state *st, const PassPlan &plan, bool scale_done) {
+    qc_system *S = st->S;
+    ScfWork &W = st->W;
+    if (plan.multi) {
+        qc_sync_pack(S->stream, W.d_sync.p, QC_SYNC_WORDS);
+        if (qc_rccl().AllReduce(W.d_sync.p, W.d_sync.p, 2 * QC_SYNC_WORDS, ncclUint64, ncclMax, (ncclComm_t)S->comm, S->stream) != ncclSuccess) return QC_ERR_RCCL;
+        QC_HIP_CHECK(hipMemcpyAsync(W.h_scal, W.d_sync.p, 2 * QC_SYNC_WORDS * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    }
+    return st->stored ? QC_OK : qc_fock_prepare_device(S, st->Dn[0].p, st->uhf ? st->Dn[1].p : nullptr, st->uhf, st, scale_done);
+}
+
+// the host's wait for the end of the pass: the sequence word or the event `ev2`, as the plan says
+static int wait_pass_end(qc_scf_state *st, const PassPlan &plan, hipEvent_t ev2) {
+    if (!plan.seq_wait) return wait_pass(ev2);
+    const int rc = wait_pass(ev2, plan.h_seq, plan.seq);
+    if (rc != QC_OK) return rc;
+    st->pass_seq = plan.seq;
+    // The word says that the pass's last kernel is through.  If the preliminaries of the next build were put behind it (UHF: density
+    // sum and fixed-point unit; a memset after a mode change), the next build's side streams - which start without a fork event -
+    // must not overtake them: then the event behind them is waited for as well.  (RHF on this path has nothing there: the kernel
+    // leaves the fixed-point unit itself and the fold left the planes clean.)
+    return !st->stored && st->S->prep.enqueued ? wait_pass(ev2) : QC_OK;
+}
+
+// what the host makes of a pass, or of its repeat, once it has waited for it; enqueues nothing
+// (`first`: the DIIS word is looked at after the pass itself only - a repeat runs no DIIS)
+static int pass_verdict(qc_scf_state *st, const PassPlan &plan, bool first) {
+    qc_system *S = st->S;
+    int rc;
     if ((rc = qc_join_check(S)) != QC_OK) return rc;                     // (the join of this pass's build is in front of everything waited for)
     qc_gate_quiet(S);                                                    // (nothing of this handle waits on the device any more)
-    if (!ranks_agree()) { fprintf(stderr, "qchem_hip: rank %d: the ranks' SCF scalars differ - replicated state diverged\n", S->rank); return QC_ERR_RCCL; }
-    if (h_ctl[QC_CTL_DIIS] != 0) return QC_DIIS_SINGULAR;                          // "DIIS failed", rhf.rs:73
-    if (h_ctl[QC_CTL_NOTCONV] != 0) return QC_EIG_NOT_CONVERGED;
-    static const bool dbg = getenv("QC_SCF_DEBUG") != nullptr;
-    const int *const ea = h_ctl + QC_CTL_EIG, *const eb = ea + QC_CTL_EIG_STRIDE;
-    if (dbg) fprintf(stderr, "[scf] ctl a: %d %d %d %d  b: %d %d %d %d  npass %d %d have_prev %d mode %d cold %d | host enqueue %.0f us, then waited %.0f us\n", ea[QC_EIG_STATE], ea[QC_EIG_LAST], ea[QC_EIG_CLEAN], ea[QC_EIG_PASSES], eb[QC_EIG_STATE], eb[QC_EIG_LAST], eb[QC_EIG_CLEAN], eb[QC_EIG_PASSES], W.npass[0], W.npass[1], (int)W.have_prev[0], W.mode[0], (int)W.cold[0], (th1 - th0) * 1e3, (th2 - th1) * 1e3);
-    if (dbg) {   // the pass's DIIS coefficients (diis.rs:50-51), newest sample first
-        double c[12] = {0};
-        const int m = (int)st->diis[0]->slots.size();
-        (void)hipMemcpy(c, st->diis[0]->d_c.p, m * sizeof(double), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[scf] diis c:");
-        for (int j = 0; j < m; ++j) fprintf(stderr, " %.3e", c[j]);
-        fprintf(stderr, "\n");
-    }
-    // the pass's event times are read by the next pass (scf_flush_timing): the last event may still be in flight when the host has seen
-    // the sequence word
-    st->timing_pending = true; st->pending_set = st->ev_cur;
-    st->pend_build_tuned = st->cur_build_tuned; st->pend_build_gen = st->cur_build_gen;
-    bool redo = false;
-    for (int s = 0; s < nspin; ++s) {
+    const unsigned long long *w = reinterpret_cast<const unsigned long long *>(st->W.h_scal);
+    for (int i = 0; plan.multi && i < QC_SYNC_WORDS; ++i)
+        if (w[QC_SYNC_WORDS + i] != ~w[i]) { fprintf(stderr, "qchem_hip: rank %d: the ranks' SCF scalars differ - replicated state diverged\n", S->rank); return QC_ERR_RCCL; }
+    if (first && plan.h_ctl[QC_CTL_DIIS] != 0) return QC_DIIS_SINGULAR;            // "DIIS failed", rhf.rs:73
+    if (plan.h_ctl[QC_CTL_NOTCONV] != 0) return QC_EIG_NOT_CONVERGED;              // (a repeat: it ran out of sweeps, no vectors to go on with)
+    return QC_OK;
+}
+
+// QC_SCF_DEBUG: the pass's control words and host times, and its DIIS coefficients (diis.rs:50-51), newest sample first
+static void debug_pass(const qc_scf_state *st, const PassPlan &plan, double us_enqueue, double us_waited) {
+    const ScfWork &W = st->W;
+    const int *const ea = plan.h_ctl + QC_CTL_EIG, *const eb = ea + QC_CTL_EIG_STRIDE;
+    fprintf(stderr, "[scf] ctl a: %d %d %d %d  b: %d %d %d %d  npass %d %d have_prev %d mode %d cold %d | host enqueue %.0f us, then waited %.0f us\n", ea[QC_EIG_STATE], ea[QC_EIG_LAST], ea[QC_EIG_CLEAN], ea[QC_EIG_PASSES], eb[QC_EIG_STATE], eb[QC_EIG_LAST], eb[QC_EIG_CLEAN], eb[QC_EIG_PASSES], W.npass[0], W.npass[1], (int)W.have_prev[0], W.mode[0], (int)W.cold[0], us_enqueue, us_waited);
+    double c[12] = {0};
+    const int m = (int)st->diis[0]->slots.size();
+    (void)hipMemcpy(c, st->diis[0]->d_c.p, m * sizeof(double), hipMemcpyDeviceToHost);
+    fprintf(stderr, "[scf] diis c:");
+    for (int j = 0; j < m; ++j) fprintf(stderr, " %.3e", c[j]);
+    fprintf(stderr, "\n");
+}
+
+// The refinement passes of the next eigensolve follow what this one needed; a spin whose refinement wanted rotations (large step, or a
+// degenerate cluster) has its eigensolve repeated the careful way: enqueues, per such spin, the eigensolve and the density and scalars
+// again, then the hand-over, the scalars' way to the host and the next build's preliminaries once more, and waits.  *redo: it happened.
+static int repeat_eigensolves(qc_scf_state *st, const PassPlan &plan, SpinStep *sp, hipEvent_t *ev, bool *redo) {
+    qc_system *S = st->S;
+    ScfWork &W = st->W;
+    hipStream_t sm = S->stream;
+    int rc;
+    for (int s = 0; s < (st->uhf ? 2 : 1); ++s) {
         const bool refined = W.cold[s] || (W.have_prev[s] && W.mode[s] == 0);       // the eigensolve reported through the control word
         if (!refined) continue;
-        const int *const eig = h_ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * s;
+        const int *const eig = plan.h_ctl + QC_CTL_EIG + QC_CTL_EIG_STRIDE * s;
         if (eig[QC_EIG_STATE] == QC_EIG_DONE) { W.npass[s] = W.cold[s] ? 3 : std::max(1, std::min(3, eig[QC_EIG_PASSES])); continue; }
         W.npass[s] = 3;
-        // the refinement wanted rotations (large step, or a degenerate cluster): repeat this spin's eigensolve the careful way
-        if (!redo) { scf_flush_timing(st); QC_HIP_CHECK(hipEventRecord(ev1, sm)); }
-        if ((rc = roothaan_redo_eig(S, W, st->ws.p + s * n, st->Cs.p + s * nn, s)) != QC_OK) return rc;
-        if ((rc = density_and_scalars(s, false)) != QC_OK) return rc;
-        redo = true;
+        // (this pass's times are read first, once, and its second event is recorded again: the repeat counts as linear algebra)
+        if (!*redo) { st->tm.flush(st->tuner()); QC_HIP_CHECK(hipEventRecord(ev[1], sm)); }
+        if ((rc = roothaan_redo_eig(S, W, sp[s])) != QC_OK) return rc;
+        if ((rc = density_and_scalars(S, W, plan, sp[s], false)) != QC_OK) return rc;
+        *redo = true;
     }
-    if (redo) {
-        st->redos += 1;
-        // the repeated eigensolves report through the same control words (Jacobi sweeps exhausted: QC_CTL_NOTCONV): hand them over again,
-        // whichever spin was repeated, and clear them for the next pass
-        QC_HIP_CHECK(hipMemcpyAsync(ctl_out, W.ctl.p, QC_CTL_WORDS * sizeof(int), hipMemcpyDefault, sm));
-        QC_HIP_CHECK(hipMemsetAsync(W.ctl.p, 0, QC_CTL_WORDS * sizeof(int), sm));
-        if ((rc = publish_scalars()) != QC_OK) return rc;
-        scale_in_kernel = false;
-        if ((rc = prepare_next()) != QC_OK) return rc;                    // (the density changed)
-        QC_HIP_CHECK(hipEventRecord(ev2, sm));
-        QC_HIP_CHECK(wait_event(ev2));
-        if ((rc = qc_join_check(S)) != QC_OK) return rc;
-        qc_gate_quiet(S);
-        if (!ranks_agree()) return QC_ERR_RCCL;
-        if (h_ctl[QC_CTL_NOTCONV] != 0) return QC_EIG_NOT_CONVERGED;     // the repeat ran out of sweeps: no vectors to go on with
-        float ms_r = 0;
-        (void)hipEventElapsedTime(&ms_r, ev1, ev2);
-        st->ms_linalg += ms_r;
-    }
+    if (!*redo) return QC_OK;
+    st->redos += 1;
+    // the repeated eigensolves report through the same control words (Jacobi sweeps exhausted: QC_CTL_NOTCONV): hand them over again,
+    // whichever spin was repeated, and clear them for the next pass
+    QC_HIP_CHECK(hipMemcpyAsync(plan.ctl_out, W.ctl.p, QC_CTL_WORDS * sizeof(int), hipMemcpyDefault, sm));
+    QC_HIP_CHECK(hipMemsetAsync(W.ctl.p, 0, QC_CTL_WORDS * sizeof(int), sm));
+    if ((rc = publish_and_prepare(st, plan, false)) != QC_OK) return rc;  // (the density changed)
+    QC_HIP_CHECK(hipEventRecord(ev[2], sm));
+    if ((rc = wait_pass(ev[2])) != QC_OK) return rc;
+    if ((rc = pass_verdict(st, plan, false)) != QC_OK) return rc;
+    st->tm.repeat_seen();
+    return QC_OK;
+}
+
+// accepts the pass: energy and rms from the scalars, the eigensolve of the next pass, new density and vectors become the current ones
+static void accept_pass(qc_scf_state *st, bool redo, double *energy, double *rms_out) {
+    ScfWork &W = st->W;
+    const int nspin = st->uhf ? 2 : 1;
     double rms_sum = 0.0, e_sum = 0.0;
     for (int s = 0; s < nspin; ++s) {
-        const double rms_s = std::sqrt(W.h_scal[2 * s + 1] / n);
+        const double rms_s = std::sqrt(W.h_scal[2 * s + 1] / W.n);
         e_sum += W.h_scal[2 * s]; rms_sum += rms_s;
         // the refinement is perturbative: on its own once the density has nearly stopped moving, behind two Jacobi sweeps
         // while it still moves, not at all in the first wild passes
@@ -649,10 +694,48 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
         W.have_prev[s] = true;
     }
     st->passes += 1;
-    qc_stamp("pass end");
-    qc_stamp_flush();
     if (energy) *energy = e_sum;
     if (rms_out) *rms_out = st->uhf ? rms_sum / 2.0 : rms_sum;
+}
+
+// one pass of the loop body.  RHF: rhf.rs:67-88.  UHF: uhf.rs:81-137 (returns the reference's `density_rms`,
+// i.e. (rms_a + rms_b) / 2, and the energy expression of uhf.rs:145-153 evaluated every pass).
+// The whole pass is enqueued without looking at the device; one synchronisation at its end returns the energy, the rms
+// and the control words (DIIS failure, eigen-refinement outcome).  Launch latency of ~50 small kernels then overlaps with
+// their execution instead of adding to it.
+static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
+    qc_system *S = st->S;
+    hipStream_t sm = S->stream;
+    int rc;
+    const double th0 = qc_now_ms();
+    qc_stamp("enter pass");
+    if ((rc = qc_tl_begin_pass(S)) != QC_OK) return rc;
+    hipEvent_t *const ev = st->tm.begin_pass();                           // start | build done | pass done
+    const PassPlan plan = plan_pass(st);
+    SpinStep sp[2] = {spin_step(st, plan, 0), st->uhf ? spin_step(st, plan, 1) : SpinStep{}};
+    bool have_F = false, redo = false;
+    if ((rc = build_G(st, ev[0], sp, &have_F)) != QC_OK) return rc;
+    qc_stamp("build out");
+    st->tm.flush(st->tuner());                                            // (the previous pass's times, now that this pass's build is out)
+    QC_HIP_CHECK(hipEventRecord(ev[1], sm));
+    qc_stamp("flush timing, ev1");
+    if ((rc = issue_spins(st, plan, sp, have_F)) != QC_OK) return rc;
+    if ((rc = publish_and_prepare(st, plan, plan.scale_in_kernel)) != QC_OK) return rc;
+    qc_stamp("roothaan out");
+    QC_HIP_CHECK(hipEventRecord(ev[2], sm));
+    qc_stamp("ev2");
+    const double th1 = qc_now_ms();
+    if ((rc = wait_pass_end(st, plan, ev[2])) != QC_OK) return rc;
+    const double th2 = qc_now_ms();
+    qc_stamp("pass seen");
+    if ((rc = pass_verdict(st, plan, true)) != QC_OK) return rc;
+    static const bool dbg = getenv("QC_SCF_DEBUG") != nullptr;
+    if (dbg) debug_pass(st, plan, (th1 - th0) * 1e3, (th2 - th1) * 1e3);
+    st->tm.pass_seen();
+    if ((rc = repeat_eigensolves(st, plan, sp, ev, &redo)) != QC_OK) return rc;
+    accept_pass(st, redo, energy, rms_out);
+    qc_stamp("pass end");
+    qc_stamp_flush();
     return QC_OK;
 }
 
@@ -684,12 +767,56 @@ static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, boo
             break;
         }
     }
-    scf_flush_timing(st);
-    out->ms_setup = st->ms_setup; out->ms_fock_total = st->ms_fock; out->ms_linalg_total = st->ms_linalg;
+    st->tm.flush(st->tuner());
+    out->ms_setup = st->ms_setup; out->ms_fock_total = st->tm.ms_fock; out->ms_linalg_total = st->tm.ms_linalg;
     out->ms_total = qc_now_ms() - t_begin;
-    out->ms_tuner = st->ms_tuner;
+    out->ms_tuner = st->tm.ms_tuner;
     return status;
 }
+
+// What a direct Fock build outside the SCF loop overwrites on the handle, saved and put back around it: the fixed-point unit (the
+// one-workgroup Roothaan path leaves the unit of the NEXT pass's build there, PassPlan::scale_in_kernel), the UHF density sum of a prepared
+// build, and the flags that let the next pass's build skip its preliminaries.  (The accumulator planes need nothing: every build's
+// closing fold leaves them zero, whatever its layout.)  With this a later qc_scf_iterate is bit for bit what it would have been.
+namespace {
+struct FockPrepSave {
+    qc_system *S;
+    DevBuf fxs, Dj;
+    const QcPrepared prep;
+    explicit FockPrepSave(qc_system *S_) : S(S_), prep(S_->prep) {}
+    int save() {
+        const size_t nn = (size_t)S->nbasis * S->nbasis;
+        if (fxs.alloc(2) != QC_OK || Dj.alloc(nn) != QC_OK) return QC_ERR_HIP;
+        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(fxs.p, S->dev.d_fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(Dj.p, S->dev.d_Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        return QC_OK;
+    }
+    int restore() {
+        const size_t nn = (size_t)S->nbasis * S->nbasis;
+        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_fxs.p, fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_Dj.p, Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+        // (a build that ran in between left the planes clean for ITS layout; the saved flags speak of the state's layout, which is zero too)
+        const bool clean = prep.gt_clean && S->prep.gt_clean; S->prep = prep; S->prep.gt_clean = clean;
+        return QC_OK;
+    }
+};
+// runs `call` between save and restore.  A failed restore counts unless the call failed (rc < 0) or, `status_first`, returned any status
+template <class F> int with_fock_prep_saved(qc_system *S, bool status_first, F call) {
+    FockPrepSave keep(S);
+    int rc = keep.save();
+    if (rc != QC_OK) return rc;
+    rc = call();
+    const int rc2 = keep.restore();
+    return status_first ? (rc != QC_OK ? rc : rc2) : (rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc));
+}
+// the guard of the post-SCF entry points that work from a pass's C and orbital energies on one rank
+int ran_on_one_rank(const qc_scf_state *st) {
+    if (st->passes == 0) return QC_ERR_INVALID;
+    return st->S->comm || st->S->nranks != 1 ? QC_ERR_UNSUPPORTED : QC_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -730,9 +857,10 @@ int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out) {
     return qc_mp2_device(S, nspin, st->Cs.p, st->ws.p, nocc, n_frozen, out);   // (reads Cs / ws, writes nothing of the state)
 }
 int qc_scf_gradient(qc_scf_state *st, double *grad) {
-    if (!st || !grad || st->passes == 0) return QC_ERR_INVALID;
+    if (!st || !grad) return QC_ERR_INVALID;
+    int rc = ran_on_one_rank(st);
+    if (rc != QC_OK) return rc;
     qc_system *S = st->S;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
     const int n = S->nbasis, nspin = st->uhf ? 2 : 1, na3 = 3 * S->natoms;
     const size_t nn = (size_t)n * n;
     QC_HIP_CHECK(hipStreamSynchronize(S->stream));
@@ -745,8 +873,7 @@ int qc_scf_gradient(qc_scf_state *st, double *grad) {
     QC_HIP_CHECK(hipEventRecord(ev[0], S->stream));
     for (int s = 0; s < nspin; ++s) QC_HIP_CHECK(hipMemcpyAsync(dP.p + s * nn, st->D[s].p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
     const int nocc[2] = {st->nocc[0], st->nocc[1]};
-    int rc = qc_gradient_w_device(S, nspin, st->Cs.p, st->ws.p, nocc, dW.p);   // (reads Cs / ws, writes nothing of the state)
-    if (rc != QC_OK) return rc;
+    if ((rc = qc_gradient_w_device(S, nspin, st->Cs.p, st->ws.p, nocc, dW.p)) != QC_OK) return rc;   // (reads Cs / ws, writes nothing of the state)
     QC_HIP_CHECK(hipEventRecord(ev[1], S->stream));
     std::vector<double> t((size_t)4 * na3);
     qc_nuclear_gradient(S, t.data());
@@ -757,65 +884,29 @@ int qc_scf_gradient(qc_scf_state *st, double *grad) {
     for (int k = 0; k < na3; ++k) grad[k] = ((t[k] + t[na3 + k]) + t[2 * na3 + k]) + t[3 * na3 + k];
     return QC_OK;
 }
-// What a direct Fock build outside the SCF loop overwrites on the handle, saved and put back around it: the fixed-point unit (the
-// one-workgroup Roothaan path leaves the unit of the NEXT pass's build there, SmallTail::fxs_out), the UHF density sum of a prepared
-// build, and the flags that let the next pass's build skip its preliminaries.  (The accumulator planes need nothing: every build's
-// closing fold leaves them zero, whatever its layout.)  With this a later qc_scf_iterate is bit for bit what it would have been.
-namespace {
-struct FockPrepSave {
-    qc_system *S;
-    DevBuf fxs, Dj;
-    const QcPrepared prep;
-    explicit FockPrepSave(qc_system *S_) : S(S_), prep(S_->prep) {}
-    int save() {
-        const size_t nn = (size_t)S->nbasis * S->nbasis;
-        if (fxs.alloc(2) != QC_OK || Dj.alloc(nn) != QC_OK) return QC_ERR_HIP;
-        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(fxs.p, S->dev.d_fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(Dj.p, S->dev.d_Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        return QC_OK;
-    }
-    int restore() {
-        const size_t nn = (size_t)S->nbasis * S->nbasis;
-        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_fxs.p, fxs.p, 2 * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        QC_HIP_CHECK(hipMemcpyAsync(S->dev.d_Dj.p, Dj.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        QC_HIP_CHECK(hipStreamSynchronize(S->stream));
-        // (a build that ran in between left the planes clean for ITS layout; the saved flags speak of the state's layout, which is zero too)
-        const bool clean = prep.gt_clean && S->prep.gt_clean; S->prep = prep; S->prep.gt_clean = clean;
-        return QC_OK;
-    }
-};
-}  // namespace
 
 int qc_scf_stability_dim(qc_scf_state *st, int kind) {
     if (!st || kind < 0 || kind > (st->uhf ? 0 : 1)) return QC_ERR_INVALID;
     return qc_stability_dim(st->S->nbasis, st->uhf, st->nocc);
 }
 int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors) {
-    if (!st || !io || st->passes == 0) return QC_ERR_INVALID;
+    if (!st || !io) return QC_ERR_INVALID;
     if (io->kind < 0 || io->kind > (st->uhf ? 0 : 1) || io->nroots < 1 || io->nroots > 8 || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
     qc_system *S = st->S;
     const int dim = qc_stability_dim(S->nbasis, st->uhf, st->nocc);
     if (dim <= 0 || io->nroots > dim) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    FockPrepSave keep(S);
-    int rc = keep.save();
+    const int rc = ran_on_one_rank(st);
     if (rc != QC_OK) return rc;
-    rc = qc_stability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, vectors);   // (reads Cs / ws, writes nothing of the state)
-    const int rc2 = keep.restore();
-    return rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc);
+    // (reads Cs / ws, writes nothing of the state)
+    return with_fock_prep_saved(S, false, [&] { return qc_stability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, vectors); });
 }
 int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double angle, double *Da, double *Db, double *energy) {
-    if (!st || !x || !Da || !Db || st->passes == 0 || kind < 0 || kind > (st->uhf ? 0 : 1) || angle != angle) return QC_ERR_INVALID;
+    if (!st || !x || !Da || !Db || kind < 0 || kind > (st->uhf ? 0 : 1) || angle != angle) return QC_ERR_INVALID;
     qc_system *S = st->S;
     if (qc_stability_dim(S->nbasis, st->uhf, st->nocc) <= 0) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    FockPrepSave keep(S);
-    int rc = keep.save();
+    const int rc = ran_on_one_rank(st);
     if (rc != QC_OK) return rc;
-    rc = qc_rotated_density_device(S, st->uhf, kind, st->nocc, st->Cs.p, st->W.H.p, x, angle, Da, Db, energy);
-    const int rc2 = keep.restore();
-    return rc != QC_OK ? rc : rc2;
+    return with_fock_prep_saved(S, true, [&] { return qc_rotated_density_device(S, st->uhf, kind, st->nocc, st->Cs.p, st->W.H.p, x, angle, Da, Db, energy); });
 }
 // mu_k = sum_A Z_A (R_A - O)_k - tr(P_t M_k): the nuclear part on the host, the trace by a fixed-order reduction on the device
 int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double mu_nuclear[3]) {
@@ -836,15 +927,12 @@ int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double m
     return QC_OK;
 }
 int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response) {
-    if (!st || !io || st->passes == 0 || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
+    if (!st || !io || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
     qc_system *S = st->S;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    FockPrepSave keep(S);
-    int rc = keep.save();
+    const int rc = ran_on_one_rank(st);
     if (rc != QC_OK) return rc;
-    rc = qc_polarizability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, response);   // (reads Cs / ws, writes nothing of the state)
-    const int rc2 = keep.restore();
-    return rc < 0 ? rc : (rc2 != QC_OK ? rc2 : rc);
+    // (reads Cs / ws, writes nothing of the state)
+    return with_fock_prep_saved(S, false, [&] { return qc_polarizability_device(S, st->uhf, st->nocc, st->Cs.p, st->ws.p, io, response); });
 }
 // CIS / TDHF from MO integrals: like qc_scf_mp2 the calls read Cs / ws and run no Fock build, so nothing of the handle needs saving
 int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors) {
@@ -855,7 +943,7 @@ int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors) {
     qc_system *S = st->S;
     const int dim = qc_stability_dim(S->nbasis, false, st->nocc);
     if (dim <= 0 || io->nroots > dim) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (const int rc = ran_on_one_rank(st)) return rc;                  // (a pass has run, see above: the number of ranks)
     return qc_excitations_device(S, st->nocc[0], st->Cs.p, st->ws.p, io, vectors);
 }
 int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *AmB) {
@@ -863,7 +951,7 @@ int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *
     if (st->uhf) return QC_ERR_UNSUPPORTED;
     qc_system *S = st->S;
     if (qc_stability_dim(S->nbasis, false, st->nocc) <= 0) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (const int rc = ran_on_one_rank(st)) return rc;                  // (a pass has run, see above: the number of ranks)
     return qc_excitation_matrices_device(S, st->nocc[0], st->Cs.p, st->ws.p, kind, ApB, AmB);
 }
 int qc_scf_begin_rhf_from(qc_system *S, const double *D, qc_scf_state **out) {
@@ -906,10 +994,10 @@ int qc_scf_spin_square(qc_scf_state *st, double *s2) {
 double qc_scf_tensor_ms(qc_scf_state *st) { return st ? st->ms_tensor : 0.0; }
 int qc_scf_timings(qc_scf_state *st, double *ms_setup, double *ms_fock, double *ms_linalg) {
     if (!st) return QC_ERR_INVALID;
-    scf_flush_timing(st);
+    st->tm.flush(st->tuner());
     if (ms_setup) *ms_setup = st->ms_setup;
-    if (ms_fock) *ms_fock = st->ms_fock;
-    if (ms_linalg) *ms_linalg = st->ms_linalg;
+    if (ms_fock) *ms_fock = st->tm.ms_fock;
+    if (ms_linalg) *ms_linalg = st->tm.ms_linalg;
     return QC_OK;
 }
 void qc_scf_end(qc_scf_state *st) { scf_state_delete(st); }
@@ -919,8 +1007,8 @@ int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon) {
 }
 int qc_scf_counters(qc_scf_state *st, double *out, int n) {
     if (!st || !out || n < 0) return QC_ERR_INVALID;
-    scf_flush_timing(st);
-    const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->ms_fock, st->ms_linalg, (double)st->builds_timed, st->ms_tuner, (double)st->passes,
+    st->tm.flush(st->tuner());
+    const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->tm.ms_fock, st->tm.ms_linalg, (double)st->tm.builds_timed, st->tm.ms_tuner, (double)st->passes,
                                         0.0, 0.0 /* reserved */, (double)st->redos,
                                         (double)st->S->assign.on.trials, st->S->assign.on.settled ? 1.0 : 0.0};
     for (int i = 0; i < n && i < QC_SCF_NCOUNTERS; ++i) out[i] = v[i];

@@ -2,7 +2,13 @@
 rms of every pass, the final orbital energies (per spin), `redos` and the passes used.
     python tools/record_small_bits.py [out.json]        (default: tests/golden/small_roothaan_bits.json; QCHEM_HIP_LIB selects the build)
 tests/test_small_roothaan_bits_gpu.py replays the same runs (run_case) and compares every word with the committed file, which was
-recorded with the library of the commit before the kernel's latency work: that work may not change one bit."""
+recorded with the library of the commit before the kernel's latency work: that work may not change one bit.
+
+A second table, PASS_CASES, does the same for the forms of an SCF pass that the first table does not reach - the generic launch sequence,
+spins side by side and serial, the event wait, stored mode, a one-rank communicator, each with and without the repeat of an eigensolve:
+    python tools/record_small_bits.py --pass [out.json]  (default: tests/golden/scf_pass_bits.json)
+tests/test_scf_pass_bits_gpu.py replays them against that file, recorded with the library of the commit before the SCF driver
+(qc_scf.cpp) was rewritten as a sequence of steps: that rewrite may not change one bit either."""
 import json
 import os
 import sys
@@ -22,20 +28,50 @@ CASES = {
     "o2_uhf": ("oxygen", "cc-pVDZ", True, (9, 7), 20, {}),              # n = 28: pre | Jacobi | post, generic-order dots, two spins
 }
 
+# name: (molecule, basis, uhf, (n_alpha, n_beta), passes, environment, options); options: "fock_mode" ("stored"), "comm" (a one-rank
+# communicator).  All n <= 64; the generic launch sequence is reached with QC_NO_SMALL_FUSED.  Every "repeat" case showed redos >= 1 with
+# the recording (parent) library at the threshold given here; none had to be changed for that.
+# (QC_NO_OPEN_SHELL_FUSED is read once per process, so inside a test session that has already run an SCF it selects nothing any more:
+# o2_uhf_generic sets QC_NO_SMALL_FUSED - read per SCF state - next to it, which selects the same generic sequence.)
+GENERIC = {"QC_NO_SMALL_FUSED": "1"}
+REPEAT = {"QC_EIG_WARM_RMS": "0.5"}
+PASS_CASES = {
+    "h2o_dz_generic": ("water", "cc-pVDZ", False, (0, 0), 15, GENERIC, {}),        # n = 24 = QC_TRI_MIN_N: Tridiag, then Refine
+    "h2o_tz_generic_repeat": ("water", "cc-pVTZ", False, (0, 0), 15, {**GENERIC, **REPEAT}, {}),   # roothaan_redo_eig, generic path
+    "c2h4_uhf_generic": ("ethylene", "6-31G_st_st", True, (8, 8), 15, GENERIC, {}),   # beta step + density on the side stream, qc_spin_join
+    "c2h4_uhf_generic_serial": ("ethylene", "6-31G_st_st", True, (8, 8), 15, {**GENERIC, "QC_NO_SPIN_PARALLEL": "1"}, {}),
+    "o2_uhf_generic": ("oxygen", "cc-pVDZ", True, (9, 7), 20, {**GENERIC, "QC_NO_OPEN_SHELL_FUSED": "1"}, {}),   # rotation-only routes, generic
+    "h2o_tz_uhf": ("water", "cc-pVTZ", True, (5, 5), 15, {}, {}),                  # fused, spins side by side: Tridiag / Refine phases, qc_spin_join_end
+    "h2o_tz_uhf_repeat": ("water", "cc-pVTZ", True, (5, 5), 15, REPEAT, {}),       # repeat after a side-by-side fused pass
+    "h2o_tz_event_wait": ("water", "cc-pVTZ", False, (0, 0), 15, {"QC_EVENT_WAIT": "1"}, {}),
+    "h2o_sto3g_stored": ("water", "STO-3G", False, (0, 0), 12, {}, {"fock_mode": "stored"}),   # tensor GEMV build, no prepare step
+    "h2o_sto3g_stored_uhf": ("water", "STO-3G", True, (5, 5), 12, {}, {"fock_mode": "stored"}),
+    "c2h4_dz_comm": ("ethylene", "cc-pVDZ", False, (0, 0), 15, {}, {"comm": True}),   # d_sync packing, all-reduce, ranks_agree, unused-slot memset
+    "c2h4_dz_comm_repeat": ("ethylene", "cc-pVDZ", False, (0, 0), 15, REPEAT, {"comm": True}),   # second collective of a pass
+}
+REPEAT_CASES = ("h2o_tz_repeat", "h2o_tz_generic_repeat", "h2o_tz_uhf_repeat", "c2h4_dz_comm_repeat")   # redos >= 1 in the record
+# (case, table of the twin, twin): the same run by another order of issue or another wait - the two records are equal word for word
+SAME_AS = (("c2h4_uhf_generic_serial", "pass", "c2h4_uhf_generic"), ("h2o_tz_event_wait", "small", "h2o_tz"))
+
 
 def hexword(x):
     return float(x).hex()
 
 
 def run_case(name):
-    """The run `name` of CASES -> {"energy": [...], "rms": [...], "orbital_energies": [[...], ...], "redos": int, "passes": int}."""
+    """The run `name` of CASES or PASS_CASES -> {"energy": [...], "rms": [...], "orbital_energies": [[...], ...], "redos": int, "passes": int}."""
     import qchem_rs_amd as q
     from conftest import load_system
-    mol, basis, uhf, (na, nb), npass, env = CASES[name]
+    mol, basis, uhf, (na, nb), npass, env, *opt = CASES[name] if name in CASES else PASS_CASES[name]
+    opt = opt[0] if opt else {}
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)                                               # (read by the library once per SCF state)
     try:
         s = q.System(load_system(mol, basis))
+        if "fock_mode" in opt:
+            s.set_fock_mode(opt["fock_mode"])
+        if opt.get("comm"):
+            s.comm_init(q.comm_unique_id(), 0, 1)
         st = q.ScfStepper(s, uhf=uhf, n_alpha=na, n_beta=nb)
         tr = [st.iterate() for _ in range(npass)]
         w = [st.orbital_energies(spin) for spin in range(2 if uhf else 1)]
@@ -50,10 +86,12 @@ def run_case(name):
 
 
 if __name__ == "__main__":
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "small_roothaan_bits.json")
-    rec = {name: run_case(name) for name in CASES}
+    args = [a for a in sys.argv[1:] if a != "--pass"]
+    table, default = (PASS_CASES, "scf_pass_bits.json") if "--pass" in sys.argv[1:] else (CASES, "small_roothaan_bits.json")
+    out = args[0] if args else os.path.join(ROOT, "tests", "golden", default)
+    rec = {name: run_case(name) for name in table}
     for name, r in rec.items():
-        print("%-14s n %2d  passes %2d  redos %d  E %s" % (name, r["n"], r["passes"], r["redos"], float.fromhex(r["energy"][-1])))
+        print("%-24s n %2d  passes %2d  redos %d  E %s" % (name, r["n"], r["passes"], r["redos"], float.fromhex(r["energy"][-1])))
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
