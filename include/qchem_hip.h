@@ -345,8 +345,13 @@ int qc_set_accumulation(qc_system *sys, int fixed_point);
 /* ---- Schwarz screening (the reference's TODO at uhf.rs:49-50: "if we could skip some of them ...").  Once per geometry the
  * GPU evaluates the (ab|ab) quartet of every shell pair; unique quartets with sqrt((ab|ab) (cd|cd)) < tau are left out of
  * the work lists (|(ab|cd)| <= that product).  Default 1e-12; 0 switches it off.  Throughput figures keep counting the
- * enumerated quartets (qc_nquartets). */
+ * enumerated quartets (qc_nquartets).  NOT screened: qc_eri_full, the stored-tensor mode (qc_set_fock_mode) and everything built on
+ * the tensor (MP2, excitations) - they run over every class's whole quartet list, not over the screened shard. */
 int qc_set_schwarz(qc_system *sys, double tau);
+/* The factors of that pass (read-only; initialises the device side if needed): for every STORED shell pair - pairs A >= B whose every
+ * primitive pair falls under the primitive cut-off are not stored and have no factor - the shell indices (A,B), 2 ints each, and
+ * Q = sqrt(max_ab (ab|ab)); Q == NULL: returns the count only. */
+int qc_schwarz_factors(qc_system *sys, int32_t *shell_ab, double *Q, int64_t capacity);
 
 /* ---- multi-GPU (not in the reference, which is single-threaded; BASELINE.json north_star).  One process per GPU.
  * Rank 0 calls qc_comm_unique_id, the host distributes the 128 bytes, every rank calls qc_comm_init, which creates

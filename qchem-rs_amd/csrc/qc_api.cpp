@@ -298,6 +298,17 @@ int qc_set_schwarz(qc_system *S, double tau) {
     S->schwarz_tau = tau;
     return qc_device_reshard(S);
 }
+// the factors the screening rule reads (pairQ comes from the device pass of the set-up), with the shells of their pairs
+int qc_schwarz_factors(qc_system *S, int32_t *shell_ab /* 2 * npairs or NULL */, double *Q /* npairs or NULL */, int64_t capacity) {
+    if (!S) return QC_ERR_INVALID;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const int64_t np = (int64_t)S->pairQ.size();
+    if (!Q) return (int)np;
+    if (!shell_ab || capacity < np) return QC_ERR_INVALID;
+    for (int64_t i = 0; i < np; ++i) { shell_ab[2 * i] = S->pairA[i]; shell_ab[2 * i + 1] = S->pairB[i]; Q[i] = S->pairQ[i]; }
+    return (int)np;
+}
 
 int qc_set_fock_mode(qc_system *S, int mode) {
     if (!S || (mode != 0 && mode != 1)) return QC_ERR_INVALID;

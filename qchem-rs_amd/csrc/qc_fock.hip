@@ -440,22 +440,22 @@ static void unsplit_jobs(const qc_system *S, bool diagonal_only, std::vector<Uns
             for (const auto &t : tasks) mx = std::max(mx, qc_bm_wave_words(c.LAB, S->pairs[t.bra].na * S->pairs[t.bra].nb, S->pairs[t.ket].na * S->pairs[t.ket].nb));
             j.lds = mx * 8;
         } else {
-            if (c.bm) {
-                j.kind = 2;
-                j.col.LAB = c.LAB; j.col.LCD = c.LCD; j.col.LGC = c.col_lgc; j.col.slot_words = c.col_slot_words; j.col.lds_bytes = c.col_lds_bytes;
-            }
+            // LDS per lane group over the class's whole task list (qc_build_shards): slot_words / lds_bytes follow the screened shard
+            // and are too small - zero for a class that keeps nothing - for the quartets a threshold has dropped from the builds
+            if (c.bm) j.kind = 2;
+            j.col.LAB = c.LAB; j.col.LCD = c.LCD; j.col.LGC = c.col_lgc; j.col.slot_words = c.col_slot_words; j.col.lds_bytes = c.col_lds_bytes;
             qc_make_slots(S, tasks, 0, false, slots);
             j.off_a = blob.put(slots.data(), slots.size() * sizeof(QcSlot)); j.count = (int)slots.size();
         }
         if (j.count) jobs.push_back(std::move(j));
     }
 }
-// (`j` must not move while its launch is in flight: the column-kernel copy of a p.p-ket class is referred to by address)
+// (`j` must not move while its launch is in flight: the column-kernel copy of its class is referred to by address)
 static int launch_unsplit(qc_system *S, const UnsplitJob &j, const unsigned char *d_blob, hipStream_t st, const QcKernelArgs &a) {
     if (j.kind == 1)
         return launch_segments(S, qc_unit_of(j.c->LAB, j.c->LCD, true), {Seg{j.c, nullptr, j.count, reinterpret_cast<const QcBundleDev *>(d_blob + j.off_a),
                                                                             reinterpret_cast<const QcKetUnit *>(d_blob + j.off_b), j.lds}}, st, a);
-    const QcClass *cls = j.kind == 2 ? &j.col : j.c;
+    const QcClass *cls = &j.col;
     return launch_segments(S, qc_unit_of(cls->LAB, cls->LCD, false), {Seg{cls, reinterpret_cast<const QcSlot *>(d_blob + j.off_a), j.count}}, st, a);
 }
 

@@ -30,7 +30,7 @@ __host__ __device__ constexpr int qc_region0(int L, int lgc) {
     return qc_hoisted(L) ? qc_hoist_chunk(L, lgc) * ((((L + 1) * (L + 2) * (L + 3) / 6) | 1) + 2) : (L + 1) * (L + 2) * (L + 3) * (L + 4) / 24;
 }
       // primitive quartets per slot
-constexpr double QC_PRIM_CUTOFF = 1e-17; // primitive pairs whose Hermite expansion block is entirely below this are dropped
+constexpr double QC_PRIM_CUTOFF = 1e-17; // primitive pairs whose Hermite expansion block is entirely below this are dropped (weak shell pairs: QC_PRIM_REL, qc_system.cpp)
 constexpr int QC_NREP = 32;             // replicas of the Fock accumulation buffer
 constexpr int QC_FX_MAXBITS = 52;       // fixed-point accumulation: finest unit 2^-52 Eh; the scale of a build follows its density (qc_fx_scale)
 constexpr double QC_SCHWARZ_TAU = 1e-12; // quartets with sqrt((ab|ab) (cd|cd)) below this are not evaluated (default)
@@ -117,7 +117,7 @@ struct QcClass {
     QcSlot *d_slots = nullptr;    // device copy of `slots`
     int slot_words = 0;           // LDS doubles per lane group
     int lds_bytes = 0;
-    int col_slot_words = 0, col_lds_bytes = 0, col_lgc = 0;   // the same for the column kernels (a pp-ket bra-major class goes through them in the set-up passes)
+    int col_slot_words = 0, col_lds_bytes = 0, col_lgc = 0;   // the same for the column kernels over the WHOLE task list: what the passes outside a build launch (a pp-ket bra-major class goes through the column kernels there)
     // bra-run mode of the low-L column classes (qc_fock_body): slots grouped by bra, batches of G padded with null slots
     int run = 0;                  // batches per workgroup (0: independent slots)
     int rb_rows = 0;              // most bra functions (na + nb) of the class: rows of the LDS row buffer

@@ -446,6 +446,9 @@ void qc_build_shards(qc_system *S, bool meta_only) {
         if (meta_only) {
             c.prim_quartets = 0; c.bytes_alg = 0; c.flops_alg = 0; c.run = 0; c.rb_rows = 0;
             class_sizes(S, c, c.tasks);
+            // (a column class in the passes that launch its WHOLE list - Schwarz pass, ERI tensor - needs these sizes, not the screened
+            // shard's: kept where class_sizes(.., c.shard) does not touch them, next to those of the p.p-ket bra-major classes)
+            if (!c.bm) { c.col_lgc = c.LGC; c.col_slot_words = c.slot_words; c.col_lds_bytes = c.lds_bytes; }
             continue;
         }
         order_tasks(S, c.tasks);

@@ -207,6 +207,9 @@ static bool pp_packed_record(const double *blk, int nab, const QcShell &A, const
     return worst <= 1e-12 * std::max(scale_e, 1e-300);
 }
 
+// a primitive pair below QC_PRIM_CUTOFF still stays if it reaches this fraction of the largest block of its shell pair (qc_build_model)
+static constexpr double QC_PRIM_REL = 1e-13;
+
 void qc_build_model(qc_system *S) {
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
     QcLap lap{"model", sdbg};
@@ -230,8 +233,13 @@ void qc_build_model(qc_system *S) {
     // O(10)), so a dropped primitive pair changes no integral by more than ~1e-16 - five orders below the 1e-10 parity
     // bar - while two-centre pairs of deeply contracted s/p shells lose a third to two thirds of their primitives.
     // (The reference evaluates them all; counts quoted as "enumerated" keep the full numbers.)
+    // A WEAK pair - largest block below 1e-4, shells far apart - keeps every primitive pair down to QC_PRIM_REL times its largest
+    // block: the absolute cut-off alone left such a pair's integrals, and its Schwarz factor sqrt(max (ab|ab)), with a RELATIVE
+    // error of up to 1e-17 / (largest block) - 1e-9 for a factor of 8e-10 - and factors are compared with thresholds over thirty
+    // orders of magnitude.  For every pair with a block of 1e-4 or more the rule drops what it dropped before; a pair whose
+    // largest block is itself below QC_PRIM_CUTOFF is not stored, as before.
     int64_t npairs_all = 0;
-    std::vector<double> blkbuf;
+    std::vector<double> blkbuf, allblk, blkmax;
     for (int a = 0; a < S->nshells; ++a)
         for (int b = 0; b <= a; ++b) {
             const QcShell &A = S->shells[a], &B = S->shells[b];
@@ -250,17 +258,26 @@ void qc_build_model(qc_system *S) {
                 d.psperm = ppermA | (ppermB << 6);
             }
             const int nab = d.na * d.nb, stride = qc_pair_stride(d.L, nab), ne = qc_nherm(d.L) * nab;
-            blkbuf.assign(stride, 0.0);
+            // every primitive pair's block first (the cut-off of a weak pair follows the pair's largest block), then the ones that stay
+            const int nij = A.nprim * B.nprim;
+            allblk.assign((size_t)nij * stride, 0.0); blkmax.assign(nij, 0.0);
+            double pairmax = 0.0;
             for (int i = 0; i < A.nprim; ++i)
                 for (int j = 0; j < B.nprim; ++j) {
                     double p, P[3];
                     const double pp = A.exps[i] + B.exps[j];
-                    std::fill(blkbuf.begin(), blkbuf.end(), 0.0);
-                    pair_hermite_matrix(A, B, i, j, half_pref / pp, blkbuf.data() + 4, &p, P);
+                    double *blk = allblk.data() + (size_t)(i * B.nprim + j) * stride;
+                    pair_hermite_matrix(A, B, i, j, half_pref / pp, blk + 4, &p, P);
                     double mx = 0.0;
-                    for (int k = 0; k < ne; ++k) mx = std::max(mx, std::fabs(blkbuf[4 + k]));
-                    if (mx < QC_PRIM_CUTOFF) continue;
-                    blkbuf[0] = p; blkbuf[1] = P[0]; blkbuf[2] = P[1]; blkbuf[3] = P[2];
+                    for (int k = 0; k < ne; ++k) mx = std::max(mx, std::fabs(blk[4 + k]));
+                    blk[0] = p; blk[1] = P[0]; blk[2] = P[1]; blk[3] = P[2];
+                    blkmax[i * B.nprim + j] = mx; pairmax = std::max(pairmax, mx);
+                }
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double mx = blkmax[i * B.nprim + j];
+                    if (mx < QC_PRIM_CUTOFF && (pairmax < QC_PRIM_CUTOFF || mx < QC_PRIM_REL * pairmax)) continue;
+                    blkbuf.assign(allblk.begin() + (size_t)(i * B.nprim + j) * stride, allblk.begin() + (size_t)(i * B.nprim + j + 1) * stride);
                     S->pairdata.insert(S->pairdata.end(), blkbuf.begin(), blkbuf.end());
                     const int nh = qc_nherm(d.L);
                     if (is_ps) {

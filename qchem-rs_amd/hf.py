@@ -47,7 +47,7 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
            "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from",
            "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability",
-           "qc_scf_excitations", "qc_scf_excitation_matrices"]
+           "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors"]
 
 
 EXCITATION_METHODS = {"cis": 0, "tdhf": 1}
@@ -226,6 +226,7 @@ def lib():
         L.qc_set_fock_mode.argtypes = [vp, C.c_int]
         L.qc_set_accumulation.argtypes = [vp, C.c_int]
         L.qc_set_schwarz.argtypes = [vp, C.c_double]
+        L.qc_schwarz_factors.argtypes = [vp, vp, vp, C.c_int64]
         L.qc_scf_tensor_ms.argtypes = [vp]; L.qc_scf_tensor_ms.restype = C.c_double
         L.qc_scf_begin_rhf.argtypes = [vp, C.POINTER(vp)]
         L.qc_scf_begin_uhf.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
@@ -384,6 +385,14 @@ class System:
     def set_schwarz(self, tau: float):
         """Schwarz threshold of the work lists (default 1e-12; 0 = every quartet, like the reference)."""
         _check(lib().qc_set_schwarz(self._h, float(tau)), "qc_set_schwarz")
+
+    def schwarz_factors(self):
+        """(ab, Q): the shell indices (A, B), A >= B, of every stored shell pair and its Schwarz factor sqrt(max (ab|ab)) as the GPU
+        computed it (qc_schwarz_factors); pairs below the primitive cut-off are not stored and do not appear."""
+        k = _check(lib().qc_schwarz_factors(self._h, None, None, 0), "qc_schwarz_factors")
+        ab = np.zeros((k, 2), np.int32); Q = np.zeros(k)
+        _check(lib().qc_schwarz_factors(self._h, ab.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p), k), "qc_schwarz_factors")
+        return ab, Q
 
     def set_shard(self, rank, nranks): _check(lib().qc_set_shard(self._h, rank, nranks), "qc_set_shard")
 

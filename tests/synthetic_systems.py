@@ -9,6 +9,10 @@ gradient term tests.  Every molecule the shipped data gives f functions lies in 
   far(R)              two centres R apart along a skew direction, single-primitive s..f shells of exponent 1.2: the Boys argument of
                       a same-centre bra against a same-centre ket is T = 1.2 R^2.
 
+  spread()            five centres strung out over 19 bohr along the skew direction (off the line by up to 1.1 bohr), contracted s and p
+                      shells on each, two pure d shells and a pure f shell: n = 37, Schwarz factors from 1e-41 to 1.4, so that screening
+                      bites at every threshold and the far pairs fall under the primitive cut-off and are not stored at all.
+
 Each builder returns (MolecularSystem, atoms); displaced() gives the same shells with one atom moved.  All are deterministic."""
 import os
 
@@ -55,6 +59,22 @@ def deep():
     return _system(DEEP_XYZ, shells)
 
 
+SPREAD_ALONG = (0.0, 2.6, 6.5, 12.0, 19.0)          # bohr along FAR_DIRECTION ...
+SPREAD_ACROSS = (0.0, 0.4, -0.7, 1.1, 0.3)          # ... and along (1, 2, -0.5)
+
+
+def spread():
+    u = np.asarray(FAR_DIRECTION) / np.linalg.norm(FAR_DIRECTION)
+    v = np.asarray((1.0, 2.0, -0.5)) / np.linalg.norm((1.0, 2.0, -0.5))
+    xyz = [tuple(a * u + b * v) for a, b in zip(SPREAD_ALONG, SPREAD_ACROSS)]
+    shells = []
+    for a in range(5):
+        shells.append((a, 0, True, [18.0 * (1 + 0.1 * a), 2.7, 0.45], [0.4, 0.7, 0.5]))
+        shells.append((a, 1, True, [3.3 * (1 + 0.07 * a), 0.55], [0.6, 0.8]))
+    shells += [(1, 2, True, [0.9], [1.0]), (3, 2, True, [0.7], [1.0]), (2, 3, True, [1.1], [1.0])]
+    return _system(xyz, shells)
+
+
 def far_distance(T):
     """the separation at which same-centre bra and ket pairs (alpha = 1.2) meet at the Boys argument T"""
     return float(np.sqrt(T / FAR_EXPONENT))
@@ -81,9 +101,9 @@ BOYS_XMAX = 41.9                     # QC_BOYS_XMAX (qc_internal.h): end of the 
 
 BUILDERS = {"tetra-pure-1": lambda: tetra(True, 1), "tetra-cart-1": lambda: tetra(False, 1),
             "tetra-pure-2": lambda: tetra(True, 2), "tetra-cart-2": lambda: tetra(False, 2),
-            "deep": deep, "far-40": lambda: far(far_distance(T_LOW)), "far-59": lambda: far(far_distance(T_HIGH))}
+            "deep": deep, "spread": spread, "far-40": lambda: far(far_distance(T_LOW)), "far-59": lambda: far(far_distance(T_HIGH))}
 SIZES = {"tetra-pure-1": (64, 9316), "tetra-cart-1": (80, 9316), "tetra-pure-2": (64, 9316), "tetra-cart-2": (80, 9316),
-         "deep": (18, 406), "far-40": (32, 666), "far-59": (32, 666)}          # (n, unique shell quartets)
+         "deep": (18, 406), "spread": (37, 4186), "far-40": (32, 666), "far-59": (32, 666)}          # (n, unique shell quartets)
 
 
 def displaced(m, atom, axis, d):
@@ -155,17 +175,22 @@ def _oracle_integrals(m):
     return _INTEGRALS[key]
 
 
-def term_energies(m, Pt, Pa, Pb, W):
-    """[Vnn, core, overlap, two-electron] of fixed AO densities, from the oracle's integrals at geometry m"""
+def term_energies(m, Pt, Pa, Pb, W, mask=None):
+    """[Vnn, core, overlap, two-electron] of fixed AO densities, from the oracle's integrals at geometry m.  mask (n, n, n, n), if
+    given, multiplies the tensor: the two-electron energy over the kept integrals alone (a screened build's energy)"""
     vnn, h, S, I = _oracle_integrals(m)
+    if mask is not None:
+        I = I * mask
     e2 = 0.5 * (np.einsum("mnls,mn,ls->", I, Pt, Pt, optimize=True) - np.einsum("mnls,ml,ns->", I, Pa, Pa, optimize=True)
                 - np.einsum("mnls,ml,ns->", I, Pb, Pb, optimize=True))
     return np.array([vnn, np.sum(Pt * h), -np.sum(W * S), e2])
 
 
-def fd_terms(m, coord, Pt, Pa, Pb, W, h=H):
+def fd_terms(m, coord, Pt, Pa, Pb, W, h=H, mask=None):
+    """five-point stencil of term_energies along one coordinate; the mask, if any, is the same at every displaced geometry (the
+    derivative of the energy over a FIXED set of kept quartets - what a gradient over screened work lists computes)"""
     atom, axis = coord
-    f = {k: term_energies(displaced(m, atom, axis, k * h), Pt, Pa, Pb, W) for k in (-2, -1, 1, 2)}
+    f = {k: term_energies(displaced(m, atom, axis, k * h), Pt, Pa, Pb, W, mask) for k in (-2, -1, 1, 2)}
     return (f[-2] - 8 * f[-1] + 8 * f[1] - f[2]) / (12 * h)
 
 

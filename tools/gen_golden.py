@@ -8,8 +8,8 @@ different restatement of the published formulas, used to pin the C oracle:
   * real solid harmonics for d/f/g from explicit textbook polynomials (the oracle uses the general closed formula),
   * per-function normalisation by numerical self-overlap,
   * a numpy SCF loop following SURVEY.md App. A with numpy.linalg.eigh.
-Run:  python tools/gen_golden.py      (about a minute; pure Python.  `python tools/gen_golden.py skew` writes
-      skew_quartets_golden.json alone)
+Run:  python tools/gen_golden.py      (minutes; pure Python.  `python tools/gen_golden.py skew` writes skew_quartets_golden.json
+      alone, `python tools/gen_golden.py schwarz` schwarz_golden.json alone)
 """
 import functools
 import itertools
@@ -335,9 +335,93 @@ def main_skew(out_dir):
     print("written", path)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/golden/schwarz_golden.json: the Schwarz factor sqrt(max_ab (ab|ab)) of every shell pair A >= B of spread() and deep()
+# (tests/synthetic_systems.py), from eri_block above; for the ss pairs a second value from the closed form
+#   (ab|ab) = sum over primitive quartets of 2 pi^{5/2} / (p q sqrt(p + q)) K_ab K_cd F_0(T),  T = p q / (p + q) |P - Q|^2,
+# in mpmath at 50 digits (normalisation included: nothing of it passes through a double before the final rounding).  Factors go down
+# to 1e-41, where only a relative comparison means anything - these two columns are what the oracle's factors are measured against.
+SCHWARZ_SYSTEMS = ("spread", "deep")
+SCHWARZ_DIGITS = 50
+
+
+def _schwarz_numeric(args):
+    name, a, b = args
+    import synthetic_systems as syn
+    shells = build_system(syn.BUILDERS[name]()[0])[1]
+    blk = eri_block(shells[a], shells[b], shells[a], shells[b])
+    na, nb = blk.shape[:2]
+    return float(math.sqrt(max(blk[i, j, i, j] for i in range(na) for j in range(nb))))
+
+
+def _schwarz_closed_form(args):
+    name, a, b = args
+    import mpmath as mp
+    import synthetic_systems as syn
+    mp.mp.dps = SCHWARZ_DIGITS
+    m = syn.BUILDERS[name]()[0]
+    first = np.concatenate([[0], np.cumsum(m.shell_nprim)])
+    pi = mp.pi
+
+    def s_shell(i):
+        """(centre, exponents, coefficients of the normalised contracted s function)"""
+        assert m.shell_L[i] == 0
+        A = [mp.mpf(float(x)) for x in m.atoms[m.shell_atom[i]].position]
+        ex = [mp.mpf(float(x)) for x in m.exponents[first[i]:first[i + 1]]]
+        co = [mp.mpf(float(c)) * (2 * e / pi) ** mp.mpf("0.75") for c, e in zip(m.coefficients[first[i]:first[i + 1]], ex)]
+        norm2 = sum(ci * cj * (pi / (ei + ej)) ** mp.mpf("1.5") for ci, ei in zip(co, ex) for cj, ej in zip(co, ex))
+        return A, ex, [c / mp.sqrt(norm2) for c in co]
+    (A, ea, ca), (B, eb, cb) = s_shell(a), s_shell(b)
+    R2 = sum((x - y) ** 2 for x, y in zip(A, B))
+    prims = []                                            # (p, P, K) of every primitive pair
+    for x, cx in zip(ea, ca):
+        for y, cy in zip(eb, cb):
+            p = x + y
+            prims.append((p, [(x * u + y * v) / p for u, v in zip(A, B)], cx * cy * mp.exp(-x * y / p * R2)))
+    total = mp.mpf(0)
+    for p, P, Kab in prims:
+        for q, Q, Kcd in prims:
+            T = p * q / (p + q) * sum((u - v) ** 2 for u, v in zip(P, Q))
+            total += 2 * pi ** mp.mpf("2.5") / (p * q * mp.sqrt(p + q)) * Kab * Kcd * mp.hyp1f1(mp.mpf("0.5"), mp.mpf("1.5"), -T)
+    return float(mp.sqrt(total))
+
+
+def main_schwarz(out_dir):
+    from multiprocessing import Pool
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import synthetic_systems as syn
+    gold = {"_generator": "tools/gen_golden.py schwarz (eri_block of the independent numpy/scipy implementation; ss pairs also in closed "
+                          "form, mpmath at %d digits; NOT reference output)" % SCHWARZ_DIGITS}
+    jobs, jobs_ss = [], []
+    for name in SCHWARZ_SYSTEMS:
+        m = syn.BUILDERS[name]()[0]
+        for a in range(m.n_shells):
+            for b in range(a + 1):
+                jobs.append((name, a, b))
+                if m.shell_L[a] == 0 and m.shell_L[b] == 0:
+                    jobs_ss.append((name, a, b))
+    with Pool(min(16, len(os.sched_getaffinity(0)))) as pool:          # (one shell pair per task: the values do not depend on the pool)
+        r_ss = pool.map_async(_schwarz_closed_form, jobs_ss, chunksize=1)
+        r = pool.map_async(_schwarz_numeric, jobs, chunksize=1)
+        q_ss, qs = r_ss.get(), r.get()
+    for name in SCHWARZ_SYSTEMS:
+        pick = lambda js, vals: ([[a, b] for n_, a, b in js if n_ == name], [v for (n_, _, _), v in zip(js, vals) if n_ == name])
+        pairs, Q = pick(jobs, qs)
+        pairs_ss, Q_ss = pick(jobs_ss, q_ss)
+        gold[name] = dict(pairs=pairs, Q=Q, ss_pairs=pairs_ss, ss_Q_closed_form=Q_ss)
+        print(name, len(pairs), "pairs, Q from %.3e to %.3e;" % (min(Q), max(Q)), len(pairs_ss), "ss pairs in closed form", flush=True)
+    path = os.path.join(out_dir, "schwarz_golden.json")
+    with open(path, "w") as f:
+        json.dump(gold, f)
+    print("written", path)
+
+
 def main():
     out_dir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
+    if sys.argv[1:] == ["schwarz"]:              # (the Schwarz file alone: the 13-primitive pairs of deep() make it a few minutes)
+        main_schwarz(out_dir)
+        return
     main_skew(out_dir)
     if sys.argv[1:] == ["skew"]:                 # (the skew file alone: seconds instead of a minute)
         return
@@ -382,6 +466,7 @@ def main():
     with open(os.path.join(out_dir, "integrals_golden.json"), "w") as f:
         json.dump(gold, f)
     print("written", os.path.join(out_dir, "integrals_golden.json"))
+    main_schwarz(out_dir)
 
 
 if __name__ == "__main__":
