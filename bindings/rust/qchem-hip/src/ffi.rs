@@ -174,6 +174,27 @@ extern "C" {
     pub fn qc_scf_excitations(st: *mut QcScfState, io: *mut QcExcitations, vectors: *mut f64) -> c_int;
     /// A + B and A - B of kind 0 (singlets) or 1 (triplets), dim x dim doubles each, either pointer null.
     pub fn qc_scf_excitation_matrices(st: *mut QcScfState, kind: c_int, apb: *mut f64, amb: *mut f64) -> c_int;
+    /// Basis functions on points (npts x 3 doubles, bohr): out npts x n, row = point.  Host only.
+    pub fn qc_basis_on_points(sys: *const QcSystem, npts: i64, xyz: *const f64, out: *mut f64) -> c_int;
+    /// A_ab = (a| 1/|r' - r| |b) for one point r (three doubles): n*n doubles, positive, exactly symmetric.  Host only.
+    pub fn qc_potential_matrix(sys: *const QcSystem, r: *const f64, out: *mut f64) -> c_int;
+    /// Stored primitive pairs of each pair order L = 0..6 (seven counts): the records the potential kernels walk per point.
+    pub fn qc_esp_records(sys: *const QcSystem, counts: *mut i64) -> c_int;
+    /// rho(r) = sum_ab D_ab phi_a(r) phi_b(r) on npts points, D n*n on the host.  GPU, batched over the points, bitwise reproducible.
+    pub fn qc_density_on_points(sys: *mut QcSystem, d: *const f64, npts: i64, xyz: *const f64, rho: *mut f64) -> c_int;
+    /// v_elec(r) = -sum_ab D_ab (a| 1/|r' - r| |b); v_nuc (nullable) = sum_A Z_A / |r - R_A|, +inf on a nucleus.
+    pub fn qc_esp_on_points(sys: *mut QcSystem, d: *const f64, npts: i64, xyz: *const f64, v_elec: *mut f64, v_nuc: *mut f64) -> c_int;
+    /// psi_k(r) for the m columns of C (n x m, leading dimension m): out m x npts.
+    pub fn qc_orbitals_on_points(sys: *mut QcSystem, m: c_int, c: *const f64, npts: i64, xyz: *const f64, out: *mut f64) -> c_int;
+    /// The same from a state's device-resident densities and orbitals; the state is left as it was.  which 0: P_alpha + P_beta, 1: P_alpha - P_beta.
+    pub fn qc_scf_density_on_points(st: *mut QcScfState, which: c_int, npts: i64, xyz: *const f64, rho: *mut f64) -> c_int;
+    /// v_total = v_nuc + v_elec of the state's total density; v_elec nullable.
+    pub fn qc_scf_esp_on_points(st: *mut QcScfState, npts: i64, xyz: *const f64, v_total: *mut f64, v_elec: *mut f64) -> c_int;
+    /// Orbitals first .. first + count - 1 of `spin` (order of qc_scf_orbital_energies): out count x npts.
+    pub fn qc_scf_orbitals_on_points(st: *mut QcScfState, spin: c_int, first: c_int, count: c_int, npts: i64, xyz: *const f64,
+                                     out: *mut f64) -> c_int;
+    /// Phase times (ms) of the handle's last point call: upload, basis values / Hermite densities, contraction, download.
+    pub fn qc_points_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

@@ -275,6 +275,47 @@ typedef struct {
 } qc_polarizability;
 int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response /* nullable: 3 x dim doubles on the host */);
 
+/* ---- the wave function in space (not in the reference): electron density, orbitals and electrostatic potential on caller-given points.
+ * Atomic units, points in bohr as npts x 3 doubles (x, y, z of a point together), f64 throughout.  With phi_a the library's basis
+ * functions (normalisation and Cartesian-to-pure transform of qc_overlap) and D a symmetric n x n matrix:
+ *   rho(r) = sum_ab D_ab phi_a(r) phi_b(r)          psi_k(r) = sum_a C_ak phi_a(r)
+ *   v_elec(r) = -sum_ab D_ab (a| 1/|r' - r| |b)     v_nuc(r) = sum_A Z_A / |r - R_A|     V(r) = v_nuc(r) + v_elec(r)
+ * v_nuc is plain IEEE division: a point on a nucleus gives +inf there (and in V), while v_elec is finite and right.
+ *
+ * Host only, no device needed (like qc_overlap / qc_dipole_matrices).  basis_on_points: out npts x n, row = point.  potential_matrix:
+ * out n x n, A_ab = (a| 1/|r' - r| |b) for one point r - the nuclear-attraction integral of a unit charge at r without its -Z; positive
+ * and exactly symmetric.  esp_records: the number of stored primitive pairs (records of the potential kernels) of each pair order
+ * L = l_a + l_b = 0..6, for work models.  QC_ERR_INVALID: null pointers, npts < 0. */
+int qc_basis_on_points(const qc_system *sys, int64_t npts, const double *xyz, double *out);
+int qc_potential_matrix(const qc_system *sys, const double r[3], double *out);
+int qc_esp_records(const qc_system *sys, int64_t counts[7]);
+
+/* GPU, density or orbitals from host pointers (the grid counterparts of qc_fock_rhf / qc_gradient).  D: n x n (a matrix that is not
+ * symmetric is taken as 1/2 (D + D^T) by the potential).  C: n x m, column = orbital, leading dimension m; out: m x npts.  v_nuc is
+ * nullable.  Points are processed in batches sized from the free device memory, so any npts works.  Primitive pairs under the
+ * library's cut-off (1e-17) are left out of the potential as they are out of the Fock build.
+ * QC_ERR_INVALID: null pointers, npts < 0, m <= 0 - checked first.  QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator.
+ * npts == 0: QC_OK, nothing is launched and nothing written.  QC_ERR_NO_DEVICE without a device.
+ * Bitwise reproducible from call to call and across fresh handles; the value of a point depends neither on the other points of the
+ * call nor on how the points are batched (every sum has a fixed order: no atomics). */
+int qc_density_on_points(qc_system *sys, const double *D, int64_t npts, const double *xyz, double *rho);
+int qc_esp_on_points(qc_system *sys, const double *D, int64_t npts, const double *xyz, double *v_elec, double *v_nuc);
+int qc_orbitals_on_points(qc_system *sys, int m, const double *C, int64_t npts, const double *xyz, double *out);
+
+/* GPU, from an SCF state: its densities (what qc_scf_density returns; available from qc_scf_begin_* on, as for qc_scf_dipole) and its
+ * orbitals (qc_scf_coefficients) are read where they lie on the device.  density: which 0 = P_alpha + P_beta, 1 = P_alpha - P_beta (an
+ * RHF state gives exactly 0).  esp: v_total = v_nuc + v_elec of P_alpha + P_beta; v_elec nullable.  orbitals: `count` orbitals of `spin`
+ * from `first`, counted from 0 in the order of qc_scf_orbital_energies; out count x npts.
+ * Errors as above; also QC_ERR_INVALID for a bad which / spin / first / count and, for the orbital call, a state before its first
+ * qc_scf_iterate.  No Fock build runs and nothing of the state is written: a following qc_scf_iterate gives the bits it would have given. */
+int qc_scf_density_on_points(qc_scf_state *st, int which, int64_t npts, const double *xyz, double *rho);
+int qc_scf_esp_on_points(qc_scf_state *st, int64_t npts, const double *xyz, double *v_total, double *v_elec);
+int qc_scf_orbitals_on_points(qc_scf_state *st, int spin, int first, int count, int64_t npts, const double *xyz, double *out);
+
+/* Phase times (ms, summed over the batches) of the handle's last point call: upload, basis values (potential: the Hermite densities of
+ * the call), contraction (GEMM + column dots; potential: the per-point kernels), download. */
+int qc_points_timings(const qc_system *sys, double ms[4]);
+
 /* ---- excited states of an RHF state (after SCF, not in the reference): configuration interaction singles (CIS, the Tamm-Dancoff
  * approximation) and time-dependent Hartree-Fock (TDHF, the random-phase approximation), singlets or triplets, at the state's last C and
  * orbital energies.  With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij delta_ab (e_a - e_i), rows and columns

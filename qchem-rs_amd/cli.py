@@ -18,6 +18,11 @@ Three additions, all opt-in:
   * `--dipole` adds the dipole moment of the converged determinant (origin 0): `dipole moment (a.u.): x y z`, the same in Debye, and
     `|mu|`; `--polarizability` adds the static dipole polarizability (coupled-perturbed HF, bohr^3): three rows and the isotropic value;
     `--json` then carries "dipole" / "polarizability" objects.  Neither combines with `--follow`.
+  * `--cube WHAT --cube-file PATH [--cube-spacing 0.2] [--cube-margin 4.0]` writes a Gaussian cube file of the converged determinant:
+    WHAT = density, spin (uhf only), esp, homo, lumo or mo:K (K from 0; uhf: alpha orbitals).  The grid is the bounding box of the nuclei
+    plus the margin, steps of the spacing (bohr) along x, y, z.  Nothing is printed for it; `--json` then carries a "cube" object (what,
+    file, shape, origin, spacing, min, max, integral = sum of the values x spacing^3).  In the esp file a nucleus closer than half a step
+    to a grid point counts at half a step (on the nucleus the potential is +inf).  Does not combine with `--follow`.
   * `rhf --cis N` / `--tdhf N` (N = 1..8) add the lowest N CIS or TDHF excited states of the converged determinant, singlets or, with
     `--triplets`, triplets: one line per state - index, energy in Eh and in eV, and for singlets the oscillator strength f; `--json` then
     carries an "excitations" list, one object per flag given (CIS first).  States that do not converge, or a reference that TDHF refuses,
@@ -32,6 +37,8 @@ import json
 import sys
 import time
 from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
 
 from . import hf
 from .loader import BasisSet, MolecularSystem
@@ -95,7 +102,22 @@ def build_parser() -> argparse.ArgumentParser:
             s.add_argument("--tdhf", type=int, default=0, metavar="N", help="also print the lowest N TDHF (RPA) excited states (1..8)")
             s.add_argument("--triplets", action="store_true", help="triplet instead of singlet excited states (requires --cis or --tdhf)")
         s.add_argument("--follow", action="store_true", help="follow instabilities downhill until the determinant is stable (at most 8 cycles)")
+        s.add_argument("--cube", default=None, metavar="WHAT",
+                       help="also write a Gaussian cube file of the converged determinant: density, " + ("spin, " if name == "uhf" else "")
+                       + "esp, homo, lumo or mo:K (K from 0" + ("; alpha orbitals)" if name == "uhf" else ")") + " (requires --cube-file)")
+        s.add_argument("--cube-file", default=None, metavar="PATH", help="where --cube writes")
+        s.add_argument("--cube-spacing", type=float, default=0.2, metavar="BOHR", help="grid spacing of --cube along x, y and z (default 0.2)")
+        s.add_argument("--cube-margin", type=float, default=4.0, metavar="BOHR", help="margin of --cube around the bounding box of the nuclei (default 4.0)")
     return p
+
+
+def cube_what(text: str, uhf: bool):
+    """("density" | "spin" | "esp" | "homo" | "lumo" | "mo", K or None) of a --cube argument, None if it is not one"""
+    if text in ("density", "esp", "homo", "lumo") or (text == "spin" and uhf):
+        return text, None
+    if text.startswith("mo:") and text[3:].isdigit():
+        return "mo", int(text[3:])
+    return None
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -115,6 +137,17 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--triplets requires --cis or --tdhf")
         if args.follow and (args.cis or args.tdhf):
             p.error("--follow cannot be combined with --cis or --tdhf")
+    if args.cube is not None:
+        if cube_what(args.cube, args.command == "uhf") is None:
+            p.error("--cube takes density, %sesp, homo, lumo or mo:K" % ("spin, " if args.command == "uhf" else ""))
+        if not args.cube_file:
+            p.error("--cube requires --cube-file")
+        if not (args.cube_spacing > 0.0) or not (args.cube_margin >= 0.0):
+            p.error("--cube-spacing must be positive and --cube-margin must not be negative")
+        if args.follow:
+            p.error("--follow cannot be combined with --cube")
+    elif args.cube_file:
+        p.error("--cube-file requires --cube")
     return args
 
 
@@ -164,6 +197,64 @@ def _print_polarizability(d: dict) -> None:
 def _properties(st, args):
     """(dipole, polarizability) JSON objects of the flags given, from the converged state"""
     return (_dipole_json(st.dipole()) if args.dipole else None, _polarizability_json(st.polarizability()) if args.polarizability else None)
+
+
+def cube_grid(system: MolecularSystem, spacing: float, margin: float):
+    """(origin (3,), shape (3,), points (nx * ny * nz, 3)) of the --cube grid: the bounding box of the nuclei plus the margin, steps of
+    `spacing` bohr along x, y, z from its low corner; points in the order of the file, x outermost and z innermost."""
+    xyz = system.coordinates()
+    origin = xyz.min(axis=0) - margin
+    shape = [int(np.floor(e / spacing + 1e-9)) + 1 for e in (xyz.max(axis=0) + margin - origin)]
+    ax = [origin[k] + spacing * np.arange(shape[k]) for k in range(3)]
+    pts = np.stack(np.meshgrid(ax[0], ax[1], ax[2], indexing="ij"), axis=-1).reshape(-1, 3)
+    return origin, shape, pts
+
+
+def write_cube(path: str, system: MolecularSystem, what: str, origin, shape, spacing: float, values) -> None:
+    """Gaussian cube: two comment lines, atom count and origin, three voxel vectors, one line per atom, then the values - x outermost, z
+    innermost, six per line, a line break after every z run.  Orbitals are written as plain volumetric data (positive atom count)."""
+    v = np.asarray(values, float).reshape(shape)
+    with open(path, "w") as f:
+        f.write("qchem-hip cube: %s\n" % what)
+        f.write("atomic units; x outermost, z innermost\n")
+        f.write("%5d%12.6f%12.6f%12.6f\n" % (len(system.atoms), origin[0], origin[1], origin[2]))
+        for k in range(3):
+            vec = [spacing if j == k else 0.0 for j in range(3)]
+            f.write("%5d%12.6f%12.6f%12.6f\n" % (shape[k], vec[0], vec[1], vec[2]))
+        for a in system.atoms:
+            f.write("%5d%12.6f%12.6f%12.6f%12.6f\n" % (a.ordinal, float(a.ordinal), a.position[0], a.position[1], a.position[2]))
+        for ix in range(shape[0]):
+            for iy in range(shape[1]):
+                run = v[ix, iy]
+                for z0 in range(0, shape[2], 6):
+                    f.write("".join("%13.5E" % x for x in run[z0:z0 + 6]) + "\n")
+
+
+def _cube(st, system: MolecularSystem, args, uhf: bool, n_alpha: int = 0) -> dict:
+    """writes the file of --cube from the converged state and returns the "cube" JSON object.  esp: the potential on a grid point closer
+    than half a step to a nucleus takes that nucleus at half a step (a grid point ON a nucleus would be +inf), everything else is the
+    library's value."""
+    what, k = cube_what(args.cube, uhf)
+    spacing = float(args.cube_spacing)
+    origin, shape, pts = cube_grid(system, spacing, float(args.cube_margin))
+    if what == "density":
+        val = st.density_on_points(pts)
+    elif what == "spin":
+        val = st.density_on_points(pts, spin=True)
+    elif what == "esp":
+        _, v_elec, _ = st.esp_on_points(pts, parts=True)
+        val = v_elec.copy()
+        for a in system.atoms:
+            val += a.ordinal / np.maximum(np.sqrt(((pts - np.asarray(a.position, float)) ** 2).sum(axis=1)), 0.5 * spacing)
+    else:
+        nocc = n_alpha if uhf and n_alpha > 0 else system.n_electrons // 2
+        k = {"homo": nocc - 1, "lumo": nocc}.get(what, k)
+        if k < 0 or k >= system.n_basis():
+            raise SystemExit("--cube %s: there is no orbital %d (%d basis functions)" % (args.cube, k, system.n_basis()))
+        val = st.orbitals_on_points(pts, k)[0]
+    write_cube(args.cube_file, system, args.cube, origin, shape, spacing, val)
+    return {"what": args.cube, "file": args.cube_file, "shape": list(shape), "origin": [float(x) for x in origin], "spacing": spacing,
+            "min": float(val.min()), "max": float(val.max()), "integral": float(val.sum() * spacing ** 3)}
 
 
 HARTREE_TO_EV = 27.211386245988
@@ -271,15 +362,15 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = grad = stab = dip = pol = None
+    mp2 = grad = stab = dip = pol = cube = None
     exc = []
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf:
+    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.cube:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
                                                              st.gradient() if args.gradient else None,
                                                              _stability(st, False) if args.stability else None) + _properties(st, args)
-                                                            + (_excitations(st, args),))
-        out, (mp2, grad, stab, dip, pol, exc) = res if res is not None else (None, (None,) * 5 + ([],))
+                                                            + (_excitations(st, args), _cube(st, system, args, False) if args.cube else None))
+        out, (mp2, grad, stab, dip, pol, exc, cube) = res if res is not None else (None, (None,) * 5 + ([], None))
     elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
@@ -324,6 +415,8 @@ def run_rhf(args) -> int:
             doc["polarizability"] = pol
         if exc:
             doc["excitations"] = exc
+        if cube is not None:
+            doc["cube"] = cube
         print(json.dumps(doc))
     if any(not e["converged"] for e in exc):
         return EXCITATIONS_FAILED
@@ -340,8 +433,8 @@ def run_uhf(args) -> int:
     if args.follow:
         return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
-    s2 = mp2 = grad = stab = dip = pol = None
-    if not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability:
+    s2 = mp2 = grad = stab = dip = pol = cube = None
+    if not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability and not args.cube:
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
@@ -363,6 +456,8 @@ def run_uhf(args) -> int:
                     if args.stability:
                         stab = _stability(st, True)
                     dip, pol = _properties(st, args)
+                    if args.cube:
+                        cube = _cube(st, system, args, True, n_alpha)
                     break
         finally:
             st.close()
@@ -404,6 +499,8 @@ def run_uhf(args) -> int:
             doc["dipole"] = dip
         if pol is not None:
             doc["polarizability"] = pol
+        if cube is not None:
+            doc["cube"] = cube
         print(json.dumps(doc))
     return 0
 

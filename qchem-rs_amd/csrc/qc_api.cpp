@@ -286,6 +286,67 @@ int qc_gradient_timings(const qc_system *S, double *ms) {
     return QC_OK;
 }
 
+// ---- values on points: the host-only pair, then the GPU entries from host matrices.  Order of the checks: arguments, sharding, an
+// empty call (QC_OK, nothing launched or written), the device.
+int qc_basis_on_points(const qc_system *S, int64_t npts, const double *xyz, double *out) {
+    if (!S || !xyz || !out || npts < 0) return QC_ERR_INVALID;
+    qc_host_basis_on_points(S, npts, xyz, out);
+    return QC_OK;
+}
+int qc_potential_matrix(const qc_system *S, const double r[3], double *out) {
+    if (!S || !r || !out) return QC_ERR_INVALID;
+    qc_host_potential_matrix(S, r, out);
+    return QC_OK;
+}
+int qc_esp_records(const qc_system *S, int64_t counts[7]) {
+    if (!S || !counts) return QC_ERR_INVALID;
+    qc_esp_record_counts(S, counts);
+    return QC_OK;
+}
+int qc_density_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *rho) {
+    if (!S || !D || !xyz || !rho || npts < 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf dD;
+    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    return qc_points_density_device(S, dD.p, npts, xyz, rho);
+}
+int qc_esp_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *v_elec, double *v_nuc) {
+    if (!S || !D || !xyz || !v_elec || npts < 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf dD;
+    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if ((rc = qc_points_esp_device(S, dD.p, npts, xyz, v_elec)) != QC_OK) return rc;
+    if (v_nuc) qc_points_vnuc(S, npts, xyz, v_nuc);
+    return QC_OK;
+}
+int qc_orbitals_on_points(qc_system *S, int m, const double *C, int64_t npts, const double *xyz, double *out) {
+    if (!S || !C || !xyz || !out || npts < 0 || m <= 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nm = (size_t)S->nbasis * m;
+    DevBuf dC;
+    if (dC.alloc(nm) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dC.p, C, nm * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    return qc_points_orbitals_device(S, m, dC.p, m, npts, xyz, out);
+}
+int qc_points_timings(const qc_system *S, double ms[4]) {
+    if (!S || !ms) return QC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = S->points_ms[i];
+    return QC_OK;
+}
+
 int qc_set_accumulation(qc_system *S, int fixed_point) {
     if (!S || (fixed_point != 0 && fixed_point != 1)) return QC_ERR_INVALID;
     S->accum_fx = fixed_point;

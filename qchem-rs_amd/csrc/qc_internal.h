@@ -269,6 +269,9 @@ struct qc_system {
     std::vector<QcClass> classes;
     QcPlanSwitches plan;
     double grad_ms[4] = {0, 0, 0, 0};         // phase times of the last gradient call (qc_gradient_timings)
+    double points_ms[4] = {0, 0, 0, 0};       // phase times of the last point call (qc_points_timings)
+    long points_batch = -1;                     // QC_POINTS_BATCH: points per batch of the point calls (0: from the free memory; -1: not read yet)
+    long points_split = -1;                     // QC_POINTS_SPLIT: largest batch whose potential splits the record list over workgroups (-1: not read yet)
     std::vector<double> pairQ;                  // Schwarz factor sqrt(max_ab (ab|ab)) of each stored pair (empty until the device pass has run)
     double imax = 0.0;                          // max pairQ^2: bound on every |(ij|kl)|
     double schwarz_tau = QC_SCHWARZ_TAU;        // 0: no screening
@@ -310,6 +313,8 @@ void qc_build_classes(qc_system *S, QcLap &lap);     // the launch classes with 
 void qc_build_shards(qc_system *S, bool meta_only = false);
 void qc_host_one_electron(const qc_system *S, int which, double *out);
 void qc_host_dipole(const qc_system *S, const double *origin /* 3 */, double *out /* 3 n*n */);
+void qc_host_basis_on_points(const qc_system *S, int64_t npts, const double *xyz, double *out /* npts x n, row = point */);
+void qc_host_potential_matrix(const qc_system *S, const double *r /* 3 */, double *out /* n*n: (a| 1/|r' - r| |b) */);
 void qc_boys_host(int nmax, double x, double *F);
 
 // Boys tables, one per total Hermite order L: row k = F_{L+j}(x_k) / j!, j = 0..7, x_k = k * QC_BOYS_DX (64-byte rows);
@@ -386,6 +391,14 @@ int qc_dipole_device(qc_system *S, const double *origin /* 3, host */, double *d
 // response (host, nullable): 3 x dim.  Runs direct Fock builds on the handle: the caller puts FockPrepSave around it.
 int qc_dipole_trace_device(qc_system *S, const double *dPa, const double *dPb, const double *dM, double *tr3);
 int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_polarizability *io, double *response);
+// values on points (qc_points.hip): density / orbitals / electronic part of the electrostatic potential on npts > 0 host points from
+// device matrices, in batches sized from the free device memory; the callers have checked the arguments.  orbitals: the m columns of dC
+// (n rows, leading dimension ldc), out m x npts.  esp needs the handle's device side (pair data, Boys tables).  vnuc: host only.
+int qc_points_density_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *rho);
+int qc_points_orbitals_device(qc_system *S, int m, const double *dC, int ldc, int64_t npts, const double *xyz, double *out);
+int qc_points_esp_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *v_elec);
+void qc_points_vnuc(const qc_system *S, int64_t npts, const double *xyz, double *v);
+void qc_esp_record_counts(const qc_system *S, int64_t counts[QC_LPAIR + 1]);
 int qc_launch_fock_classes(qc_system *S, const QcFockArgs &a, float *class_ms /*nullable*/, float *unit_ms = nullptr /*nullable, 14*/, bool nofork = false);
 // hipEvent time of a build inside an SCF pass that ran under stream assignment `gen` (no-op once the choice is made)
 void qc_fock_feedback(qc_system *S, float build_ms, unsigned gen);

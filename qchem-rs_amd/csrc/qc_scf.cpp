@@ -926,6 +926,52 @@ int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double m
     for (int k = 0; k < 3; ++k) { mu[k] = nuc[k] - tr[k]; if (mu_nuclear) mu_nuclear[k] = nuc[k]; }
     return QC_OK;
 }
+// ---- values on points from the state's own densities and orbitals (qc_points.hip): they are read where they lie on the device; no Fock
+// build runs and nothing of the state or of a prepared build is written, so a following qc_scf_iterate is unchanged.
+// which 0: P_alpha + P_beta, 1: P_alpha - P_beta (an RHF state: exactly zero, nothing is launched)
+int qc_scf_density_on_points(qc_scf_state *st, int which, int64_t npts, const double *xyz, double *rho) {
+    if (!st || !xyz || !rho || npts < 0 || which < 0 || which > 1) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    if (!st->uhf) {
+        if (which == 1) { std::fill(rho, rho + npts, 0.0); return QC_OK; }
+        return qc_points_density_device(S, st->D[0].p, npts, xyz, rho);
+    }
+    DevBuf P;
+    if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
+    qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, which ? -1.0 : 1.0, st->D[1].p, P.p);
+    return qc_points_density_device(S, P.p, npts, xyz, rho);
+}
+// v_total = v_nuc + v_elec of P_alpha + P_beta; the nuclear part on the host, as in qc_scf_dipole
+int qc_scf_esp_on_points(qc_scf_state *st, int64_t npts, const double *xyz, double *v_total, double *v_elec) {
+    if (!st || !xyz || !v_total || npts < 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    DevBuf P;
+    if (st->uhf) {
+        if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
+        qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, 1.0, st->D[1].p, P.p);
+    }
+    std::vector<double> ve(npts);
+    const int rc = qc_points_esp_device(S, st->uhf ? P.p : st->D[0].p, npts, xyz, ve.data());
+    if (rc != QC_OK) return rc;
+    qc_points_vnuc(S, npts, xyz, v_total);
+    for (int64_t k = 0; k < npts; ++k) { v_total[k] += ve[k]; if (v_elec) v_elec[k] = ve[k]; }
+    return QC_OK;
+}
+// orbitals first .. first + count - 1 of `spin`, counted from 0 in the order of qc_scf_orbital_energies; out: count x npts
+int qc_scf_orbitals_on_points(qc_scf_state *st, int spin, int first, int count, int64_t npts, const double *xyz, double *out) {
+    if (!st || !xyz || !out || npts < 0 || spin < 0 || spin > (st->uhf ? 1 : 0)) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    const int n = S->nbasis;
+    if (first < 0 || count <= 0 || first >= n || count > n - first || st->passes == 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    return qc_points_orbitals_device(S, count, st->Cs.p + (size_t)spin * n * n + first, n, npts, xyz, out);
+}
+
 int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response) {
     if (!st || !io || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
     qc_system *S = st->S;

@@ -396,3 +396,66 @@ void qc_host_dipole(const qc_system *S, const double *origin, double *out) {
                     }
         }
 }
+
+// ---- basis functions on points, on the host: out[k * n + a] = phi_a(r_k).  Per shell the contracted radial part, the Cartesian
+// monomials as running products (x^0 = 1 at a point on the centre), the rows of the shell's transform - normalisation as for the overlap.
+void qc_host_basis_on_points(const qc_system *S, int64_t npts, const double *xyz, double *out) {
+    const int n = S->nbasis;
+    for (int64_t k = 0; k < npts; ++k)
+        for (const QcShell &A : S->shells) {
+            const double d[3] = {xyz[3 * k] - A.A[0], xyz[3 * k + 1] - A.A[1], xyz[3 * k + 2] - A.A[2]};
+            const double r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+            double radial = 0.0;
+            for (int i = 0; i < A.nprim; ++i) radial += A.coefs[i] * std::exp(-A.exps[i] * r2);
+            double pw[3][QC_LMAX + 1];
+            for (int q = 0; q < 3; ++q) { pw[q][0] = 1.0; for (int i = 1; i <= A.L; ++i) pw[q][i] = pw[q][i - 1] * d[q]; }
+            double mono[qc_ncart(QC_LMAX)];
+            for (int x = 0; x < A.ncart; ++x) {
+                const unsigned char *c = qc_md_cart(A.L, x);
+                mono[x] = pw[0][c[0]] * pw[1][c[1]] * pw[2][c[2]] * radial;
+            }
+            for (int f = 0; f < A.nfunc; ++f) {
+                double v = 0.0;
+                for (int x = 0; x < A.ncart; ++x) v += A.T[(size_t)f * A.ncart + x] * mono[x];
+                out[(size_t)k * n + A.off + f] = v;
+            }
+        }
+}
+
+// ---- the potential of a unit point charge at r in the basis: out_ab = (a| 1/|r' - r| |b), positive - the nuclear-attraction sum of
+// qc_host_one_electron for one centre without its -Z; exactly symmetric (diagonal blocks: one triangle, mirrored)
+void qc_host_potential_matrix(const qc_system *S, const double *r, double *out) {
+    const int n = S->nbasis;
+    std::fill(out, out + (size_t)n * n, 0.0);
+    std::vector<double> R0;
+    for (int a = 0; a < S->nshells; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const QcShell &A = S->shells[a], &B = S->shells[b];
+            const size_t nca = A.ncart, ncb = B.ncart;
+            std::vector<double> cart(nca * ncb, 0.0);
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
+                    double PC[3];
+                    for (int k = 0; k < 3; ++k) PC[k] = (ea * A.A[k] + eb * B.A[k]) / p - r[k];
+                    E1 E[3];
+                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+                    hermite_r_host(A.L + B.L, p, PC, R0);
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
+                            cart[x * ncb + y] += cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, R0.data()));
+                        }
+                }
+            for (int fa = 0; fa < A.nfunc; ++fa)
+                for (int fb = 0; fb < B.nfunc; ++fb) {
+                    if (a == b && fb > fa) continue;
+                    double v = 0.0;
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * ncb + y];
+                    out[(size_t)(A.off + fa) * n + B.off + fb] = v;
+                    out[(size_t)(B.off + fb) * n + A.off + fa] = v;
+                }
+        }
+}

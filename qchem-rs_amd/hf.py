@@ -47,7 +47,9 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
            "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from",
            "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability",
-           "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors"]
+           "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors",
+           "qc_basis_on_points", "qc_potential_matrix", "qc_esp_records", "qc_density_on_points", "qc_esp_on_points", "qc_orbitals_on_points",
+           "qc_scf_density_on_points", "qc_scf_esp_on_points", "qc_scf_orbitals_on_points", "qc_points_timings"]
 
 
 EXCITATION_METHODS = {"cis": 0, "tdhf": 1}
@@ -256,6 +258,16 @@ def lib():
         L.qc_scf_polarizability.argtypes = [vp, C.POINTER(_Polarizability), vp]
         L.qc_scf_excitations.argtypes = [vp, C.POINTER(_Excitations), vp]
         L.qc_scf_excitation_matrices.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_basis_on_points.argtypes = [vp, C.c_int64, vp, vp]
+        L.qc_potential_matrix.argtypes = [vp, vp, vp]
+        L.qc_esp_records.argtypes = [vp, vp]
+        L.qc_density_on_points.argtypes = [vp, vp, C.c_int64, vp, vp]
+        L.qc_esp_on_points.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+        L.qc_orbitals_on_points.argtypes = [vp, C.c_int, vp, C.c_int64, vp, vp]
+        L.qc_scf_density_on_points.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
+        L.qc_scf_esp_on_points.argtypes = [vp, C.c_int64, vp, vp, vp]
+        L.qc_scf_orbitals_on_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]
+        L.qc_points_timings.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -320,6 +332,62 @@ class System:
         fn = "qc_dipole_matrices_gpu" if gpu else "qc_dipole_matrices"
         _check(getattr(lib(), fn)(self._h, _origin_ptr(origin), M.ctypes.data_as(C.c_void_p)), fn)
         return M
+
+    def basis_on_points(self, points):
+        """(npts, n): the basis functions on points (bohr; anything that reshapes to (npts, 3)) - qc_basis_on_points, host only."""
+        P = _points(points)
+        out = np.zeros((len(P), self.n))
+        _check(lib().qc_basis_on_points(self._h, len(P), _ptr(P), _ptr(out)), "qc_basis_on_points")
+        return out
+
+    def potential_matrix(self, r):
+        """(n, n): A_ab = (a| 1/|r' - r| |b), the potential of a unit charge at r in the basis (qc_potential_matrix, host only)."""
+        A = np.zeros((self.n, self.n))
+        _check(lib().qc_potential_matrix(self._h, _origin_ptr(r), _ptr(A)), "qc_potential_matrix")
+        return A
+
+    def esp_records(self):
+        """stored primitive pairs of each pair order L = 0..6: the records the potential kernels walk per point (qc_esp_records)"""
+        c = np.zeros(7, np.int64)
+        _check(lib().qc_esp_records(self._h, _ptr(c)), "qc_esp_records")
+        return c
+
+    def _density_arg(self, D, what):
+        Dm = np.ascontiguousarray(D, np.float64)
+        if Dm.size != self.n * self.n:
+            raise QcError(what + ": D must be n x n")
+        return Dm
+
+    def density_on_points(self, D, points):
+        """(npts,): rho(r) = sum_ab D_ab phi_a(r) phi_b(r) on the GPU (qc_density_on_points)."""
+        Dm, P = self._density_arg(D, "qc_density_on_points"), _points(points)
+        rho = np.zeros(len(P))
+        _check(lib().qc_density_on_points(self._h, _ptr(Dm), len(P), _ptr(P), _ptr(rho)), "qc_density_on_points")
+        return rho
+
+    def esp_on_points(self, D, points, parts: bool = False):
+        """(npts,): the electrostatic potential V = v_nuc + v_elec of the nuclei and the density D on the GPU (qc_esp_on_points);
+        parts=True: (V, v_elec, v_nuc).  A point on a nucleus has v_nuc = V = +inf and a finite v_elec."""
+        Dm, P = self._density_arg(D, "qc_esp_on_points"), _points(points)
+        ve, vn = np.zeros(len(P)), np.zeros(len(P))
+        _check(lib().qc_esp_on_points(self._h, _ptr(Dm), len(P), _ptr(P), _ptr(ve), _ptr(vn)), "qc_esp_on_points")
+        return (vn + ve, ve, vn) if parts else vn + ve
+
+    def orbitals_on_points(self, C_mo, points):
+        """(m, npts): psi_k(r) = sum_a C_ak phi_a(r) for the m columns of C (n, m) on the GPU (qc_orbitals_on_points)."""
+        Cm = np.ascontiguousarray(C_mo, np.float64)
+        if Cm.ndim == 1:
+            Cm = Cm.reshape(-1, 1)
+        if Cm.ndim != 2 or Cm.shape[0] != self.n or Cm.shape[1] < 1:
+            raise QcError("qc_orbitals_on_points: C must be n x m")
+        P = _points(points)
+        out = np.zeros((Cm.shape[1], len(P)))
+        _check(lib().qc_orbitals_on_points(self._h, Cm.shape[1], _ptr(Cm), len(P), _ptr(P), _ptr(out)), "qc_orbitals_on_points")
+        return out
+
+    def points_timings(self):
+        """Phase times (ms) of the handle's last point call: upload, basis values / Hermite densities, contraction, download."""
+        ms = np.zeros(4); _check(lib().qc_points_timings(self._h, _ptr(ms)), "qc_points_timings"); return ms
 
     def eri(self):
         I = np.zeros((self.n,) * 4); _check(lib().qc_eri_full(self._h, I.reshape(-1)), "qc_eri_full"); return I
@@ -453,6 +521,18 @@ def _origin_ptr(origin):
     return (C.c_double * 3)(*o.tolist())
 
 
+def _points(points) -> np.ndarray:
+    """(npts, 3) C-contiguous doubles from anything that reshapes to it"""
+    P = np.ascontiguousarray(points, np.float64)
+    if P.size % 3:
+        raise QcError("points must reshape to (npts, 3)")
+    return P.reshape(-1, 3)
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
 PROFILE_UNITS = 20   # QC_PROFILE_UNITS in include/qchem_hip.h
 
 
@@ -558,6 +638,42 @@ class ScfStepper:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _check(lib().qc_scf_dipole(self._st, _origin_ptr(origin), p(mu), p(nuc)), "qc_scf_dipole")
         return (mu, nuc) if nuclear else mu
+
+    def density_on_points(self, points, spin: bool = False):
+        """(npts,): the state's electron density P_alpha + P_beta on points (bohr), or with spin=True the spin density
+        P_alpha - P_beta (exactly zero for RHF) - qc_scf_density_on_points; the state is left as it was."""
+        P = _points(points)
+        rho = np.zeros(len(P))
+        _check(lib().qc_scf_density_on_points(self._st, 1 if spin else 0, len(P), _ptr(P), _ptr(rho)), "qc_scf_density_on_points")
+        return rho
+
+    def esp_on_points(self, points, parts: bool = False):
+        """(npts,): the electrostatic potential of the nuclei and the state's density (qc_scf_esp_on_points); parts=True:
+        (V, v_elec, v_nuc).  The state is left as it was."""
+        P = _points(points)
+        v, ve = np.zeros(len(P)), np.zeros(len(P))
+        _check(lib().qc_scf_esp_on_points(self._st, len(P), _ptr(P), _ptr(v), _ptr(ve)), "qc_scf_esp_on_points")
+        if not parts:
+            return v
+        with np.errstate(invalid="ignore"):
+            return v, ve, v - ve
+
+    def orbitals_on_points(self, points, orbitals, spin: int = 0):
+        """(len(orbitals), npts): MOs of the state's last Roothaan step on points; `orbitals`: an index or a sequence of indices, counted
+        from 0 in the order of orbital_energies(spin) - qc_scf_orbitals_on_points, one call per run of consecutive indices."""
+        P = _points(points)
+        idx = [int(i) for i in np.atleast_1d(np.asarray(orbitals)).reshape(-1)]
+        out = np.zeros((len(idx), len(P)))
+        j = 0
+        while j < len(idx):
+            run = 1
+            while j + run < len(idx) and idx[j + run] == idx[j] + run:
+                run += 1
+            blk = np.zeros((run, len(P)))
+            _check(lib().qc_scf_orbitals_on_points(self._st, int(spin), idx[j], run, len(P), _ptr(P), _ptr(blk)), "qc_scf_orbitals_on_points")
+            out[j:j + run] = blk
+            j += run
+        return out
 
     def polarizability(self, tol: float = 0.0, max_iterations: int = 0, response: bool = False) -> "PolarizabilityOutput":
         """Static dipole polarizability by coupled-perturbed HF at the state's last orbitals (qc_scf_polarizability); the state is left as
