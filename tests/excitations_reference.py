@@ -7,7 +7,7 @@ With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij 
   both      A - B = Delta + (ib|ja) - (ij|ab)                    A = 1/2 [(A + B) + (A - B)]
 
 CIS: A X = w X by numpy.linalg.eigh.  TDHF: (A - B)(A + B) R = w^2 R by numpy.linalg.eig, R = X + Y normalised so that R^T (A + B) R = w,
-L = X - Y = (A + B) R / w, hence L . R = X^T X - Y^T Y = 1.  Singlet transition dipoles mu_k = sqrt 2 r . X_k (CIS) or sqrt 2 r . R_k (TDHF),
+L = X - Y = (A + B) R / w, hence L . R = X^T X - Y^T Y = 1 (tdhf_sym: the same through the symmetric (A - B)^1/2 (A + B) (A - B)^1/2).  Singlet transition dipoles mu_k = sqrt 2 r . X_k (CIS) or sqrt 2 r . R_k (TDHF),
 oscillator strengths f_k = 2/3 w_k |mu_k|^2; triplets have none.
 
 spin_orbital_cis builds the CIS matrix a second time, from antisymmetrised spin-orbital integrals <pq||rs>: A_ia,jb = Delta + <aj||ib>.  Its
@@ -45,6 +45,21 @@ def tdhf(P, M):
     order = np.argsort(w2.real)
     w, V = np.sqrt(w2.real[order]), V.real[:, order]
     Rv = V * np.sqrt(w / np.einsum("ik,ij,jk->k", V, P, V))[None, :]
+    return w, Rv.T, (P @ Rv / w[None, :]).T
+
+
+def tdhf_sym(P, M):
+    """tdhf() through the symmetric problem: H = M^1/2 P M^1/2 by numpy.linalg.eigh, H T = w^2 T with |T_k| = 1, R = M^1/2 T w^-1/2 (so that
+    R^T P R = T^T H T / w = w), L = P R / w (so that L . R = 1).  Same return value, the signs of the states apart; for the dimensions at which
+    a non-symmetric eigensolver is slow and loose (proved against tdhf() in tests/test_excitations_host.py)."""
+    s, U = np.linalg.eigh(M)
+    assert s[0] > 0.0, "A - B is not positive definite"
+    Mh = (U * np.sqrt(s)[None, :]) @ U.T
+    H = Mh @ P @ Mh
+    w2, T = np.linalg.eigh(0.5 * (H + H.T))
+    assert w2[0] > 0.0, "A + B is not positive definite"
+    w = np.sqrt(w2)
+    Rv = (Mh @ T) / np.sqrt(w)[None, :]
     return w, Rv.T, (P @ Rv / w[None, :]).T
 
 

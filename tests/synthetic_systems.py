@@ -13,8 +13,14 @@ gradient term tests.  Every molecule the shipped data gives f functions lies in 
                       shells on each, two pure d shells and a pure f shell: n = 37, Schwarz factors from 1e-41 to 1.4, so that screening
                       bites at every threshold and the far pairs fall under the primitive cut-off and are not stored at all.
 
-Each builder returns (MolecularSystem, atoms); displaced() gives the same shells with one atom moved.  All are deterministic."""
+Each builder returns (MolecularSystem, atoms); displaced() gives the same shells with one atom moved.  All are deterministic.
+
+TILE_SYSTEMS are molecules of the shipped data, two of them in an edited basis, chosen by their counts of occupied and virtual orbitals
+(o, v): the excited-state assembly kernel works on 32 x 32 tiles of virtual pairs and the reduced-space kernels stride over a vector
+1024 elements at a time.  load_system() loads one of them, or any mol/basis pair of the shipped data."""
+import json
 import os
+import tempfile
 
 import numpy as np
 
@@ -104,6 +110,60 @@ BUILDERS = {"tetra-pure-1": lambda: tetra(True, 1), "tetra-cart-1": lambda: tetr
             "deep": deep, "spread": spread, "far-40": lambda: far(far_distance(T_LOW)), "far-59": lambda: far(far_distance(T_HIGH))}
 SIZES = {"tetra-pure-1": (64, 9316), "tetra-cart-1": (80, 9316), "tetra-pure-2": (64, 9316), "tetra-cart-2": (80, 9316),
          "deep": (18, 406), "spread": (37, 4186), "far-40": (32, 666), "far-59": (32, 666)}          # (n, unique shell quartets)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Molecules by orbital counts (the excited states, the stability analysis and CPHF past one tile and past dimension 1024).
+
+DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data")
+
+
+def _edit_cartesian_o_d(b):
+    """6-311++G**: the d shell of oxygen as six Cartesian functions (n + 1)"""
+    d = [sh for sh in b["elements"]["8"]["electron_shells"] if sh["angular_momentum"] == [2]]
+    assert len(d) == 1 and d[0]["function_type"] == "gto_spherical"
+    d[0]["function_type"] = "gto_cartesian"
+
+
+def _edit_cut_vtz(b):
+    """cc-pVTZ without the f shell of oxygen, without the d shell of hydrogen and with two of the three contractions of the oxygen p shell"""
+    O, H = b["elements"]["8"]["electron_shells"], b["elements"]["1"]["electron_shells"]
+    assert [sh["angular_momentum"] for sh in O] == [[0], [1], [2], [2], [3]] and [sh["angular_momentum"] for sh in H] == [[0], [1], [2]]
+    assert len(O[1]["coefficients"]) == 3
+    del O[1]["coefficients"][2]
+    del O[4]
+    del H[2]
+
+
+EDITED_BASES = {"6-311++G_st_st+cart-d": ("6-311++G_st_st", _edit_cartesian_o_d), "cc-pVTZ-cut": ("cc-pVTZ", _edit_cut_vtz)}
+
+# name -> (n, o, v); d = o v.  What each reaches: tests/test_excitations_gpu.py
+TILE_SYSTEMS = {"water/6-311++G_st_st": (36, 5, 31), "water/6-311++G_st_st+cart-d": (37, 5, 32), "water/cc-pVTZ-cut": (38, 5, 33),
+                "water/cc-pVTZ": (58, 5, 53), "ethylene/6-311++G_st_st": (72, 8, 64), "chloroform/6-31G_st_st": (77, 29, 48)}
+
+
+def load_system(name):
+    """MolecularSystem of "mol/basis": a basis file of data/basis, or one of EDITED_BASES written to a temporary directory from its file"""
+    mol, basis = name.split("/")
+    mol = os.path.join(DATA, "mol", mol + ".json")
+    if basis not in EDITED_BASES:
+        return q.MolecularSystem.load(mol, q.BasisSet.load(os.path.join(DATA, "basis", basis + ".json")))
+    parent, edit = EDITED_BASES[basis]
+    with open(os.path.join(DATA, "basis", parent + ".json")) as f:
+        b = json.load(f)
+    edit(b)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, basis + ".json")
+        with open(path, "w") as f:
+            json.dump(b, f)
+        return q.MolecularSystem.load(mol, q.BasisSet.load(path))
+
+
+def orbital_counts(m):
+    """(n, o, v) of the closed-shell determinant of a MolecularSystem"""
+    from oracle.oracle import Oracle
+    n, o = Oracle(m).n, int(np.sum(m.atomic_numbers())) // 2
+    return n, o, n - o
 
 
 def displaced(m, atom, axis, d):

@@ -12,6 +12,23 @@ the dipole matrices of tests/dipole_reference.py.
   ethylene/6-31G    26  8   18  144  triplet A + B has a negative root: an unstable reference
   benzene/STO-3G    36  21  15  315  o > 16 (second row of MFMA tiles), near-degenerate CIS singlets, a negative CIS triplet root
 
+Past one 32 x 32 tile of (a, b) in the assembly kernel (grid: pairs i >= j, ceil(v / 32), ceil(v / 32)) and past the first trip of the
+1024-thread loops of the one-workgroup subspace kernels (synthetic_systems.TILE_SYSTEMS; n, o and v are asserted before anything else, and
+tests/test_excitations_host.py proves on the CPU that A + B and A - B of all six are positive definite for both kinds, so TDHF must run):
+
+  water/6-311++G**                 36  5   31  155   one tile, one column short of full
+  water/6-311++G**, O d Cartesian  37  5   32  160   exactly one full tile; odd n
+  water/cc-pVTZ, cut               38  5   33  165   a second tile one wide: the skipped tile of the diagonal blocks, the exchange tile read from
+                                                     another tile, the mirror store and the a < v, b < v guards at their tightest
+                                                     (cut: no O f, no H d, two of the three contractions of the O p shell)
+  water/cc-pVTZ                    58  5   53  265   f functions, a partial second tile of 21
+  ethylene/6-311++G**              72  8   64  512   n > 64; two full tiles each way; the lowest triplet root of A + B is 0.0139, w_1(TDHF triplet) = 0.062
+  chloroform/6-31G**               77  29  48  1392  d > 1024 in every subspace kernel; o > 16; n > 64; 435 occupied pairs x 2 x 2 tiles
+
+(In the case names a basis goes by the name of its file: 6-311++G_st_st, 6-31G_st_st; +cart-d and -cut are the two edited ones.)  The (ij|ab) chain
+reaches these through the matrices alone: qc_quarter_second with M = o, qc_quarter_third with M = v > 32 on a batch of o^2, qc_quarter_last
+with o^2 v rows.  From d = 512 on the TDHF reference is excitations_reference.tdhf_sym.
+
 Bounds.
   matrices     |M - M_ref| <= 8 n u E + 1e-14 elementwise, u = 2.2e-16, E the four-index transform of |I| with |C_occ|, |C_virt| combined with
                the coefficients of the formula (4 E_iajb + E_ibja + E_ijab for singlet A + B, ...): the forward error of four chained
@@ -35,7 +52,17 @@ Measured on an MI355X (tol 1e-7, 8 roots or d):
   water/cc-pVDZ    1.4e-13         3.7e-14         0.020               9 (67) / 19 (82)              23 (521)                   3.0e-14
   ethylene/6-31G   1.7e-14         1.5e-14         0.026               9 (71) / 11 (80)              21 (497)                   4.5e-14
   benzene/STO-3G   4.2e-14         3.0e-14         0.011               33 (102) / 12 (85)            43 (587)                   2.4e-14
-eigvalsh(A + B)[0] against qc_scf_stability: <= 9.4e-15.  TDHF |w^2 - w_ref^2| <= 8e-14 against a-posteriori bounds of 2e-8 .. 3e-7;
+  case                    max|P - P_ref|  max|M - M_ref|  worst |.| / bound   CIS s / t rounds (products)   TDHF s / t rounds (products)   max|w_CIS - w_ref|
+  water/6-311++G**        1.1e-13         4.9e-14         0.038               31 (107) / 49 (141)           57 (1114) / 68 (1067)          4.5e-14
+  water/6-311++G** cart   5.9e-14         3.5e-14         0.037               37 (114) / 49 (133)           62 (1037) / 70 (1118)          9.3e-14
+  water/cc-pVTZ, cut      1.4e-12         4.1e-13         0.016               12 (78) / 12 (80)             28 (560) / 26 (536)            2.7e-14
+  water/cc-pVTZ           2.3e-12         1.0e-12         0.010               11 (80) / 14 (91)             31 (747) / 33 (684)            2.8e-14
+  ethylene/6-311++G**     2.9e-13         2.2e-13         0.027               17 (101) / 19 (122)           42 (996) / 36 (752)            2.3e-14
+  chloroform/6-31G**      8.4e-14         2.6e-14         0.049               16 (108) / 19 (118)           35 (774) / 31 (725)            3.4e-14
+Every solver converges within its default cap of 100 rounds on the six; the diffuse functions of 6-311++G** cost TDHF on water 57 to 70 of them.
+On these six: eigvalsh(A + B)[0] against qc_scf_stability <= 4.5e-14 (ethylene, chloroform); TDHF |w^2 - w_ref^2| <= 1.6e-12 (chloroform)
+against a-posteriori bounds of 1.8e-8 .. 3.7e-7; |L . R - 1| <= 6.0e-15; w_1 of the ethylene triplets 0.0618.
+The first table: eigvalsh(A + B)[0] against qc_scf_stability: <= 9.4e-15.  TDHF |w^2 - w_ref^2| <= 8e-14 against a-posteriori bounds of 2e-8 .. 3e-7;
 |L . R - 1| <= 4e-15.  H2: 2 sum mu_z^2 / w = 6.495195553902852 against alpha_zz = 6.495195553902849 (bound 6.6e-7)."""
 import ctypes
 import json
@@ -46,6 +73,7 @@ import pytest
 
 import dipole_reference as D
 import excitations_reference as X
+import synthetic_systems as Y
 from test_stability_gpu import _mol, converged
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +83,12 @@ U = 2.2e-16
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {"h2@1.4": ("h2@1.4/6-31G", 4, 1), "water/STO-3G": ("water/STO-3G", 7, 5), "water/6-31G": ("water/6-31G", 13, 5),
          "water/cc-pVDZ": ("water/cc-pVDZ", 24, 5), "ethylene/6-31G": ("ethylene/6-31G", 26, 8), "benzene/STO-3G": ("benzene/STO-3G", 36, 21)}
-NAMES = list(CASES)
+SMALL = list(CASES)                                  # v <= 19: one partial tile of the assembly kernel, d <= 315
+TILES = list(Y.TILE_SYSTEMS)                         # v = 31 .. 64 and d = 1392: see the module docstring
+CASES.update({name: (name, n, o) for name, (n, o, _) in Y.TILE_SYSTEMS.items()})
+NAMES = SMALL + TILES
+BIG = "chloroform/6-31G_st_st"
+SYM_FROM = 512                                       # from this dimension on the TDHF reference is excitations_reference.tdhf_sym
 _cache = {}
 
 
@@ -64,19 +97,36 @@ class Case:
 
     def __init__(self, name):
         self.name, (_, self.n, self.nocc) = name, CASES[name]
+        m = _mol(name)
         self.s, self.st, _ = converged(name)
-        assert self.s.n == self.n
+        # n, o and v before anything else: an edited basis that changed nothing, or another molecule, fails here
+        assert self.s.n == self.n and int(np.sum(m.atomic_numbers())) // 2 == self.nocc
+        if name in Y.TILE_SYSTEMS:
+            assert (self.s.n, self.nocc, self.s.n - self.nocc) == Y.TILE_SYSTEMS[name]
         self.I, self.C, self.eps = self.s.eri(), self.st.coefficients(0), self.st.orbital_energies(0)
         self.d = self.nocc * (self.n - self.nocc)
+        assert self.st.stability_dim(0) == self.d                        # (the library's own count of occupied orbitals)
         self.PM = [X.matrices_rhf(self.I, self.C, self.eps, self.nocc, k) for k in (0, 1)]
-        _, Mdip = D.overlap_and_dipole(_mol(name))
+        _, Mdip = D.overlap_and_dipole(m)
         self.r = X.rhs(self.C, self.nocc, Mdip)
-        self._cis = {}
+        self._cis, self._tdhf, self._pow = {}, {}, {}
 
     def cis_ref(self, kind):
         if kind not in self._cis:
             self._cis[kind] = X.cis(*self.PM[kind])
         return self._cis[kind]
+
+    def tdhf_ref(self, kind):
+        """(w, R, L) of the reference, ascending: numpy.linalg.eig below d = 512, the symmetric form from there on"""
+        if kind not in self._tdhf:
+            self._tdhf[kind] = (X.tdhf_sym if self.d >= SYM_FROM else X.tdhf)(*self.PM[kind])
+        return self._tdhf[kind]
+
+    def m_power(self, p):
+        """(A - B)^p, the same matrix for both kinds"""
+        if p not in self._pow:
+            self._pow[p] = _sym_power(self.PM[0][1], p)
+        return self._pow[p]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -95,9 +145,25 @@ def case(name):
 
 # ---- 1. the matrices
 
+XT = 32          # tile of qc_exc_assemble_kernel
+
+
+def _where(err, bound, o, v):
+    """the element with the worst err / bound by the coordinates of the assembly kernel: occupied block (i, j) and tile of (a, b)"""
+    if bound is None:
+        bound = np.zeros_like(err)                   # (an asymmetry: every nonzero difference is beyond its bound)
+    e = int(np.argmax(err / bound if bound.any() else err))
+    row, col = divmod(e, o * v)
+    (i, a), (j, b) = divmod(row, v), divmod(col, v)
+    bad = err > bound
+    tiles = sorted({(int(x) // XT, int(y) // XT) for x, y in zip(np.nonzero(bad)[0] % v, np.nonzero(bad)[1] % v)})
+    return ("worst element [%d, %d]: block (i, j) = (%d, %d), (a, b) = (%d, %d) in tile (%d, %d) of %d x %d; error %.3e, bound %.3e; %d elements beyond their "
+            "bound, in the tiles %s" % (row, col, i, j, a, b, a // XT, b // XT, XT, XT, err[row, col], bound[row, col], int(bad.sum()), tiles[:16]))
+
 @pytest.mark.parametrize("name", NAMES)
 def test_matrices_are_exactly_symmetric_and_match_the_reference(name):
-    """Measured maxima: the table in the module docstring (at most 4.3 % of the bound)."""
+    """Measured maxima: the tables in the module docstring (at most 4.9 % of the bound).  A failure names the occupied block (i, j) and the
+    32 x 32 tile of (a, b) of the worst element and lists the tiles that hold elements beyond their bound."""
     c = case(name)
     o, v, n = c.nocc, c.n - c.nocc, c.n
     Co, Cv, aI = np.abs(c.C[:, :o]), np.abs(c.C[:, o:]), np.abs(c.I)
@@ -114,13 +180,16 @@ def test_matrices_are_exactly_symmetric_and_match_the_reference(name):
         eP, eM = np.abs(P - Pr), np.abs(M - Mr)
         print(name, "kind", kind, "max|P - P_ref|", float(eP.max()), "max|M - M_ref|", float(eM.max()), "worst ratio to the bound", float((eP / bP).max()),
               float((eM / bM).max()), "smallest bound", float(bP.min()), float(bM.min()))
-        assert P.shape == (c.d, c.d) and np.array_equal(P, P.T) and np.array_equal(M, M.T)
-        assert np.all(eP <= bP) and np.all(eM <= bM)
+        assert P.shape == (c.d, c.d) and M.shape == (c.d, c.d)
+        assert np.array_equal(P, P.T), "A + B is not symmetric: " + _where(np.abs(P - P.T), None, o, v)
+        assert np.array_equal(M, M.T), "A - B is not symmetric: " + _where(np.abs(M - M.T), None, o, v)
+        assert np.all(eP <= bP), "A + B: " + _where(eP, bP, o, v)
+        assert np.all(eM <= bM), "A - B: " + _where(eM, bM, o, v)
 
 
 # ---- 2. against the direct-build operator of the stability analysis
 
-@pytest.mark.parametrize("name", ["water/cc-pVDZ", "ethylene/6-31G"])
+@pytest.mark.parametrize("name", ["water/cc-pVDZ", "ethylene/6-31G", "ethylene/6-311++G_st_st", BIG])
 def test_a_plus_b_is_the_operator_of_the_stability_analysis(name):
     c = case(name)
     for kind in (0, 1):
@@ -166,7 +235,7 @@ def test_cis(name, kind):
 
 # ---- 4. TDHF
 
-TDHF_CASES = [(n, 0) for n in NAMES] + [(n, 1) for n in ("h2@1.4", "water/STO-3G", "water/6-31G", "water/cc-pVDZ")]
+TDHF_CASES = [(n, 0) for n in NAMES] + [(n, 1) for n in ["h2@1.4", "water/STO-3G", "water/6-31G", "water/cc-pVDZ"] + TILES]
 
 
 def _sym_power(M, p):
@@ -181,12 +250,13 @@ def test_tdhf(name, kind):
     nroots = min(8, c.d)
     r = c.st.excitations("tdhf", kind=kind, nroots=nroots, tol=TOL, vectors=True)
     P, M = c.PM[kind]
-    w_ref = X.tdhf(P, M)[0]
+    w_ref = c.tdhf_ref(kind)[0]
     w_cis = c.cis_ref(kind)[0]
+    assert not r.reference_unstable, "TDHF refused a reference whose A + B and A - B are positive definite"
     Rv, Lv, w = r.vectors[0], r.vectors[1], r.energies
     WR = [P @ Rv[k] - w[k] * Lv[k] for k in range(nroots)]
     WL = [M @ Lv[k] - w[k] * Rv[k] for k in range(nroots)]
-    Mh, Mih = _sym_power(M, 0.5), _sym_power(M, -0.5)
+    Mh, Mih = c.m_power(0.5), c.m_power(-0.5)
     apost = np.array([np.linalg.norm(Mh @ WR[k] + w[k] * (Mih @ WL[k])) / np.linalg.norm(Mih @ Rv[k]) for k in range(nroots)])
     lr = np.abs(np.einsum("ki,ki->k", Lv, Rv) - 1.0)
     err2 = np.abs(w ** 2 - w_ref[:nroots] ** 2)
@@ -275,10 +345,10 @@ def test_tdhf_oscillator_strengths_match_the_states_of_the_reference(name):
     nroots = min(8, c.d)
     r = c.st.excitations("tdhf", kind=0, nroots=nroots, tol=TOL, vectors=True)
     P, M = c.PM[0]
-    w_ref, R_ref, _ = X.tdhf(P, M)
+    w_ref, R_ref, _ = c.tdhf_ref(0)
     mu_ref = X.transition_dipoles(c.r, R_ref)
     f_ref = X.oscillator_strengths(w_ref, mu_ref)
-    Mh, Mih, Mi = _sym_power(M, 0.5), _sym_power(M, -0.5), np.linalg.inv(M)
+    Mh, Mih, Mi = c.m_power(0.5), c.m_power(-0.5), np.linalg.inv(M)
     rq = np.linalg.norm(c.r @ Mh, axis=1)                                    # |M^1/2 r^q|
     assert r.converged
     for k in range(nroots):
@@ -320,11 +390,10 @@ def test_h2_tdhf_sum_over_states_is_the_static_polarizability():
 
 # ---- 6. determinism, and the state is left as it was
 
-@pytest.mark.parametrize("method", ["cis", "tdhf"])
-def test_a_call_is_bitwise_reproducible(method):
+def _reproducible(name, method):
     runs = []
     for handle in range(2):
-        s, st, _ = converged("water/cc-pVDZ")
+        s, st, _ = converged(name)
         for _ in range(2 - handle):
             r = st.excitations(method, kind=0, nroots=4, tol=TOL, vectors=True)
             runs.append((r.energies, r.residuals, r.vectors, r.oscillator, r.transition_dipole, (r.iterations, r.products, r.nconverged)))
@@ -333,15 +402,26 @@ def test_a_call_is_bitwise_reproducible(method):
         for a, b in zip(runs[0][:5], other[:5]):
             assert np.array_equal(a, b)
         assert runs[0][5] == other[5]
+    return runs[0]
 
 
-def test_the_state_is_left_exactly_as_it_was():
-    """Two identical states of water/cc-pVTZ (n = 58, the fused path) after 6 passes; excitations and matrices on one of them; one more
-    pass on both: energy, rms and density bit for bit equal.  MP2 before and after the calls is identical too."""
+@pytest.mark.parametrize("method", ["cis", "tdhf"])
+def test_a_call_is_bitwise_reproducible(method):
+    _reproducible("water/cc-pVDZ", method)
+
+
+@pytest.mark.parametrize("method", ["cis", "tdhf"])
+def test_a_call_is_bitwise_reproducible_past_dimension_1024(method):
+    """chloroform/6-31G**, d = 1392: the fixed-order sums of the one-workgroup kernels over two trips of 1024, 435 occupied pairs x 2 x 2 tiles."""
+    energies, residuals = _reproducible(BIG, method)[:2]
+    assert np.all(energies > 0.1) and np.all(residuals <= TOL)           # (two runs that both failed alike would be equal too)
+
+
+def _left_as_it_was(name):
     import qchem_rs_amd as q
     out = []
     for touch in (False, True):
-        s = q.System(_mol("water/cc-pVTZ"))
+        s = q.System(_mol(name))
         st = q.ScfStepper(s)
         for _ in range(6):
             st.iterate()
@@ -356,8 +436,19 @@ def test_the_state_is_left_exactly_as_it_was():
         out.append((e, rms, st.density(0)))
         st.close(); s.close()
     (e0, r0, D0), (e1, r1, D1) = out
-    print("water/cc-pVTZ", e0, e1, r0, r1)
+    print(name, e0, e1, r0, r1)
     assert e0 == e1 and r0 == r1 and np.array_equal(D0, D1)
+
+
+def test_the_state_is_left_exactly_as_it_was():
+    """Two identical states of water/cc-pVTZ (n = 58, the fused path) after 6 passes; excitations and matrices on one of them; one more
+    pass on both: energy, rms and density bit for bit equal.  MP2 before and after the calls is identical too."""
+    _left_as_it_was("water/cc-pVTZ")
+
+
+def test_the_state_is_left_exactly_as_it_was_past_dimension_1024():
+    """The same on chloroform/6-31G** (n = 77, the generic path; d = 1392)."""
+    _left_as_it_was(BIG)
 
 
 # ---- 7. errors on a live state

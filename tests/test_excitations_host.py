@@ -11,7 +11,11 @@ of H2 at 1.4 bohr / 6-31G, water/STO-3G, water_crawford/STO-3G and water/cc-pVDZ
      finite-field test pins (tests/test_dipole_host.py).  Bound 1e-10 (a non-symmetric eigenproblem against a linear solve); measured
      2.7e-15 (H2), 5.9e-14 (water/STO-3G), 7.5e-13 (water/cc-pVDZ).
   4. Pinned excitation energies and oscillator strengths, produced by an independent script: reproduced to 1e-8.
-  5. The C surface without a device: symbols, struct size, null arguments, and the command-line flags."""
+  5. The C surface without a device: symbols, struct size, null arguments, and the command-line flags.
+  6. tdhf_sym (the symmetric form, for the dimensions at which numpy.linalg.eig is slow and loose) equals tdhf: w to 1e-10, R and L up to sign to 1e-8.
+  7. The six systems of synthetic_systems.TILE_SYSTEMS (numpy RHF with DIIS, max|dD| <= 1e-10) have the n, o and v the GPU tests count on, A + B and
+     A - B positive definite for singlets and triplets (so TDHF must run on every one of them), their nine lowest CIS roots more than 1e-3 Eh
+     apart, and A + B equal to hessian_rhf to 1e-12."""
 import ctypes
 import os
 
@@ -22,6 +26,7 @@ from conftest import load_system
 import dipole_reference as D
 import excitations_reference as X
 import stability_reference as R
+import synthetic_systems as Y
 from test_dipole_host import _h2, _numpy_rhf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -114,6 +119,97 @@ def test_pinned_values(states, name):
         err = float(np.abs(f[:len(want)] - np.array(want)).max())
         print(name, method, "f", f[:len(want)].tolist(), "err", err)
         assert err <= 1e-8
+
+
+@pytest.mark.parametrize("name", list(SYSTEMS))
+def test_symmetric_tdhf_reference_is_the_non_symmetric_one(states, name):
+    """w to 1e-10, R and L up to the sign of a state to 1e-8 (the issue's bounds; every root of these systems is simple).
+    Measured: w 2e-16 .. 1e-13, vectors 3e-16 .. 4.6e-12."""
+    c = states[name]
+    for kind in (0, 1):
+        P, M = c["PM"][kind]
+        w, Rv, Lv = X.tdhf(P, M)
+        ws, Rs, Ls = X.tdhf_sym(P, M)
+        sign = np.sign(np.einsum("ki,ki->k", Rv, Rs))
+        ew = float(np.abs(w - ws).max())
+        eR, eL = float(np.abs(Rv - sign[:, None] * Rs).max()), float(np.abs(Lv - sign[:, None] * Ls).max())
+        norm = max(float(np.abs(np.einsum("ki,ij,kj->k", Rs, P, Rs) - ws).max()), float(np.abs(np.einsum("ki,ki->k", Ls, Rs) - 1.0).max()))
+        print(name, "kind", kind, "|w - w_sym|", ew, "|R - R_sym|", eR, "|L - L_sym|", eL, "|R^T P R - w|, |L.R - 1|", norm)
+        assert ws.shape == w.shape and Rs.shape == Rv.shape and Ls.shape == Lv.shape and np.all(np.diff(ws) >= 0)
+        assert ew <= 1e-10 and eR <= 1e-8 and eL <= 1e-8 and norm <= 1e-10
+
+
+# ---- the systems past one assembly tile and past dimension 1024: what the GPU tests rest on
+
+def _numpy_rhf_diis(S, H, I, nocc, eps=1e-10):
+    """(C, eps) of an RHF state converged to max|dD| <= eps with Pulay's DIIS on F D S - S D F (eight Fock matrices); the orbitals are
+    those of the Fock matrix of the final density, not of an extrapolated one."""
+    n = S.shape[0]
+    G2 = (I - 0.5 * I.transpose(0, 2, 1, 3)).reshape(n * n, n * n)       # G[D] = J[D] - K[D] / 2 as one matrix-vector product
+    fock = lambda Dm: H + (G2 @ Dm.reshape(-1)).reshape(n, n)
+    C, _ = R.orbitals(H, S)
+    Dm = 2.0 * C[:, :nocc] @ C[:, :nocc].T
+    Fs, Es = [], []
+    for _ in range(300):
+        F = fock(Dm)
+        Fs.append(F); Es.append(F @ Dm @ S - S @ Dm @ F)
+        Fs, Es = Fs[-8:], Es[-8:]
+        if len(Fs) > 1:
+            k = len(Fs)
+            B = -np.ones((k + 1, k + 1)); B[k, k] = 0.0
+            B[:k, :k] = [[float(np.sum(a * b)) for b in Es] for a in Es]
+            rhs = np.zeros(k + 1); rhs[k] = -1.0
+            F = sum(ci * Fi for ci, Fi in zip(np.linalg.lstsq(B, rhs, rcond=None)[0][:k], Fs))
+        C, _ = R.orbitals(F, S)
+        Dn = 2.0 * C[:, :nocc] @ C[:, :nocc].T
+        done = np.abs(Dn - Dm).max() <= eps
+        Dm = Dn
+        if done:
+            return R.orbitals(fock(Dm), S)
+    raise AssertionError("numpy RHF with DIIS did not converge")
+
+
+@pytest.fixture(scope="module")
+def tile_states():
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            from oracle.oracle import Oracle
+            m = Y.load_system(name)
+            o = Oracle(m)
+            nocc = int(np.sum(m.atomic_numbers())) // 2
+            I = Y.oracle_tensor(o)
+            C, eps = _numpy_rhf_diis(o.overlap(), o.kinetic() + o.nuclear(), I, nocc)
+            cache.clear()                                                  # (one tensor of n = 77 at a time)
+            cache[name] = (o.n, nocc, I, C, eps)
+        return cache[name]
+    return get
+
+
+# min eig(A + B) singlet / triplet and min eig(A - B), computed once on the CPU: pinned to 2e-3 so that a changed system shows
+TILE_MINIMA = {"water/6-311++G_st_st": (0.387, 0.353, 0.375), "water/6-311++G_st_st+cart-d": (0.387, 0.353, 0.375), "water/cc-pVTZ-cut": (0.417, 0.370, 0.398),
+               "water/cc-pVTZ": (0.413, 0.364, 0.394), "ethylene/6-311++G_st_st": (0.220, 0.0139, 0.200), "chloroform/6-31G_st_st": (0.187, 0.104, 0.163)}
+
+
+@pytest.mark.parametrize("name", list(Y.TILE_SYSTEMS))
+def test_tile_systems_have_their_orbital_counts_and_stable_separated_states(tile_states, name):
+    n, nocc, I, C, eps = tile_states(name)
+    want = Y.TILE_SYSTEMS[name]
+    assert (n, nocc, n - nocc) == want                                      # (first: an edit of a basis that changes nothing fails here)
+    for kind in (0, 1):
+        P, M = X.matrices_rhf(I, C, eps, nocc, kind)
+        lo_p, lo_m = float(np.linalg.eigvalsh(P)[0]), float(np.linalg.eigvalsh(M)[0])
+        w = np.linalg.eigvalsh(0.5 * (P + M))
+        gap = float(np.diff(w[:9]).min())
+        err = float(np.abs(P - R.hessian_rhf(I, C, eps, nocc, kind)).max())
+        print(name, "n o v d", n, nocc, n - nocc, P.shape[0], "kind", kind, "min eig(A + B)", lo_p, "min eig(A - B)", lo_m, "smallest gap of the nine lowest CIS roots", gap,
+              "|A + B - hessian_rhf|", err)
+        assert P.shape == (want[1] * want[2],) * 2
+        assert lo_p > 0.0 and lo_m > 0.0
+        assert gap > 1e-3
+        assert err <= 1e-12
+        assert abs(lo_p - TILE_MINIMA[name][kind]) <= 2e-3 and abs(lo_m - TILE_MINIMA[name][2]) <= 2e-3
 
 
 # ---- the C surface without a device

@@ -13,7 +13,10 @@ Measured on an MI355X (max |alpha - alpha_ref| / smallest bound / lambda_min / r
   water/cc-pVDZ UHF (5, 5)   4.9e-15  8.3e-7   0.376  10  27     benzene/6-31G RHF          6.1e-11  8.5e-5   0.0099 17  43
   oxygen/cc-pVDZ (9, 7) min  2.5e-14  1.6e-5   0.0229 13  33     UHF against RHF water      1.0e-10
   water/STO-3G RHF (dim 10)  2.2e-15  1.2e-8   0.736   4   9
-  h_atom/6-311++G** (1, 0)   2.2e-16  3.4e-7   0.381   1   3   (begun from its self-consistent density, see begun_converged)"""
+  h_atom/6-311++G** (1, 0)   2.2e-16  3.4e-7   0.381   1   3   (begun from its self-consistent density, see begun_converged)
+  chloroform/6-31G** RHF     1.1e-13  5.9e-6   0.187  14  39     the same to 1e-9           1.1e-13  9.7e-8   0.187  16  46
+chloroform/6-31G** has dim = 29 x 48 = 1392 > 1024, the length of one trip of the expand kernel's loops (error / bound: 1.9e-8 at tol 1e-7,
+1.2e-6 at 1e-9; |H U - r| / (10 tol): 0.033 and 0.084)."""
 import ctypes
 
 import numpy as np
@@ -21,6 +24,7 @@ import pytest
 
 from conftest import load_system
 import dipole_reference as D
+import synthetic_systems as Y
 from test_stability_gpu import _mol, converged, h2
 
 pytestmark = pytest.mark.gpu
@@ -39,26 +43,27 @@ def reference(s, st, m, uhf, nocc):
     return a, H, r, 4.0
 
 
-def bound(H, r, c, alpha_ref):
+def bound(H, r, c, alpha_ref, tol=TOL):
     lam = float(np.linalg.eigvalsh(H)[0])
     assert lam > 0, "the case is unsuitable: (A + B) is not positive definite (lambda_min %g)" % lam
     rn = np.linalg.norm(r, axis=1)
-    return c * rn[:, None] * TOL / lam + 1e-9 * float(np.abs(alpha_ref).max()), lam
+    return c * rn[:, None] * tol / lam + 1e-9 * float(np.abs(alpha_ref).max()), lam
 
 
-def check(name, s, st, m, uhf, nocc):
-    p = st.polarizability(tol=TOL, response=True)
-    a_ref, H, r, c = reference(s, st, m, uhf, nocc)
-    B, lam = bound(H, r, c, a_ref)
+def check(name, s, st, m, uhf, nocc, tol=TOL, ref=None):
+    """ref: the value of reference() of a call before, for a second solve on the same state"""
+    p = st.polarizability(tol=tol, response=True)
+    a_ref, H, r, c = ref or reference(s, st, m, uhf, nocc)
+    B, lam = bound(H, r, c, a_ref, tol)
     err = np.abs(p.alpha - a_ref)
     resid = [float(np.linalg.norm(H @ p.response[q] - r[q])) for q in range(3)]
     print(name, "uhf" if uhf else "rhf", "alpha", p.alpha.tolist(), "ref", a_ref.tolist(), "max err", float(err.max()), "bound", B.tolist(), "lambda_min", lam,
           "residuals", p.residuals, "|H U - r|", resid, "asymmetry", p.asymmetry, "iterations", p.iterations, "builds", p.builds, "ms", p.ms_total, p.ms_builds)
-    assert p.converged and np.all(p.residuals <= TOL)
+    assert p.converged and np.all(p.residuals <= tol)
     assert np.all(err <= B)
     assert p.asymmetry <= float(B.max())
     assert np.array_equal(p.alpha, p.alpha.T) and abs(p.isotropic - np.trace(p.alpha) / 3.0) <= 1e-15 * abs(p.isotropic)
-    assert p.response.shape == (3, H.shape[0]) and max(resid) <= 10 * TOL
+    assert p.response.shape == (3, H.shape[0]) and max(resid) <= 10 * tol
     return p, a_ref, B
 
 
@@ -155,6 +160,23 @@ def test_benzene_needs_more_vectors_than_the_subspace_holds_at_once():
     try:
         assert st.stability_dim(0) == 21 * 45 > 40
         p, _, _ = check("benzene/6-31G", s, st, load_system("benzene", "6-31G"), False, (21, 21))
+        assert p.builds > 40                                             # (more vectors than the subspace holds: the collapse has run)
+    finally:
+        st.close(); s.close()
+
+
+def test_chloroform_has_vectors_longer_than_one_stride_of_the_expand_kernel():
+    """dim = 29 x 48 = 1392 > 1024: the second trip of every loop of the one-workgroup expand kernel, with three right-hand sides.  At tol 1e-7
+    the solver is done after 13 rounds and 39 builds, one vector short of a full subspace, so the collapse does not run; the same state solved to
+    1e-9 (the same bound with that tol) needs more than 40 builds, and the collapse runs on vectors of 1392."""
+    name = "chloroform/6-31G_st_st"
+    s, st, _ = converged(name)
+    try:
+        assert (s.n, st.stability_dim(0)) == (77, 1392) and Y.TILE_SYSTEMS[name] == (77, 29, 48)
+        m = _mol(name)
+        ref = reference(s, st, m, False, (29, 29))
+        check(name, s, st, m, False, (29, 29), ref=ref)
+        p, _, _ = check(name + " to 1e-9", s, st, m, False, (29, 29), tol=1e-9, ref=ref)
         assert p.builds > 40                                             # (more vectors than the subspace holds: the collapse has run)
     finally:
         st.close(); s.close()
