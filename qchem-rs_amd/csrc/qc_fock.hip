@@ -34,9 +34,7 @@ static QcKernelArgs base_args(qc_system *S, const QcFockArgs &fa) {
 
 static Seg seg_of(const QcClass &c) {
     if (c.bm) return Seg{&c, nullptr, (int)c.bundles.size(), c.d_bundles, c.d_ketlist, c.lds_bytes};
-    Seg sg{&c, c.d_slots, (int)c.slots.size()};
-    sg.run = c.run; sg.rb_rows = c.rb_rows;
-    return sg;
+    return Seg{&c, c.d_slots, (int)c.slots.size()};
 }
 
 void qc_drop_launch_plan(qc_system *S) { delete S->launch_plan; S->launch_plan = nullptr; }
@@ -88,21 +86,11 @@ static int launch_segments(qc_system *S, int unit, const std::vector<Seg> &segs,
     for (const Seg &sg : segs) {
         const int G = 64 >> sg.c->LGC;
         const int waves = (sg.nslots + G - 1) / G;
-        int seg_lds = sg.c->lds_bytes;
-        t.seg_run[k] = sg.run; t.seg_rbrows[k] = 0;
-        if (sg.run > 0) {
-            grid += (waves + sg.run - 1) / sg.run;
-            // row buffer of the wave: exchange rows per spin + the J_ab block; only while it leaves the class its waves per CU
-            const int rb_bytes = ((base.Dk1 ? 2 : 1) * sg.rb_rows * S->nbasis + sg.rb_rows * sg.rb_rows) * 8;
-            static const bool no_rb = getenv("QC_NO_ROWBUF") != nullptr;             // (A/B switch)
-            if (!no_rb && base.eri_out == nullptr && base.schwarz_out == nullptr && rb_bytes <= 6 * 1024) { t.seg_rbrows[k] = sg.rb_rows; seg_lds += rb_bytes; }
-        } else {
-            static const int per_cu = getenv("QC_TIER_WG_PER_CU") ? std::max(1, atoi(getenv("QC_TIER_WG_PER_CU"))) : 32;     // (A/B switch)
-            grid += std::min(waves, 256 * per_cu);
-        }
+        static const int per_cu = getenv("QC_TIER_WG_PER_CU") ? std::max(1, atoi(getenv("QC_TIER_WG_PER_CU"))) : 32;     // (A/B switch)
+        grid += std::min(waves, 256 * per_cu);
         t.seg_end[k] = grid; t.seg_code[k] = (sg.c->LCD << 4) | sg.c->LGC; t.seg_lab[k] = sg.c->LAB;
         t.seg_nslots[k] = sg.nslots; t.seg_words[k] = sg.c->slot_words; t.seg_slots[k] = sg.d_slots;
-        lds = std::max(lds, seg_lds);
+        lds = std::max(lds, sg.c->lds_bytes);
         ++k;
     }
     t.nseg = k;

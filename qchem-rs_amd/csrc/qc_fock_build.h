@@ -14,8 +14,7 @@ struct EventList {
 };
 
 // segment of one launch: a class bucket with its slots (column kernels) or bundles (bra-major kernels)
-struct Seg { const QcClass *c; const QcSlot *d_slots; int nslots; const QcBundleDev *d_bundles = nullptr; const QcKetUnit *d_ketlist = nullptr; int lds = 0;
-             int run = 0, rb_rows = 0; };     // (bra-run mode of the class's own slot list; the set-up passes bring independent slots)
+struct Seg { const QcClass *c; const QcSlot *d_slots; int nslots; const QcBundleDev *d_bundles = nullptr; const QcKetUnit *d_ketlist = nullptr; int lds = 0; };
 
 struct QcLaunchPlan {
     std::vector<std::vector<int>> units; std::vector<std::vector<Seg>> segs;

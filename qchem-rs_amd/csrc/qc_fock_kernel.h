@@ -317,17 +317,254 @@ __device__ __forceinline__ void qc_build_r(double *__restrict__ Rw, const int2 *
     }
 }
 
-// `run` > 0 (bra-run mode, low-L classes): the slot list is grouped by bra pair - every batch of G slots shares one bra, padded with
-// null slots (ket < 0) - and workgroup `blk` works through the `run` consecutive batches [blk run, (blk + 1) run).  With `rb_rows` > 0 the
-// wave keeps the targets that belong to the bra - J_ab and the exchange rows of the bra's functions, (na + nb) x n per spin - in an
-// LDS row buffer across the batches of one bra and flushes what is non-zero when the bra changes: one global atomic (pair) and one
-// fixed-point conversion per touched element and bra run instead of per slot (the memory-side atomics of these classes were a third
-// of a benzene build's; cf. the bra-major kernels).  run == 0: slots are independent, grid-stride over batches.
+// ---- the body of the column kernels.  qc_fock_body (below) is the batch loop; carved out of it as functions of their own, inlined into
+// it: the matrix-core contraction and the Schwarz and tensor outputs.  Staging, the VALU contractions (hoisted low-L form, cooperative
+// R table, their shared step 3) and the two digestion forms stand in the body itself: moving any of them, text unchanged, cost some
+// column kernel registers or scratch (profiles/r15_column_body_kernel_resources.md).
+
+// -DQC_PHASE_TIMING: clock ticks per phase of the body, QC_T(i) closes phase i (the pieces take the clock as `clk`)
+#ifdef QC_PHASE_TIMING
+struct QcPhaseClock {
+    long long tph[8] = {}, tlast = 0;
+    __device__ __forceinline__ void start() { tlast = wall_clock64(); }
+    __device__ __forceinline__ void stamp(int i) { const long long t_ = wall_clock64(); tph[i] += t_ - tlast; tlast = t_; }
+};
+#else
+struct QcPhaseClock {
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void stamp(int) {}
+};
+#endif
+#define QC_T(i) clk.stamp(i)
+
+// What the carved-out pieces share about the slot that the lane's group works on in this batch (filled by the body from its own locals,
+// passed by const reference: it dissolves after inlining)
+struct QcSlotView {
+    int lane, li, n;              // lane of the wave, lane of the group
+    const int2 *plan;             // recurrence plan of the cooperative R table (LDS)
+    QcSlot sl;
+    QcPairDesc pb, pk;
+    int nb, nd, nab, ncd;
+    double *Rw, *Iblk;            // the group's LDS region: R tables, then the block I[nab][ncd]
+    const double *braBase, *ketBase;
+    int strideB, strideK;
+    int len, cbeg, cend;          // primitive quartets and ket columns [cbeg, cend) of the slot (0 when the group is idle)
+};
+
+// Contraction, high-order kets (LCD >= 4) under bras of L >= 3: both Hermite contractions on the matrix cores.  One slot per wave.
+//   step 2  W[h1][c] += sum_h2 Rm[h1][h2] Ee[h2][c],  Rm[h1][h2] = (-1)^{|h2|} R_{h1+h2},  Ee = E_cd,kl * pref
+//   step 3  I[ab][c] += sum_h1 Et[ab][h1] W[h1][c]
+// as v_mfma_f64_16x16x4 tiles.  The VALU form reads one R value from LDS per FMA in every lane (7056 reads
+// per lane for (ff|ff)); here the gathered Rm fragment is spread over the wave (110 reads per lane) and the W
+// accumulators - result layout C[4r + (l >> 4)][l & 15] - are, register for register, the B operands
+// B[k = l >> 4][j = l & 15] of step 3's k-steps, so nothing moves between the two products.
+template <int LAB, int LCD>
+__device__ __forceinline__ void qc_contract_mfma(const QcKernelArgs &a, const QcSlotView &v, QcPhaseClock &clk) {
+    constexpr int L = LAB + LCD, HAB = qc_nherm(LAB), HCD = qc_nherm(LCD);
+    typedef double qc_d4 __attribute__((ext_vector_type(4)));
+    constexpr int MT = (HAB + 15) / 16, KS = (HCD + 3) / 4;
+    const int lane = v.lane, nab = v.nab, ncd = v.ncd, strideB = v.strideB, strideK = v.strideK, len = v.len, cbeg = v.cbeg, cend = v.cend;
+    const QcSlot &sl = v.sl;
+    const QcPairDesc &pb = v.pb, &pk = v.pk;
+    double *const Rw = v.Rw, *const Iblk = v.Iblk;
+    const double *braBase = v.braBase, *ketBase = v.ketBase;
+    const int2 *const plan = v.plan;
+    const int i16 = lane & 15, q4 = lane >> 4;
+    const uint4 *__restrict__ gi = a.gidx + qc_gidx_off(LAB, LCD) + lane;         // this lane's gather records, one per k-step
+    const char *const Rb = reinterpret_cast<const char *>(Rw);
+    const double *__restrict__ pdT = a.pairdataT;
+    const int K_cd = pk.K;
+    // One pass over the slot's primitive quartets for the column tiles [col0, col0 + 16 NT); NT is a compile-time constant of the
+    // instance (a run-time bound put a branch around every matrix instruction)
+    auto tile = [&](auto ntc, const int col0) {
+        constexpr int NT = decltype(ntc)::value;
+        constexpr bool AHEAD = MT * NT <= 12;           // registers for a second set of step-3 A fragments
+        qc_d4 Wacc[MT][NT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) Wacc[mt][nt] = qc_d4{0.0, 0.0, 0.0, 0.0};
+        // A fragments of step 3, row tile `it`: Et[ab][h1], shared by the column tiles (clamped loads, masked to zero outside the block)
+        auto load_e = [&](const double *__restrict__ Et, int it, double (&av)[MT][4]) {
+            const int ab = 16 * it + i16;
+            const double *row = Et + (size_t)min(ab, nab - 1) * HAB;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int h1 = 16 * mt + 4 * r + q4;
+                    const double val = row[min(h1, HAB - 1)];
+                    av[mt][r] = (ab < nab && h1 < HAB) ? val : 0.0;
+                }
+        };
+        // step 3 for the bra primitive pair whose expansion block is Et; avE = the fragments of row tile 0 (requested by the caller
+        // before the Boys function of the pair's last primitive quartet); with registers to spare the next tile's travel one ahead
+        auto flush = [&](const double *__restrict__ Et, double (&avE)[MT][4]) {
+            const int MI = (nab + 15) / 16;
+            for (int it = 0; it < MI; ++it) {
+                double avN[AHEAD ? MT : 1][4];
+                if constexpr (AHEAD) load_e(Et, min(it + 1, MI - 1), avN);
+                else { if (it > 0) load_e(Et, it, avE); }
+                __builtin_amdgcn_sched_barrier(0);
+                qc_d4 acc[NT][2];                       // two accumulators per column tile: consecutive matrix instructions are independent
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) acc[nt][0] = acc[nt][1] = qc_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+                            acc[nt][r & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(avE[mt][r], Wacc[mt][nt][r], acc[nt][r & 1], 0, 0, 0);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const int c = col0 + 16 * nt + i16;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int abr = 16 * it + q4 + 4 * r;
+                        if (abr < nab && c < cend) Iblk[abr * ncd + c] += acc[nt][0][r] + acc[nt][1][r];     // this lane alone owns the element
+                    }
+                }
+                if constexpr (AHEAD) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) avE[mt][r] = avN[mt][r];
+                }
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) Wacc[mt][nt] = qc_d4{0.0, 0.0, 0.0, 0.0};
+        };
+        int ij = sl.lo / K_cd, kl = sl.lo - ij * K_cd;
+        for (int itq = 0; itq < len; ++itq) {
+            QC_T(4);
+            const bool last = kl == K_cd - 1 || itq == len - 1;      // of this bra primitive pair: step 3 follows
+            const double *__restrict__ Et = pdT + pb.doff + (size_t)ij * strideB + 4;     // [ab][h]
+            const double4 cb = *reinterpret_cast<const double4 *>(braBase + (size_t)ij * strideB);
+            const double *ket = ketBase + (size_t)kl * strideK;
+            const double4 ck = *reinterpret_cast<const double4 *>(ket);
+            double avE[MT][4];
+            if (last) load_e(Et, 0, avE);
+            const double p = cb.x, q = ck.x;
+            const double X = cb.y - ck.y, Y = cb.z - ck.z, Z = cb.w - ck.w;
+            const double pref = qc_rsqrt(p + q);
+            const double alpha = p * q * (pref * pref);
+            // Operand fragments of k-step ks.  B = the column tiles of the ket block (plain loads, clamped: rows past HCD meet a zero
+            // A value, columns past ncd are never read back); A = the gathered, signed R values: which LDS word lane l reads for row
+            // tile mt comes from a host-built record (qc_build_gidx), eight u16 per k-step and lane.
+            const double *Ecd = ket + 4;
+            auto load_b = [&](int ks, double (&bv)[NT]) {
+                const int h2 = min(4 * ks + q4, HCD - 1);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) bv[nt] = Ecd[(size_t)h2 * ncd + min(col0 + 16 * nt + i16, ncd - 1)];
+            };
+            auto gather = [&](const uint4 rec, double (&raw)[MT]) {
+                const unsigned w[3] = {rec.x, rec.y, rec.z};
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const unsigned off = (mt & 1) ? (w[mt >> 1] >> 16) : (w[mt >> 1] & 0xffffu);
+                    raw[mt] = *reinterpret_cast<const double *>(Rb + off);
+                }
+            };
+            auto scale = [&](const unsigned recw, const double (&raw)[MT], double (&av)[MT]) {
+                const unsigned fl = recw >> 16;
+                const double sg = (fl & 2u) ? ((fl & 1u) ? -pref : pref) : 0.0;          // sign of the ket order, scale, validity
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) av[mt] = sg * raw[mt];
+            };
+            // B fragments and gather records travel PD k-steps ahead of their matrix instructions (a k-step is MT NT of them, 64 cycles
+            // each; a ket block comes from the L2 / the memory-side cache in 500-1200): the first PD are requested before the Boys
+            // function and the R table, a buffer is refilled as soon as its instructions have issued.  The R values of step ks + 1
+            // are read from LDS before the instructions of step ks and scaled after them.
+            constexpr int PD = MT * NT >= 12 ? 3 : (MT * NT >= 6 ? 4 : 6);
+            double bv[PD][NT], avA[MT];
+            uint4 gr[PD];
+#pragma unroll
+            for (int d = 0; d < PD; ++d) { load_b(min(d, KS - 1), bv[d]); gr[d] = gi[64 * min(d + 1, KS - 1)]; }
+            const uint4 gr0 = gi[0];
+            double F[L + 1];
+            qc_boys<L>(alpha * (X * X + Y * Y + Z * Z), a.boys, F);
+            __syncthreads();                  // previous iteration's readers of Rw are done
+            QC_T(1);
+            qc_build_r<L, 64>(Rw, plan, lane, alpha, X, Y, Z, F);
+            QC_T(2);
+            { double raw[MT]; gather(gr0, raw); scale(gr0.w, raw, avA); }
+            for (int ks0 = 0; ks0 < KS; ks0 += PD) {
+#pragma unroll
+                for (int d = 0; d < PD; ++d) {
+                    const int ks = ks0 + d;
+                    if (ks >= KS) break;
+                    double raw[MT];
+                    const unsigned recw = gr[d].w;
+                    gather(gr[d], raw);       // (k-step ks + 1; past the end: the last one again, unused)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+                            Wacc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(avA[mt], bv[d][nt], Wacc[mt][nt], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (ks + PD < KS) load_b(ks + PD, bv[d]);
+                    gr[d] = gi[64 * min(ks + PD + 1, KS - 1)];
+                    scale(recw, raw, avA);
+                }
+            }
+            QC_T(3);
+            if (last) flush(Et, avE);
+            if (++kl == K_cd) { kl = 0; ++ij; }
+        }
+        QC_T(4);
+    };
+    for (int col0 = cbeg; col0 < cend; col0 += 64) {       // this slot's ket columns, 64 at a time
+        switch (min(4, (cend - col0 + 15) / 16)) {
+            case 1: tile(std::integral_constant<int, 1>{}, col0); break;
+            case 2: tile(std::integral_constant<int, 2>{}, col0); break;
+            case 3: tile(std::integral_constant<int, 3>{}, col0); break;
+            default: tile(std::integral_constant<int, 4>{}, col0); break;
+        }
+    }
+}
+
+// Output: Schwarz factor of pair P from the complete (P|P) block (unsplit slot): by the Schwarz inequality the largest |(ab|cd)| of the
+// block sits on its diagonal, so no index matching is needed
+template <int C>
+__device__ __forceinline__ void qc_out_schwarz(const QcKernelArgs &a, const QcSlotView &v) {
+    double m = 0.0;
+    for (int x = v.li; x < v.nab * v.ncd; x += C) m = fmax(m, fabs(v.Iblk[x]));
+#pragma unroll
+    for (int o = C / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, C));
+    if (v.li == 0) a.schwarz_out[v.sl.bra] = sqrt(m);
+}
+// Output: (ij|kl) materialised with its 8 symmetry images: the tensor molint::eri returns (qc_eri_full, MP2, stored Fock mode; the host
+// hands this mode unsplit slots, so plain stores are complete values)
+template <int C>
+__device__ __forceinline__ void qc_out_tensor(const QcKernelArgs &a, const QcSlotView &v) {
+    const int nb = v.nb, nd = v.nd, nab = v.nab, ncd = v.ncd;
+    const QcPairDesc &pb = v.pb, &pk = v.pk;
+    const size_t n1 = v.n, n2 = n1 * n1, n3 = n2 * n1;
+    for (int x = v.li; x < nab * ncd; x += C) {
+        const int ab = x / ncd, cd = x - ab * ncd;
+        const size_t i = pb.offa + ab / nb, j = pb.offb + ab % nb, k = pk.offa + cd / nd, l = pk.offb + cd % nd;
+        const double val = v.Iblk[x];
+        double *o = a.eri_out;
+        o[i * n3 + j * n2 + k * n1 + l] = val; o[j * n3 + i * n2 + k * n1 + l] = val;
+        o[i * n3 + j * n2 + l * n1 + k] = val; o[j * n3 + i * n2 + l * n1 + k] = val;
+        o[k * n3 + l * n2 + i * n1 + j] = val; o[l * n3 + k * n2 + i * n1 + j] = val;
+        o[k * n3 + l * n2 + j * n1 + i] = val; o[l * n3 + k * n2 + j * n1 + i] = val;
+    }
+}
+
+// The body of every column kernel: workgroup `blk` of the `nblk` of its segment takes the batches blk, blk + nblk, ... of G consecutive
+// slots of the segment's list (longest first, so the grid-stride deal balances itself); lane group g works on slot g of the batch.  Per
+// batch: zero the block and stage the density tiles, contract (matrix-core tiles, the hoisted low-L form or the cooperative R table,
+// the last two sharing step 3), then one output: Schwarz factor, the materialised tensor, or digestion into G.
 // (MFMA_OK = false: the instance of a launch that never sees f-ket classes - qc_fock_tier_kernel<LAB, 2> - keeps the VALU form of its d.d / f.p-ket
 // bodies and with it its two waves per SIMD)
 template <int LAB, int LCD, int LGC, bool MFMA_OK = true>
 __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot *__restrict__ slots, const int nslots, const int slot_words,
-                                             const int blk, const int nblk, const int run = 0, const int rb_rows = 0) {
+                                             const int blk, const int nblk) {
     constexpr int L = LAB + LCD, HAB = qc_nherm(LAB), HCD = qc_nherm(LCD);
     static_assert(LGC >= 4, "a lane group is made of whole 16-lane rows (DPP row broadcasts)");
     constexpr int C = 1 << LGC, G = 64 >> LGC;
@@ -352,64 +589,14 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
         const int2 *__restrict__ gp = a.rplan + qc_plan_off(L);
         for (int i = lane; i < qc_nplan(L); i += 64) plan[i] = gp[i];
     }
-#ifdef QC_PHASE_TIMING
-    long long tph[8] = {};
-#define QC_T(i) do { const long long t_ = wall_clock64(); tph[i] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define QC_T(i) do {} while (0)
-#endif
-    // bra-run mode: row buffer behind the groups' regions (and the plan): exchange rows [spin][na + nb][n], then J_ab[nab]
-    const bool use_rb = rb_rows > 0 && digest;
-    double *const rbK = lds + (size_t)G * slot_words + (HOIST ? 0 : qc_nplan(L));
-    double *const rbJ = rbK + (size_t)(uhf ? 2 : 1) * rb_rows * n;
-    if (use_rb) {
-        for (int i = lane; i < (uhf ? 2 : 1) * rb_rows * n + rb_rows * rb_rows; i += 64) rbK[i] = 0.0;
-        __syncthreads();
-    }
-    int rb_bra = -1;                                       // bra whose targets the row buffer holds (wave-uniform)
-    // what is non-zero in the row buffer goes to Gt: rows of the bra's functions (a first, then b), then the J_ab block
-    auto rb_flush = [&](const int bra) {
-        const QcPairDesc pf = a.pairs[bra];
-        const int na = pf.na, nb = pf.nb, rows = na + nb;
-        const float inn = __builtin_amdgcn_rcpf((float)n), inb = __builtin_amdgcn_rcpf((float)nb);
-        const size_t rep = (size_t)(blk % a.nrep) * a.rep_stride;
-        for (int s = 0; s < (uhf ? 2 : 1); ++s) {
-            double *Gs = (s ? a.G1 : a.G0) + rep;
-            double *Ks = rbK + (size_t)s * rb_rows * n;
-            for (int x = lane; x < rows * n; x += 64) {
-                const double v = Ks[x];
-                if (v != 0.0) {
-                    const int r = qc_fdiv(x, inn), col = x - r * n;
-                    qc_gadd(&Gs[(size_t)(r < na ? pf.offa + r : pf.offb + r - na) * n + col], v, fxscale, a.fx_lo);
-                    Ks[x] = 0.0;
-                }
-            }
-        }
-        for (int ab = lane; ab < na * nb; ab += 64) {
-            const double v = rbJ[ab];
-            if (v != 0.0) {
-                const int r = qc_fdiv(ab, inb);
-                const size_t o = (size_t)(pf.offa + r) * n + pf.offb + ab - r * nb;
-                qc_gadd2(&a.G0[rep + o], &a.G1[rep + o], uhf, v, fxscale, a.fx_lo);
-                rbJ[ab] = 0.0;
-            }
-        }
-        __syncthreads();
-    };
+    QcPhaseClock clk;
     const int nbatch = (nslots + G - 1) / G;
-    const int w_begin = run > 0 ? blk * run : blk, w_end = run > 0 ? min(nbatch, (blk + 1) * run) : nbatch, w_step = run > 0 ? 1 : nblk;
-    for (int wave = w_begin; wave < w_end; wave += w_step) {
-#ifdef QC_PHASE_TIMING
-        long long tlast = wall_clock64();
-#endif
+    for (int wave = blk; wave < nbatch; wave += nblk) {
+        clk.start();
         const int slot = wave * G + g;
         const QcSlot sl = slots[min(slot, nslots - 1)];
-        const bool active = slot < nslots && sl.ket >= 0;  // (null slots pad the batches of the bra-run mode)
-        if (use_rb) {
-            const int bra0 = __builtin_amdgcn_readfirstlane(slots[min(wave * G, nslots - 1)].bra);
-            if (bra0 != rb_bra) { if (rb_bra >= 0) rb_flush(rb_bra); rb_bra = bra0; }
-        }
-        const QcPairDesc pb = a.pairs[sl.bra], pk = a.pairs[max(sl.ket, 0)];
+        const bool active = slot < nslots;
+        const QcPairDesc pb = a.pairs[sl.bra], pk = a.pairs[sl.ket];
         const int na = pb.na, nb = pb.nb, nc = pk.na, nd = pk.nb;
         const int nab = na * nb, ncd = nc * nd;
         const float inb = __builtin_amdgcn_rcpf((float)nb), inc = __builtin_amdgcn_rcpf((float)nc), ind = __builtin_amdgcn_rcpf((float)nd);
@@ -444,173 +631,12 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
         const double *braBase = pd + pb.doff, *ketBase = pd + pk.doff;
         const int npass = (LGC == 6) ? (ncd + 63) / 64 : 1;  // > 1 only for ket pairs with more than 64 function pairs
         const int cbeg = active ? sl.c0 : 0, cend = active ? sl.c1 : 0;   // ket columns of this slot (all of them unless the host split the class)
+        QcSlotView v;
+        v.lane = lane; v.li = li; v.n = n; v.plan = plan; v.sl = sl; v.pb = pb; v.pk = pk; v.nb = nb; v.nd = nd; v.nab = nab; v.ncd = ncd;
+        v.Rw = Rw; v.Iblk = Iblk; v.braBase = braBase; v.ketBase = ketBase; v.strideB = strideB; v.strideK = strideK; v.len = len; v.cbeg = cbeg; v.cend = cend;
 
         if constexpr (MFMA) {
-          // ---- high-order kets (LCD >= 4): both Hermite contractions on the matrix cores.  One slot per wave.
-          //   step 2  W[h1][c] += sum_h2 Rm[h1][h2] Ee[h2][c],  Rm[h1][h2] = (-1)^{|h2|} R_{h1+h2},  Ee = E_cd,kl * pref
-          //   step 3  I[ab][c] += sum_h1 Et[ab][h1] W[h1][c]
-          // as v_mfma_f64_16x16x4 tiles.  The VALU form reads one R value from LDS per FMA in every lane (7056 reads
-          // per lane for (ff|ff)); here the gathered Rm fragment is spread over the wave (110 reads per lane) and the W
-          // accumulators - result layout C[4r + (l >> 4)][l & 15] - are, register for register, the B operands
-          // B[k = l >> 4][j = l & 15] of step 3's k-steps, so nothing moves between the two products.
-          typedef double qc_d4 __attribute__((ext_vector_type(4)));
-          constexpr int MT = (HAB + 15) / 16, KS = (HCD + 3) / 4;
-          const int i16 = lane & 15, q4 = lane >> 4;
-          const uint4 *__restrict__ gi = a.gidx + qc_gidx_off(LAB, LCD) + lane;         // this lane's gather records, one per k-step
-          const char *const Rb = reinterpret_cast<const char *>(Rw);
-          const double *__restrict__ pdT = a.pairdataT;
-          const int K_cd = pk.K;
-          // One pass over the slot's primitive quartets for the column tiles [col0, col0 + 16 NT); NT is a compile-time constant of the
-          // instance (a run-time bound put a branch around every matrix instruction)
-          auto tile = [&](auto ntc, const int col0) {
-            constexpr int NT = decltype(ntc)::value;
-            constexpr bool AHEAD = MT * NT <= 12;           // registers for a second set of step-3 A fragments
-            qc_d4 Wacc[MT][NT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) Wacc[mt][nt] = qc_d4{0.0, 0.0, 0.0, 0.0};
-            // A fragments of step 3, row tile `it`: Et[ab][h1], shared by the column tiles (clamped loads, masked to zero outside the block)
-            auto load_e = [&](const double *__restrict__ Et, int it, double (&av)[MT][4]) {
-                const int ab = 16 * it + i16;
-                const double *row = Et + (size_t)min(ab, nab - 1) * HAB;
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int h1 = 16 * mt + 4 * r + q4;
-                        const double v = row[min(h1, HAB - 1)];
-                        av[mt][r] = (ab < nab && h1 < HAB) ? v : 0.0;
-                    }
-            };
-            // step 3 for the bra primitive pair whose expansion block is Et; avE = the fragments of row tile 0 (requested by the caller
-            // before the Boys function of the pair's last primitive quartet); with registers to spare the next tile's travel one ahead
-            auto flush = [&](const double *__restrict__ Et, double (&avE)[MT][4]) {
-                const int MI = (nab + 15) / 16;
-                for (int it = 0; it < MI; ++it) {
-                    double avN[AHEAD ? MT : 1][4];
-                    if constexpr (AHEAD) load_e(Et, min(it + 1, MI - 1), avN);
-                    else { if (it > 0) load_e(Et, it, avE); }
-                    __builtin_amdgcn_sched_barrier(0);
-                    qc_d4 acc[NT][2];                       // two accumulators per column tile: consecutive matrix instructions are independent
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[nt][0] = acc[nt][1] = qc_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-#pragma unroll
-                            for (int nt = 0; nt < NT; ++nt)
-                                acc[nt][r & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(avE[mt][r], Wacc[mt][nt][r], acc[nt][r & 1], 0, 0, 0);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const int c = col0 + 16 * nt + i16;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int abr = 16 * it + q4 + 4 * r;
-                            if (abr < nab && c < cend) Iblk[abr * ncd + c] += acc[nt][0][r] + acc[nt][1][r];     // this lane alone owns the element
-                        }
-                    }
-                    if constexpr (AHEAD) {
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) avE[mt][r] = avN[mt][r];
-                    }
-                }
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) Wacc[mt][nt] = qc_d4{0.0, 0.0, 0.0, 0.0};
-            };
-            int ij = sl.lo / K_cd, kl = sl.lo - ij * K_cd;
-            for (int itq = 0; itq < len; ++itq) {
-                QC_T(4);
-                const bool last = kl == K_cd - 1 || itq == len - 1;      // of this bra primitive pair: step 3 follows
-                const double *__restrict__ Et = pdT + pb.doff + (size_t)ij * strideB + 4;     // [ab][h]
-                const double4 cb = *reinterpret_cast<const double4 *>(braBase + (size_t)ij * strideB);
-                const double *ket = ketBase + (size_t)kl * strideK;
-                const double4 ck = *reinterpret_cast<const double4 *>(ket);
-                double avE[MT][4];
-                if (last) load_e(Et, 0, avE);
-                const double p = cb.x, q = ck.x;
-                const double X = cb.y - ck.y, Y = cb.z - ck.z, Z = cb.w - ck.w;
-                const double pref = qc_rsqrt(p + q);
-                const double alpha = p * q * (pref * pref);
-                // Operand fragments of k-step ks.  B = the column tiles of the ket block (plain loads, clamped: rows past HCD meet a zero
-                // A value, columns past ncd are never read back); A = the gathered, signed R values: which LDS word lane l reads for row
-                // tile mt comes from a host-built record (qc_build_gidx), eight u16 per k-step and lane.
-                const double *Ecd = ket + 4;
-                auto load_b = [&](int ks, double (&bv)[NT]) {
-                    const int h2 = min(4 * ks + q4, HCD - 1);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) bv[nt] = Ecd[(size_t)h2 * ncd + min(col0 + 16 * nt + i16, ncd - 1)];
-                };
-                auto gather = [&](const uint4 rec, double (&raw)[MT]) {
-                    const unsigned w[3] = {rec.x, rec.y, rec.z};
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const unsigned off = (mt & 1) ? (w[mt >> 1] >> 16) : (w[mt >> 1] & 0xffffu);
-                        raw[mt] = *reinterpret_cast<const double *>(Rb + off);
-                    }
-                };
-                auto scale = [&](const unsigned recw, const double (&raw)[MT], double (&av)[MT]) {
-                    const unsigned fl = recw >> 16;
-                    const double sg = (fl & 2u) ? ((fl & 1u) ? -pref : pref) : 0.0;          // sign of the ket order, scale, validity
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) av[mt] = sg * raw[mt];
-                };
-                // B fragments and gather records travel PD k-steps ahead of their matrix instructions (a k-step is MT NT of them, 64 cycles
-                // each; a ket block comes from the L2 / the memory-side cache in 500-1200): the first PD are requested before the Boys
-                // function and the R table, a buffer is refilled as soon as its instructions have issued.  The R values of step ks + 1
-                // are read from LDS before the instructions of step ks and scaled after them.
-                constexpr int PD = MT * NT >= 12 ? 3 : (MT * NT >= 6 ? 4 : 6);
-                double bv[PD][NT], avA[MT];
-                uint4 gr[PD];
-#pragma unroll
-                for (int d = 0; d < PD; ++d) { load_b(min(d, KS - 1), bv[d]); gr[d] = gi[64 * min(d + 1, KS - 1)]; }
-                const uint4 gr0 = gi[0];
-                double F[L + 1];
-                qc_boys<L>(alpha * (X * X + Y * Y + Z * Z), a.boys, F);
-                __syncthreads();                  // previous iteration's readers of Rw are done
-                QC_T(1);
-                qc_build_r<L, 64>(Rw, plan, lane, alpha, X, Y, Z, F);
-                QC_T(2);
-                { double raw[MT]; gather(gr0, raw); scale(gr0.w, raw, avA); }
-                for (int ks0 = 0; ks0 < KS; ks0 += PD) {
-#pragma unroll
-                    for (int d = 0; d < PD; ++d) {
-                        const int ks = ks0 + d;
-                        if (ks >= KS) break;
-                        double raw[MT];
-                        const unsigned recw = gr[d].w;
-                        gather(gr[d], raw);       // (k-step ks + 1; past the end: the last one again, unused)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                            for (int nt = 0; nt < NT; ++nt)
-                                Wacc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(avA[mt], bv[d][nt], Wacc[mt][nt], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (ks + PD < KS) load_b(ks + PD, bv[d]);
-                        gr[d] = gi[64 * min(ks + PD + 1, KS - 1)];
-                        scale(recw, raw, avA);
-                    }
-                }
-                QC_T(3);
-                if (last) flush(Et, avE);
-                if (++kl == K_cd) { kl = 0; ++ij; }
-            }
-            QC_T(4);
-          };
-          for (int col0 = cbeg; col0 < cend; col0 += 64) {       // this slot's ket columns, 64 at a time
-              switch (min(4, (cend - col0 + 15) / 16)) {
-                  case 1: tile(std::integral_constant<int, 1>{}, col0); break;
-                  case 2: tile(std::integral_constant<int, 2>{}, col0); break;
-                  case 3: tile(std::integral_constant<int, 3>{}, col0); break;
-                  default: tile(std::integral_constant<int, 4>{}, col0); break;
-              }
-          }
+          qc_contract_mfma<LAB, LCD>(a, v, clk);
         } else {
         for (int pass = 0; pass < npass; ++pass) {
             const int col = pass * 64 + li;
@@ -782,27 +808,9 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
         if (active) {
             const double f = (pb.shA_eq_shB ? 0.5 : 1.0) * (pk.shA_eq_shB ? 0.5 : 1.0) * (sl.bra == sl.ket ? 0.5 : 1.0);
             if (a.schwarz_out != nullptr) {
-                // Schwarz factor of pair P from the complete (P|P) block (unsplit slot): by the Schwarz inequality the largest
-                // |(ab|cd)| of the block sits on its diagonal, so no index matching is needed
-                double m = 0.0;
-                for (int x = li; x < nab * ncd; x += C) m = fmax(m, fabs(Iblk[x]));
-#pragma unroll
-                for (int o = C / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, C));
-                if (li == 0) a.schwarz_out[sl.bra] = sqrt(m);
+                qc_out_schwarz<C>(a, v);
             } else if (a.eri_out != nullptr) {
-                // materialise (ij|kl) with its 8 symmetry images: the tensor molint::eri returns (qc_eri_full, MP2, stored Fock
-                // mode; the host hands this mode unsplit slots, so plain stores are complete values)
-                const size_t n1 = n, n2 = n1 * n1, n3 = n2 * n1;
-                for (int x = li; x < nab * ncd; x += C) {
-                    const int ab = x / ncd, cd = x - ab * ncd;
-                    const size_t i = pb.offa + ab / nb, j = pb.offb + ab % nb, k = pk.offa + cd / nd, l = pk.offb + cd % nd;
-                    const double v = Iblk[x];
-                    double *o = a.eri_out;
-                    o[i * n3 + j * n2 + k * n1 + l] = v; o[j * n3 + i * n2 + k * n1 + l] = v;
-                    o[i * n3 + j * n2 + l * n1 + k] = v; o[j * n3 + i * n2 + l * n1 + k] = v;
-                    o[k * n3 + l * n2 + i * n1 + j] = v; o[l * n3 + k * n2 + i * n1 + j] = v;
-                    o[k * n3 + l * n2 + j * n1 + i] = v; o[l * n3 + k * n2 + j * n1 + i] = v;
-                }
+                qc_out_tensor<C>(a, v);
             } else {
                 double *G0 = a.G0 + rep, *G1 = a.G1 + rep;
                 const double fj = 2.0 * f, fk = -a.cK * f;
@@ -880,7 +888,6 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                     double s = 0.0;
 #pragma unroll 4
                     for (int cd = cbeg; cd < cend; ++cd) s = fma(Iblk[ab * ncd + cd], tDj_cd[cd], s);
-                    if (use_rb) { qc_ds_add(&rbJ[ab], fj * s); continue; }
                     const int r = qc_fdiv(ab, inb);
                     const size_t o = (size_t)(pb.offa + r) * n + pb.offb + ab - r * nb;
                     qc_gadd2(&G0[o], &G1[o], uhf, fj * s, fxscale, a.fx_lo);
@@ -896,7 +903,6 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                 // K blocks: Gt_ac -= cK f sum_bd I D_bd, and the ad / bc / bd images
                 for (int s = 0; s < (uhf ? 2 : 1); ++s) {
                     double *Gs = s ? G1 : G0;
-                    double *const Ks = rbK + (size_t)s * rb_rows * n;     // (row buffer: rows of a, then rows of b)
                     const double *t_ac = tK + s * ktile, *t_ad = t_ac + na * nc, *t_bc = t_ad + na * nd, *t_bd = t_bc + nb * nc;
                     for (int x = li; x < na * nc; x += C) {          // (i,k) <- sum_{j,l} I[ij,kl] D[j,l]
                         const int i = qc_fdiv(x, inc), k = x - i * nc;
@@ -905,8 +911,7 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                         for (int j = 0; j < nb; ++j)
 #pragma unroll 3
                             for (int l = l0; l < l1; ++l) acc = fma(Iblk[(i * nb + j) * ncd + k * nd + l], t_bd[j * nd + l], acc);
-                        if (use_rb) qc_ds_add(&Ks[i * n + pk.offa + k], fk * acc);
-                        else qc_gadd(&Gs[(size_t)(pb.offa + i) * n + pk.offa + k], fk * acc, fxscale, a.fx_lo);
+                        qc_gadd(&Gs[(size_t)(pb.offa + i) * n + pk.offa + k], fk * acc, fxscale, a.fx_lo);
                     }
                     for (int x = li; x < na * nd; x += C) {          // (i,l) <- sum_{j,k} I[ij,kl] D[j,k]
                         const int i = qc_fdiv(x, ind), l = x - i * nd;
@@ -915,8 +920,7 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                         for (int j = 0; j < nb; ++j)
 #pragma unroll 3
                             for (int k = k0; k < k1; ++k) acc = fma(Iblk[(i * nb + j) * ncd + k * nd + l], t_bc[j * nc + k], acc);
-                        if (use_rb) qc_ds_add(&Ks[i * n + pk.offb + l], fk * acc);
-                        else qc_gadd(&Gs[(size_t)(pb.offa + i) * n + pk.offb + l], fk * acc, fxscale, a.fx_lo);
+                        qc_gadd(&Gs[(size_t)(pb.offa + i) * n + pk.offb + l], fk * acc, fxscale, a.fx_lo);
                     }
                     for (int x = li; x < nb * nc; x += C) {          // (j,k) <- sum_{i,l} I[ij,kl] D[i,l]
                         const int j = qc_fdiv(x, inc), k = x - j * nc;
@@ -925,8 +929,7 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                         for (int i = 0; i < na; ++i)
 #pragma unroll 3
                             for (int l = l0; l < l1; ++l) acc = fma(Iblk[(i * nb + j) * ncd + k * nd + l], t_ad[i * nd + l], acc);
-                        if (use_rb) qc_ds_add(&Ks[(na + j) * n + pk.offa + k], fk * acc);
-                        else qc_gadd(&Gs[(size_t)(pb.offb + j) * n + pk.offa + k], fk * acc, fxscale, a.fx_lo);
+                        qc_gadd(&Gs[(size_t)(pb.offb + j) * n + pk.offa + k], fk * acc, fxscale, a.fx_lo);
                     }
                     for (int x = li; x < nb * nd; x += C) {          // (j,l) <- sum_{i,k} I[ij,kl] D[i,k]
                         const int j = qc_fdiv(x, ind), l = x - j * nd;
@@ -935,8 +938,7 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
                         for (int i = 0; i < na; ++i)
 #pragma unroll 3
                             for (int k = k0; k < k1; ++k) acc = fma(Iblk[(i * nb + j) * ncd + k * nd + l], t_ac[i * nc + k], acc);
-                        if (use_rb) qc_ds_add(&Ks[(na + j) * n + pk.offb + l], fk * acc);
-                        else qc_gadd(&Gs[(size_t)(pb.offb + j) * n + pk.offb + l], fk * acc, fxscale, a.fx_lo);
+                        qc_gadd(&Gs[(size_t)(pb.offb + j) * n + pk.offb + l], fk * acc, fxscale, a.fx_lo);
                     }
                 }
                 }
@@ -945,7 +947,6 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
         __syncthreads();   // the slot regions are reused by the next batch of slots
         QC_T(6);
     }
-    if (use_rb && rb_bra >= 0) rb_flush(rb_bra);
 #ifdef QC_PHASE_TIMING
 #ifdef QC_PHASE_ALL
     if (lane == 0 && blk < 2 && digest)
@@ -953,7 +954,7 @@ __device__ __forceinline__ void qc_fock_body(const QcKernelArgs &a, const QcSlot
     if (MFMA && lane == 0 && blk < 2 && digest)
 #endif
         printf("[phase] <%d,%d,%d> blk %d/%d nslots %d: setup %lld  boys+hdr %lld  rtab %lld  kloop %lld  flush %lld  tail %lld  products %lld  atomics %lld  (10 ns units)\n", LAB, LCD, LGC, blk, nblk, nslots,
-               tph[0], tph[1], tph[2], tph[3], tph[4], tph[5], tph[7], tph[6]);
+               clk.tph[0], clk.tph[1], clk.tph[2], clk.tph[3], clk.tph[4], clk.tph[5], clk.tph[7], clk.tph[6]);
 #endif
 #undef QC_T
 }
@@ -971,10 +972,16 @@ struct QcTierArgs {
     int seg_code[QC_MAXSEG];       // (LCD << 4) | LGC
     int seg_nslots[QC_MAXSEG];
     int seg_words[QC_MAXSEG];
-    int seg_run[QC_MAXSEG];        // bra-run mode: batches per workgroup (0: independent slots, grid-stride)
-    int seg_rbrows[QC_MAXSEG];     // ... rows of the LDS row buffer (0: none)
     const QcSlot *seg_slots[QC_MAXSEG];
 };
+// the segment s that workgroup blockIdx.x belongs to, the workgroup's place blk among the segment's nblk, and the segment's slot list
+struct QcSegment { int s, blk, nblk, nslots, words; const QcSlot *slots; };
+__device__ __forceinline__ QcSegment qc_find_segment(const QcTierArgs &a) {
+    int s = 0;
+    while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg_end[s]) ++s;
+    const int b0 = s ? a.seg_end[s - 1] : 0;
+    return QcSegment{s, (int)blockIdx.x - b0, a.seg_end[s] - b0, a.seg_nslots[s], a.seg_words[s], a.seg_slots[s]};
+}
 
 // (TIER 2 = the tier-1 launch of a build without f-ket classes - every segment an LCD = 4 bucket, any basis without f functions: the same
 // launch unit, but a kernel that does not carry the register footprint of the matrix-core bodies and so keeps two waves per SIMD:
@@ -986,20 +993,15 @@ void qc_fock_tier_kernel(const QcTierArgs a) {
     // the high-L tiers are few, long, latency-bound waves: let them win issue arbitration against the many short
     // low-L waves they share a SIMD with
     if constexpr (TIER >= 1) __builtin_amdgcn_s_setprio(3);
-    int s = 0;
-    while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg_end[s]) ++s;
-    const int b0 = s ? a.seg_end[s - 1] : 0;
-    const int blk = blockIdx.x - b0, nblk = a.seg_end[s] - b0;
-    const QcSlot *slots = a.seg_slots[s];
-    const int nslots = a.seg_nslots[s], words = a.seg_words[s];
-#define QC_CASE(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, slots, nslots, words, blk, nblk, a.seg_run[s], a.seg_rbrows[s]); break;
+    const QcSegment sg = qc_find_segment(a);
+#define QC_CASE(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
     if constexpr (TIER == 0) {
-        switch (a.seg_code[s]) { QC_CASE(2, 4) QC_CASE(3, 4) QC_CASE(3, 5) default: break; }
+        switch (a.seg_code[sg.s]) { QC_CASE(2, 4) QC_CASE(3, 4) QC_CASE(3, 5) default: break; }
     } else if constexpr (TIER == 1) {
-        switch (a.seg_code[s]) { QC_CASE(4, 5) QC_CASE(4, 6) QC_CASE(5, 6) QC_CASE(6, 6) default: break; }
+        switch (a.seg_code[sg.s]) { QC_CASE(4, 5) QC_CASE(4, 6) QC_CASE(5, 6) QC_CASE(6, 6) default: break; }
     } else {
-#define QC_CASE_V(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC, false>(a.base, slots, nslots, words, blk, nblk, a.seg_run[s], a.seg_rbrows[s]); break;
-        switch (a.seg_code[s]) { QC_CASE_V(4, 5) QC_CASE_V(4, 6) default: break; }
+#define QC_CASE_V(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC, false>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
+        switch (a.seg_code[sg.s]) { QC_CASE_V(4, 5) QC_CASE_V(4, 6) default: break; }
 #undef QC_CASE_V
     }
 #undef QC_CASE
@@ -1019,30 +1021,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC_T1LOW_WAV
 void qc_fock_tier1_low_kernel(const QcTierArgs a) {
     qc_tl_stamp(a.base.tl, 0);
     __builtin_amdgcn_s_setprio(3);
-    int s = 0;
-    while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg_end[s]) ++s;
-    const int b0 = s ? a.seg_end[s - 1] : 0;
-    const int blk = blockIdx.x - b0, nblk = a.seg_end[s] - b0;
-    const QcSlot *slots = a.seg_slots[s];
-    const int nslots = a.seg_nslots[s], words = a.seg_words[s];
-#define QC_CASE(LAB, LCD, LGC) case ((LAB) << 8 | (LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, slots, nslots, words, blk, nblk, a.seg_run[s], a.seg_rbrows[s]); break;
+    const QcSegment sg = qc_find_segment(a);
+#define QC_CASE(LAB, LCD, LGC) case ((LAB) << 8 | (LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
     // V = 0: bra classes 0, 1, 2;  V = 1: 3 and 4 (994 + 350 workgroups on H2O/cc-pVTZ, 22 / 31 KB of LDS: still four per CU);  V = 2: 5 and 6
     // (46 + 4 workgroups, 42 / 56 KB) - the f.d / f.f bras stay out of the launch of classes 3 and 4 because their LDS would halve its waves
     if constexpr (V == 0) {
-        switch ((a.seg_lab[s] << 8) | a.seg_code[s]) {
+        switch ((a.seg_lab[sg.s] << 8) | a.seg_code[sg.s]) {
             QC_CASE(0, 5, 6) QC_CASE(0, 6, 6)
             QC_CASE(1, 4, 5) QC_CASE(1, 4, 6) QC_CASE(1, 5, 6) QC_CASE(1, 6, 6)
             QC_CASE(2, 4, 5) QC_CASE(2, 4, 6) QC_CASE(2, 5, 6) QC_CASE(2, 6, 6)
             default: break;
         }
     } else if constexpr (V == 1) {
-        switch ((a.seg_lab[s] << 8) | a.seg_code[s]) {
+        switch ((a.seg_lab[sg.s] << 8) | a.seg_code[sg.s]) {
             QC_CASE(3, 4, 5) QC_CASE(3, 4, 6) QC_CASE(3, 5, 6) QC_CASE(3, 6, 6)
             QC_CASE(4, 4, 5) QC_CASE(4, 4, 6) QC_CASE(4, 5, 6) QC_CASE(4, 6, 6)
             default: break;
         }
     } else {
-        switch ((a.seg_lab[s] << 8) | a.seg_code[s]) {
+        switch ((a.seg_lab[sg.s] << 8) | a.seg_code[sg.s]) {
             QC_CASE(5, 4, 5) QC_CASE(5, 4, 6) QC_CASE(5, 5, 6) QC_CASE(5, 6, 6)
             QC_CASE(6, 4, 5) QC_CASE(6, 4, 6) QC_CASE(6, 5, 6) QC_CASE(6, 6, 6)
             default: break;
@@ -1051,29 +1048,20 @@ void qc_fock_tier1_low_kernel(const QcTierArgs a) {
 #undef QC_CASE
     qc_tl_stamp(a.base.tl, 1);
 }
+// One launch of a column kernel.  The dynamic-LDS cap of the instantiation is raised once, to the device maximum (the attribute is
+// process-wide, so a per-handle high-water mark would let one handle lower another's cap; the flag only saves the repeated call).
+template <void (*KERN)(const QcTierArgs)>
+int qc_launch_column(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) {
+    static std::atomic<bool> raised{false};
+    if (lds > 48 * 1024 && !raised.load(std::memory_order_acquire)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, QC_LDS_MAX);
+        if (e != hipSuccess) return QC_ERR_HIP;
+        raised.store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64), lds, st, a);
+    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
+}
 template <int V>
-int qc_launch_tier1_low_impl(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) {
-    static std::atomic<bool> raised{false};
-    if (lds > 48 * 1024 && !raised.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(qc_fock_tier1_low_kernel<V>), hipFuncAttributeMaxDynamicSharedMemorySize, QC_LDS_MAX);
-        if (e != hipSuccess) return QC_ERR_HIP;
-        raised.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(qc_fock_tier1_low_kernel<V>, dim3(grid), dim3(64), lds, st, a);
-    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
-}
-
+int qc_launch_tier1_low_impl(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier1_low_kernel<V>>(grid, lds, st, a); }
 template <int LAB, int TIER>
-int qc_launch_tier(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) {
-    auto kern = qc_fock_tier_kernel<LAB, TIER>;
-    // the dynamic-LDS cap of this instantiation is raised once, to the device maximum (the attribute is process-wide, so a
-    // per-handle high-water mark would let one handle lower another's cap; the flag only saves the repeated call)
-    static std::atomic<bool> raised{false};
-    if (lds > 48 * 1024 && !raised.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, QC_LDS_MAX);
-        if (e != hipSuccess) return QC_ERR_HIP;
-        raised.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, st, a);
-    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
-}
+int qc_launch_tier(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier_kernel<LAB, TIER>>(grid, lds, st, a); }

@@ -118,9 +118,6 @@ struct QcClass {
     int slot_words = 0;           // LDS doubles per lane group
     int lds_bytes = 0;
     int col_slot_words = 0, col_lds_bytes = 0, col_lgc = 0;   // the same for the column kernels over the WHOLE task list: what the passes outside a build launch (a pp-ket bra-major class goes through the column kernels there)
-    // bra-run mode of the low-L column classes (qc_fock_body): slots grouped by bra, batches of G padded with null slots
-    int run = 0;                  // batches per workgroup (0: independent slots)
-    int rb_rows = 0;              // most bra functions (na + nb) of the class: rows of the LDS row buffer
     // bra-major classes (ket = ss or ps pair, LAB + LCD <= QC_LREG): `bundles` replace `slots`
     bool bm = false;
     int bm_rows = 0;              // most bra functions (na + nb) of a bundle: rows of the kernels' exchange buffer
@@ -251,7 +248,7 @@ struct QcTimeline {
 struct QcPlanSwitches {
     bool no_bm_pp = false, no_bm_ps4 = false, no_t1_merge = false, no_bm_merge = false;
     long bm_pp_min = 8192, mfma4_max = 1024, bm_merge_max = 262144;
-    int bm_pq = 32, bm_pp_pq = 96, bm_unit = 8, bm_pp_unit = 8, bm_gain = 0, bra_run = 0;
+    int bm_pq = 32, bm_pp_pq = 96, bm_unit = 8, bm_pp_unit = 8, bm_gain = 0;
     static QcPlanSwitches from_env();
 };
 

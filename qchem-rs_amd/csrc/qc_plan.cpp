@@ -2,8 +2,8 @@
 // Host-only integer code; tests/host/plan_dump_main.cpp prints everything it decides.  In the order it runs:
 //   qc_build_classes   every unique quartet (pair P >= pair Q) gets a launch class (classify), two kinds of short lists move
 //                      (short_pp_list_to_columns, short_lgc5_lists_to_wave64), the classes are made and the launch merges decided;
-//   qc_build_shards    per class: order, screen, deal to the ranks, cut (bundles with the chunk decision, or slots with the tile split and
-//                      the optional bra-run grouping), work model, sizes.  With meta_only: the sizes alone, over the whole task lists.
+//   qc_build_shards    per class: order, screen, deal to the ranks, cut (bundles with the chunk decision, or slots with the tile split),
+//                      work model, sizes.  With meta_only: the sizes alone, over the whole task lists.
 // The A/B switches of all of it: QcPlanSwitches (qc_internal.h; table in DESIGN.md 2).
 #include <algorithm>
 #include <cstdlib>
@@ -18,7 +18,7 @@ QcPlanSwitches QcPlanSwitches::from_env() {
     w.bm_pp_min = num("QC_BM_PP_MIN", w.bm_pp_min); w.mfma4_max = num("QC_MFMA4_MAX", w.mfma4_max); w.bm_merge_max = num("QC_BM_MERGE_MAX", w.bm_merge_max);
     w.bm_pq = (int)num("QC_BM_PQ", w.bm_pq); w.bm_pp_pq = (int)num("QC_BM_PP_PQ", w.bm_pp_pq);
     w.bm_unit = (int)num("QC_BM_UNIT", w.bm_unit); w.bm_pp_unit = (int)num("QC_BM_PP_UNIT", w.bm_pp_unit);
-    w.bm_gain = (int)num("QC_BM_GAIN", w.bm_gain); w.bra_run = (int)num("QC_BRA_RUN", w.bra_run);
+    w.bm_gain = (int)num("QC_BM_GAIN", w.bm_gain);
     return w;
 }
 
@@ -305,40 +305,10 @@ void cut_bundles(const qc_system *S, QcClass &c, int itmax) {
     }
 }
 
-// Low-L classes (16- / 32-lane groups: several slots per wave): bra-run mode.  Slots are grouped by bra pair - heavy bras
-// first, inside a bra the longest slots first - every batch of G slots gets one bra (null slots pad), and a workgroup takes
-// `run` consecutive batches, so that the targets that belong to the bra stay in its LDS row buffer across them.
-// MEASURED AND NOT THE DEFAULT (round 3, benzene/cc-pVDZ, classes alone): (pp|pp)-type bucket 0.274 ms with independent slots,
-// 0.65 ms in bra runs of 7-8 batches WITH OR WITHOUT the row buffer - removing most of the class's global atomics changes
-// nothing (they are not what its waves wait for), while equal-length runs of one bra lose the load balance of the
-// length-sorted grid-stride list (a heavy bra's run is 5x the average).  QC_BRA_RUN=<batches> switches it on for A/B and
-// for counting atomic requests (tools/run_pmc.sh).
-void group_bra_runs(const qc_system *S, QcClass &c) {
-    c.run = 0; c.rb_rows = 0;
-    if (!(c.LGC <= 5 && c.LCD <= 3 && S->nbasis <= 128 && S->plan.bra_run > 0 && !c.slots.empty())) return;
-    const size_t G = 64 >> c.LGC;
-    std::vector<std::vector<QcSlot>> by;             // bras by first appearance in the cost-sorted slot list
-    std::vector<int> where(S->pairs.size(), -1);
-    for (const auto &sl : c.slots) {
-        if (where[sl.bra] < 0) { where[sl.bra] = (int)by.size(); by.emplace_back(); }
-        by[where[sl.bra]].push_back(sl);
-    }
-    std::vector<QcSlot> grouped;
-    for (auto &v : by) {
-        sort_descending(v, PRIM_KEYS, slot_length);
-        for (const auto &sl : v) grouped.push_back(sl);
-        while (grouped.size() % G) grouped.push_back(QcSlot{v[0].bra, -1, 0, 0, 0, 0});
-        c.rb_rows = std::max(c.rb_rows, S->pairs[v[0].bra].na + S->pairs[v[0].bra].nb);
-    }
-    c.slots.swap(grouped);
-    c.run = S->plan.bra_run;
-}
-
 void cut_slots(const qc_system *S, QcClass &c, int itmax) {
     qc_make_slots(S, c.shard, itmax, false, c.slots);
     // a matrix-core class (one slot per wave) with fewer slots than the chip has SIMDs: one wave per 16-column tile
     if ((qc_mfma_always(c.LAB, c.LCD) || (S->has_fkets && qc_use_mfma(c.LAB, c.LCD))) && c.LGC == 6 && c.slots.size() * 4 <= 1024) qc_make_slots(S, c.shard, itmax, true, c.slots);
-    group_bra_runs(S, c);
 }
 
 void work_model(const qc_system *S, QcClass &c) {
@@ -444,7 +414,7 @@ void qc_build_shards(qc_system *S, bool meta_only) {
         auto &c = S->classes[ci];
         c.shard.clear(); c.slots.clear(); c.bundles.clear(); c.ketlist.clear();
         if (meta_only) {
-            c.prim_quartets = 0; c.bytes_alg = 0; c.flops_alg = 0; c.run = 0; c.rb_rows = 0;
+            c.prim_quartets = 0; c.bytes_alg = 0; c.flops_alg = 0;
             class_sizes(S, c, c.tasks);
             // (a column class in the passes that launch its WHOLE list - Schwarz pass, ERI tensor - needs these sizes, not the screened
             // shard's: kept where class_sizes(.., c.shard) does not touch them, next to those of the p.p-ket bra-major classes)

@@ -12,7 +12,7 @@
 //   flags   pp_ok has_fkets merge_t1 merge_bm nquartets nscreened
 //   meta    ci LAB LCD LGC bm | slot_words lds_bytes col_slot_words col_lds_bytes col_lgc bm_rows | ntasks, hash of the task list
 //           (the class as qc_build_model leaves it: sizes over the whole task list, tasks in bucket order)
-//   class   ci LAB LCD LGC bm | slot_words lds_bytes col_slot_words col_lds_bytes col_lgc run rb_rows bm_rows ket_packed |
+//   class   ci LAB LCD LGC bm | slot_words lds_bytes col_slot_words col_lds_bytes col_lgc bm_rows ket_packed |
 //           prim_quartets bytes_alg flops_alg (hex floats) | qc_lgc_for of the widest ket | ntasks nshard nslots nbundles nketlist
 //   t / s   ci bra ket                                  tasks / shard
 //   sl      ci bra ket lo hi c0 c1                      slots
@@ -97,8 +97,8 @@ int main(int argc, char **argv) {
         const QcClass &c = S->classes[ci];
         int widest = 0;
         for (const auto &t : c.tasks) widest = std::max(widest, S->pairs[t.ket].na * S->pairs[t.ket].nb);
-        std::printf("class %zu %d %d %d %d %d %d %d %d %d %d %d %d %d %lld %a %a %d %zu %zu %zu %zu %zu\n", ci, c.LAB, c.LCD, c.LGC, (int)c.bm, c.slot_words, c.lds_bytes,
-                    c.col_slot_words, c.col_lds_bytes, c.col_lgc, c.run, c.rb_rows, c.bm_rows, (int)c.ket_packed, (long long)c.prim_quartets, c.bytes_alg, c.flops_alg,
+        std::printf("class %zu %d %d %d %d %d %d %d %d %d %d %d %lld %a %a %d %zu %zu %zu %zu %zu\n", ci, c.LAB, c.LCD, c.LGC, (int)c.bm, c.slot_words, c.lds_bytes,
+                    c.col_slot_words, c.col_lds_bytes, c.col_lgc, c.bm_rows, (int)c.ket_packed, (long long)c.prim_quartets, c.bytes_alg, c.flops_alg,
                     qc_lgc_for(c.LAB, c.LCD, widest), c.tasks.size(), c.shard.size(), c.slots.size(), c.bundles.size(), c.ketlist.size());
         for (const auto &t : c.tasks) std::printf("t %zu %d %d\n", ci, t.bra, t.ket);
         for (const auto &t : c.shard) std::printf("s %zu %d %d\n", ci, t.bra, t.ket);

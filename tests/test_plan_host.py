@@ -72,10 +72,10 @@ class Dump:
                 self.meta.append(dict(LAB=f[1], LCD=f[2], LGC=f[3], bm=f[4], slot_words=f[5], lds_bytes=f[6], col_slot_words=f[7], col_lds_bytes=f[8],
                                       col_lgc=f[9], bm_rows=f[10], ntasks=f[11]))
             elif tag == "class":
-                f = list(map(int, v[:15])) + [float.fromhex(v[15]), float.fromhex(v[16])] + list(map(int, v[17:]))
+                f = list(map(int, v[:13])) + [float.fromhex(v[13]), float.fromhex(v[14])] + list(map(int, v[15:]))
                 self.classes.append(dict(LAB=f[1], LCD=f[2], LGC=f[3], bm=f[4], slot_words=f[5], lds_bytes=f[6], col_slot_words=f[7], col_lds_bytes=f[8],
-                                         col_lgc=f[9], run=f[10], rb_rows=f[11], bm_rows=f[12], ket_packed=f[13], prim_quartets=f[14], bytes_alg=f[15],
-                                         flops_alg=f[16], lgc_widest=f[17], counts=tuple(f[18:23]), tasks=[], shard=[], slots=[], bundles=[], ketlist=[]))
+                                         col_lgc=f[9], bm_rows=f[10], ket_packed=f[11], prim_quartets=f[12], bytes_alg=f[13],
+                                         flops_alg=f[14], lgc_widest=f[15], counts=tuple(f[16:21]), tasks=[], shard=[], slots=[], bundles=[], ketlist=[]))
             else:
                 c = self.classes[int(v[0])]
                 rec = tuple(map(int, v[1:]))
@@ -157,7 +157,7 @@ def check_column_class(d, c):
         lengths.append(hi - lo)
     for (bra, ket), rects in by_task.items():
         assert exactly_once(rects, d.pairs[bra]["K"] * d.pairs[ket]["K"], d.pairs[ket]["na"] * d.pairs[ket]["nb"]), (bra, ket)
-    assert c["run"] == 0 and all(a >= b for a, b in zip(lengths, lengths[1:]))
+    assert all(a >= b for a, b in zip(lengths, lengths[1:]))
     assert not c["bundles"] and not c["ketlist"]
 
 

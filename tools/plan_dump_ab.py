@@ -16,7 +16,7 @@ SYSTEMS = [("water", "STO-3G"), ("water", "cc-pVDZ"), ("water", "cc-pVTZ"), ("ox
 SHARDS = [(0, 1), (1, 3), (7, 8)]
 SWITCH_SYSTEMS = [("water", "cc-pVDZ"), ("water", "cc-pVTZ"), ("benzene", "cc-pVDZ")]
 SWITCHES = ["QC_BM_PP_MIN=1", "QC_NO_BM_PP=1", "QC_NO_BM_PS4=1", "QC_MFMA4_MAX=0", "QC_NO_T1_MERGE=1", "QC_NO_BM_MERGE=1", "QC_BM_UNIT=0",
-            "QC_BM_GAIN=100", "QC_BRA_RUN=4"]
+            "QC_BM_GAIN=100"]
 
 args = [a for a in sys.argv[1:] if a != "--keep"]
 keep = "--keep" in sys.argv
