@@ -78,6 +78,38 @@ pub struct QcPolarizability {
     pub ms_builds: f64,
 }
 
+/// qc_multipoles (include/qchem_hip.h): in order (0..4), origin; out the total, nuclear and electronic Cartesian moments of the
+/// orders 0..order (components by order ascending, then x power descending, then y power descending; the rest zero) and the traceless
+/// quadrupole xx xy xz yy yz zz of the total second moments.
+#[repr(C)]
+pub struct QcMultipoles {
+    pub order: i32,
+    pub reserved: i32,
+    pub origin: [f64; 3],
+    pub total: [f64; 35],
+    pub nuclear: [f64; 35],
+    pub electronic: [f64; 35],
+    pub quadrupole_traceless: [f64; 6],
+}
+
+/// qc_esp_fit (include/qchem_hip.h): in (0 = default) nscales and scales of the van der Waals radii (4: 1.4 1.6 1.8 2.0), density in
+/// points per bohr^2 (1 per Angstrom^2); out the number of points, the constraint, rms and relative rms of the fit, the dipole of the
+/// charges (origin 0), and times (ms).
+#[repr(C)]
+pub struct QcEspFit {
+    pub nscales: i32,
+    pub reserved0: i32,
+    pub scales: [f64; 8],
+    pub density: f64,
+    pub npts: i64,
+    pub total_charge: f64,
+    pub rms: f64,
+    pub rrms: f64,
+    pub dipole: [f64; 3],
+    pub ms_total: f64,
+    pub ms_potential: f64,
+}
+
 /// qc_excitations (include/qchem_hip.h): in method (0 CIS, 1 TDHF), kind (0 singlets, 1 triplets), nroots (1..8), max_iterations
 /// (0: 100), tol (0: 1e-6); out excitation energies (Eh, ascending), residual norms, oscillator strengths, transition dipoles
 /// (x, y, z per state; both zero for triplets), counts, the flag of a reference TDHF refuses, and times.
@@ -195,6 +227,30 @@ extern "C" {
                                      out: *mut f64) -> c_int;
     /// Phase times (ms) of the handle's last point call: upload, basis values / Hermite densities, contraction, download.
     pub fn qc_points_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
+    /// Number of Cartesian components of the orders 0..order: 1, 4, 10, 20, 35; -1 outside 0..4.
+    pub fn qc_multipole_count(order: c_int) -> c_int;
+    /// Multipole matrices <a| (x-Ox)^i (y-Oy)^j (z-Oz)^k |b>: qc_multipole_count(order) x n*n doubles, each exactly symmetric; origin
+    /// null = 0.  Host only.
+    pub fn qc_multipole_matrices(sys: *const QcSystem, order: c_int, origin: *const f64, out: *mut f64) -> c_int;
+    /// The same from the GPU kernel qc_scf_multipoles uses.
+    pub fn qc_multipole_matrices_gpu(sys: *mut QcSystem, order: c_int, origin: *const f64, out: *mut f64) -> c_int;
+    /// Total Cartesian moments of the state's density up to io.order about io.origin.  The state is left as it was.
+    pub fn qc_scf_multipoles(st: *mut QcScfState, io: *mut QcMultipoles) -> c_int;
+    /// scheme 0 Mulliken (Mayer bond orders), 1 Loewdin (Wiberg indices).  charges: natoms; spin, orbital (n), bond_orders
+    /// (natoms x natoms) nullable.  The state is left as it was.
+    pub fn qc_scf_populations(st: *mut QcScfState, scheme: c_int, charges: *mut f64, spin: *mut f64, orbital: *mut f64,
+                              bond_orders: *mut f64) -> c_int;
+    /// The same from host densities: nspin 1 (D n*n, the factor 2 included) or 2 ([Da; Db]).
+    pub fn qc_populations(sys: *mut QcSystem, scheme: c_int, nspin: c_int, d: *const f64, charges: *mut f64, spin: *mut f64,
+                          orbital: *mut f64, bond_orders: *mut f64) -> c_int;
+    /// The Merz-Kollman grid: capacity points of three doubles; capacity < *npts is QC_ERR_INVALID with *npts filled.  Host only.
+    pub fn qc_esp_fit_points(sys: *const QcSystem, cfg: *const QcEspFit, capacity: i64, xyz: *mut f64, npts: *mut i64) -> c_int;
+    /// Charges fitted to the potential v on the points, sum = total_charge; fills io's outputs.  Host only.
+    pub fn qc_esp_fit_solve(sys: *const QcSystem, npts: i64, xyz: *const f64, v: *const f64, total_charge: f64, io: *mut QcEspFit,
+                            charges: *mut f64) -> c_int;
+    /// Charges fitted to the state's potential on the library's grid (xyz null) or the caller's points; v_out nullable.
+    pub fn qc_scf_esp_charges(st: *mut QcScfState, io: *mut QcEspFit, npts: i64, xyz: *const f64, charges: *mut f64,
+                              v_out: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

@@ -316,6 +316,80 @@ int qc_scf_orbitals_on_points(qc_scf_state *st, int spin, int first, int count, 
  * the call), contraction (GEMM + column dots; potential: the per-point kernels), download. */
 int qc_points_timings(const qc_system *sys, double ms[4]);
 
+/* ---- Cartesian multipole moments, population analysis and ESP-fitted charges (after SCF, not in the reference).  Atomic units, host
+ * pointers.  Common to the GPU calls below: QC_ERR_INVALID for bad arguments, checked before the device is touched; QC_ERR_NO_DEVICE
+ * without a gfx950 device; QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator; bitwise reproducible from call to call
+ * and across fresh handles (every sum has a fixed order: no float atomics); a state is left exactly as it was (no Fock build runs).
+ *
+ * Multipole matrices M_c = <a| (x - O_x)^i (y - O_y)^j (z - O_z)^k |b> of all orders l = i + j + k <= order, order 0 .. 4:
+ * qc_multipole_count(order) = (order+1)(order+2)(order+3)/6 = 1, 4, 10, 20, 35 matrices of n*n doubles one after the other (-1 outside
+ * 0 .. 4), each exactly symmetric, in the library's basis functions (normalisation and Cartesian-to-pure transform of the overlap).
+ * Components by l ascending, inside an order i descending, then j descending: c = 0 the overlap, 1 .. 3 x y z (the dipole matrices),
+ * 4 .. 9 xx xy xz yy yz zz, and so on.  A call of a lower order gives the leading matrices of a higher one bit for bit.
+ * origin: three doubles, NULL = (0, 0, 0).  The first needs no device; the second runs the kernel qc_scf_multipoles uses.
+ * QC_ERR_INVALID: a null handle or `out`, an order outside 0 .. 4. */
+#define QC_MULTIPOLE_MAX_ORDER 4
+int qc_multipole_count(int order);
+int qc_multipole_matrices(const qc_system *sys, int order, const double *origin, double *out);
+int qc_multipole_matrices_gpu(qc_system *sys, int order, const double *origin, double *out);
+
+/* Total Cartesian moments of a state.  In: order (0 .. 4), origin.  Out, per component c < qc_multipole_count(order) (the rest 0):
+ * nuclear[c] = sum_A Z_A (R_A - O)^c on the host, electronic[c] = -tr(P_t M_c) with P_t = P_alpha + P_beta the state's density on the
+ * device (available from qc_scf_begin_* on, as for qc_scf_dipole), total = nuclear + electronic; total[0] is the molecular charge and
+ * total[1 .. 3] the dipole moment.  quadrupole_traceless: xx xy xz yy yz zz of (3 Q_ab - delta_ab tr Q) / 2 from the total second
+ * moments Q; 0 when order < 2.  QC_ERR_INVALID: a null pointer, an order outside 0 .. 4. */
+typedef struct {
+    int32_t order, reserved;
+    double origin[3];
+    double total[35], nuclear[35], electronic[35];
+    double quadrupole_traceless[6];
+} qc_multipoles;
+int qc_scf_multipoles(qc_scf_state *st, qc_multipoles *io);
+
+/* Population analysis.  scheme 0: Mulliken charges with Mayer bond orders; 1: Loewdin charges with Wiberg indices in the Loewdin basis.
+ * With P_t = P_alpha + P_beta, P_s = P_alpha - P_beta, "a in A" = function a sits on atom A, and A_x = P_x S (scheme 0) or
+ * A_x = S^1/2 P_x S^1/2 (scheme 1; S^1/2 = S X with X the S^-1/2 of the SCF set-up):
+ *   N_A = sum_{a in A} (A_t)_aa,  charges[A] = Z_A - N_A,  spin[A] = sum_{a in A} (A_s)_aa,  orbital[a] = (A_t)_aa,
+ *   bond_orders[A, B] = sum_{a in A, b in B} (A_t)_ab (A_t)_ba + (A_s)_ab (A_s)_ba  (exactly symmetric; the diagonal as computed).
+ * charges: natoms.  spin (nullable): natoms, exactly 0 for an RHF state or nspin 1.  orbital (nullable): n.  bond_orders (nullable):
+ * natoms x natoms.  The first reads the state's densities, S and X where they lie on the device.  The second takes host densities in
+ * the qc_fock_rhf / qc_gradient conventions (nspin 1: D n*n with the factor 2; nspin 2: [Da; Db]) and builds S and X itself with the
+ * kernels and the eigensolver of the SCF set-up.  QC_ERR_INVALID: a null handle, state, D or `charges`, a scheme outside 0 .. 1, an
+ * nspin outside 1 .. 2. */
+int qc_scf_populations(qc_scf_state *st, int scheme, double *charges, double *spin, double *orbital, double *bond_orders);
+int qc_populations(qc_system *sys, int scheme, int nspin, const double *D, double *charges, double *spin, double *orbital, double *bond_orders);
+
+/* Charges fitted to the electrostatic potential (Merz-Kollman).
+ * In (0 = default): nscales (at most 8) and scales - factors of the van der Waals radii of the shells of points, default 4: 1.4 1.6
+ * 1.8 2.0; density - points per bohr^2 of sphere surface, default 1 per Angstrom^2 (1 bohr = QC_BOHR_ANGSTROM Angstrom).
+ * Out: npts; total_charge (the constraint); rms of V - V_fit over the points and rrms = rms / rms(V); dipole = sum_A q_A R_A (origin 0);
+ * wall times of the state call and of its potential (ms).
+ * Radii in Angstrom: H 1.20, He 1.40, C 1.70, N 1.55, O 1.52, F 1.47, Ne 1.54, Si 2.10, P 1.80, S 1.80, Cl 1.75, Ar 1.88, all others
+ * 2.00.  Grid, deterministic: for each scale f (in the order given), each atom A (input order) and k = 0 .. N - 1 with R = f r_A and
+ * N = ceil(density 4 pi R^2): z = 1 - (2k + 1) / N, phi = k pi (3 - sqrt 5), point R_A + R (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi,
+ * z); a point is kept if and only if its distance to every other atom B is >= f r_B.
+ * qc_esp_fit_points (host only): the grid into xyz (capacity points of 3 doubles) and its size into *npts; capacity < *npts is
+ * QC_ERR_INVALID with *npts filled and nothing written (xyz nullable when capacity is 0).
+ * qc_esp_fit_solve (host only): the charges that minimise sum_p (v_p - sum_A q_A / |r_p - R_A|)^2 subject to sum_A q_A = total_charge -
+ * the (natoms + 1)^2 system [A^T A, 1; 1^T, 0] accumulated in point order, solved by LU with partial pivoting; fills the outputs of io
+ * (io's inputs are not read).  QC_ERR_INVALID: null pointers, npts < natoms, a point on a nucleus, a non-finite v, a singular system.
+ * qc_scf_esp_charges: the potential of the state on the library's grid for io's inputs (xyz NULL; npts is ignored) or on the caller's
+ * npts points - exactly the V of qc_scf_esp_on_points, bit for bit, returned in v_out (nullable; npts or io->npts doubles) - and the
+ * fit with total_charge = sum Z - n_alpha - n_beta.  Errors as above and as qc_scf_esp_on_points. */
+#define QC_BOHR_ANGSTROM 0.529177210903
+typedef struct {
+    int32_t nscales, reserved0;
+    double scales[8];
+    double density;
+    int64_t npts;
+    double total_charge, rms, rrms;
+    double dipole[3];
+    double ms_total, ms_potential;
+} qc_esp_fit;
+int qc_esp_fit_points(const qc_system *sys, const qc_esp_fit *cfg, int64_t capacity, double *xyz, int64_t *npts);
+int qc_esp_fit_solve(const qc_system *sys, int64_t npts, const double *xyz, const double *v, double total_charge, qc_esp_fit *io, double *charges);
+int qc_scf_esp_charges(qc_scf_state *st, qc_esp_fit *io, int64_t npts, const double *xyz, double *charges, double *v_out);
+
 /* ---- excited states of an RHF state (after SCF, not in the reference): configuration interaction singles (CIS, the Tamm-Dancoff
  * approximation) and time-dependent Hartree-Fock (TDHF, the random-phase approximation), singlets or triplets, at the state's last C and
  * orbital energies.  With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij delta_ab (e_a - e_i), rows and columns

@@ -28,6 +28,12 @@ Three additions, all opt-in:
     carries an "excitations" list, one object per flag given (CIS first).  States that do not converge, or a reference that TDHF refuses,
     are reported on stderr and end the command with exit status 1 after everything else has been printed.  The flags do not exist on
     `uhf` and do not combine with `--follow`.
+  * `--multipoles [ORDER]` (0..4, default 2) adds the total Cartesian multipole moments of the converged determinant (origin 0), one
+    `multipole moments order L (a.u.):` line per order, and the traceless quadrupole in a.u. and Debye Angstrom; `--charges` with a comma
+    list of mulliken, lowdin, esp adds per scheme a `SCHEME charges:` line and one line per atom - index, element, charge and, for `uhf`,
+    the spin population (esp: no spin; then an `esp fit:` line with the number of points, rms and rrms, and the dipole of the charges);
+    `--bond-orders` adds `mayer bond orders:` and one line per atom pair above 0.05.  `--json` then carries "multipoles", "charges" (a
+    list, one object per scheme) and "bond_orders" (the whole matrix).  None combines with `--follow`.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -97,6 +103,10 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--stability", action="store_true", help="also print the lowest eigenvalue(s) of the orbital Hessian and whether the determinant is a minimum")
         s.add_argument("--dipole", action="store_true", help="also print the dipole moment of the converged determinant (a.u. and Debye)")
         s.add_argument("--polarizability", action="store_true", help="also print the static dipole polarizability (coupled-perturbed HF, bohr^3)")
+        s.add_argument("--multipoles", type=int, nargs="?", const=2, default=None, metavar="ORDER",
+                       help="also print the total Cartesian multipole moments up to ORDER (0..4, default 2) and the traceless quadrupole")
+        s.add_argument("--charges", default=None, metavar="SCHEMES", help="also print atomic charges: a comma list of mulliken, lowdin, esp")
+        s.add_argument("--bond-orders", action="store_true", help="also print the Mayer bond orders above 0.05")
         if name == "rhf":
             s.add_argument("--cis", type=int, default=0, metavar="N", help="also print the lowest N CIS excited states (1..8)")
             s.add_argument("--tdhf", type=int, default=0, metavar="N", help="also print the lowest N TDHF (RPA) excited states (1..8)")
@@ -129,6 +139,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--frozen-core must not be negative")
     if args.follow and (args.mp2 or args.gradient or args.dipole or args.polarizability):
         p.error("--follow cannot be combined with --mp2, --gradient, --dipole or --polarizability")
+    if args.multipoles is not None and not 0 <= args.multipoles <= 4:
+        p.error("--multipoles takes an order from 0 to 4")
+    if args.charges is not None and charge_schemes(args.charges) is None:
+        p.error("--charges takes a comma list of mulliken, lowdin and esp")
+    if args.follow and wants_charge_properties(args):
+        p.error("--follow cannot be combined with --multipoles, --charges or --bond-orders")
     if args.command == "rhf":
         for flag, nstates in (("--cis", args.cis), ("--tdhf", args.tdhf)):
             if nstates < 0 or nstates > 8:
@@ -197,6 +213,96 @@ def _print_polarizability(d: dict) -> None:
 def _properties(st, args):
     """(dipole, polarizability) JSON objects of the flags given, from the converged state"""
     return (_dipole_json(st.dipole()) if args.dipole else None, _polarizability_json(st.polarizability()) if args.polarizability else None)
+
+
+AU_TO_DEBYE_ANGSTROM = AU_TO_DEBYE * hf.BOHR_ANGSTROM
+CHARGE_SCHEMES = ("mulliken", "lowdin", "esp")
+ELEMENTS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr").split()
+
+
+def element(z: int) -> str:
+    return ELEMENTS[z] if 0 < z < len(ELEMENTS) else "Z%d" % z
+
+
+def charge_schemes(text: str):
+    """the schemes of a --charges argument (a comma list of mulliken, lowdin, esp) in the order given, None if it is not one"""
+    names = [t.strip() for t in text.split(",")]
+    return names if names and all(t in CHARGE_SCHEMES for t in names) and len(set(names)) == len(names) else None
+
+
+def wants_charge_properties(args) -> bool:
+    return args.multipoles is not None or args.charges is not None or args.bond_orders
+
+
+def _multipoles_json(r: "hf.MultipolesOutput") -> dict:
+    qt = r.quadrupole_traceless[np.triu_indices(3)]
+    return {"order": r.order, "origin": r.origin.tolist(), "components": ["x" * i + "y" * j + "z" * k for i, j, k in hf.multipole_components(r.order)],
+            "total": r.total.tolist(), "nuclear": r.nuclear.tolist(), "electronic": r.electronic.tolist(),
+            "quadrupole_traceless_au": qt.tolist(), "quadrupole_traceless_debye_angstrom": (qt * AU_TO_DEBYE_ANGSTROM).tolist()}
+
+
+def _print_multipoles(d: dict) -> None:
+    lo = 0
+    for l in range(d["order"] + 1):
+        cnt = (l + 1) * (l + 2) // 2
+        print("multipole moments order %d (a.u.): %s" % (l, " ".join("%.8f" % x for x in d["total"][lo:lo + cnt])))
+        lo += cnt
+    if d["order"] >= 2:
+        print("traceless quadrupole (a.u.): %.8f %.8f %.8f %.8f %.8f %.8f" % tuple(d["quadrupole_traceless_au"]))
+        print("traceless quadrupole (Debye Angstrom): %.8f %.8f %.8f %.8f %.8f %.8f" % tuple(d["quadrupole_traceless_debye_angstrom"]))
+
+
+def _charges_json(st, scheme: str) -> dict:
+    if scheme == "esp":
+        r = st.esp_charges()
+        return {"scheme": scheme, "charges": r.charges.tolist(), "npts": len(r.points), "rms": r.rms, "rrms": r.rrms, "dipole": r.dipole.tolist(),
+                "total_charge": r.total_charge, "timings_ms": {"total": r.ms_total, "potential": r.ms_potential}}
+    r = st.populations(scheme)
+    return {"scheme": scheme, "charges": r.charges.tolist(), "spin": r.spin.tolist()}
+
+
+def _print_charges(system: MolecularSystem, d: dict, uhf: bool) -> None:
+    print("%s charges:" % d["scheme"])
+    for i, (atom, c) in enumerate(zip(system.atoms, d["charges"])):
+        line = "%d %s %.8f" % (i, element(atom.ordinal), c)
+        print(line + " %.8f" % d["spin"][i] if uhf and "spin" in d else line)
+    if d["scheme"] == "esp":
+        print("esp fit: %d points, rms %.8f, rrms %.8f" % (d["npts"], d["rms"], d["rrms"]))
+        print("esp charges dipole (a.u.): %.8f %.8f %.8f" % tuple(d["dipole"]))
+
+
+BOND_ORDER_PRINT_THRESHOLD = 0.05
+
+
+def _print_bond_orders(system: MolecularSystem, bo) -> None:
+    print("mayer bond orders:")
+    for i in range(len(bo)):
+        for j in range(i + 1, len(bo)):
+            if bo[i][j] > BOND_ORDER_PRINT_THRESHOLD:
+                print("%d %s - %d %s %.8f" % (i, element(system.atoms[i].ordinal), j, element(system.atoms[j].ordinal), bo[i][j]))
+
+
+def _charge_properties(st, args):
+    """{"multipoles", "charges", "bond_orders"} JSON objects of the flags given, from the converged state; None without any of them"""
+    if not wants_charge_properties(args):
+        return None
+    out = {}
+    if args.multipoles is not None:
+        out["multipoles"] = _multipoles_json(st.multipoles(args.multipoles))
+    if args.charges is not None:
+        out["charges"] = [_charges_json(st, scheme) for scheme in charge_schemes(args.charges)]
+    if args.bond_orders:
+        out["bond_orders"] = st.populations("mulliken", bond_orders=True).bond_orders.tolist()
+    return out
+
+
+def _print_charge_properties(system: MolecularSystem, chg: dict, uhf: bool) -> None:
+    if "multipoles" in chg:
+        _print_multipoles(chg["multipoles"])
+    for d in chg.get("charges", []):
+        _print_charges(system, d, uhf)
+    if "bond_orders" in chg:
+        _print_bond_orders(system, chg["bond_orders"])
 
 
 def cube_grid(system: MolecularSystem, spacing: float, margin: float):
@@ -362,15 +468,16 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = grad = stab = dip = pol = cube = None
+    mp2 = grad = stab = dip = pol = cube = chg = None
     exc = []
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.cube:
+    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.cube or wants_charge_properties(args):
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
                                                              st.gradient() if args.gradient else None,
                                                              _stability(st, False) if args.stability else None) + _properties(st, args)
-                                                            + (_excitations(st, args), _cube(st, system, args, False) if args.cube else None))
-        out, (mp2, grad, stab, dip, pol, exc, cube) = res if res is not None else (None, (None,) * 5 + ([], None))
+                                                            + (_excitations(st, args), _cube(st, system, args, False) if args.cube else None,
+                                                               _charge_properties(st, args)))
+        out, (mp2, grad, stab, dip, pol, exc, cube, chg) = res if res is not None else (None, (None,) * 5 + ([], None, None))
     elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
@@ -399,6 +506,8 @@ def run_rhf(args) -> int:
         _print_polarizability(pol)
     for e in exc:
         _print_excitations(e)
+    if chg is not None:
+        _print_charge_properties(system, chg, False)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -417,6 +526,8 @@ def run_rhf(args) -> int:
             doc["excitations"] = exc
         if cube is not None:
             doc["cube"] = cube
+        if chg is not None:
+            doc.update(chg)
         print(json.dumps(doc))
     if any(not e["converged"] for e in exc):
         return EXCITATIONS_FAILED
@@ -433,8 +544,9 @@ def run_uhf(args) -> int:
     if args.follow:
         return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
-    s2 = mp2 = grad = stab = dip = pol = cube = None
-    if not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability and not args.cube:
+    s2 = mp2 = grad = stab = dip = pol = cube = chg = None
+    if (not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability and not args.cube
+            and not wants_charge_properties(args)):
         out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
@@ -458,6 +570,7 @@ def run_uhf(args) -> int:
                     dip, pol = _properties(st, args)
                     if args.cube:
                         cube = _cube(st, system, args, True, n_alpha)
+                    chg = _charge_properties(st, args)
                     break
         finally:
             st.close()
@@ -483,6 +596,8 @@ def run_uhf(args) -> int:
         _print_dipole(dip)
     if pol is not None:
         _print_polarizability(pol)
+    if chg is not None:
+        _print_charge_properties(system, chg, True)
     if args.json:
         doc = {"method": "uhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -501,6 +616,8 @@ def run_uhf(args) -> int:
             doc["polarizability"] = pol
         if cube is not None:
             doc["cube"] = cube
+        if chg is not None:
+            doc.update(chg)
         print(json.dumps(doc))
     return 0
 

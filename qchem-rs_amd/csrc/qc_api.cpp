@@ -175,6 +175,61 @@ int qc_dipole_matrices_gpu(qc_system *S, const double *origin, double *out) {
     return QC_OK;
 }
 
+int qc_multipole_count(int order) { return order < 0 || order > QC_MULTIPOLE_MAX_ORDER ? -1 : qc_nherm(order); }
+int qc_multipole_matrices(const qc_system *S, int order, const double *origin, double *out) {
+    if (!S || !out || qc_multipole_count(order) < 0) return QC_ERR_INVALID;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    qc_host_multipole(S, order, origin ? origin : zero, out);
+    return QC_OK;
+}
+int qc_multipole_matrices_gpu(qc_system *S, int order, const double *origin, double *out) {
+    if (!S || !out || qc_multipole_count(order) < 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t all = (size_t)qc_nherm(order) * S->nbasis * S->nbasis;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    DevBuf M;
+    if (M.alloc(all) != QC_OK) return QC_ERR_HIP;
+    if ((rc = qc_multipole_device(S, order, origin ? origin : zero, M.p)) != QC_OK) return rc;
+    QC_HIP_CHECK(hipMemcpyAsync(out, M.p, all * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    return QC_OK;
+}
+
+// populations from host densities: S by the one-electron kernel, X as the SCF set-up forms it (Loewdin only)
+int qc_populations(qc_system *S, int scheme, int nspin, const double *D, double *charges, double *spin, double *orbital, double *bond_orders) {
+    if (!S || !D || !charges || scheme < 0 || scheme > 1 || nspin < 1 || nspin > 2) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf dD, dS, dX;
+    if (dD.alloc(nspin * nn) != QC_OK || dS.alloc(nn) != QC_OK || (scheme == 1 && dX.alloc(nn) != QC_OK)) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if ((rc = qc_one_electron_device(S, 0, dS.p)) != QC_OK) return rc;
+    if (scheme == 1 && (rc = qc_population_x_device(S, dS.p, dX.p)) != QC_OK) return rc;
+    std::vector<double> Nt(S->natoms), Ns(S->natoms);
+    if ((rc = qc_population_device(S, scheme, dD.p, nspin == 2 ? dD.p + nn : nullptr, dS.p, dX.p, Nt.data(), Ns.data(), orbital, bond_orders)) != QC_OK) return rc;
+    for (int a = 0; a < S->natoms; ++a) { charges[a] = S->Z[a] - Nt[a]; if (spin) spin[a] = Ns[a]; }
+    return QC_OK;
+}
+
+int qc_esp_fit_points(const qc_system *S, const qc_esp_fit *cfg, int64_t capacity, double *xyz, int64_t *npts) {
+    int nscales; double scales[8], density;
+    if (!S || !npts || capacity < 0 || (capacity > 0 && !xyz) || !qc_espfit_config(cfg, &nscales, scales, &density)) return QC_ERR_INVALID;
+    std::vector<double> pts;
+    qc_espfit_grid(S, nscales, scales, density, pts);
+    *npts = (int64_t)(pts.size() / 3);
+    if (capacity < *npts) return QC_ERR_INVALID;
+    std::copy(pts.begin(), pts.end(), xyz);
+    return QC_OK;
+}
+int qc_esp_fit_solve(const qc_system *S, int64_t npts, const double *xyz, const double *v, double total_charge, qc_esp_fit *io, double *charges) {
+    if (!S || !xyz || !v || !io || !charges || npts < 0 || !std::isfinite(total_charge)) return QC_ERR_INVALID;
+    return qc_espfit_solve(S, npts, xyz, v, total_charge, io, charges);
+}
+
 int qc_set_stream(qc_system *S, void *hip_stream) {
     if (!S) return QC_ERR_INVALID;
     if (S->own_stream && S->stream) { (void)hipStreamDestroy(S->stream); S->own_stream = false; }

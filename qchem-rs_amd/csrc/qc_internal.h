@@ -387,6 +387,20 @@ int qc_dipole_device(qc_system *S, const double *origin /* 3, host */, double *d
 // dEps, by a reduced-space iteration on the Hessian-vector product of the stability analysis; io's inputs are checked by the caller,
 // response (host, nullable): 3 x dim.  Runs direct Fock builds on the handle: the caller puts FockPrepSave around it.
 int qc_dipole_trace_device(qc_system *S, const double *dPa, const double *dPb, const double *dM, double *tr3);
+// Cartesian multipoles: the qc_nherm(order) matrices of order 0 .. 4 on the host (qc_system.cpp) and on the device
+// (qc_one_electron.hip; origin: three doubles on the host), and tr[c] = tr((Pa + Pb) M_c) for `count` matrices (qc_response.hip)
+void qc_host_multipole(const qc_system *S, int order, const double *origin /* 3 */, double *out /* qc_nherm(order) n*n */);
+int qc_multipole_device(qc_system *S, int order, const double *origin, double *d_out);
+int qc_multipole_trace_device(qc_system *S, int count, const double *dPa, const double *dPb, const double *dM, double *tr);
+// ESP-fitted charges, host numerics (qc_espfit.cpp).  config: cfg's inputs with the defaults filled in (scales: 8 doubles), false = bad;
+// grid: the points in the documented order; solve: the constrained fit, fills io's outputs (the caller has checked the pointers)
+bool qc_espfit_config(const qc_esp_fit *cfg, int *nscales, double *scales, double *density);
+void qc_espfit_grid(const qc_system *S, int nscales, const double *scales, double density, std::vector<double> &xyz);
+int qc_espfit_solve(const qc_system *S, int64_t npts, const double *xyz, const double *v, double total_charge, qc_esp_fit *io, double *charges);
+// population analysis (qc_population.hip): see the head of that file
+int qc_population_x_device(qc_system *S, const double *dS, double *dX);
+int qc_population_device(qc_system *S, int scheme, const double *dPa, const double *dPb, const double *dS, const double *dX, double *Nt, double *Ns,
+                         double *orbital, double *bond_orders);
 int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_polarizability *io, double *response);
 // values on points (qc_points.hip): density / orbitals / electronic part of the electrostatic potential on npts > 0 host points from
 // device matrices, in batches sized from the free device memory; the callers have checked the arguments.  orbitals: the m columns of dC
@@ -459,6 +473,7 @@ struct QcDevShell { double A[3]; int L, nprim, ncart, nfunc, off, coff, poff, to
 struct QcShellBlob {
     const QcDevShell *sh; const double *exps, *coefs, *T; const int *Z; const double *xyz;
     const int *cshell; int nc;              // shell of each Cartesian component
+    const int *aoff, *flist;                // the basis functions of atom A, ascending: flist[aoff[A] .. aoff[A + 1])
     QcDev<unsigned char> mem;
 };
 int qc_shell_blob(qc_system *S, const QcShellBlob **out);

@@ -1,6 +1,6 @@
 // qc_md.h - the McMurchie-Davidson primitives every integral consumer outside the Fock kernels shares, host and device:
 // Hermite expansion E^{ij}_t, Boys function, the Hermite-Coulomb recurrence step, the overlap / kinetic / nuclear-attraction / dipole sums of
-// one Cartesian pair, and the order of the Cartesian components.  Users: the host model and host one-electron matrices
+// one Cartesian pair, the Hermite moments behind the Cartesian multipoles, and the order of the Cartesian components.  Users: the host model and host one-electron matrices
 // (qc_system.cpp), the one-electron kernel (qc_one_electron.hip), the gradient kernels (qc_grad.hip).  The Fock kernels keep their
 // own interpolated Boys function and staged tables.
 //
@@ -112,6 +112,40 @@ template <class E1> __host__ __device__ inline double qc_md_dip(const E1 *E, con
     for (int q = 0; q < 3; ++q) s[q] = E[q].g(a[q], b[q], 0);
     s[k] = E[k].g(a[k], b[k], 1) + PO * s[k];
     return f * s[0] * s[1] * s[2];
+}
+// ---- Cartesian multipole moments <a| (x - O_x)^i (y - O_y)^j (z - O_z)^k |b>, i + j + k <= QC_MOM_MAX.  Components by total order
+// ascending, inside an order as qc_md_cart (its table ends at QC_LMAX, hence one of its own here).
+constexpr int QC_MOM_MAX = 4;
+struct QcMdMomTab { unsigned char l[qc_nherm(QC_MOM_MAX)][3]; };
+constexpr QcMdMomTab qc_md_make_mom() {
+    QcMdMomTab c{};
+    int k = 0;
+    for (int L = 0; L <= QC_MOM_MAX; ++L)
+        for (int lx = L; lx >= 0; --lx)
+            for (int ly = L - lx; ly >= 0; --ly, ++k) { c.l[k][0] = (unsigned char)lx; c.l[k][1] = (unsigned char)ly; c.l[k][2] = (unsigned char)(L - lx - ly); }
+    return c;
+}
+constexpr QcMdMomTab qc_md_mom_tab = qc_md_make_mom();
+__host__ __device__ inline const unsigned char *qc_md_mom_comp(int c) { return qc_md_mom_tab.l[c]; }
+// Hermite moments of one axis, M[m * (QC_MOM_MAX + 1) + t] = int (x - O)^m Lambda_t dx / sqrt(pi/p), m <= mmax (X = P - O):
+//   M^0_t = delta_t0,  M^(m+1)_t = X M^m_t + t M^m_(t-1) + M^m_(t+1) / 2p,  M^m_t = 0 for t > m
+__host__ __device__ inline void qc_md_mom_herm(int mmax, double X, double p, double *M) {
+    constexpr int W = QC_MOM_MAX + 1;
+    const double h = 0.5 / p;
+    for (int k = 0; k < W * W; ++k) M[k] = 0.0;
+    M[0] = 1.0;
+    for (int m = 0; m < mmax; ++m)
+        for (int t = 0; t <= m + 1; ++t)
+            M[(m + 1) * W + t] = X * M[m * W + t] + (t > 0 ? t * M[m * W + t - 1] : 0.0) + (t < m ? h * M[m * W + t + 1] : 0.0);
+}
+// the 1-D factors of one axis for the pair (i, j): F[m] = sum_{t <= min(m, i + j)} E^{ij}_t M^m_t, m <= mmax; m = 1 is E_1 + X E_0
+template <class E1> __host__ __device__ inline void qc_md_mom_1d(const E1 &E, int i, int j, int mmax, const double *M, double *F) {
+    constexpr int W = QC_MOM_MAX + 1;
+    for (int m = 0; m <= mmax; ++m) {
+        double s = 0.0;
+        for (int t = 0; t <= m && t <= i + j; ++t) s += E.g(i, j, t) * M[m * W + t];
+        F[m] = s;
+    }
 }
 // sum_axis <a| d^2/dx^2 |b> (second derivative of the ket primitive: b + 2, b, b - 2 terms; eb: its exponent); T = -1/2 (pi/p)^{3/2} x this
 template <class E1> __host__ __device__ inline double qc_md_kin(const E1 *E, const int *a, const int *b, double eb) {

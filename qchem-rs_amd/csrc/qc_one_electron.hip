@@ -1,4 +1,4 @@
-// qc_one_electron.hip - overlap, kinetic-energy, nuclear-attraction and dipole matrices on the GPU.
+// qc_one_electron.hip - overlap, kinetic-energy, nuclear-attraction, dipole and Cartesian multipole matrices on the GPU.
 //
 // Replaces molint::overlap / kinetic / nuclear (call sites rhf.rs:41-43, uhf.rs:52-54) - the first "next" row of the
 // scope table: the last CPU-only start-up phase of an SCF run.  Same McMurchie-Davidson formulas as the
@@ -143,6 +143,63 @@ __global__ __launch_bounds__(64) void qc_dipole_kernel(int nshells, const QcDevS
     }
 }
 
+// Cartesian multipole matrices out[c * n * n + ..] = <a| (x - O_x)^i (y - O_y)^j (z - O_z)^k |b>, the count = qc_nherm(order) components of
+// qc_md_mom_comp in one launch: the shape of the dipole kernel with `count` Cartesian LDS blocks (dynamic: count x 10 x 10 doubles, 28 KB at
+// order 4).  Per primitive pair the Hermite moments of the three axes, per Cartesian pair the 1-D factors of every power - shared by all
+// components.
+__global__ __launch_bounds__(64) void qc_multipole_kernel(int nshells, int order, const QcDevShell *__restrict__ sh, const double *__restrict__ exps,
+                                                          const double *__restrict__ coefs, const double *__restrict__ Tm, double ox, double oy, double oz,
+                                                          int n, double *__restrict__ out) {
+    extern __shared__ double mcart[];
+    constexpr int W = QC_MOM_MAX + 1;
+    int a = 0, rem = blockIdx.x;
+    while (rem > a) { rem -= a + 1; ++a; }
+    const int b = rem;
+    if (a >= nshells) return;
+    const QcDevShell A = sh[a], B = sh[b];
+    const int lane = threadIdx.x, nca = A.ncart, ncb = B.ncart, count = qc_nherm(order);
+    for (int i = lane; i < count * MAXC * MAXC; i += 64) mcart[i] = 0.0;
+    __syncthreads();
+    const double O[3] = {ox, oy, oz};
+    const int npp = A.nprim * B.nprim;
+    for (int pp = lane; pp < npp; pp += 64) {
+        const int i = pp / B.nprim, j = pp - i * B.nprim;
+        const double ea = exps[A.poff + i], eb = exps[B.poff + j], p = ea + eb, cc = coefs[A.poff + i] * coefs[B.poff + j];
+        E1 E[3];
+        double M[3][W * W];
+        for (int k = 0; k < 3; ++k) {
+            E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+            qc_md_mom_herm(order, (ea * A.A[k] + eb * B.A[k]) / p - O[k], p, M[k]);
+        }
+        const double s3 = pow(M_PI / p, 1.5);
+        for (int x = 0; x < nca; ++x) {
+            const unsigned char *ax = qc_md_cart(A.L, x);
+            for (int y = 0; y < ncb; ++y) {
+                const unsigned char *by = qc_md_cart(B.L, y);
+                double F[3][W];
+                for (int k = 0; k < 3; ++k) qc_md_mom_1d(E[k], ax[k], by[k], order, M[k], F[k]);
+                for (int c = 0; c < count; ++c) {
+                    const unsigned char *m = qc_md_mom_comp(c);
+                    (void)__builtin_amdgcn_ds_atomic_fadd_f64((lds_double *)&mcart[(c * MAXC + x) * MAXC + y], cc * (s3 * F[0][m[0]] * F[1][m[1]] * F[2][m[2]]));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // Cartesian -> the shells' functions, both triangles, as above
+    const double *Ta = Tm + A.toff, *Tb = Tm + B.toff;
+    const size_t nn = (size_t)n * n;
+    for (int f = lane; f < count * A.nfunc * B.nfunc; f += 64) {
+        const int c = f / (A.nfunc * B.nfunc), fab = f - c * A.nfunc * B.nfunc, fa = fab / B.nfunc, fb = fab - fa * B.nfunc;
+        if (a == b && fb > fa) continue;
+        double v = 0.0;
+        for (int x = 0; x < nca; ++x)
+            for (int y = 0; y < ncb; ++y) v += Ta[fa * nca + x] * Tb[fb * ncb + y] * mcart[(c * MAXC + x) * MAXC + y];
+        out[c * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+        out[c * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+    }
+}
+
 }  // namespace
 
 // The handle's shell blob: uploaded at the first call, in one allocation and one copy; a failure leaves the handle without one.
@@ -163,7 +220,7 @@ int qc_shell_blob(qc_system *S, const QcShellBlob **out) {
             tm.insert(tm.end(), q.T.begin(), q.T.end());
             hs[s] = d;
         }
-        // sections in 256-byte steps: [shells | exps | coefs | T | cshell | Z | xyz]
+        // sections in 256-byte steps: [shells | exps | coefs | T | cshell | Z | xyz | aoff | flist]
         std::vector<unsigned char> host;
         auto put = [&host](const void *src, size_t bytes) {
             const size_t at = host.size();
@@ -175,6 +232,14 @@ int qc_shell_blob(qc_system *S, const QcShellBlob **out) {
         const size_t o_co = put(co.data(), co.size() * sizeof(double)), o_tm = put(tm.data(), tm.size() * sizeof(double));
         const size_t o_cs = put(cshell.data(), cshell.size() * sizeof(int)), o_z = put(S->Z.data(), S->Z.size() * sizeof(int));
         const size_t o_x = put(S->xyz.data(), S->xyz.size() * sizeof(double));
+        // the basis functions of each atom, ascending: atom A owns flist[aoff[A] .. aoff[A + 1])  (population analysis)
+        std::vector<int> aoff(S->natoms + 1, 0), flist;
+        for (int at = 0; at < S->natoms; ++at) {
+            for (const QcShell &q : S->shells)
+                if (q.atom == at) for (int f = 0; f < q.nfunc; ++f) flist.push_back(q.off + f);
+            aoff[at + 1] = (int)flist.size();
+        }
+        const size_t o_ao = put(aoff.data(), aoff.size() * sizeof(int)), o_fl = put(flist.data(), flist.size() * sizeof(int));
         std::unique_ptr<QcShellBlob> B(new QcShellBlob{});
         if (B->mem.alloc(host.size()) != QC_OK) return QC_ERR_HIP;
         QC_HIP_CHECK(hipMemcpy(B->mem.p, host.data(), host.size(), hipMemcpyHostToDevice));
@@ -183,6 +248,7 @@ int qc_shell_blob(qc_system *S, const QcShellBlob **out) {
         B->exps = reinterpret_cast<const double *>(m + o_ex); B->coefs = reinterpret_cast<const double *>(m + o_co);
         B->T = reinterpret_cast<const double *>(m + o_tm); B->xyz = reinterpret_cast<const double *>(m + o_x);
         B->cshell = reinterpret_cast<const int *>(m + o_cs); B->Z = reinterpret_cast<const int *>(m + o_z);
+        B->aoff = reinterpret_cast<const int *>(m + o_ao); B->flist = reinterpret_cast<const int *>(m + o_fl);
         B->nc = (int)cshell.size();
         S->shell_blob = B.release();
     }
@@ -210,5 +276,18 @@ int qc_dipole_device(qc_system *S, const double *origin, double *d_out) {
     const int npairs = S->nshells * (S->nshells + 1) / 2;
     hipLaunchKernelGGL(qc_dipole_kernel, dim3(npairs), dim3(64), 0, S->stream, S->nshells, B->sh, B->exps, B->coefs, B->T, origin[0], origin[1], origin[2],
                        S->nbasis, d_out);
+    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
+}
+
+// order 0 .. QC_MOM_MAX; origin: three doubles on the host; d_out: qc_nherm(order) n x n device matrices
+int qc_multipole_device(qc_system *S, int order, const double *origin, double *d_out) {
+    if (order < 0 || order > QC_MOM_MAX) return QC_ERR_INVALID;
+    const QcShellBlob *B;
+    const int rc = qc_shell_blob(S, &B);
+    if (rc != QC_OK) return rc;
+    const int npairs = S->nshells * (S->nshells + 1) / 2;
+    const size_t lds = (size_t)qc_nherm(order) * MAXC * MAXC * sizeof(double);
+    hipLaunchKernelGGL(qc_multipole_kernel, dim3(npairs), dim3(64), lds, S->stream, S->nshells, order, B->sh, B->exps, B->coefs, B->T, origin[0], origin[1],
+                       origin[2], S->nbasis, d_out);
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }

@@ -48,6 +48,17 @@ int qc_dipole_trace_device(qc_system *S, const double *dPa, const double *dPb, c
     return QC_OK;
 }
 
+// the same trace for `count` matrices (the Cartesian multipoles): one workgroup per matrix
+int qc_multipole_trace_device(qc_system *S, int count, const double *dPa, const double *dPb, const double *dM, double *tr) {
+    DevBuf out;
+    if (out.alloc(count) != QC_OK) return QC_ERR_HIP;
+    hipLaunchKernelGGL(qc_dipole_trace_kernel, dim3(count), dim3(256), 0, S->stream, (size_t)S->nbasis * S->nbasis, dPa, dPb, dM, out.p);
+    QC_HIP_CHECK(hipGetLastError());
+    QC_HIP_CHECK(hipMemcpyAsync(tr, out.p, count * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    return QC_OK;
+}
+
 int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const double *dC, const double *dEps, qc_polarizability *io, double *response) {
     const double t_begin = qc_now_ms();
     constexpr int NR = QC_CPHF_NRHS, LD = QC_STAB_MAXSUB;

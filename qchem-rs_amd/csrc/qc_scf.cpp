@@ -926,6 +926,74 @@ int qc_scf_dipole(qc_scf_state *st, const double *origin, double mu[3], double m
     for (int k = 0; k < 3; ++k) { mu[k] = nuc[k] - tr[k]; if (mu_nuclear) mu_nuclear[k] = nuc[k]; }
     return QC_OK;
 }
+// total Cartesian moments up to io->order: the nuclear sums on the host, tr(P_t M_c) by the fixed-order trace on the device
+int qc_scf_multipoles(qc_scf_state *st, qc_multipoles *io) {
+    if (!st || !io || qc_multipole_count(io->order) < 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const int count = qc_multipole_count(io->order);
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    const double *O = io->origin;
+    double tr[35];
+    for (int c = 0; c < 35; ++c) io->total[c] = io->nuclear[c] = io->electronic[c] = 0.0;
+    for (double &q : io->quadrupole_traceless) q = 0.0;
+    for (int a = 0; a < S->natoms; ++a) {
+        double pw[3][QC_MULTIPOLE_MAX_ORDER + 1];
+        for (int k = 0; k < 3; ++k) { pw[k][0] = 1.0; for (int m = 1; m <= io->order; ++m) pw[k][m] = pw[k][m - 1] * (S->xyz[3 * a + k] - O[k]); }
+        for (int c = 0, l = 0; l <= io->order; ++l)
+            for (int i = l; i >= 0; --i)
+                for (int j = l - i; j >= 0; --j, ++c) io->nuclear[c] += S->Z[a] * (pw[0][i] * pw[1][j] * pw[2][l - i - j]);
+    }
+    DevBuf M;
+    if (M.alloc(count * nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    int rc = qc_multipole_device(S, io->order, O, M.p);
+    if (rc != QC_OK) return rc;
+    if ((rc = qc_multipole_trace_device(S, count, st->D[0].p, st->uhf ? st->D[1].p : nullptr, M.p, tr)) != QC_OK) return rc;
+    for (int c = 0; c < count; ++c) { io->electronic[c] = -tr[c]; io->total[c] = io->nuclear[c] - tr[c]; }
+    if (io->order >= 2) {
+        const double *Q = io->total + 4, t = Q[0] + Q[3] + Q[5];           // xx xy xz yy yz zz
+        for (int k = 0; k < 6; ++k) io->quadrupole_traceless[k] = 0.5 * (3.0 * Q[k] - ((k == 0 || k == 3 || k == 5) ? t : 0.0));
+    }
+    return QC_OK;
+}
+// populations of the state's densities with its own S and X, where they lie on the device (qc_population.hip)
+int qc_scf_populations(qc_scf_state *st, int scheme, double *charges, double *spin, double *orbital, double *bond_orders) {
+    if (!st || !charges || scheme < 0 || scheme > 1) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    std::vector<double> Nt(S->natoms), Ns(S->natoms);
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    const int rc = qc_population_device(S, scheme, st->D[0].p, st->uhf ? st->D[1].p : nullptr, st->W.S.p, st->W.X.p, Nt.data(), Ns.data(), orbital, bond_orders);
+    if (rc != QC_OK) return rc;
+    for (int a = 0; a < S->natoms; ++a) { charges[a] = S->Z[a] - Nt[a]; if (spin) spin[a] = Ns[a]; }
+    return QC_OK;
+}
+// charges fitted to the state's potential on the library's grid or the caller's points: the V of qc_scf_esp_on_points, then the host fit
+int qc_scf_esp_charges(qc_scf_state *st, qc_esp_fit *io, int64_t npts, const double *xyz, double *charges, double *v_out) {
+    int nscales; double scales[8], density;
+    if (!st || !io || !charges || (xyz && npts < 0) || !qc_espfit_config(io, &nscales, scales, &density)) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (xyz && npts < S->natoms) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const double t0 = qc_now_ms();
+    std::vector<double> grid;
+    if (!xyz) {
+        qc_espfit_grid(S, nscales, scales, density, grid);
+        xyz = grid.data(); npts = (int64_t)(grid.size() / 3);
+        if (npts < S->natoms) return QC_ERR_INVALID;
+    }
+    std::vector<double> v(npts);
+    int rc = qc_scf_esp_on_points(st, npts, xyz, v.data(), nullptr);
+    if (rc != QC_OK) return rc;
+    const double t1 = qc_now_ms();
+    int nz = 0;
+    for (int a = 0; a < S->natoms; ++a) nz += S->Z[a];
+    if ((rc = qc_espfit_solve(S, npts, xyz, v.data(), (double)(nz - st->nocc[0] - st->nocc[1]), io, charges)) != QC_OK) return rc;
+    if (v_out) std::copy(v.begin(), v.end(), v_out);
+    io->ms_potential = t1 - t0; io->ms_total = qc_now_ms() - t0;
+    return QC_OK;
+}
 // ---- values on points from the state's own densities and orbitals (qc_points.hip): they are read where they lie on the device; no Fock
 // build runs and nothing of the state or of a prepared build is written, so a following qc_scf_iterate is unchanged.
 // which 0: P_alpha + P_beta, 1: P_alpha - P_beta (an RHF state: exactly zero, nothing is launched)

@@ -397,6 +397,53 @@ void qc_host_dipole(const qc_system *S, const double *origin, double *out) {
         }
 }
 
+// ---- Cartesian multipole matrices on the host: out[c * n * n + ..] = <a| (x - O_x)^i (y - O_y)^j (z - O_z)^k |b> for the qc_nherm(order)
+// components c of qc_md_mom_comp; normalisation and transform T as for the overlap.  Per primitive pair the Hermite moments of the three
+// axes (qc_md_mom_herm), per Cartesian pair the 1-D factors of every power (qc_md_mom_1d), per component their product.
+void qc_host_multipole(const qc_system *S, int order, const double *origin, double *out) {
+    constexpr int W = QC_MOM_MAX + 1;
+    const int n = S->nbasis, count = qc_nherm(order);
+    const size_t nn = (size_t)n * n;
+    std::fill(out, out + count * nn, 0.0);
+    for (int a = 0; a < S->nshells; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const QcShell &A = S->shells[a], &B = S->shells[b];
+            const size_t nca = A.ncart, ncb = B.ncart;
+            std::vector<double> cart(count * nca * ncb, 0.0);
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
+                    E1 E[3];
+                    double M[3][W * W];
+                    for (int k = 0; k < 3; ++k) {
+                        E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+                        qc_md_mom_herm(order, (ea * A.A[k] + eb * B.A[k]) / p - origin[k], p, M[k]);
+                    }
+                    const double s3 = std::pow(M_PI / p, 1.5);
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            double F[3][W];
+                            for (int k = 0; k < 3; ++k) qc_md_mom_1d(E[k], ca[k], cb[k], order, M[k], F[k]);
+                            for (int c = 0; c < count; ++c) {
+                                const unsigned char *m = qc_md_mom_comp(c);
+                                cart[(c * nca + x) * ncb + y] += cc * (s3 * F[0][m[0]] * F[1][m[1]] * F[2][m[2]]);
+                            }
+                        }
+                }
+            for (int c = 0; c < count; ++c)
+                for (int fa = 0; fa < A.nfunc; ++fa)
+                    for (int fb = 0; fb < B.nfunc; ++fb) {
+                        if (a == b && fb > fa) continue;               // diagonal blocks: one triangle, mirrored (exactly symmetric output)
+                        double v = 0.0;
+                        for (size_t x = 0; x < nca; ++x)
+                            for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[(c * nca + x) * ncb + y];
+                        out[c * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+                        out[c * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+                    }
+        }
+}
+
 // ---- basis functions on points, on the host: out[k * n + a] = phi_a(r_k).  Per shell the contracted radial part, the Cartesian
 // monomials as running products (x^0 = 1 at a point on the centre), the rows of the shell's transform - normalisation as for the overlap.
 void qc_host_basis_on_points(const qc_system *S, int64_t npts, const double *xyz, double *out) {

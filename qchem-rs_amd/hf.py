@@ -49,7 +49,12 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability",
            "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors",
            "qc_basis_on_points", "qc_potential_matrix", "qc_esp_records", "qc_density_on_points", "qc_esp_on_points", "qc_orbitals_on_points",
-           "qc_scf_density_on_points", "qc_scf_esp_on_points", "qc_scf_orbitals_on_points", "qc_points_timings"]
+           "qc_scf_density_on_points", "qc_scf_esp_on_points", "qc_scf_orbitals_on_points", "qc_points_timings",
+           "qc_multipole_count", "qc_multipole_matrices", "qc_multipole_matrices_gpu", "qc_scf_multipoles",
+           "qc_scf_populations", "qc_populations", "qc_esp_fit_points", "qc_esp_fit_solve", "qc_scf_esp_charges"]
+
+POPULATION_SCHEMES = {"mulliken": 0, "lowdin": 1}
+BOHR_ANGSTROM = 0.529177210903   # QC_BOHR_ANGSTROM in include/qchem_hip.h
 
 
 EXCITATION_METHODS = {"cis": 0, "tdhf": 1}
@@ -134,6 +139,82 @@ class PolarizabilityOutput:
     ms_builds: float
     asymmetry: float = 0.0
     response: Optional[np.ndarray] = None
+
+
+class _Multipoles(C.Structure):
+    _fields_ = [("order", C.c_int32), ("reserved", C.c_int32), ("origin", C.c_double * 3), ("total", C.c_double * 35),
+                ("nuclear", C.c_double * 35), ("electronic", C.c_double * 35), ("quadrupole_traceless", C.c_double * 6)]
+
+
+def multipole_components(order: int):
+    """the exponents (i, j, k) of the Cartesian components up to `order`, in the library's order: by i + j + k ascending, then i
+    descending, then j descending"""
+    return [(i, j, l - i - j) for l in range(order + 1) for i in range(l, -1, -1) for j in range(l - i, -1, -1)]
+
+
+@dataclass
+class MultipolesOutput:
+    """qc_multipoles: the total, nuclear and electronic Cartesian moments (count,) of the orders 0 .. order about `origin`, in e bohr^l,
+    components as multipole_components(order); quadrupole_traceless (3, 3) = (3 Q_ab - delta_ab tr Q) / 2 of the total second moments
+    (zero when order < 2)."""
+    order: int
+    origin: np.ndarray
+    total: np.ndarray
+    nuclear: np.ndarray
+    electronic: np.ndarray
+    quadrupole_traceless: np.ndarray
+
+    def of_order(self, l: int) -> np.ndarray:
+        """the total moments of order l alone"""
+        lo = l * (l + 1) * (l + 2) // 6
+        return self.total[lo:lo + (l + 1) * (l + 2) // 2]
+
+
+@dataclass
+class PopulationsOutput:
+    """qc_scf_populations / qc_populations: charges (natoms,), spin populations N_A(alpha) - N_A(beta) (natoms,; exactly zero for a closed
+    shell), gross populations per basis function (n,), and with bond_orders the Mayer (Mulliken) or Wiberg (Loewdin) matrix
+    (natoms, natoms), diagonal as computed."""
+    scheme: str
+    charges: np.ndarray
+    spin: np.ndarray
+    orbital: np.ndarray
+    bond_orders: Optional[np.ndarray] = None
+
+
+class _EspFit(C.Structure):
+    _fields_ = [("nscales", C.c_int32), ("reserved0", C.c_int32), ("scales", C.c_double * 8), ("density", C.c_double), ("npts", C.c_int64),
+                ("total_charge", C.c_double), ("rms", C.c_double), ("rrms", C.c_double), ("dipole", C.c_double * 3),
+                ("ms_total", C.c_double), ("ms_potential", C.c_double)]
+
+
+def _esp_cfg(scales, density) -> "_EspFit":
+    io = _EspFit()
+    if scales is not None:
+        sc = [float(x) for x in scales]
+        if not 1 <= len(sc) <= 8:
+            raise QcError("esp fit: 1 to 8 scales")
+        io.nscales = len(sc)
+        for k, x in enumerate(sc):
+            io.scales[k] = x
+    if density is not None:
+        io.density = float(density)
+    return io
+
+
+@dataclass
+class EspChargesOutput:
+    """qc_esp_fit: charges (natoms,) fitted to the potential on `points` (npts, 3) with sum = total_charge; rms of V - V_fit and
+    rrms = rms / rms(V); dipole = sum_A q_A R_A (origin 0); potential: the fitted V (npts,) when the call computed it."""
+    charges: np.ndarray
+    total_charge: float
+    rms: float
+    rrms: float
+    dipole: np.ndarray
+    points: np.ndarray
+    potential: Optional[np.ndarray] = None
+    ms_total: float = 0.0
+    ms_potential: float = 0.0
 
 
 class _Excitations(C.Structure):
@@ -268,6 +349,15 @@ def lib():
         L.qc_scf_esp_on_points.argtypes = [vp, C.c_int64, vp, vp, vp]
         L.qc_scf_orbitals_on_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]
         L.qc_points_timings.argtypes = [vp, vp]
+        L.qc_multipole_count.argtypes = [C.c_int]
+        L.qc_multipole_matrices.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_multipole_matrices_gpu.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_scf_multipoles.argtypes = [vp, C.POINTER(_Multipoles)]
+        L.qc_scf_populations.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.qc_populations.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        L.qc_esp_fit_points.argtypes = [vp, C.POINTER(_EspFit), C.c_int64, vp, C.POINTER(C.c_int64)]
+        L.qc_esp_fit_solve.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.POINTER(_EspFit), vp]
+        L.qc_scf_esp_charges.argtypes = [vp, C.POINTER(_EspFit), C.c_int64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -332,6 +422,54 @@ class System:
         fn = "qc_dipole_matrices_gpu" if gpu else "qc_dipole_matrices"
         _check(getattr(lib(), fn)(self._h, _origin_ptr(origin), M.ctypes.data_as(C.c_void_p)), fn)
         return M
+
+    def multipole_matrices(self, order: int, origin=None, gpu: bool = False):
+        """(count, n, n): the Cartesian multipole matrices <a| (x - O_x)^i (y - O_y)^j (z - O_z)^k |b> of the orders 0 .. order <= 4,
+        components as multipole_components(order) - qc_multipole_matrices on the host, or with gpu=True the kernel the SCF moments use."""
+        count = lib().qc_multipole_count(int(order))
+        if count < 0:
+            raise QcError("qc_multipole_matrices: " + _ERR[QC_ERR_INVALID])
+        M = np.zeros((count, self.n, self.n))
+        fn = "qc_multipole_matrices_gpu" if gpu else "qc_multipole_matrices"
+        _check(getattr(lib(), fn)(self._h, int(order), _origin_ptr(origin), _ptr(M)), fn)
+        return M
+
+    def populations(self, D, scheme: str = "mulliken", Db=None, bond_orders: bool = False) -> "PopulationsOutput":
+        """Population analysis of host densities on the GPU (qc_populations).  RHF: D in the qc_fock_rhf convention (the factor 2
+        included); UHF: D = D_alpha, Db = D_beta.  scheme "mulliken" (Mayer bond orders) or "lowdin" (Wiberg indices)."""
+        if scheme not in POPULATION_SCHEMES:
+            raise QcError("populations: scheme must be 'mulliken' or 'lowdin'")
+        n, na = self.n, len(self.mol.atoms)
+        Dm = np.ascontiguousarray(D if Db is None else np.concatenate([np.asarray(D).reshape(n, n), np.asarray(Db).reshape(n, n)]), dtype=np.float64)
+        if Dm.size != (1 if Db is None else 2) * n * n:
+            raise QcError("qc_populations: densities must be n x n")
+        q, sp, orb = np.zeros(na), np.zeros(na), np.zeros(n)
+        bo = np.zeros((na, na)) if bond_orders else None
+        _check(lib().qc_populations(self._h, POPULATION_SCHEMES[scheme], 1 if Db is None else 2, _ptr(Dm), _ptr(q), _ptr(sp), _ptr(orb),
+                                    None if bo is None else _ptr(bo)), "qc_populations")
+        return PopulationsOutput(scheme, q, sp, orb, bo)
+
+    def esp_fit_points(self, scales=None, density=None):
+        """(npts, 3): the Merz-Kollman grid of the molecule (qc_esp_fit_points, host only) - golden-spiral points on the van der Waals
+        spheres scaled by `scales` (default 1.4 1.6 1.8 2.0) at `density` points per bohr^2 (default 1 per Angstrom^2), outside every
+        other atom's scaled sphere."""
+        cfg, k = _esp_cfg(scales, density), C.c_int64()
+        rc = lib().qc_esp_fit_points(self._h, C.byref(cfg), 0, None, C.byref(k))
+        if rc != QC_OK and k.value == 0:
+            _check(rc, "qc_esp_fit_points")
+        P = np.zeros((k.value, 3))
+        _check(lib().qc_esp_fit_points(self._h, C.byref(cfg), k.value, _ptr(P), C.byref(k)), "qc_esp_fit_points")
+        return P
+
+    def esp_fit_solve(self, points, v, total_charge: float = 0.0) -> "EspChargesOutput":
+        """Charges on the atoms that reproduce the potential v on `points` best in the least-squares sense, with sum = total_charge
+        (qc_esp_fit_solve, host only)."""
+        P, vv = _points(points), np.ascontiguousarray(v, np.float64).reshape(-1)
+        if vv.size != len(P):
+            raise QcError("qc_esp_fit_solve: one potential value per point")
+        io, q = _EspFit(), np.zeros(len(self.mol.atoms))
+        _check(lib().qc_esp_fit_solve(self._h, len(P), _ptr(P), _ptr(vv), float(total_charge), C.byref(io), _ptr(q)), "qc_esp_fit_solve")
+        return EspChargesOutput(q, io.total_charge, io.rms, io.rrms, np.array(io.dipole), P)
 
     def basis_on_points(self, points):
         """(npts, n): the basis functions on points (bohr; anything that reshapes to (npts, 3)) - qc_basis_on_points, host only."""
@@ -638,6 +776,41 @@ class ScfStepper:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _check(lib().qc_scf_dipole(self._st, _origin_ptr(origin), p(mu), p(nuc)), "qc_scf_dipole")
         return (mu, nuc) if nuclear else mu
+
+    def multipoles(self, order: int = 2, origin=None) -> "MultipolesOutput":
+        """Total Cartesian multipole moments of the state up to `order` <= 4 about `origin` (None: 0) - qc_scf_multipoles; the state is
+        left as it was."""
+        io = _Multipoles(order=int(order))
+        if origin is not None:
+            o = _origin_ptr(origin)
+            for k in range(3):
+                io.origin[k] = o[k]
+        _check(lib().qc_scf_multipoles(self._st, C.byref(io)), "qc_scf_multipoles")
+        cnt = lib().qc_multipole_count(int(order))
+        t = io.quadrupole_traceless
+        Q = np.array([[t[0], t[1], t[2]], [t[1], t[3], t[4]], [t[2], t[4], t[5]]])
+        return MultipolesOutput(int(order), np.array(io.origin), np.array(io.total[:cnt]), np.array(io.nuclear[:cnt]), np.array(io.electronic[:cnt]), Q)
+
+    def populations(self, scheme: str = "mulliken", bond_orders: bool = False) -> "PopulationsOutput":
+        """Charges, spin populations and gross orbital populations of the state, "mulliken" or "lowdin", and with bond_orders the Mayer or
+        Wiberg bond-order matrix (qc_scf_populations); the state is left as it was."""
+        if scheme not in POPULATION_SCHEMES:
+            raise QcError("populations: scheme must be 'mulliken' or 'lowdin'")
+        na = len(self.system.mol.atoms)
+        q, sp, orb = np.zeros(na), np.zeros(na), np.zeros(self.system.n)
+        bo = np.zeros((na, na)) if bond_orders else None
+        _check(lib().qc_scf_populations(self._st, POPULATION_SCHEMES[scheme], _ptr(q), _ptr(sp), _ptr(orb), None if bo is None else _ptr(bo)),
+               "qc_scf_populations")
+        return PopulationsOutput(scheme, q, sp, orb, bo)
+
+    def esp_charges(self, points=None, scales=None, density=None) -> "EspChargesOutput":
+        """Charges fitted to the state's electrostatic potential (qc_scf_esp_charges) on the library's Merz-Kollman grid (points None;
+        scales / density as System.esp_fit_points) or on the caller's points; the state is left as it was."""
+        io = _esp_cfg(scales, density)
+        P = self.system.esp_fit_points(scales, density) if points is None else _points(points)
+        q, v = np.zeros(len(self.system.mol.atoms)), np.zeros(len(P))
+        _check(lib().qc_scf_esp_charges(self._st, C.byref(io), len(P), None if points is None else _ptr(P), _ptr(q), _ptr(v)), "qc_scf_esp_charges")
+        return EspChargesOutput(q, io.total_charge, io.rms, io.rrms, np.array(io.dipole), P, v, io.ms_total, io.ms_potential)
 
     def density_on_points(self, points, spin: bool = False):
         """(npts,): the state's electron density P_alpha + P_beta on points (bohr), or with spin=True the spin density
