@@ -148,8 +148,10 @@ int qc_scf_timings(qc_scf_state *st, double *ms_setup, double *ms_fock, double *
 int qc_scf_set_stop_rule(qc_scf_state *st, double epsilon);
 /* out[0 .. n) of: ms_setup, ms_fock (builds that contained a tuner run are left out), ms_linalg, builds counted in ms_fock, host ms of
  * the first build's timing passes, passes done, two slots that are reserved, always 0, passes whose eigensolve was
- * repeated, trials of the online stream-assignment search so far (handle-wide), 1 once that search has ended */
-#define QC_SCF_NCOUNTERS 11
+ * repeated, trials of the online stream-assignment search so far (handle-wide), 1 once that search has ended, then the Roothaan steps
+ * (one per spin and pass; steps, not launches) that went through the one-workgroup kernel of n <= 64, by eigensolve route: refinement of the previous vectors
+ * (one launch), tridiagonal start (between two launches), a Jacobi kernel (between two launches) */
+#define QC_SCF_NCOUNTERS 14
 int qc_scf_counters(qc_scf_state *st, double *out, int n);
 void qc_scf_end(qc_scf_state *st);
 

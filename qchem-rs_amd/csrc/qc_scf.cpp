@@ -71,6 +71,7 @@ struct ScfWork {
     // for the 0.024 Eh lower broken-symmetry determinant after ~60 passes).
     bool rotations_only = false;
     bool small_fused = false;              // n <= QC_SMALL_MAXN: the Roothaan step runs as one workgroup with its matrices in LDS (qc_scf_small.hip)
+    int64_t small_steps[3] = {0, 0, 0}; // Roothaan steps through the one-workgroup kernel by route: Refine, Tridiag, the Jacobi routes (qc_scf_counters)
     bool cold[2] = {false, false};         // this pass's eigensolve of the spin started from the tridiagonal path (no previous vectors involved)
     int npass[2] = {3, 3};                 // refinement passes enqueued per eigensolve (follows what the last one needed)
     int mode[2] = {2, 2};                  // eigensolve of the next pass: 0 refinement, 1 two Jacobi sweeps + refinement, 2 Jacobi
@@ -368,6 +369,7 @@ int roothaan_small(qc_system *S, ScfWork &W, const PassPlan &plan, const SpinSte
     a.tl = S->tl.cur ? S->tl.cur + QC_TL_W * (QC_NUNITS + 2) : nullptr;
     const EigRoute route = eig_route(W, p.spin, n);
     W.cold[p.spin] = route == EigRoute::Tridiag;
+    W.small_steps[route == EigRoute::Refine ? 0 : route == EigRoute::Tridiag ? 1 : 2] += 1;
     int rc = QC_OK;
     if (route != EigRoute::Refine) {
         QcSmallArgs pre = a;
@@ -1124,7 +1126,8 @@ int qc_scf_counters(qc_scf_state *st, double *out, int n) {
     st->tm.flush(st->tuner());
     const double v[QC_SCF_NCOUNTERS] = {st->ms_setup, st->tm.ms_fock, st->tm.ms_linalg, (double)st->tm.builds_timed, st->tm.ms_tuner, (double)st->passes,
                                         0.0, 0.0 /* reserved */, (double)st->redos,
-                                        (double)st->S->assign.on.trials, st->S->assign.on.settled ? 1.0 : 0.0};
+                                        (double)st->S->assign.on.trials, st->S->assign.on.settled ? 1.0 : 0.0,
+                                        (double)st->W.small_steps[0], (double)st->W.small_steps[1], (double)st->W.small_steps[2]};
     for (int i = 0; i < n && i < QC_SCF_NCOUNTERS; ++i) out[i] = v[i];
     return QC_OK;
 }

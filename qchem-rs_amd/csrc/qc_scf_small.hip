@@ -7,7 +7,7 @@
 //   post   C = X C' (rhf.rs:76), new density (rhf.rs:169-181), electronic energy and diagonal rms (rhf.rs:84-88)
 // At n = 58 each of those launches is a 4-5 us latency kernel (16 tiles of 16 x 16, operands from L2) and the pass is bound by launch
 // gaps.  Here four waves - one per SIMD of one CU, 512 registers each - own a 2 x 2 set of 16 x 16 tiles each.  A matrix is a 64 x 66
-// block of LDS (34 KB; four of them in the CU's 160 KB) whose padding rows and columns are zeroed once and never written again, so a
+// block of LDS (34 KB; four of them in the CU's 160 KB) whose padding rows and columns are zeroed once and afterwards receive zeros only, so a
 // product is 16 k-steps of four independent f64 MFMAs per wave fed by four ds_read_b64 with no bounds test anywhere (leading dimension
 // 66 = 2 mod 4 doubles: the row-strided fragments hit distinct bank pairs), all operands requested before the first matrix
 // instruction; phases are separated by s_barrier instead of kernel boundaries; whatever streams in from L2 (Fock / error matrices of the
@@ -16,6 +16,8 @@
 // a first LDS form with 16 waves of one tile each was no faster than the launches it replaced: 128 registers per lane serialise the
 // loads; bounds tests as branches put a wait behind every load.)  All reductions have a fixed order: results are deterministic.
 #include <atomic>
+#include <cstddef>
+#include <type_traits>
 
 #include "qc_internal.h"
 #include "qc_refine_rule.h"
@@ -35,15 +37,42 @@ __device__ __forceinline__ double qcs_readlane(double v, int lane) {
 }
 __device__ __forceinline__ int qcs_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
+// A uniform / per-lane integer as a value the compiler knows nothing about.  Tests against n and the column index are loop invariants;
+// hoisted out of the refinement loop and shared between products they are some hundred lane masks that do not fit the scalar registers
+// and come back from the lanes of a vector register two v_readlane each.  A phase, a refinement pass and a product each start from a
+// fresh copy, so their tests are formed where they are used (a scalar compare in front of a branch, a v_cmp in front of a select).
+__device__ __forceinline__ int qcs_fresh(int v) { asm volatile("" : "+s"(v)); return v; }
+__device__ __forceinline__ int qcs_fresh_v(int v) { asm volatile("" : "+v"(v)); return v; }
+
+// A field of the launch's arguments, read from the kernarg segment where it is used.  QcSmallArgs is 128 dwords, more than a wave has
+// scalar registers: taken as the kernel's parameter it is loaded whole at the top, and what of it stays live competes with the lane
+// masks of the element loops for the scalar registers.  The offset goes through an empty asm statement, so the load cannot be hoisted
+// to the top (nor merged with another read of the same field: a phase reads what it needs once, where it starts).
+template <typename T>
+__device__ __forceinline__ T qcs_karg(unsigned off) {
+    asm volatile("" : "+s"(off));
+    typedef const __attribute__((address_space(4))) char *kptr;
+    return *(const __attribute__((address_space(4))) T *)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+#define QCS_A(f) qcs_karg<decltype(QcSmallArgs::f)>((unsigned)offsetof(QcSmallArgs, f))
+#define QCS_AI(f, i) qcs_karg<std::remove_extent_t<decltype(QcSmallArgs::f)>>((unsigned)(offsetof(QcSmallArgs, f) + sizeof(QcSmallArgs::f[0]) * (i)))
+// element `off` bytes behind a uniform base: the scalar-base form of a global load / store, no 64-bit address per element.  The offset
+// is made opaque HERE: its zero extension then stands in the block of the access, where instruction selection can fold it into the
+// scalar-base form; extended where the offsets are formed (another block) every access got a v_lshl_add_u64 and a register pair.
+__device__ __forceinline__ double qcs_ld(const double *base, unsigned off) { off = qcs_fresh_v(off); return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + off); }
+__device__ __forceinline__ void qcs_st(double *base, unsigned off, double v) { off = qcs_fresh_v(off); *reinterpret_cast<double *>(reinterpret_cast<char *>(base) + off) = v; }
+
 // C = alpha op(A) op(B) on the zero-padded 64 x 66 blocks.  QUAD (n > 32): wave w owns the tiles (w >> 1) + 2 a, (w & 1) + 2 b, a, b in
 // {0, 1} - the partial edge tiles of a 58 x 58 matrix are spread evenly - and runs all 16 k-steps; otherwise (n <= 32) one tile per wave, 8
-// k-steps.  `ks` limits the k-steps (density: only the occupied columns, KMASK).  Padding operands are zeros, padding results are not stored.
+// k-steps.  `ks` limits the k-steps (density: only the occupied columns, KMASK).  Padding operands are zeros, padding results are stored as zeros.
 // Lane maps of v_mfma_f64_16x16x4 as in qc_gemm_tile (qc_linalg.hip); the k-steps of a tile run in ascending order, so an element is the
 // same chain of fused multiply-adds as there.  C must not alias A or B; the caller separates phases by barriers.
 template <bool TA, bool TB, bool QUAD, bool KMASK>
 __device__ __forceinline__ void qcs_gemm_t(const double *__restrict__ A, const double *__restrict__ B, double *__restrict__ C, int n, int ks,
                                            int kdim, double alpha) {
     constexpr int NT = QUAD ? 2 : 1, NK = QUAD ? 16 : 8, ld = QCS_LD;
+    n = qcs_fresh(n); ks = qcs_fresh(ks);
+    if constexpr (!KMASK) __builtin_assume(QUAD ? (ks > NK / 2 && ks <= NK) : (ks >= 1 && ks <= NK));     // (kdim = n, and n > 32 with 2 x 2 tiles)
     const int wave = qcs_wave(), lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
     const int r0 = (wave >> 1) * 16, c0 = (wave & 1) * 16;
     const int a_s = TA ? 1 : ld, a_k = TA ? ld : 1, b_s = TB ? ld : 1, b_k = TB ? 1 : ld;
@@ -78,19 +107,18 @@ __device__ __forceinline__ void qcs_gemm_t(const double *__restrict__ A, const d
         for (int y = 0; y < NT; ++y) {
             const int col = c0 + 32 * y + li;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
+            for (int r = 0; r < 4; ++r) {                  // (the padding of C is zero and gets zeros: a select, no lane mask per store)
                 const int row = r0 + 32 * x + lk + 4 * r;
-                if (row < n && col < n) C[row * ld + col] = alpha * acc[x][y][r];
+                C[row * ld + col] = (row < n && col < n) ? alpha * acc[x][y][r] : 0.0;
             }
         }
 }
 // KMASK: kdim < n (the density, C_occ C_occ^T): operands past kdim are not padding and are masked
-template <bool TA, bool TB, bool KMASK = false>
+template <bool QUAD, bool TA, bool TB, bool KMASK = false>
 __device__ __forceinline__ void qcs_gemm(const double *__restrict__ A, const double *__restrict__ B, double *__restrict__ C, int n, int kdim,
                                          double alpha) {
     const int ks = (kdim + 3) >> 2;
-    if (n > 32) qcs_gemm_t<TA, TB, true, KMASK>(A, B, C, n, ks, kdim, alpha);
-    else qcs_gemm_t<TA, TB, false, KMASK>(A, B, C, n, ks, kdim, alpha);
+    qcs_gemm_t<TA, TB, QUAD, KMASK>(A, B, C, n, ks, kdim, alpha);
 }
 
 // sum over the workgroup of NV values per thread, fixed order: lanes by shuffles, waves by thread j (nv <= NV of them are wanted)
@@ -170,17 +198,36 @@ __device__ __forceinline__ bool qcs_qr_solve(double (&col)[13], int lane, double
 //   refine  B0 / B2: the vectors and their update in turn (X^T A X where the update will go)    B3: F'
 //           B1: A X, X^T X, I + E, at the end X = S^-1/2 for post
 //   post    B1: X = S^-1/2    C = X C' in whichever of B0 / B2 C' is not in    B3: the density
+// One instance per shape (QUAD: n > 32, 2 x 2 tiles per wave) and per set of phases PH (1 pre, 2 refine, 4 post) that a launch runs: an
+// instance holds only the products and branches of its launch.  The arguments are read through QCS_A / QCS_AI, never through `a`.
+template <bool QUAD, int PH>
 __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a) {
     extern __shared__ double lds[];
     constexpr int ld = QCS_LD, BUF = QCS_BUF;
-    const int n = a.n;
+    {   // every cache line of the argument block is requested once, together, before the first field is read: the reads at the use sites
+        // then hit the scalar cache instead of paying the block's memory latency one line after the other
+        int t0, t1, t2, t3, t4, t5, t6, t7, t8;
+        static_assert(sizeof(QcSmallArgs) == 512, "one request per 64-byte line of QcSmallArgs");
+        asm volatile("s_load_dword %0, %9, 0x0\n\ts_load_dword %1, %9, 0x40\n\ts_load_dword %2, %9, 0x80\n\ts_load_dword %3, %9, 0xc0\n\t"
+                     "s_load_dword %4, %9, 0x100\n\ts_load_dword %5, %9, 0x140\n\ts_load_dword %6, %9, 0x180\n\ts_load_dword %7, %9, 0x1c0\n\t"
+                     "s_load_dword %8, %9, 0x1fc\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3), "=&s"(t4), "=&s"(t5), "=&s"(t6), "=&s"(t7), "=&s"(t8)
+                     : "s"(__builtin_amdgcn_kernarg_segment_ptr()));
+    }
+    const int n0 = QCS_A(n);
     double *B0 = lds, *B1 = lds + BUF, *B2 = lds + 2 * BUF, *B3 = lds + 3 * BUF;
     double *sm = lds + 4 * BUF;
     double *lam = sm, *red = lam + 64, *dots = red + QCS_W * 12, *cvec = dots + 12, *Bl = cvec + 12, *scal = Bl + 144, *gsh = scal + 8;
     int *partner = reinterpret_cast<int *>(gsh + 12 * 16), *rank_s = partner + 64, *flg = rank_s + 64;
-    const int tid = threadIdx.x, rr = tid >> 6, cc = tid & 63;           // this thread's elements: rows rr + 4 q, column cc
-    const bool cok = cc < n;
-    if (a.tl != nullptr && tid == 0) a.tl[0] = wall_clock64();
+    const int tid0 = threadIdx.x, rr0 = qcs_wave(), cc0 = tid0 & 63;     // this thread's elements: rows rr + 4 q (uniform in a wave), column cc
+    // n, tid, rr, cc and the column test of a scope (qcs_fresh); the launcher guarantees the instance's range of n
+#define QCS_FRESH() const int n = qcs_fresh(n0), tid = qcs_fresh_v(tid0), rr = qcs_fresh(rr0), cc = qcs_fresh_v(cc0); \
+                    __builtin_assume(tid >= 0 && tid < QCS_T); \
+                    __builtin_assume(QUAD ? (n > 32 && n <= 64) : (n >= 1 && n <= 32)); __builtin_assume(rr >= 0 && rr < QCS_W); \
+                    __builtin_assume(cc >= 0 && cc < 64); const bool cok = cc < n; \
+                    const int nq = qcs_fresh_v(cok ? (n - rr + QCS_W - 1) / QCS_W : 0); (void)nq   /* this thread's elements inside the matrix: q < nq */
+    QCS_FRESH();
+    { unsigned long long *const tl = QCS_A(tl); if (tl != nullptr && tid == 0) tl[0] = wall_clock64(); }
     bool ok = true;                                                      // (uniform) the eigenvectors for `post` exist
     double *Cpv = B0;                                                    // ... and the block they are in
 #ifdef QC_SMALL_TIMING
@@ -191,16 +238,22 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
 #define QCS_STAMP() do {} while (0)
 #endif
     // element loops: all of a thread's loads are requested before the first use; out-of-range elements read element 0 and are not stored
+    // to global memory.  A row is in range for a whole wave or not at all (scalar branch), a column for a lane: global stores of a loop
+    // stand under ONE lane mask (QCS_PUT), stores to the padded blocks of LDS under none - the padding is zero and gets zeros (QCS_PUTL).
 #define QCS_EACH(q, i) _Pragma("unroll") for (int q = 0, i = rr; q < QCS_E; ++q, i += QCS_W)
-#define QCS_IN(i) (cok && (i) < n)
-#define QCS_GX(i) (gx[q])                                                // (inside QCS_EACH(q, i) only)
-    // the sixteen offsets are formed once: re-formed at every load (two tests, a multiplication and a select each) they cost the phases
+#define QCS_IN(i) (q < nq)                                               // (inside QCS_EACH(q, i) only) cok && i < n as ONE vector compare
+#define QCS_GX(i) (gx[q])                                                // (inside QCS_EACH(q, i) only: byte offset of element (i, cc))
+#define QCS_GET(p) qcs_ld(p, gx[q])                                      // (likewise) element (i, cc) of the n x n matrix p in global memory
+#define QCS_PUT(p, v) do { if (cok) QCS_EACH(q, i) if (i < n) qcs_st(p, gx[q], v); } while (0)
+#define QCS_PUTL(B, v) QCS_EACH(q, i) (B)[i * ld + cc] = QCS_IN(i) ? (v) : 0.0
+    // the sixteen byte offsets are formed once: re-formed at every load (two tests, a multiplication and a select each) they cost the phases
     // that stream matrices from L2 more than the loads themselves
     unsigned gx[QCS_E];
-    QCS_EACH(q, i) gx[q] = QCS_IN(i) ? (unsigned)(i * n + cc) : 0u;
+    QCS_EACH(q, i) gx[q] = QCS_IN(i) ? (unsigned)(i * n + cc) * 8u : 0u;
 
     // The padding of the four blocks (rows and columns >= n) and lam are zero for the whole kernel: products run over 64 x 64 without
-    // bounds tests, and nothing ever stores there.  The interior is not zeroed: every element of it is written before it is read.  Runs
+    // bounds tests, and nothing stores anything but zeros there (but for the flat copy of the error matrix that the generic-order dots lay
+    // over B3, which is zeroed whole behind them).  The interior is not zeroed: every element of it is written before it is read.  Runs
     // once, in whichever phase comes first, between that phase's requests to L2 and its stores to LDS (the barrier after those covers it).
     auto zero_padding = [&]() {
         for (int b = 0; b < 4; ++b) {
@@ -211,34 +264,39 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
         if (tid < 64) { lam[tid] = 0.0; partner[tid] = -1; }
     };
 
-    if (a.phases & 1) {
+    if (PH & 1) {
+        QCS_FRESH();
+        const int m = QCS_A(m);                                          // (uniform) the DIIS window
         // ---- e = F D S - S D F
         {
             double f[QCS_E], d[QCS_E], s[QCS_E], g[QCS_E];
-            const bool haveF = a.F != nullptr;                           // (uniform)
-            const double *__restrict__ fsrc = haveF ? a.F : a.H;
-            QCS_EACH(q, i) {
-                const int x = QCS_GX(i);
-                f[q] = fsrc[x]; d[q] = a.D[x]; s[q] = a.S[x];
-                g[q] = haveF ? 0.0 : a.G[x];
+            const double *const aF = QCS_A(F);
+            const bool haveF = aF != nullptr;                            // (uniform)
+            {
+                const double *__restrict__ fsrc = haveF ? aF : QCS_A(H), *__restrict__ aD = QCS_A(D), *__restrict__ aS = QCS_A(S), *__restrict__ aG = QCS_A(G);
+                QCS_EACH(q, i) {
+                    f[q] = QCS_GET(fsrc); d[q] = QCS_GET(aD); s[q] = QCS_GET(aS);
+                    g[q] = haveF ? 0.0 : QCS_GET(aG);
+                }
             }
-            const bool hasB = tid < a.maxlen * a.maxlen;
-            const double bl = a.Bmat[hasB ? tid : 0];
+            const int ML = QCS_A(maxlen);
+            const bool hasB = tid < ML * ML;
+            const double bl = QCS_A(Bmat)[hasB ? tid : 0];
             zero_padding();
             if (hasB) Bl[tid] = bl;
-            QCS_EACH(q, i)
-                if (QCS_IN(i)) {
-                    double fv = f[q];
-                    if (!haveF) { fv = 1.0 * f[q] + 1.0 * g[q]; a.F_out[i * n + cc] = fv; }    // the arithmetic of qc_axpby(1, H, 1, G)
-                    B0[i * ld + cc] = fv; B1[i * ld + cc] = d[q]; B2[i * ld + cc] = s[q];
-                }
+            if (!haveF) {
+                QCS_EACH(q, i) f[q] = 1.0 * f[q] + 1.0 * g[q];           // the arithmetic of qc_axpby(1, H, 1, G)
+                double *const aFo = QCS_A(F_out);
+                QCS_PUT(aFo, f[q]);
+            }
+            QCS_PUTL(B0, f[q]); QCS_PUTL(B1, d[q]); QCS_PUTL(B2, s[q]);
         }
         __syncthreads();
         QCS_STAMP();
-        qcs_gemm<false, false>(B0, B1, B3, n, n, 1.0);                   // F D
+        qcs_gemm<QUAD, false, false>(B0, B1, B3, n, n, 1.0);                   // F D
         __syncthreads();
         QCS_STAMP();
-        qcs_gemm<false, false>(B3, B2, B0, n, n, 1.0);                   // (F D) S
+        qcs_gemm<QUAD, false, false>(B3, B2, B0, n, n, 1.0);                   // (F D) S
         __syncthreads();
         QCS_STAMP();
         {
@@ -248,30 +306,30 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             QCS_EACH(q, i) {
                 const int ic = min(i, 63);
                 e[q] = B0[ic * ld + cc] - B0[cc * ld + ic];              // FDS - (FDS)^T = FDS - SDF (zero in the padding)
-                if (QCS_IN(i)) a.E_out[i * n + cc] = e[q];
                 part[0] = fma(e[q], e[q], part[0]);
             }
+            { double *const aE = QCS_A(E_out); QCS_PUT(aE, e[q]); }
             // <e_0, e_j>, diis.rs:43-45: the older error matrices three at a time (48 loads in flight)
 #pragma unroll
             for (int j0 = 1; j0 < 12; j0 += 3) {
-                if (j0 < a.m) {                                          // (uniform)
+                if (j0 < m) {                                            // (uniform)
                     double o[3][QCS_E];
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
-                        const double *__restrict__ src = a.errs[j0 + u < a.m ? j0 + u : 0];      // (past the window: any valid matrix, weight 0)
-                        QCS_EACH(q, i) o[u][q] = src[QCS_GX(i)];
+                        const double *__restrict__ src = QCS_AI(errs, j0 + u < m ? j0 + u : 0);  // (past the window: any valid matrix, weight 0)
+                        QCS_EACH(q, i) o[u][q] = QCS_GET(src);
                     }
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
                         constexpr int JMAX = 11;
                         const int j = j0 + u < JMAX ? j0 + u : JMAX;
-                        const double w = j0 + u < a.m ? 1.0 : 0.0;
+                        const double w = j0 + u < m ? 1.0 : 0.0;
                         QCS_EACH(q, i) part[j] = fma(e[q] * w, o[u][q], part[j]);                // (e is zero outside the matrix)
                     }
                 }
             }
-            qcs_block_sums<12>(part, a.m, red, dots);
-            if (a.dots_generic) {
+            qcs_block_sums<12>(part, m, red, dots);
+            if (QCS_A(dots_generic)) {
                 // Open-shell runs: the dot products in the summation order of the generic launch sequence (qc_dots_kernel, qc_linalg.hip: 1024
                 // threads, thread t sums the elements t + 1024 u in ascending u, lanes by the shuffle tree, the sixteen wave sums in
                 // order).  The trajectories of such runs - crawls along saddles of the UHF functional, DESIGN.md 1 - depend on the last bit
@@ -281,8 +339,8 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 QCS_EACH(q, i) if (QCS_IN(i)) B3[i * n + cc] = e[q];
                 __syncthreads();
                 const int wave = qcs_wave(), lane = tid & 63;
-                for (int j = 0; j < a.m; ++j) {
-                    const double *__restrict__ yj = a.errs[j];
+                for (int j = 0; j < m; ++j) {
+                    const double *__restrict__ yj = QCS_AI(errs, j);
                     for (int r = 0; r < 4; ++r) {
                         const int t = r * QCS_T + tid;
                         double av[4], bv[4];
@@ -297,7 +355,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     }
                 }
                 __syncthreads();
-                if (tid < a.m) {
+                if (tid < m) {
                     double tsum = 0.0;
                     for (int k = 0; k < 16; ++k) tsum += gsh[tid * 16 + k];
                     dots[tid] = tsum;
@@ -312,28 +370,33 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
         double fo0[3][QCS_E];
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            const double *__restrict__ src = a.focks[u < a.m ? u : 0];
-            QCS_EACH(q, i) fo0[u][q] = src[QCS_GX(i)];
+            const double *__restrict__ src = QCS_AI(focks, u < m ? u : 0);
+            QCS_EACH(q, i) fo0[u][q] = QCS_GET(src);
         }
         if (qcs_wave() == 0) {
-            const int lane = tid, m = a.m, M = m + 1, ML = a.maxlen;
+            const int lane = tid, M = m + 1, ML = QCS_A(maxlen);
+            int sl[12], myslot = 0;                                      // the window's slots, live in this block only; lane j's own
+#pragma unroll
+            for (int j = 0; j < 12; ++j) { sl[j] = QCS_AI(slot, j); myslot = lane == j ? sl[j] : myslot; }
+            const int slot0 = sl[0];
             if (lane < m) {
                 const double d = dots[lane];
-                const int p = a.slot[0] * ML + a.slot[lane], q = a.slot[lane] * ML + a.slot[0];
-                Bl[p] = d; Bl[q] = d; a.Bmat[p] = d; a.Bmat[q] = d;
+                const int p = slot0 * ML + myslot, q = myslot * ML + slot0;
+                double *const aB = QCS_A(Bmat);
+                Bl[p] = d; Bl[q] = d; aB[p] = d; aB[q] = d;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             double cj = lane == 0 ? 1.0 : 0.0;                           // diis.rs:33-38: the newest Fock matrix while the window is short
-            if (m >= a.minlen) {
+            if (m >= QCS_A(minlen)) {
                 double col[13], x[13];
 #pragma unroll
                 for (int i = 0; i < 13; ++i) {
                     double v = 0.0;
                     if (i < M && lane <= M) {
                         if (lane == M) v = i == m ? 1.0 : 0.0;                                   // right-hand side
-                        else if (i < m && lane < m) v = Bl[a.slot[i] * ML + a.slot[lane]];
+                        else if (i < m && lane < m) v = Bl[sl[i < 12 ? i : 0] * ML + myslot];
                         else v = (i == m && lane == m) ? 0.0 : 1.0;                              // border +1, corner 0
                     }
                     col[i] = v;
@@ -346,21 +409,22 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
 #undef QCS_QR
                     default: break;
                 }
-                if (!solved) { if (lane == 0) *a.diis_flag = 1; }        // "DIIS failed" (rhf.rs:73); c stays (1, 0, ...)
+                if (!solved) { if (lane == 0) *QCS_A(diis_flag) = 1; }        // "DIIS failed" (rhf.rs:73); c stays (1, 0, ...)
                 else {
                     cj = 0.0;
 #pragma unroll
                     for (int j = 0; j < 12; ++j) if (lane == j && j < m) cj = x[j];
                 }
             }
-            if (lane < 12) { cvec[lane] = cj; a.c_out[lane] = cj; }
+            if (lane < 12) { cvec[lane] = cj; QCS_A(c_out)[lane] = cj; }
         } else {
             const int w3 = qcs_wave() - 1;                               // rows w3 + 3 q
+            const double *__restrict__ aX = QCS_A(X);
             double xr[22];
 #pragma unroll
-            for (int q = 0; q < 22; ++q) { const int i = w3 + 3 * q; xr[q] = a.X[(cok && i < n) ? i * n + cc : 0]; }
+            for (int q = 0; q < 22; ++q) { const int i = w3 + 3 * q; xr[q] = qcs_ld(aX, (cok && i < n) ? (unsigned)(i * n + cc) * 8u : 0u); }
 #pragma unroll
-            for (int q = 0; q < 22; ++q) { const int i = w3 + 3 * q; if (cok && i < n) B2[i * ld + cc] = xr[q]; }
+            for (int q = 0; q < 22; ++q) { const int i = w3 + 3 * q; if (i < n) B2[i * ld + cc] = cok ? xr[q] : 0.0; }     // (uniform test; rows past 63 are outside the block)
         }
         __syncthreads();
         QCS_STAMP();
@@ -370,68 +434,72 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             QCS_EACH(q, i) acc[q] = 0.0;
 #pragma unroll
             for (int j0 = 0; j0 < 12; j0 += 3) {
-                if (j0 < a.m) {                                          // (uniform)
+                if (j0 < m) {                                            // (uniform)
                     double o[3][QCS_E];
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
                         if (j0 == 0) { QCS_EACH(q, i) o[u][q] = fo0[u][q]; }
                         else {
-                            const double *__restrict__ src = a.focks[j0 + u < a.m ? j0 + u : 0];
-                            QCS_EACH(q, i) o[u][q] = src[QCS_GX(i)];
+                            const double *__restrict__ src = QCS_AI(focks, j0 + u < m ? j0 + u : 0);
+                            QCS_EACH(q, i) o[u][q] = QCS_GET(src);
                         }
                     }
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
-                        if (j0 + u < a.m) {                              // (uniform)
+                        if (j0 + u < m) {                                // (uniform)
                             const double c = cvec[j0 + u];
                             QCS_EACH(q, i) acc[q] = fma(c, o[u][q], acc[q]);
                         }
                     }
                 }
             }
-            QCS_EACH(q, i) if (QCS_IN(i)) B0[i * ld + cc] = acc[q];
+            QCS_PUTL(B0, acc[q]);
         }
         __syncthreads();
         QCS_STAMP();
         // the refinement's start vectors are requested ahead of the product that hides them and go to B0 once that product has read it
-        const bool refine = (a.phases & 2) != 0;                         // (uniform)
+        constexpr bool refine = (PH & 2) != 0;
         double v0[QCS_E];
-        QCS_EACH(q, i) v0[q] = refine ? a.V0[QCS_GX(i)] : 0.0;
-        qcs_gemm<false, false>(B0, B2, B1, n, n, 1.0);                   // F X
+        if (refine) { const double *__restrict__ aV = QCS_A(V0); QCS_EACH(q, i) v0[q] = QCS_GET(aV); }
+        qcs_gemm<QUAD, false, false>(B0, B2, B1, n, n, 1.0);                   // F X
         __syncthreads();
         QCS_STAMP();
         if (refine) {
-            QCS_EACH(q, i) if (QCS_IN(i)) B0[i * ld + cc] = v0[q];
+            QCS_PUTL(B0, v0[q]);
             if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
         }
-        qcs_gemm<true, false>(B2, B1, B3, n, n, 1.0);                    // X^T (F X)
+        qcs_gemm<QUAD, true, false>(B2, B1, B3, n, n, 1.0);                    // X^T (F X)
         __syncthreads();
         QCS_STAMP();
-        QCS_EACH(q, i) if (QCS_IN(i)) a.Fp[i * n + cc] = B3[i * ld + cc];
+        { double *const aFp = QCS_A(Fp); QCS_PUT(aFp, B3[i * ld + cc]); }
     }
 
-    if (a.phases & 2) {
+    if (PH & 2) {
         // ---- eigenvectors of F' (B3) by refinement from V0: the passes of qc_eig_refine_async (qc_eig_refine.hip) back to back
         // (after `pre` in the same launch everything is in place: V0 in B0, F' in B3, the flags cleared, and X = S^-1/2 still in B2)
-        const bool post = (a.phases & 4) != 0;                           // (uniform)
+        QCS_FRESH();
+        constexpr bool post = (PH & 4) != 0;
         double xpost[QCS_E];                                             // X of this thread's elements for `post`, held across the refinement
-        if (!(a.phases & 1)) {
+        if (!(PH & 1)) {
             double v[QCS_E], f[QCS_E];
-            QCS_EACH(q, i) { const int x = QCS_GX(i); v[q] = a.V0[x]; f[q] = a.Fp[x]; xpost[q] = post ? a.X[x] : 0.0; }
+            const double *__restrict__ aV = QCS_A(V0), *__restrict__ aFp = QCS_A(Fp), *__restrict__ aX = QCS_A(X);
+            QCS_EACH(q, i) { v[q] = QCS_GET(aV); f[q] = QCS_GET(aFp); xpost[q] = post ? QCS_GET(aX) : 0.0; }
             zero_padding();
-            QCS_EACH(q, i) if (QCS_IN(i)) { B0[i * ld + cc] = v[q]; B3[i * ld + cc] = f[q]; }
+            QCS_PUTL(B0, v[q]); QCS_PUTL(B3, f[q]);
             if (tid < QC_CTL_EIG_STRIDE) flg[tid] = 0;
             __syncthreads();
         } else QCS_EACH(q, i) xpost[q] = B2[min(i, 63) * ld + cc];
         QCS_STAMP();
         int state = QC_EIG_RUNNING, last = 0, clean = 0;                 // (uniform) the decisions of a pass: every thread takes them, thread 0 files them in flg
         double *X = B0, *Xn = B2;
-        for (int pass = 0; pass < a.npass; ++pass) {
-            qcs_gemm<false, false>(B3, X, B1, n, n, 1.0);                // A X
+        const int npass = QCS_A(npass);
+        for (int pass = 0; pass < npass; ++pass) {
+            QCS_FRESH();
+            qcs_gemm<QUAD, false, false>(B3, X, B1, n, n, 1.0);                // A X
             __syncthreads();
-            qcs_gemm<true, false>(X, B1, Xn, n, n, 1.0);                 // S = X^T A X
+            qcs_gemm<QUAD, true, false>(X, B1, Xn, n, n, 1.0);                 // S = X^T A X
             __syncthreads();
-            qcs_gemm<true, false>(X, X, B1, n, n, 1.0);                  // X^T X
+            qcs_gemm<QUAD, true, false>(X, X, B1, n, n, 1.0);                  // X^T X
             __syncthreads();
             QCS_STAMP();
             const double *Sm = Xn, *XtX = B1;
@@ -443,7 +511,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                 double rsum = 0.0;
                 QCS_EACH(q, i) {
                     const int ic = min(i, 63);
-                    const double r = ((QCS_IN(i) && ic == cc) ? 1.0 : 0.0) - XtX[ic * ld + cc];
+                    const double r = ((i < n ? i : -1) == cc ? 1.0 : 0.0) - XtX[ic * ld + cc];     // (the diagonal inside the matrix)
                     rsum = fma(r, r, rsum);
                 }
 #pragma unroll
@@ -525,6 +593,7 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
             if (state != QC_EIG_RUNNING) break;
             // M = I + E with exact rotations on the strong pairs, into B1 in place of X^T X
             {
+                QCS_FRESH();
                 double mv[QCS_E];
                 const double lj = lam[cc];
                 QCS_EACH(q, i) {
@@ -544,11 +613,11 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     mv[q] = mm;
                 }
                 __syncthreads();
-                QCS_EACH(q, i) if (QCS_IN(i)) B1[i * ld + cc] = mv[q];
+                QCS_PUTL(B1, mv[q]);
             }
             __syncthreads();
             QCS_STAMP();
-            qcs_gemm<false, false>(X, B1, Xn, n, n, 1.0);                // X (I + E): error now ~ emax^2
+            qcs_gemm<QUAD, false, false>(X, B1, Xn, n, n, 1.0);                // X (I + E): error now ~ emax^2
             __syncthreads();
             QCS_STAMP();
             if (tid == 0) flg[QC_EIG_PASSES] += 1;                                   // passes used
@@ -560,97 +629,102 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
                     for (int j = j0; j < j0 + 16; ++j) r += (j < n && QC_REF_BEFORE(lam, j, wi, idx)) ? 1 : 0;
                     r += __shfl_xor(r, 1, 64);
                     r += __shfl_xor(r, 2, 64);
-                    if ((tid & 3) == 0 && idx < n) { rank_s[idx] = r; a.w_out[r] = wi; }
+                    if ((tid & 3) == 0 && idx < n) { rank_s[idx] = r; QCS_A(w_out)[r] = wi; }
                 }
                 __syncthreads();
                 const int rc = cok ? rank_s[cc] : 0;
-                QCS_EACH(q, i) if (QCS_IN(i)) X[i * ld + rc] = Xn[i * ld + cc];
+                if (cok) QCS_EACH(q, i) if (i < n) X[i * ld + rc] = Xn[i * ld + cc];
                 state = QC_EIG_DONE;
                 break;
             }
-            if (last || pass == a.npass - 1) { state = QC_EIG_ROTATE; break; }      // coupling inside a degenerate cluster, or passes exhausted
+            if (last || pass == npass - 1) { state = QC_EIG_ROTATE; break; }      // coupling inside a degenerate cluster, or passes exhausted
             double *t = X; X = Xn; Xn = t;
         }
         ok = state == QC_EIG_DONE;
         if (tid == 0) flg[QC_EIG_STATE] = state;
         __syncthreads();
-        if (tid < QC_CTL_EIG_STRIDE) a.ctl[tid] = flg[tid];
+        if (tid < QC_CTL_EIG_STRIDE) QCS_A(ctl)[tid] = flg[tid];
         if (ok) {
-            QCS_EACH(q, i) if (QCS_IN(i)) a.Cp_out[i * n + cc] = X[i * ld + cc];
+            { double *const aCp = QCS_A(Cp_out); QCS_PUT(aCp, X[i * ld + cc]); }
             Cpv = X;
-            if (post) QCS_EACH(q, i) if (QCS_IN(i)) B1[i * ld + cc] = xpost[q];   // X = S^-1/2 for C = X C' (B1 is free once the last update is formed)
+            if (post) QCS_PUTL(B1, xpost[q]);                             // X = S^-1/2 for C = X C' (B1 is free once the last update is formed)
         }
         __syncthreads();
         QCS_STAMP();
     }
 
-    if ((a.phases & 4) && ok) {
+    if ((PH & 4) && ok) {
+        QCS_FRESH();
         // ---- C = X C', D = dfac C_occ C_occ^T, energy, rms
         double h[QCS_E], g[QCS_E];                                       // H and G of this thread's elements: requested now, used at the end
         double dold = 0.0;
-        if (!(a.phases & 2)) {                                           // (after the refinement in the same launch X is in B1 already)
+        const double *__restrict__ aH = QCS_A(H), *__restrict__ aG = QCS_A(G);
+        if (!(PH & 2)) {                                                 // (after the refinement in the same launch X is in B1 already)
             double xv[QCS_E], cp[QCS_E];
-            QCS_EACH(q, i) { const int x = QCS_GX(i); xv[q] = a.X[x]; cp[q] = a.Cp_in[x]; }
-            QCS_EACH(q, i) { const int x = QCS_GX(i); h[q] = a.H[x]; g[q] = a.G[x]; }
-            dold = a.Dold[tid < n ? tid * n + tid : 0];
+            const double *__restrict__ aX = QCS_A(X), *__restrict__ aCi = QCS_A(Cp_in);
+            QCS_EACH(q, i) { xv[q] = QCS_GET(aX); cp[q] = QCS_GET(aCi); }
+            QCS_EACH(q, i) { h[q] = QCS_GET(aH); g[q] = QCS_GET(aG); }
+            dold = QCS_A(Dold)[tid < n ? tid * n + tid : 0];
             zero_padding();
-            QCS_EACH(q, i) if (QCS_IN(i)) { B1[i * ld + cc] = xv[q]; B0[i * ld + cc] = cp[q]; }
+            QCS_PUTL(B1, xv[q]); QCS_PUTL(B0, cp[q]);
             __syncthreads();
         } else {
-            QCS_EACH(q, i) { const int x = QCS_GX(i); h[q] = a.H[x]; g[q] = a.G[x]; }
-            dold = a.Dold[tid < n ? tid * n + tid : 0];
+            QCS_EACH(q, i) { h[q] = QCS_GET(aH); g[q] = QCS_GET(aG); }
+            dold = QCS_A(Dold)[tid < n ? tid * n + tid : 0];
         }
         QCS_STAMP();
         double *const Cm = Cpv == B2 ? B0 : B2;                          // (the block the eigenvectors are not in)
-        qcs_gemm<false, false>(B1, Cpv, Cm, n, n, 1.0);                  // C
+        qcs_gemm<QUAD, false, false>(B1, Cpv, Cm, n, n, 1.0);                  // C
         __syncthreads();
-        if (a.nocc > 0) qcs_gemm<false, true, true>(Cm, Cm, B3, n, a.nocc, a.dfac);         // C_occ C_occ^T
-        else QCS_EACH(q, i) if (QCS_IN(i)) B3[i * ld + cc] = 0.0;
-        QCS_EACH(q, i) if (QCS_IN(i)) a.C_out[i * n + cc] = Cm[i * ld + cc];
+        const int nocc = QCS_A(nocc);
+        if (nocc > 0) qcs_gemm<QUAD, false, true, true>(Cm, Cm, B3, n, nocc, QCS_A(dfac));        // C_occ C_occ^T
+        else QCS_PUTL(B3, 0.0);
+        { double *const aC = QCS_A(C_out); QCS_PUT(aC, Cm[i * ld + cc]); }
         __syncthreads();
         QCS_STAMP();
         double part[3] = {0.0, 0.0, 0.0};
         QCS_EACH(q, i) {
             const int ic = min(i, 63);
             const double dn = B3[ic * ld + cc];                                                  // (zero in the padding)
-            if (QCS_IN(i)) a.Dn[i * n + cc] = dn;
             part[0] = fma(QCS_IN(i) ? B3[cc * ld + ic] : 0.0, 2.0 * h[q] + g[q], part[0]);      // tr(Dn (2H + G)) = sum_ij Dn_ji (2H + G)_ij
             part[2] += fabs(dn);
         }
+        { double *const aDn = QCS_A(Dn); QCS_PUT(aDn, B3[i * ld + cc]); }
         if (tid < n) { const double d = B3[tid * ld + tid] - dold; part[1] = d * d; }
         qcs_block_sums<3>(part, 3, red, scal);
         if (tid == 0) {
-            a.scal_out[0] = 0.5 * scal[0]; a.scal_out[1] = scal[1];
-            if (a.fxs_out) {     // fixed-point unit of the build that will digest Dn (qc_fx_scale_kernel, qc_linalg.hip): 2^S (4 imax sum|D|) <= 2^60
-                const double bound = 4.0 * a.imax * scal[2];
+            double *const aso = QCS_A(scal_out), *const fxs = QCS_A(fxs_out);
+            aso[0] = 0.5 * scal[0]; aso[1] = scal[1];
+            if (fxs) {     // fixed-point unit of the build that will digest Dn (qc_fx_scale_kernel, qc_linalg.hip): 2^S (4 imax sum|D|) <= 2^60
+                const double bound = 4.0 * QCS_A(imax) * scal[2];
                 int e = 0;
                 if (bound > 0.0 && bound < 1e300) (void)frexp(bound, &e);
                 else if (!(bound < 1e300)) e = 1100;
                 int S = 60 - e;
                 S = S > QC_FX_MAXBITS ? QC_FX_MAXBITS : (S < -900 ? -900 : S);
-                a.fxs_out[0] = ldexp(1.0, S); a.fxs_out[1] = (bound < 1e300) ? ldexp(1.0, -S) : __builtin_nan("");
+                fxs[0] = ldexp(1.0, S); fxs[1] = (bound < 1e300) ? ldexp(1.0, -S) : __builtin_nan("");
             }
         }
         QCS_STAMP();
     }
-    if (a.ctl_all) {
+    if (int *const ctl_all = QCS_A(ctl_all)) {
         __threadfence();
         __syncthreads();
         if (tid < QC_CTL_WORDS) {
-            int *p = a.ctl_all + tid;
-            a.ctl_out[tid] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            int *p = ctl_all + tid;
+            QCS_A(ctl_out)[tid] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __threadfence_system();
-    if (a.tl != nullptr && tid == 0) a.tl[1] = wall_clock64();
-    if (a.seq_out) {     // the host polls this word instead of the stream's event (which the packet processor signals some microseconds later)
+    { unsigned long long *const tl = QCS_A(tl); if (tl != nullptr && tid == 0) tl[1] = wall_clock64(); }
+    if (unsigned *const seq_out = QCS_A(seq_out)) {     // the host polls this word instead of the stream's event (which the packet processor signals some microseconds later)
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(a.seq_out, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (tid == 0) __hip_atomic_store(seq_out, QCS_A(seq), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 #ifdef QC_SMALL_TIMING
     if (tid == 0) {
-        printf("[small n=%d phases %d m %d] stamps (10 ns):", n, a.phases, a.m);
+        printf("[small n=%d phases %d m %d] stamps (10 ns):", n, PH, QCS_A(m));
         for (int k = 1; k < nph; ++k) printf(" %lld", tph[k] - tph[k - 1]);
         printf("\n");
     }
@@ -658,6 +732,10 @@ __global__ __launch_bounds__(QCS_T) void qc_scf_small_kernel(const QcSmallArgs a
 #undef QCS_EACH
 #undef QCS_IN
 #undef QCS_GX
+#undef QCS_GET
+#undef QCS_PUT
+#undef QCS_PUTL
+#undef QCS_FRESH
 #undef QCS_STAMP
 }
 
@@ -665,13 +743,27 @@ size_t qc_scf_small_lds_bytes(int) { return (size_t)(4 * QCS_BUF + QCS_SMALL_DOU
 
 int qc_scf_small_launch(hipStream_t st, const QcSmallArgs &a) {
     if (a.n < 1 || a.n > QC_SMALL_MAXN || a.m < 1 || a.m > 12) return QC_ERR_INVALID;
+    // the instance of the launch's shape and phases; each needs its dynamic LDS raised once
+    typedef void (*kernel_t)(const QcSmallArgs);
+    static const struct { int phases; kernel_t k[2]; } table[] = {
+        {1, {qc_scf_small_kernel<false, 1>, qc_scf_small_kernel<true, 1>}},       // pre (before the tridiagonal start or a Jacobi kernel)
+        {4, {qc_scf_small_kernel<false, 4>, qc_scf_small_kernel<true, 4>}},       // post (behind a Jacobi kernel)
+        {6, {qc_scf_small_kernel<false, 6>, qc_scf_small_kernel<true, 6>}},       // refine + post (behind the tridiagonal start)
+        {7, {qc_scf_small_kernel<false, 7>, qc_scf_small_kernel<true, 7>}},       // the whole step
+    };
+    constexpr int NI = sizeof(table) / sizeof(table[0]);
+    static std::atomic<bool> raised[NI][2];
+    int t = 0;
+    while (t < NI && table[t].phases != a.phases) ++t;
+    if (t == NI) return QC_ERR_INVALID;
+    const int quad = a.n > 32 ? 1 : 0;
+    const kernel_t kernel = table[t].k[quad];
     const size_t lds = qc_scf_small_lds_bytes(a.n);
-    static std::atomic<bool> raised{false};
-    if (!raised.load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(qc_scf_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (!raised[t][quad].load(std::memory_order_acquire)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return QC_ERR_HIP;
-        raised.store(true, std::memory_order_release);
+        raised[t][quad].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(qc_scf_small_kernel, dim3(1), dim3(QCS_T), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(QCS_T), lds, st, a);
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
