@@ -251,6 +251,30 @@ extern "C" {
     /// Charges fitted to the state's potential on the library's grid (xyz null) or the caller's points; v_out nullable.
     pub fn qc_scf_esp_charges(st: *mut QcScfState, io: *mut QcEspFit, npts: i64, xyz: *const f64, charges: *mut f64,
                               v_out: *mut f64) -> c_int;
+    /// External point charges of the handle: npc points (npc x 3 doubles, bohr) with npc charges, copied; npc == 0 removes the set.
+    /// Host only.  SCF states begun afterwards are embedded (H = T + V + V_pc); states that are alive keep their set.
+    pub fn qc_set_point_charges(sys: *mut QcSystem, npc: i64, xyz: *const f64, q: *const f64) -> c_int;
+    pub fn qc_point_charge_count(sys: *const QcSystem) -> i64;
+    /// E_nq = sum_A sum_c Z_A q_c / |R_A - R_c| of the handle's set (host).
+    pub fn qc_point_charge_nuclear_energy(sys: *const QcSystem) -> f64;
+    /// Count and E_nq of the set the state began with.
+    pub fn qc_scf_point_charge_count(st: *const QcScfState) -> i64;
+    pub fn qc_scf_point_charge_nuclear_energy(st: *const QcScfState) -> f64;
+    /// V_pc = -sum_c q_c A(R_c), n*n doubles, exactly symmetric: on the host, and by the kernels the SCF set-up uses.
+    pub fn qc_point_charge_matrix(sys: *const QcSystem, out: *mut f64) -> c_int;
+    pub fn qc_point_charge_matrix_gpu(sys: *mut QcSystem, out: *mut f64) -> c_int;
+    /// B^k_ab = dA_ab(r)/dr_k, k = x, y, z: 3 n*n doubles.  Host only.
+    pub fn qc_field_matrix(sys: *const QcSystem, r: *const f64, out: *mut f64) -> c_int;
+    /// E = -grad V of the molecule alone on npts points, npts x 3 doubles each; e_nuc nullable.
+    pub fn qc_field_on_points(sys: *mut QcSystem, d: *const f64, npts: i64, xyz: *const f64, e_elec: *mut f64, e_nuc: *mut f64) -> c_int;
+    /// The same from the state's total density: e_total = e_nuc + e_elec; e_elec nullable.  The state is left as it was.
+    pub fn qc_scf_field_on_points(st: *mut QcScfState, npts: i64, xyz: *const f64, e_total: *mut f64, e_elec: *mut f64) -> c_int;
+    /// terms: 2 x npc x 3 doubles, dE_nq/dR_c then d tr(P_t V_pc)/dR_c at a fixed density (conventions of qc_gradient).
+    pub fn qc_point_charge_gradient(sys: *mut QcSystem, nspin: c_int, d: *const f64, terms: *mut f64) -> c_int;
+    /// grad: npc x 3 doubles, dE/dR_c = -q_c E_total(R_c) at the state, for the charges it began with.
+    pub fn qc_scf_point_charge_gradient(st: *mut QcScfState, grad: *mut f64) -> c_int;
+    /// Phase times (ms) of the handle's last embedding call: upload, Hermite sums over the charges, assembly or contraction, download.
+    pub fn qc_point_charge_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

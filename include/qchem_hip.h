@@ -392,6 +392,66 @@ int qc_esp_fit_points(const qc_system *sys, const qc_esp_fit *cfg, int64_t capac
 int qc_esp_fit_solve(const qc_system *sys, int64_t npts, const double *xyz, const double *v, double total_charge, qc_esp_fit *io, double *charges);
 int qc_scf_esp_charges(qc_scf_state *st, qc_esp_fit *io, int64_t npts, const double *xyz, double *charges, double *v_out);
 
+/* ---- point-charge embedding (not in the reference): the molecule in the field of external point charges, the electrostatic half of a
+ * QM/MM driver.  Atomic units, coordinates in bohr, f64 throughout.  A charge set is npc points R_c (npc x 3 doubles) with charges q_c -
+ * any finite doubles, negative ones and 0 included.  With A_ab(r) = (a| 1/|r' - r| |b), what qc_potential_matrix returns:
+ *   V_pc = -sum_c q_c A(R_c)   (n x n, exactly symmetric)        E_nq = sum_A sum_c Z_A q_c / |R_A - R_c|
+ * The charge-charge energy belongs to the caller and appears nowhere.  The charges are not atoms: qc_nelectrons, qc_nuclear_repulsion
+ * and qc_hf_output.nuclear_repulsion do not see them.
+ *
+ * qc_set_point_charges (host only, works without a device): the inputs are copied; npc == 0 removes the set.  QC_ERR_INVALID, with the
+ * handle's set left as it was: a null handle, npc < 0, null arrays with npc > 0, a coordinate or charge that is not finite, a charge at
+ * distance exactly 0 from an atom.  SCF states begun afterwards take a snapshot of the set: their H = T + V + V_pc, so the Hueckel guess,
+ * the electronic energy (it contains tr(P V_pc)), qc_scf_matrix(.., 1) and everything computed from C and the orbital energies belong to
+ * the embedded Hamiltonian; the total energy is electronic + nuclear repulsion + E_nq.  States that are alive keep the set they began
+ * with (qc_scf_point_charge_count / qc_scf_point_charge_nuclear_energy report it).  The fixed-density calls use the handle's current set.
+ * With no charges set nothing changes: no kernel is launched, nothing allocated, every result keeps its bits.
+ * qc_point_charge_count: the number of charges of the handle's set.  qc_point_charge_nuclear_energy: E_nq, on the host. */
+int qc_set_point_charges(qc_system *sys, int64_t npc, const double *xyz, const double *q);
+int64_t qc_point_charge_count(const qc_system *sys);
+double qc_point_charge_nuclear_energy(const qc_system *sys);
+int64_t qc_scf_point_charge_count(const qc_scf_state *st);
+double qc_scf_point_charge_nuclear_energy(const qc_scf_state *st);
+
+/* V_pc of the handle's set, n*n doubles on the host (all zero without charges).  The first runs on the host, serially, and needs no
+ * device: the reference statement.  The second runs the kernels the SCF set-up uses (qc_embed.hip): per stored primitive pair the
+ * Hermite-Coulomb tables of all charges summed in a fixed order (tiles of 256 charges, each summed in an order that depends on the
+ * numbers of records and charges alone, tile sums added ascending), then one assembly from the stored pair data - primitive pairs under the library's cut-off (1e-17) are left out as they are out of the Fock
+ * build.  Bitwise reproducible from call to call and across fresh handles; works on a sharded handle (every rank builds it whole).
+ * QC_ERR_INVALID: null pointers.  QC_ERR_NO_DEVICE (the second) without a device. */
+int qc_point_charge_matrix(const qc_system *sys, double *out);
+int qc_point_charge_matrix_gpu(qc_system *sys, double *out);
+
+/* The electric field of the molecule alone (never of the charges) on caller-given points: E = -grad V with V, v_elec and v_nuc exactly
+ * those of qc_esp_on_points; outputs npts x 3 doubles (x, y, z of a point together).
+ * qc_field_matrix (host only): out = 3 n*n doubles, B^k_ab = dA_ab(r)/dr_k for k = x, y, z - the derivative companion of
+ * qc_potential_matrix, each matrix exactly symmetric; e_elec_k(r) = tr(D B^k).
+ * qc_field_on_points / qc_scf_field_on_points (GPU): e_elec = -grad v_elec, e_nuc(r) = sum_A Z_A (r - R_A) / |r - R_A|^3, e_total =
+ * e_nuc + e_elec.  Nullable arguments (e_nuc; e_elec of the state call), errors, the treatment of npts == 0 and of a matrix that is not
+ * symmetric, bitwise reproducibility and the independence of a point's value from the other points of the call are those of
+ * qc_esp_on_points / qc_scf_esp_on_points.  A point on a nucleus gives a non-finite e_nuc (and e_total) and a finite, correct e_elec.
+ * The phase times of these calls are reported by qc_points_timings. */
+int qc_field_matrix(const qc_system *sys, const double r[3], double *out);
+int qc_field_on_points(qc_system *sys, const double *D, int64_t npts, const double *xyz, double *e_elec, double *e_nuc);
+int qc_scf_field_on_points(qc_scf_state *st, int64_t npts, const double *xyz, double *e_total, double *e_elec);
+
+/* Gradients with point charges.
+ * qc_point_charge_gradient: fixed density, in the conventions of qc_gradient (nspin 1: D with the factor 2; nspin 2: [Da; Db]), for the
+ * handle's current set.  terms receives 2 x npc x 3 doubles: dE_nq/dR_c, then d tr(P_t V_pc)/dR_c = -q_c e_elec(R_c).
+ * qc_scf_point_charge_gradient: grad receives npc x 3 doubles, dE/dR_c at the state for the charges it began with; this is
+ * -q_c e_total(R_c) with the field of qc_scf_field_on_points.  Both: npc == 0 is QC_OK with nothing written.
+ * qc_gradient on a handle with charges: term 0 gains dE_nq/dR_A, term 1 gains sum_ab P_t,ab d(V_pc)_ab/dR_A - the basis-function
+ * derivatives only, because the charges stay put.  qc_scf_gradient on an embedded state returns the full dE/dR_A with both additions,
+ * for the charges the state began with.  Without charges both give the bits they gave before.
+ * Errors as qc_gradient (QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator).  Bitwise reproducible from call to call and
+ * across fresh handles; a state is left exactly as it was. */
+int qc_point_charge_gradient(qc_system *sys, int nspin, const double *D, double *terms);
+int qc_scf_point_charge_gradient(qc_scf_state *st, double *grad);
+
+/* Phase times (ms) of the handle's last embedding call (qc_point_charge_matrix_gpu, the V_pc of an SCF set-up, the point-charge terms
+ * of a gradient call): upload, Hermite sums over the charges, assembly or contraction, download. */
+int qc_point_charge_timings(const qc_system *sys, double ms[4]);
+
 /* ---- excited states of an RHF state (after SCF, not in the reference): configuration interaction singles (CIS, the Tamm-Dancoff
  * approximation) and time-dependent Hartree-Fock (TDHF, the random-phase approximation), singlets or triplets, at the state's last C and
  * orbital energies.  With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij delta_ab (e_a - e_i), rows and columns

@@ -34,6 +34,12 @@ Three additions, all opt-in:
     the spin population (esp: no spin; then an `esp fit:` line with the number of points, rms and rrms, and the dipole of the charges);
     `--bond-orders` adds `mayer bond orders:` and one line per atom pair above 0.05.  `--json` then carries "multipoles", "charges" (a
     list, one object per scheme) and "bond_orders" (the whole matrix).  None combines with `--follow`.
+  * `--point-charges FILE` embeds the molecule in external point charges: FILE is a JSON list of `{"charge": q, "position": [x, y, z]}`,
+    positions in bohr like the molecule files, any real charges.  One line comes first, `point charges: N, nuclei-charges energy: E_nq`;
+    the `electronic energy` then contains tr(P V_pc), `nuclear repulsion energy` stays the atoms' own and `hartree fock energy` is
+    their sum plus E_nq (never the charge-charge energy).  With `--gradient` the atoms' rows are the full dE/dR_A and one row per charge
+    follows - `qI gx gy gz`, dE/dR_c; `--json` then carries a "point_charges" object (count, nuclear_energy, gradient).  Does not
+    combine with `--follow`.  Output without the flag is unchanged.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -117,6 +123,8 @@ def build_parser() -> argparse.ArgumentParser:
                        + "esp, homo, lumo or mo:K (K from 0" + ("; alpha orbitals)" if name == "uhf" else ")") + " (requires --cube-file)")
         s.add_argument("--cube-file", default=None, metavar="PATH", help="where --cube writes")
         s.add_argument("--cube-spacing", type=float, default=0.2, metavar="BOHR", help="grid spacing of --cube along x, y and z (default 0.2)")
+        s.add_argument("--point-charges", default=None, metavar="FILE",
+                       help='embed the molecule in external point charges: a JSON list of {"charge": q, "position": [x, y, z]} (bohr)')
         s.add_argument("--cube-margin", type=float, default=4.0, metavar="BOHR", help="margin of --cube around the bounding box of the nuclei (default 4.0)")
     return p
 
@@ -153,6 +161,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--triplets requires --cis or --tdhf")
         if args.follow and (args.cis or args.tdhf):
             p.error("--follow cannot be combined with --cis or --tdhf")
+    if args.follow and args.point_charges:
+        p.error("--follow cannot be combined with --point-charges")
     if args.cube is not None:
         if cube_what(args.cube, args.command == "uhf") is None:
             p.error("--cube takes density, %sesp, homo, lumo or mo:K" % ("spin, " if args.command == "uhf" else ""))
@@ -175,6 +185,38 @@ def _print_mp2(mp2: "hf.Mp2Output", e_hf: float) -> None:
 def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
     return {"e_os": mp2.e_os, "e_ss": mp2.e_ss, "e_corr": mp2.e_corr, "e_total": e_hf + mp2.e_corr, "n_frozen": mp2.n_frozen,
             "timings_ms": {"tensor": mp2.ms_tensor, "transform": mp2.ms_transform, "energy": mp2.ms_energy}}
+
+
+def load_point_charges(path: str):
+    """(positions (npc, 3) in bohr, charges (npc,)) of a --point-charges file: a JSON list of {"charge": q, "position": [x, y, z]},
+    positions read as the molecule files are"""
+    with open(path) as f:
+        doc = json.load(f)
+    pos = np.array([[float(x) for x in c["position"]] for c in doc], float).reshape(-1, 3)
+    return pos, np.array([float(c["charge"]) for c in doc], float)
+
+
+def _embedded(system: MolecularSystem, args):
+    """what the drivers run on: the molecule itself, or with --point-charges a handle that carries the charges (one line is printed)"""
+    if not args.point_charges:
+        return system
+    pos, q = load_point_charges(args.point_charges)
+    handle = hf.System(system)
+    handle.set_point_charges(pos, q)
+    print("point charges: %d, nuclei-charges energy: %s" % (len(q), fmt_f(handle.point_charge_nuclear_energy())))
+    return handle
+
+
+def _gradient(st, pc_rows: list):
+    """the nuclear gradient of a state; the rows of its point charges, if it has any, go to pc_rows"""
+    if st.point_charge_count() > 0:
+        pc_rows.append(st.point_charge_gradient())
+    return st.gradient()
+
+
+def _print_charge_gradient(rows) -> None:
+    for i, row in enumerate(rows):
+        print("q%d %.10f %.10f %.10f" % (i, row[0], row[1], row[2]))
 
 
 def _print_gradient(system: MolecularSystem, g) -> None:
@@ -469,17 +511,18 @@ def run_rhf(args) -> int:
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
     mp2 = grad = stab = dip = pol = cube = chg = None
-    exc = []
+    exc, pc_rows = [], []
+    molecule, system = system, _embedded(system, args)
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
     if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.cube or wants_charge_properties(args):
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
-                                                             st.gradient() if args.gradient else None,
+                                                             _gradient(st, pc_rows) if args.gradient else None,
                                                              _stability(st, False) if args.stability else None) + _properties(st, args)
-                                                            + (_excitations(st, args), _cube(st, system, args, False) if args.cube else None,
+                                                            + (_excitations(st, args), _cube(st, molecule, args, False) if args.cube else None,
                                                                _charge_properties(st, args)))
         out, (mp2, grad, stab, dip, pol, exc, cube, chg) = res if res is not None else (None, (None,) * 5 + ([], None, None))
     elif args.gradient:
-        res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, st.gradient()))
+        res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, _gradient(st, pc_rows)))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
     elif args.mp2:
         res = hf.restricted_mp2(system, config, args.frozen_core or 0)
@@ -497,7 +540,9 @@ def run_rhf(args) -> int:
     if mp2 is not None:
         _print_mp2(mp2, out.total_energy())
     if grad is not None:
-        _print_gradient(system, grad)
+        _print_gradient(molecule, grad)
+    for rows in pc_rows:
+        _print_charge_gradient(rows)
     if stab is not None:
         _print_stability(stab)
     if dip is not None:
@@ -507,7 +552,7 @@ def run_rhf(args) -> int:
     for e in exc:
         _print_excitations(e)
     if chg is not None:
-        _print_charge_properties(system, chg, False)
+        _print_charge_properties(molecule, chg, False)
     if args.json:
         doc = {"method": "rhf", "iterations": out.iterations, "electronic_energy": out.electronic_energy,
                "nuclear_repulsion": out.nuclear_repulsion, "total_energy": out.total_energy(),
@@ -516,6 +561,10 @@ def run_rhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if args.point_charges:
+            doc["point_charges"] = {"count": system.point_charge_count(), "nuclear_energy": out.embedding_nuclear_energy}
+            if pc_rows:
+                doc["point_charges"]["gradient"] = pc_rows[0].tolist()
         if stab is not None:
             doc["stability"] = stab
         if dip is not None:
@@ -545,12 +594,14 @@ def run_uhf(args) -> int:
         return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
     s2 = mp2 = grad = stab = dip = pol = cube = chg = None
+    pc_rows = []
+    embedded = _embedded(system, args)
     if (not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability and not args.cube
             and not wants_charge_properties(args)):
-        out = hf.unrestricted_hartree_fock(system, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
+        out = hf.unrestricted_hartree_fock(embedded, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
-        handle = hf.System(system)
+        handle = embedded if args.point_charges else hf.System(system)
         st = hf.ScfStepper(handle, uhf=True, n_alpha=n_alpha, n_beta=n_beta)
         out = None
         try:
@@ -560,11 +611,12 @@ def run_uhf(args) -> int:
                     if extension:
                         s2 = st.spin_square()
                     out = hf.UnrestrictedHartreeFockOutput(list(st.orbital_energies(0)), list(st.orbital_energies(1)), e,
-                                                           handle.nuclear_repulsion(), it)
+                                                           handle.nuclear_repulsion(), it,
+                                                           embedding_nuclear_energy=st.embedding_nuclear_energy())
                     if args.mp2:
                         mp2 = st.mp2(args.frozen_core or 0)
                     if args.gradient:
-                        grad = st.gradient()
+                        grad = _gradient(st, pc_rows)
                     if args.stability:
                         stab = _stability(st, True)
                     dip, pol = _properties(st, args)
@@ -590,6 +642,8 @@ def run_uhf(args) -> int:
         _print_mp2(mp2, out.total_energy())
     if grad is not None:
         _print_gradient(system, grad)
+    for rows in pc_rows:
+        _print_charge_gradient(rows)
     if stab is not None:
         _print_stability(stab)
     if dip is not None:
@@ -608,6 +662,10 @@ def run_uhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if args.point_charges:
+            doc["point_charges"] = {"count": len(load_point_charges(args.point_charges)[1]), "nuclear_energy": out.embedding_nuclear_energy}
+            if pc_rows:
+                doc["point_charges"]["gradient"] = pc_rows[0].tolist()
         if stab is not None:
             doc["stability"] = stab
         if dip is not None:

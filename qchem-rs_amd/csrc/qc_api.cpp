@@ -5,7 +5,7 @@
 #include <cstring>
 #include <new>
 
-#include "qc_internal.h"
+#include "qc_embed.h"
 
 namespace {
 
@@ -333,7 +333,14 @@ int qc_gradient(qc_system *S, int nspin, const double *D, const double *W, doubl
     QC_HIP_CHECK(hipMemcpyAsync(dP.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
     QC_HIP_CHECK(hipMemcpyAsync(dW.p, W, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
     qc_nuclear_gradient(S, terms);
-    return qc_gradient_device(S, nspin, dP.p, dW.p, terms + na3, S->grad_ms);
+    if ((rc = qc_gradient_device(S, nspin, dP.p, dW.p, terms + na3, S->grad_ms)) != QC_OK || S->pc.empty()) return rc;
+    // point charges on the handle: term 0 gains dE_nq/dR_A, term 1 the basis-function derivatives of tr(P_t V_pc)
+    std::vector<double> gn(na3), ge(na3);
+    if (nspin == 2) qc_axpby(S->stream, S->nbasis, 1.0, dP.p, 1.0, dP.p + nn, dP.p);
+    if ((rc = qc_pc_atom_gradient_device(S, S->pc, dP.p, ge.data())) != QC_OK) return rc;
+    qc_pc_nuclear_gradient(S, S->pc, gn.data(), nullptr);
+    for (int k = 0; k < na3; ++k) { terms[k] += gn[k]; terms[na3 + k] += ge[k]; }
+    return QC_OK;
 }
 int qc_gradient_timings(const qc_system *S, double *ms) {
     if (!S || !ms) return QC_ERR_INVALID;
@@ -399,6 +406,89 @@ int qc_orbitals_on_points(qc_system *S, int m, const double *C, int64_t npts, co
 int qc_points_timings(const qc_system *S, double ms[4]) {
     if (!S || !ms) return QC_ERR_INVALID;
     for (int i = 0; i < 4; ++i) ms[i] = S->points_ms[i];
+    return QC_OK;
+}
+
+// ---- point-charge embedding (qc_embed.h).  The set lives on the handle as [x, y, z, q] per charge; an SCF state copies it when it begins.
+int qc_set_point_charges(qc_system *S, int64_t npc, const double *xyz, const double *q) {
+    if (!S || npc < 0 || (npc > 0 && (!xyz || !q))) return QC_ERR_INVALID;
+    std::vector<double> pc(4 * (size_t)npc);
+    for (int64_t c = 0; c < npc; ++c) {
+        for (int k = 0; k < 3; ++k) pc[4 * c + k] = xyz[3 * c + k];
+        pc[4 * c + 3] = q[c];
+        for (int k = 0; k < 4; ++k) if (!std::isfinite(pc[4 * c + k])) return QC_ERR_INVALID;
+        for (int a = 0; a < S->natoms; ++a) {
+            const double dx = xyz[3 * c] - S->xyz[3 * a], dy = xyz[3 * c + 1] - S->xyz[3 * a + 1], dz = xyz[3 * c + 2] - S->xyz[3 * a + 2];
+            if (dx * dx + dy * dy + dz * dz == 0.0) return QC_ERR_INVALID;
+        }
+    }
+    S->pc.swap(pc);
+    return QC_OK;
+}
+int64_t qc_point_charge_count(const qc_system *S) { return S ? (int64_t)(S->pc.size() / 4) : QC_ERR_INVALID; }
+double qc_point_charge_nuclear_energy(const qc_system *S) { return S ? qc_pc_nuclear_energy(S, S->pc) : 0.0; }
+int qc_point_charge_matrix(const qc_system *S, double *out) {
+    if (!S || !out) return QC_ERR_INVALID;
+    qc_host_point_charge_matrix(S, S->pc, out);
+    return QC_OK;
+}
+int qc_point_charge_matrix_gpu(qc_system *S, double *out) {
+    if (!S || !out) return QC_ERR_INVALID;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf M;
+    if (M.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    if ((rc = qc_pc_matrix_device(S, S->pc, M.p)) != QC_OK) return rc;
+    const double t0 = qc_now_ms();
+    QC_HIP_CHECK(hipMemcpyAsync(out, M.p, nn * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    S->pc_ms[3] = qc_now_ms() - t0;
+    return QC_OK;
+}
+int qc_point_charge_timings(const qc_system *S, double ms[4]) {
+    if (!S || !ms) return QC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = S->pc_ms[i];
+    return QC_OK;
+}
+int qc_field_matrix(const qc_system *S, const double r[3], double *out) {
+    if (!S || !r || !out) return QC_ERR_INVALID;
+    qc_host_field_matrix(S, r, out);
+    return QC_OK;
+}
+int qc_field_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *e_elec, double *e_nuc) {
+    if (!S || !D || !xyz || !e_elec || npts < 0) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    DevBuf dD;
+    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if ((rc = qc_points_field_device(S, dD.p, npts, xyz, e_elec, S->points_ms)) != QC_OK) return rc;
+    if (e_nuc) qc_points_enuc(S, npts, xyz, e_nuc);
+    return QC_OK;
+}
+// terms = [dE_nq/dR_c | d tr(P_t V_pc)/dR_c], the second -q_c E_elec(R_c) by the field kernels at the charges
+int qc_point_charge_gradient(qc_system *S, int nspin, const double *D, double *terms) {
+    if (!S || !D || !terms || (nspin != 1 && nspin != 2)) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const int64_t npc = (int64_t)(S->pc.size() / 4);
+    if (npc == 0) return QC_OK;
+    int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    DevBuf dD;
+    if (dD.alloc(nspin * nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (nspin == 2) qc_axpby(S->stream, n, 1.0, dD.p, 1.0, dD.p + nn, dD.p);
+    std::vector<double> xyz(3 * (size_t)npc);
+    for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) xyz[3 * c + k] = S->pc[4 * c + k];
+    if ((rc = qc_points_field_device(S, dD.p, npc, xyz.data(), terms + 3 * npc, S->pc_ms)) != QC_OK) return rc;
+    for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) terms[3 * (npc + c) + k] *= -S->pc[4 * c + 3];
+    qc_pc_nuclear_gradient(S, S->pc, nullptr, terms);
     return QC_OK;
 }
 

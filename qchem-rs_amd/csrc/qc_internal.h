@@ -269,6 +269,11 @@ struct qc_system {
     double points_ms[4] = {0, 0, 0, 0};       // phase times of the last point call (qc_points_timings)
     long points_batch = -1;                     // QC_POINTS_BATCH: points per batch of the point calls (0: from the free memory; -1: not read yet)
     long points_split = -1;                     // QC_POINTS_SPLIT: largest batch whose potential splits the record list over workgroups (-1: not read yet)
+    // point-charge embedding (qc_embed.h): the handle's current charge set, [x, y, z, q] per charge (qc_set_point_charges)
+    std::vector<double> pc;
+    double pc_ms[4] = {0, 0, 0, 0};           // phase times of the last embedding call (qc_point_charge_timings)
+    long pc_batch = -1;                         // QC_PC_BATCH: charges per batch of the embedding calls (0: the default; -1: not read yet)
+    int pc_orient = 0;                          // QC_PC_ORIENT (read with it): 0 chosen from the sizes, 1 lane = record, 2 lane = charge
     std::vector<double> pairQ;                  // Schwarz factor sqrt(max_ab (ab|ab)) of each stored pair (empty until the device pass has run)
     double imax = 0.0;                          // max pairQ^2: bound on every |(ij|kl)|
     double schwarz_tau = QC_SCHWARZ_TAU;        // 0: no screening

@@ -12,8 +12,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "qc_fock_kernel.h"
-#include "qc_md.h"
+#include "qc_esp.h"
 
 namespace {
 
@@ -78,12 +77,8 @@ __global__ __launch_bounds__(PT_WG) void qc_points_rowdot_kernel(int n, int B, c
     rho[k] = acc;
 }
 
-// ---- Hermite densities.  The pair data holds E[h][ab] in basis functions with sqrt(2) pi^{5/4} / p folded in (the pair half of the
-// ERI prefactor, qc_build_model); the nuclear-attraction integral carries 2 pi / p instead: the ratio is the constant below.  The
-// records carry MINUS Lambda, so that v_elec = sum_h rec_h R_h.
-constexpr double ESP_RESCALE = 1.41421356237309504880 / 1.33133536380038971280;      // sqrt(2) / pi^{1/4}
-struct EspGroups { long long off[QC_LPAIR + 1]; };       // first double of the records of order L in the record array
-
+// ---- Hermite densities (the rescaling of the stored blocks: ESP_RESCALE, qc_esp.h).  The records carry MINUS Lambda, so that
+// v_elec = sum_h rec_h R_h.
 // One workgroup per stored shell pair A >= B; item (primitive pair, word of its record) per lane, every Lambda_h one sequential sum over
 // ab.  D need not be symmetric: an off-diagonal pair takes D_ab + D_ba (= 2 D_ab for a symmetric D, exactly), a diagonal pair's block
 // holds both orders itself.
@@ -112,47 +107,7 @@ __global__ __launch_bounds__(64) void qc_esp_hermite_kernel(const QcPairDesc *__
     }
 }
 
-// ---- the Hermite-Coulomb table R^0_tuv, t + u + v <= L, in ONE array of nherm(L) registers: level n overwrites level n + 1 from the
-// highest order down (an entry of order N reads orders N - 1 and N - 2 of the level above, which are still in place), the step is
-// qc_md_r_step's.  The plan is a compile-time list, every index a constant: nothing is addressed dynamically.
-struct EspRStep { short dst, s1, s2; signed char ax, cf, seed; };        // seed >= 0: R[0] = (-2p)^seed F_seed
-template <int L> struct EspRPlan { EspRStep s[qc_rwork(L)]; };
-template <int L> constexpr EspRPlan<L> esp_make_rplan() {
-    EspRPlan<L> P{};
-    int k = 0;
-    P.s[k++] = EspRStep{0, 0, 0, 0, 0, (signed char)L};
-    for (int n = L - 1; n >= 0; --n) {
-        for (int N = L - n; N >= 1; --N)
-            for (int t = N; t >= 0; --t)
-                for (int u = N - t; u >= 0; --u) {
-                    const int v = N - t - u;
-                    EspRStep e{(short)qc_hidx(t, u, v), 0, 0, 0, 0, -1};
-                    if (t) { e.ax = 0; e.s1 = (short)qc_hidx(t - 1, u, v); e.cf = (signed char)(t - 1); e.s2 = (short)(t > 1 ? qc_hidx(t - 2, u, v) : 0); }
-                    else if (u) { e.ax = 1; e.s1 = (short)qc_hidx(t, u - 1, v); e.cf = (signed char)(u - 1); e.s2 = (short)(u > 1 ? qc_hidx(t, u - 2, v) : 0); }
-                    else { e.ax = 2; e.s1 = (short)qc_hidx(t, u, v - 1); e.cf = (signed char)(v - 1); e.s2 = (short)(v > 1 ? qc_hidx(t, u, v - 2) : 0); }
-                    P.s[k++] = e;
-                }
-        P.s[k++] = EspRStep{0, 0, 0, 0, 0, (signed char)n};
-    }
-    return P;
-}
-template <int L> inline constexpr EspRPlan<L> esp_rplan = esp_make_rplan<L>();
-
-template <int L, int S>
-__device__ __forceinline__ void esp_rstep(double (&R)[qc_nherm(L)], const double (&seed)[L + 1], const double (&X)[3]) {
-    constexpr EspRStep e = esp_rplan<L>.s[S];
-    if constexpr (e.seed >= 0) R[0] = seed[e.seed];
-    else if constexpr (e.cf > 0) R[e.dst] = X[e.ax] * R[e.s1] + (double)e.cf * R[e.s2];
-    else R[e.dst] = X[e.ax] * R[e.s1];
-}
-template <int L, int... S>
-__device__ __forceinline__ void esp_rtable(double (&R)[qc_nherm(L)], const double (&seed)[L + 1], const double (&X)[3], std::integer_sequence<int, S...>) {
-    (esp_rstep<L, S>(R, seed, X), ...);
-}
-
-// records of order L per LDS tile (16 KB at the most); a tile is also the unit of the fixed summation order: see below
-__host__ __device__ constexpr int esp_tile(int L) { return 2048 / (4 + qc_nherm(L)); }
-
+// ---- the potential: the table R^0_tuv of a (record, point) by the compile-time plan of qc_esp.h, records in LDS tiles of esp_tile(L)
 // v[k] += sum over the records of order L.  The sum of a point is  (((v + c_0) + c_1) + ...)  over the tiles' sums c_i, each tile summed
 // from zero in list order: the same additions whether one workgroup walks all tiles (partial == null, gridDim.y = 1) or the tiles are
 // spread over gridDim.y and qc_esp_sum_kernel adds their sums afterwards in the same order (few points: the chip would starve).
@@ -204,19 +159,6 @@ template <int L>
 void esp_launch(hipStream_t st, dim3 grid, int nrec, const double *rec, const double *boys, int B, const double *xyz, double *v, double *partial, int tile0) {
     hipLaunchKernelGGL(qc_esp_points_kernel<L>, grid, dim3(PT_WG), 0, st, nrec, rec, boys, B, xyz, v, partial, tile0);
 }
-
-// hipEvents of one call's phases, destroyed on every path out
-struct PhaseClock {
-    hipEvent_t e[5] = {};
-    double *ms;
-    explicit PhaseClock(double *ms_) : ms(ms_) { for (int i = 0; i < 4; ++i) ms[i] = 0.0; }
-    int create() { for (auto &x : e) if (hipEventCreate(&x) != hipSuccess) return QC_ERR_HIP; return QC_OK; }
-    void mark(int i, hipStream_t st) { (void)hipEventRecord(e[i], st); }
-    void add(int first, int last) {                        // (after the stream has been waited for)
-        for (int i = first; i < last; ++i) { float t = 0.f; if (hipEventElapsedTime(&t, e[i], e[i + 1]) == hipSuccess) ms[i] += t; }
-    }
-    ~PhaseClock() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // Points of a batch: what a quarter of the free device memory holds at `doubles_per_point`, a multiple of the workgroup, within
 // [256, PT_BATCH_CAP].  QC_POINTS_BATCH=<points> (a test switch, read once per handle at its first point call) replaces it.
@@ -309,31 +251,20 @@ void qc_esp_record_counts(const qc_system *S, int64_t counts[QC_LPAIR + 1]) {
     for (const QcPairDesc &d : S->pairs) counts[d.L] += d.K;
 }
 
-// v_elec on npts > 0 host points from a device density; the device side of the handle is initialised (pair data, Boys tables)
-int qc_points_esp_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *v_elec) {
+// the records of dD (EspRecords, qc_esp.h)
+int EspRecords::build(qc_system *S, const double *dD, PhaseClock &clk) {
     const int n = S->nbasis, npairs = (int)S->pairs.size();
-    int64_t cnt[QC_LPAIR + 1];
     qc_esp_record_counts(S, cnt);
-    EspGroups g{};
-    int ntiles[QC_LPAIR + 1], tile0[QC_LPAIR + 1], tiles_all = 0;
     size_t words = 0;
+    tiles_all = 0;
     for (int L = 0; L <= QC_LPAIR; ++L) {
         g.off[L] = (long long)words; words += (size_t)cnt[L] * (4 + qc_nherm(L));
         tile0[L] = tiles_all; ntiles[L] = (int)((cnt[L] + esp_tile(L) - 1) / esp_tile(L)); tiles_all += ntiles[L];
     }
     std::vector<int> recstart(npairs);
     { int64_t run[QC_LPAIR + 1] = {}; for (int i = 0; i < npairs; ++i) { recstart[i] = (int)run[S->pairs[i].L]; run[S->pairs[i].L] += S->pairs[i].K; } }
-    const int64_t bmax = batch_points(S, npts, 8);
-    // few points: the tiles go to workgroups of their own.  The largest batch that does so, and the most points such a batch has
-    const int64_t split_max = std::min<int64_t>(S->points_split, (int64_t)(PT_SPLIT_WORDS / (size_t)std::max(tiles_all, 1)));
-    const int64_t rem = npts % bmax, split_pts = bmax <= split_max ? bmax : (rem > 0 && rem <= split_max ? rem : 0);
-    DevBuf rec, dxyz, dv, partial;
     QcDev<int> drs;
-    if (rec.alloc(words) != QC_OK || drs.alloc(npairs) != QC_OK || dxyz.alloc(3 * bmax) != QC_OK || dv.alloc(bmax) != QC_OK ||
-        partial.alloc((size_t)tiles_all * split_pts) != QC_OK)
-        return QC_ERR_HIP;
-    PhaseClock clk(S->points_ms);
-    if (clk.create() != QC_OK) return QC_ERR_HIP;
+    if (rec.alloc(words) != QC_OK || drs.alloc(npairs) != QC_OK) return QC_ERR_HIP;
     hipStream_t st = S->stream;
     clk.mark(0, st);
     QC_HIP_CHECK(hipMemcpyAsync(drs.p, recstart.data(), (size_t)npairs * sizeof(int), hipMemcpyHostToDevice, st));
@@ -343,6 +274,27 @@ int qc_points_esp_device(qc_system *S, const double *dD, int64_t npts, const dou
     clk.mark(2, st);
     QC_HIP_CHECK(hipStreamSynchronize(st));                 // (recstart is read by the copy until here)
     clk.add(0, 2);
+    return QC_OK;
+}
+
+// v_elec on npts > 0 host points from a device density; the device side of the handle is initialised (pair data, Boys tables)
+int qc_points_esp_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *v_elec) {
+    PhaseClock clk(S->points_ms);
+    if (clk.create() != QC_OK) return QC_ERR_HIP;
+    EspRecords E;
+    int rc = E.build(S, dD, clk);
+    if (rc != QC_OK) return rc;
+    const DevBuf &rec = E.rec;
+    const EspGroups &g = E.g;
+    const int64_t *cnt = E.cnt;
+    const int *ntiles = E.ntiles, *tile0 = E.tile0, tiles_all = E.tiles_all;
+    const int64_t bmax = batch_points(S, npts, 8);
+    // few points: the tiles go to workgroups of their own.  The largest batch that does so, and the most points such a batch has
+    const int64_t split_max = std::min<int64_t>(S->points_split, (int64_t)(PT_SPLIT_WORDS / (size_t)std::max(tiles_all, 1)));
+    const int64_t rem = npts % bmax, split_pts = bmax <= split_max ? bmax : (rem > 0 && rem <= split_max ? rem : 0);
+    DevBuf dxyz, dv, partial;
+    if (dxyz.alloc(3 * bmax) != QC_OK || dv.alloc(bmax) != QC_OK || partial.alloc((size_t)tiles_all * split_pts) != QC_OK) return QC_ERR_HIP;
+    hipStream_t st = S->stream;
     for (int64_t k0 = 0; k0 < npts; k0 += bmax) {
         const int nb = (int)std::min(bmax, npts - k0);
         const bool split = nb <= split_pts;

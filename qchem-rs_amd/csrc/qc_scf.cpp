@@ -11,7 +11,7 @@
 #include <memory>
 #include <new>
 
-#include "qc_internal.h"
+#include "qc_embed.h"
 
 namespace {
 
@@ -112,6 +112,10 @@ int scf_setup(qc_system *S, ScfWork &W, std::vector<double> &h_eht) {
     if (rc1 == QC_OK) rc1 = qc_one_electron_device(S, 2, W.eig[0].t2.p);
     if (rc1 != QC_OK) return rc1;
     qc_axpby(st, n, 1.0, W.eig[0].t1.p, 1.0, W.eig[0].t2.p, W.H.p);
+    if (!S->pc.empty()) {                                   // point-charge embedding: H = T + V + V_pc (whole on every rank, like T and V)
+        if ((rc1 = qc_pc_matrix_device(S, S->pc, W.eig[0].t1.p)) != QC_OK) return rc1;
+        qc_axpby(st, n, 1.0, W.H.p, 1.0, W.eig[0].t1.p, W.H.p);
+    }
     std::vector<double> s(nn), h(nn);
     QC_HIP_CHECK(hipMemcpyAsync(s.data(), W.S.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
     QC_HIP_CHECK(hipMemcpyAsync(h.data(), W.H.p, nn * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -214,6 +218,7 @@ struct qc_scf_state {
     PassTiming tm;
     unsigned pass_seq = 0;                     // sequence number of the last pass whose end the host saw through the pinned word
     bool event_wait = getenv("QC_EVENT_WAIT") != nullptr;      // (A/B switch, read per SCF state: the stream's event instead)
+    std::vector<double> pc;                    // the handle's point charges when the state began ([x, y, z, q] each): what its H contains
     ~qc_scf_state() {
         if (S && S->prep.owner == this) { S->prep.prepared = false; S->prep.owner = nullptr; }
         delete diis[0]; delete diis[1];
@@ -448,6 +453,7 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
     if (st->G.alloc(nspin * nn) != QC_OK || st->Cs.alloc(nspin * nn) != QC_OK || st->ws.alloc(nspin * n) != QC_OK) return QC_ERR_HIP;
     std::vector<double> h_eht;
     lap("state buffers");
+    st->pc = S->pc;
     if ((rc = scf_setup(S, st->W, h_eht)) != QC_OK) return rc;           // rhf.rs:41-49
     lap("S, T, V, X = S^-1/2");
     for (int s = 0; s < nspin; ++s) {                                     // rhf.rs:50 / uhf.rs:60-63
@@ -884,6 +890,13 @@ int qc_scf_gradient(qc_scf_state *st, double *grad) {
     QC_HIP_CHECK(hipEventElapsedTime(&pw, ev[0], ev[1]));
     S->grad_ms[0] += pw;                                                    // (phase 0: P/W build + Cartesian transform)
     for (int k = 0; k < na3; ++k) grad[k] = ((t[k] + t[na3 + k]) + t[2 * na3 + k]) + t[3 * na3 + k];
+    if (st->pc.empty()) return QC_OK;
+    // an embedded state: + dE_nq/dR_A + the basis-function derivatives of tr(P_t V_pc), for the charges the state began with
+    std::vector<double> gn(na3), ge(na3);
+    if (nspin == 2) qc_axpby(S->stream, n, 1.0, dP.p, 1.0, dP.p + nn, dP.p);
+    if ((rc = qc_pc_atom_gradient_device(S, st->pc, dP.p, ge.data())) != QC_OK) return rc;
+    qc_pc_nuclear_gradient(S, st->pc, gn.data(), nullptr);
+    for (int k = 0; k < na3; ++k) grad[k] += gn[k] + ge[k];
     return QC_OK;
 }
 
@@ -1031,6 +1044,40 @@ int qc_scf_esp_on_points(qc_scf_state *st, int64_t npts, const double *xyz, doub
     for (int64_t k = 0; k < npts; ++k) { v_total[k] += ve[k]; if (v_elec) v_elec[k] = ve[k]; }
     return QC_OK;
 }
+// the field of the molecule alone, E = -grad V of qc_scf_esp_on_points: e_total = e_nuc + e_elec, npts x 3 each
+int qc_scf_field_on_points(qc_scf_state *st, int64_t npts, const double *xyz, double *e_total, double *e_elec) {
+    if (!st || !xyz || !e_total || npts < 0) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (npts == 0) return QC_OK;
+    DevBuf P;
+    if (st->uhf) {
+        if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
+        qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, 1.0, st->D[1].p, P.p);
+    }
+    std::vector<double> ee(3 * (size_t)npts);
+    const int rc = qc_points_field_device(S, st->uhf ? P.p : st->D[0].p, npts, xyz, ee.data(), S->points_ms);
+    if (rc != QC_OK) return rc;
+    qc_points_enuc(S, npts, xyz, e_total);
+    for (int64_t k = 0; k < 3 * npts; ++k) { e_total[k] += ee[k]; if (e_elec) e_elec[k] = ee[k]; }
+    return QC_OK;
+}
+// dE/dR_c = -q_c E_total(R_c) for the charges the state began with, npc x 3
+int qc_scf_point_charge_gradient(qc_scf_state *st, double *grad) {
+    if (!st || !grad) return QC_ERR_INVALID;
+    qc_system *S = st->S;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    const int64_t npc = (int64_t)(st->pc.size() / 4);
+    if (npc == 0) return QC_OK;
+    std::vector<double> xyz(3 * (size_t)npc);
+    for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) xyz[3 * c + k] = st->pc[4 * c + k];
+    const int rc = qc_scf_field_on_points(st, npc, xyz.data(), grad, nullptr);
+    if (rc != QC_OK) return rc;
+    for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) grad[3 * c + k] *= -st->pc[4 * c + 3];
+    return QC_OK;
+}
+int64_t qc_scf_point_charge_count(const qc_scf_state *st) { return st ? (int64_t)(st->pc.size() / 4) : QC_ERR_INVALID; }
+double qc_scf_point_charge_nuclear_energy(const qc_scf_state *st) { return st ? qc_pc_nuclear_energy(st->S, st->pc) : 0.0; }
 // orbitals first .. first + count - 1 of `spin`, counted from 0 in the order of qc_scf_orbital_energies; out: count x npts
 int qc_scf_orbitals_on_points(qc_scf_state *st, int spin, int first, int count, int64_t npts, const double *xyz, double *out) {
     if (!st || !xyz || !out || npts < 0 || spin < 0 || spin > (st->uhf ? 1 : 0)) return QC_ERR_INVALID;

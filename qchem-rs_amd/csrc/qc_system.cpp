@@ -13,6 +13,7 @@
 
 #include <cstdlib>
 
+#include "qc_embed.h"
 #include "qc_md.h"
 
 namespace {
@@ -505,4 +506,133 @@ void qc_host_potential_matrix(const qc_system *S, const double *r, double *out) 
                     out[(size_t)(B.off + fb) * n + A.off + fa] = v;
                 }
         }
+}
+
+// ---- point-charge embedding on the host (qc_embed.h): the reference statements of what qc_embed.hip computes
+// E_nq = sum_A sum_c Z_A q_c / |R_A - R_c|, atoms outside, charges in list order
+double qc_pc_nuclear_energy(const qc_system *S, const std::vector<double> &pc) {
+    double e = 0.0;
+    for (int a = 0; a < S->natoms; ++a)
+        for (size_t c = 0; c < pc.size() / 4; ++c) {
+            const double dx = S->xyz[3 * a] - pc[4 * c], dy = S->xyz[3 * a + 1] - pc[4 * c + 1], dz = S->xyz[3 * a + 2] - pc[4 * c + 2];
+            e += (double)S->Z[a] * pc[4 * c + 3] / std::sqrt(dx * dx + dy * dy + dz * dz);
+        }
+    return e;
+}
+
+void qc_pc_nuclear_gradient(const qc_system *S, const std::vector<double> &pc, double *ga, double *gc) {
+    const size_t npc = pc.size() / 4;
+    if (ga) std::fill(ga, ga + 3 * S->natoms, 0.0);
+    if (gc) std::fill(gc, gc + 3 * npc, 0.0);
+    for (int a = 0; a < S->natoms; ++a)
+        for (size_t c = 0; c < npc; ++c) {
+            double d[3], r2 = 0.0;
+            for (int k = 0; k < 3; ++k) { d[k] = S->xyz[3 * a + k] - pc[4 * c + k]; r2 += d[k] * d[k]; }
+            const double f = -(double)S->Z[a] * pc[4 * c + 3] / (r2 * std::sqrt(r2));
+            for (int k = 0; k < 3; ++k) { if (ga) ga[3 * a + k] += f * d[k]; if (gc) gc[3 * c + k] -= f * d[k]; }
+        }
+}
+
+// V_pc = -sum_c q_c A(R_c): the nuclear-attraction sum of qc_host_one_electron with the charges as centres - per primitive pair the
+// Hermite-Coulomb tables of all charges summed first, then one contraction; exactly symmetric (diagonal blocks: one triangle, mirrored)
+void qc_host_point_charge_matrix(const qc_system *S, const std::vector<double> &pc, double *out) {
+    const int n = S->nbasis;
+    std::fill(out, out + (size_t)n * n, 0.0);
+    std::vector<double> R0, Rs;
+    for (int a = 0; a < S->nshells; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const QcShell &A = S->shells[a], &B = S->shells[b];
+            const size_t nca = A.ncart, ncb = B.ncart;
+            std::vector<double> cart(nca * ncb, 0.0);
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
+                    double P[3];
+                    for (int k = 0; k < 3; ++k) P[k] = (ea * A.A[k] + eb * B.A[k]) / p;
+                    E1 E[3];
+                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+                    Rs.assign(qc_nherm(A.L + B.L), 0.0);
+                    for (size_t c = 0; c < pc.size() / 4; ++c) {
+                        const double PC[3] = {P[0] - pc[4 * c], P[1] - pc[4 * c + 1], P[2] - pc[4 * c + 2]};
+                        hermite_r_host(A.L + B.L, p, PC, R0);
+                        for (size_t h = 0; h < Rs.size(); ++h) Rs[h] += pc[4 * c + 3] * R0[h];
+                    }
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
+                            cart[x * ncb + y] -= cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, Rs.data()));
+                        }
+                }
+            for (int fa = 0; fa < A.nfunc; ++fa)
+                for (int fb = 0; fb < B.nfunc; ++fb) {
+                    if (a == b && fb > fa) continue;
+                    double v = 0.0;
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * ncb + y];
+                    out[(size_t)(A.off + fa) * n + B.off + fb] = v;
+                    out[(size_t)(B.off + fb) * n + A.off + fa] = v;
+                }
+        }
+}
+
+// B^k_ab = dA_ab(r)/dr_k, k = x, y, z: qc_host_potential_matrix with the table of order L + 1 shifted by one unit along k,
+// d/dr_x R_tuv(P - r) = -R_{t+1,u,v}; exactly symmetric
+void qc_host_field_matrix(const qc_system *S, const double *r, double *out) {
+    const int n = S->nbasis;
+    const size_t nn = (size_t)n * n;
+    std::fill(out, out + 3 * nn, 0.0);
+    std::vector<double> R0, Rk[3];
+    for (int a = 0; a < S->nshells; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const QcShell &A = S->shells[a], &B = S->shells[b];
+            const size_t nca = A.ncart, ncb = B.ncart;
+            const int L = A.L + B.L;
+            std::vector<double> cart(3 * nca * ncb, 0.0);
+            for (int i = 0; i < A.nprim; ++i)
+                for (int j = 0; j < B.nprim; ++j) {
+                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
+                    double PC[3];
+                    for (int k = 0; k < 3; ++k) PC[k] = (ea * A.A[k] + eb * B.A[k]) / p - r[k];
+                    E1 E[3];
+                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
+                    hermite_r_host(L + 1, p, PC, R0);
+                    for (int k = 0; k < 3; ++k) Rk[k].assign(qc_nherm(L), 0.0);
+                    for (int t = 0; t <= L; ++t)
+                        for (int u = 0; t + u <= L; ++u)
+                            for (int v = 0; t + u + v <= L; ++v) {
+                                Rk[0][qc_hidx(t, u, v)] = -R0[qc_hidx(t + 1, u, v)];
+                                Rk[1][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u + 1, v)];
+                                Rk[2][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u, v + 1)];
+                            }
+                    for (size_t x = 0; x < nca; ++x)
+                        for (size_t y = 0; y < ncb; ++y) {
+                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
+                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
+                            for (int k = 0; k < 3; ++k) cart[(k * nca + x) * ncb + y] += cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, Rk[k].data()));
+                        }
+                }
+            for (int k = 0; k < 3; ++k)
+                for (int fa = 0; fa < A.nfunc; ++fa)
+                    for (int fb = 0; fb < B.nfunc; ++fb) {
+                        if (a == b && fb > fa) continue;
+                        double v = 0.0;
+                        for (size_t x = 0; x < nca; ++x)
+                            for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[(k * nca + x) * ncb + y];
+                        out[k * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+                        out[k * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+                    }
+        }
+}
+
+void qc_points_enuc(const qc_system *S, int64_t npts, const double *xyz, double *e) {
+    for (int64_t k = 0; k < npts; ++k) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int a = 0; a < S->natoms; ++a) {
+            const double d[3] = {xyz[3 * k] - S->xyz[3 * a], xyz[3 * k + 1] - S->xyz[3 * a + 1], xyz[3 * k + 2] - S->xyz[3 * a + 2]};
+            const double r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], r3 = r2 * std::sqrt(r2);
+            for (int x = 0; x < 3; ++x) s[x] += (double)S->Z[a] * d[x] / r3;
+        }
+        for (int x = 0; x < 3; ++x) e[3 * k + x] = s[x];
+    }
 }

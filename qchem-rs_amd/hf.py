@@ -51,7 +51,11 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_basis_on_points", "qc_potential_matrix", "qc_esp_records", "qc_density_on_points", "qc_esp_on_points", "qc_orbitals_on_points",
            "qc_scf_density_on_points", "qc_scf_esp_on_points", "qc_scf_orbitals_on_points", "qc_points_timings",
            "qc_multipole_count", "qc_multipole_matrices", "qc_multipole_matrices_gpu", "qc_scf_multipoles",
-           "qc_scf_populations", "qc_populations", "qc_esp_fit_points", "qc_esp_fit_solve", "qc_scf_esp_charges"]
+           "qc_scf_populations", "qc_populations", "qc_esp_fit_points", "qc_esp_fit_solve", "qc_scf_esp_charges",
+           "qc_set_point_charges", "qc_point_charge_count", "qc_point_charge_nuclear_energy", "qc_scf_point_charge_count",
+           "qc_scf_point_charge_nuclear_energy", "qc_point_charge_matrix", "qc_point_charge_matrix_gpu", "qc_field_matrix",
+           "qc_field_on_points", "qc_scf_field_on_points", "qc_point_charge_gradient", "qc_scf_point_charge_gradient",
+           "qc_point_charge_timings"]
 
 POPULATION_SCHEMES = {"mulliken": 0, "lowdin": 1}
 BOHR_ANGSTROM = 0.529177210903   # QC_BOHR_ANGSTROM in include/qchem_hip.h
@@ -358,6 +362,19 @@ def lib():
         L.qc_esp_fit_points.argtypes = [vp, C.POINTER(_EspFit), C.c_int64, vp, C.POINTER(C.c_int64)]
         L.qc_esp_fit_solve.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.POINTER(_EspFit), vp]
         L.qc_scf_esp_charges.argtypes = [vp, C.POINTER(_EspFit), C.c_int64, vp, vp, vp]
+        L.qc_set_point_charges.argtypes = [vp, C.c_int64, vp, vp]
+        L.qc_point_charge_count.argtypes = [vp]; L.qc_point_charge_count.restype = C.c_int64
+        L.qc_point_charge_nuclear_energy.argtypes = [vp]; L.qc_point_charge_nuclear_energy.restype = C.c_double
+        L.qc_scf_point_charge_count.argtypes = [vp]; L.qc_scf_point_charge_count.restype = C.c_int64
+        L.qc_scf_point_charge_nuclear_energy.argtypes = [vp]; L.qc_scf_point_charge_nuclear_energy.restype = C.c_double
+        L.qc_point_charge_matrix.argtypes = [vp, vp]
+        L.qc_point_charge_matrix_gpu.argtypes = [vp, vp]
+        L.qc_field_matrix.argtypes = [vp, vp, vp]
+        L.qc_field_on_points.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+        L.qc_scf_field_on_points.argtypes = [vp, C.c_int64, vp, vp, vp]
+        L.qc_point_charge_gradient.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_scf_point_charge_gradient.argtypes = [vp, vp]
+        L.qc_point_charge_timings.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -526,6 +543,60 @@ class System:
     def points_timings(self):
         """Phase times (ms) of the handle's last point call: upload, basis values / Hermite densities, contraction, download."""
         ms = np.zeros(4); _check(lib().qc_points_timings(self._h, _ptr(ms)), "qc_points_timings"); return ms
+
+    # ---- point-charge embedding (include/qchem_hip.h, "point-charge embedding")
+    def set_point_charges(self, positions=None, charges=None):
+        """The handle's external point charges: positions (npc, 3) in bohr, charges (npc,) - any finite values; None or empty removes
+        the set (qc_set_point_charges, host only).  SCF states begun afterwards are embedded; states that are alive keep their set."""
+        P = _points(positions if positions is not None else np.zeros((0, 3)))
+        q = np.ascontiguousarray(charges if charges is not None else np.zeros(0), np.float64).reshape(-1)
+        if q.size != len(P):
+            raise QcError("qc_set_point_charges: one charge per position")
+        _check(lib().qc_set_point_charges(self._h, len(P), _ptr(P) if len(P) else None, _ptr(q) if len(P) else None), "qc_set_point_charges")
+
+    def point_charge_count(self) -> int: return int(lib().qc_point_charge_count(self._h))
+
+    def point_charge_nuclear_energy(self) -> float:
+        """E_nq = sum_A sum_c Z_A q_c / |R_A - R_c| of the handle's set (0.0 without charges)."""
+        return lib().qc_point_charge_nuclear_energy(self._h)
+
+    def point_charge_matrix(self, gpu: bool = False):
+        """(n, n): V_pc = -sum_c q_c A(R_c) of the handle's set - qc_point_charge_matrix on the host, or with gpu=True the kernels the
+        SCF set-up uses (qc_point_charge_matrix_gpu)."""
+        V = np.zeros((self.n, self.n))
+        fn = "qc_point_charge_matrix_gpu" if gpu else "qc_point_charge_matrix"
+        _check(getattr(lib(), fn)(self._h, _ptr(V)), fn)
+        return V
+
+    def field_matrix(self, r):
+        """(3, n, n): B^k_ab = dA_ab(r)/dr_k, the derivative companion of potential_matrix (qc_field_matrix, host only)."""
+        B = np.zeros((3, self.n, self.n))
+        _check(lib().qc_field_matrix(self._h, _origin_ptr(r), _ptr(B)), "qc_field_matrix")
+        return B
+
+    def field_on_points(self, D, points, parts: bool = False):
+        """(npts, 3): the electric field E = -grad V of the nuclei and the density D on the GPU (qc_field_on_points); parts=True:
+        (E, e_elec, e_nuc).  A point on a nucleus has a non-finite e_nuc and a finite e_elec."""
+        Dm, P = self._density_arg(D, "qc_field_on_points"), _points(points)
+        ee, en = np.zeros((len(P), 3)), np.zeros((len(P), 3))
+        _check(lib().qc_field_on_points(self._h, _ptr(Dm), len(P), _ptr(P), _ptr(ee), _ptr(en)), "qc_field_on_points")
+        with np.errstate(invalid="ignore"):
+            return (en + ee, ee, en) if parts else en + ee
+
+    def point_charge_gradient(self, D, Db=None):
+        """(2, npc, 3): dE_nq/dR_c and d tr(P_t V_pc)/dR_c of the handle's charges at a fixed density (qc_point_charge_gradient).
+        RHF: D in the qc_fock_rhf convention; UHF: D = D_alpha, Db = D_beta."""
+        n, npc = self.n, self.point_charge_count()
+        Dm = np.ascontiguousarray(D if Db is None else np.concatenate([np.asarray(D).reshape(n, n), np.asarray(Db).reshape(n, n)]), dtype=np.float64)
+        if Dm.size != (1 if Db is None else 2) * n * n:
+            raise QcError("qc_point_charge_gradient: densities must be n x n")
+        t = np.zeros((2, npc, 3))
+        _check(lib().qc_point_charge_gradient(self._h, 1 if Db is None else 2, _ptr(Dm), _ptr(t)), "qc_point_charge_gradient")
+        return t
+
+    def point_charge_timings(self):
+        """Phase times (ms) of the handle's last embedding call: upload, Hermite sums over the charges, assembly or contraction, download."""
+        ms = np.zeros(4); _check(lib().qc_point_charge_timings(self._h, _ptr(ms)), "qc_point_charge_timings"); return ms
 
     def eri(self):
         I = np.zeros((self.n,) * 4); _check(lib().qc_eri_full(self._h, I.reshape(-1)), "qc_eri_full"); return I
@@ -831,6 +902,32 @@ class ScfStepper:
         with np.errstate(invalid="ignore"):
             return v, ve, v - ve
 
+    def field_on_points(self, points, parts: bool = False):
+        """(npts, 3): the electric field of the nuclei and the state's density, E = -grad V of esp_on_points (qc_scf_field_on_points);
+        parts=True: (E, e_elec, e_nuc).  The state is left as it was."""
+        P = _points(points)
+        e, ee = np.zeros((len(P), 3)), np.zeros((len(P), 3))
+        _check(lib().qc_scf_field_on_points(self._st, len(P), _ptr(P), _ptr(e), _ptr(ee)), "qc_scf_field_on_points")
+        if not parts:
+            return e
+        with np.errstate(invalid="ignore"):
+            return e, ee, e - ee
+
+    def point_charge_count(self) -> int:
+        """charges of the set the state began with (its H contains their V_pc)"""
+        return int(lib().qc_scf_point_charge_count(self._st))
+
+    def embedding_nuclear_energy(self) -> float:
+        """E_nq of the charges the state began with: total energy = electronic + nuclear repulsion + this."""
+        return lib().qc_scf_point_charge_nuclear_energy(self._st)
+
+    def point_charge_gradient(self):
+        """(npc, 3): dE/dR_c at the state for the charges it began with, -q_c E(R_c) (qc_scf_point_charge_gradient); the state is left
+        as it was."""
+        g = np.zeros((self.point_charge_count(), 3))
+        _check(lib().qc_scf_point_charge_gradient(self._st, _ptr(g)), "qc_scf_point_charge_gradient")
+        return g
+
     def orbitals_on_points(self, points, orbitals, spin: int = 0):
         """(len(orbitals), npts): MOs of the state's last Roothaan step on points; `orbitals`: an index or a sequence of indices, counted
         from 0 in the order of orbital_energies(spin) - qc_scf_orbitals_on_points, one call per run of consecutive indices."""
@@ -968,9 +1065,10 @@ class RestrictedHartreeFockOutput:
     nuclear_repulsion: float
     iterations: int
     timings_ms: dict = field(default_factory=dict)
+    embedding_nuclear_energy: float = 0.0    # E_nq of the point charges the run was embedded in (System.set_point_charges)
 
     def total_energy(self) -> float:
-        return self.electronic_energy + self.nuclear_repulsion
+        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy
 
 
 @dataclass
@@ -981,9 +1079,10 @@ class UnrestrictedHartreeFockOutput:
     nuclear_repulsion: float
     iterations: int
     timings_ms: dict = field(default_factory=dict)
+    embedding_nuclear_energy: float = 0.0    # E_nq of the point charges the run was embedded in (System.set_point_charges)
 
     def total_energy(self) -> float:
-        return self.electronic_energy + self.nuclear_repulsion
+        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy
 
 
 def _as_system(system) -> System:
@@ -1007,8 +1106,9 @@ def _run(fn, system, config, uhf):
     t = dict(setup=out.ms_setup, fock=out.ms_fock_total, linalg=out.ms_linalg_total, total=out.ms_total, tuner=out.ms_tuner)
     if uhf:
         return UnrestrictedHartreeFockOutput(wa.tolist(), wb.tolist(), out.electronic_energy, out.nuclear_repulsion,
-                                             int(out.iterations), t)
-    return RestrictedHartreeFockOutput(wa.tolist(), out.electronic_energy, out.nuclear_repulsion, int(out.iterations), t)
+                                             int(out.iterations), t, sysh.point_charge_nuclear_energy())
+    return RestrictedHartreeFockOutput(wa.tolist(), out.electronic_energy, out.nuclear_repulsion, int(out.iterations), t,
+                                       sysh.point_charge_nuclear_energy())
 
 
 def restricted_hartree_fock(system, config: HartreeFockConfig) -> Optional[RestrictedHartreeFockOutput]:
@@ -1035,9 +1135,10 @@ def _stepped(system, config: HartreeFockConfig, uhf: bool, after):
                 t = st.timings()
                 if uhf:
                     out = UnrestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), st.orbital_energies(1).tolist(), e,
-                                                        sysh.nuclear_repulsion(), it, t)
+                                                        sysh.nuclear_repulsion(), it, t, st.embedding_nuclear_energy())
                 else:
-                    out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, t)
+                    out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, t,
+                                                      st.embedding_nuclear_energy())
                 return out, after(st)
         return None
     finally:
@@ -1112,9 +1213,10 @@ def stabilize(system, config: HartreeFockConfig, n_alpha: int = 0, n_beta: int =
                 return None
             if is_uhf:
                 out = UnrestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), st.orbital_energies(1).tolist(), e,
-                                                    sysh.nuclear_repulsion(), it, st.timings())
+                                                    sysh.nuclear_repulsion(), it, st.timings(), st.embedding_nuclear_energy())
             else:
-                out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, st.timings())
+                out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, st.timings(),
+                                                  st.embedding_nuclear_energy())
             s2 = st.spin_square()
             follow, lowest = None, None
             for kind in ((0,) if is_uhf else (1, 0)):
