@@ -350,6 +350,20 @@ int qc_gradient_timings(const qc_system *S, double *ms) {
 
 // ---- values on points: the host-only pair, then the GPU entries from host matrices.  Order of the checks: arguments, sharding, an
 // empty call (QC_OK, nothing launched or written), the device.
+// Those checks and the density: D (nspin blocks of n x n on the host) -> the total density at the head of dD, on the handle's stream.
+// args_ok: the caller's own argument checks; empty: nothing to compute - QC_OK with dD left empty.
+static int density_to_device(qc_system *S, bool args_ok, bool empty, int nspin, const double *D, DevBuf &dD) {
+    if (!S || !D || !args_ok || (nspin != 1 && nspin != 2)) return QC_ERR_INVALID;
+    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
+    if (empty) return QC_OK;
+    const int rc = qc_device_init(S);
+    if (rc != QC_OK) return rc;
+    const size_t nn = (size_t)S->nbasis * S->nbasis;
+    if (dD.alloc(nspin * nn) != QC_OK) return QC_ERR_HIP;
+    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    if (nspin == 2) qc_axpby(S->stream, S->nbasis, 1.0, dD.p, 1.0, dD.p + nn, dD.p);
+    return QC_OK;
+}
 int qc_basis_on_points(const qc_system *S, int64_t npts, const double *xyz, double *out) {
     if (!S || !xyz || !out || npts < 0) return QC_ERR_INVALID;
     qc_host_basis_on_points(S, npts, xyz, out);
@@ -366,27 +380,14 @@ int qc_esp_records(const qc_system *S, int64_t counts[7]) {
     return QC_OK;
 }
 int qc_density_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *rho) {
-    if (!S || !D || !xyz || !rho || npts < 0) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    if (npts == 0) return QC_OK;
-    int rc = qc_device_init(S);
-    if (rc != QC_OK) return rc;
-    const size_t nn = (size_t)S->nbasis * S->nbasis;
     DevBuf dD;
-    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    return qc_points_density_device(S, dD.p, npts, xyz, rho);
+    const int rc = density_to_device(S, xyz && rho && npts >= 0, npts == 0, 1, D, dD);
+    return rc != QC_OK || !dD.p ? rc : qc_points_density_device(S, dD.p, npts, xyz, rho);
 }
 int qc_esp_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *v_elec, double *v_nuc) {
-    if (!S || !D || !xyz || !v_elec || npts < 0) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    if (npts == 0) return QC_OK;
-    int rc = qc_device_init(S);
-    if (rc != QC_OK) return rc;
-    const size_t nn = (size_t)S->nbasis * S->nbasis;
     DevBuf dD;
-    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    int rc = density_to_device(S, xyz && v_elec && npts >= 0, npts == 0, 1, D, dD);
+    if (rc != QC_OK || !dD.p) return rc;
     if ((rc = qc_points_esp_device(S, dD.p, npts, xyz, v_elec)) != QC_OK) return rc;
     if (v_nuc) qc_points_vnuc(S, npts, xyz, v_nuc);
     return QC_OK;
@@ -457,33 +458,19 @@ int qc_field_matrix(const qc_system *S, const double r[3], double *out) {
     return QC_OK;
 }
 int qc_field_on_points(qc_system *S, const double *D, int64_t npts, const double *xyz, double *e_elec, double *e_nuc) {
-    if (!S || !D || !xyz || !e_elec || npts < 0) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    if (npts == 0) return QC_OK;
-    int rc = qc_device_init(S);
-    if (rc != QC_OK) return rc;
-    const size_t nn = (size_t)S->nbasis * S->nbasis;
     DevBuf dD;
-    if (dD.alloc(nn) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
+    int rc = density_to_device(S, xyz && e_elec && npts >= 0, npts == 0, 1, D, dD);
+    if (rc != QC_OK || !dD.p) return rc;
     if ((rc = qc_points_field_device(S, dD.p, npts, xyz, e_elec, S->points_ms)) != QC_OK) return rc;
     if (e_nuc) qc_points_enuc(S, npts, xyz, e_nuc);
     return QC_OK;
 }
 // terms = [dE_nq/dR_c | d tr(P_t V_pc)/dR_c], the second -q_c E_elec(R_c) by the field kernels at the charges
 int qc_point_charge_gradient(qc_system *S, int nspin, const double *D, double *terms) {
-    if (!S || !D || !terms || (nspin != 1 && nspin != 2)) return QC_ERR_INVALID;
-    if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
-    const int64_t npc = (int64_t)(S->pc.size() / 4);
-    if (npc == 0) return QC_OK;
-    int rc = qc_device_init(S);
-    if (rc != QC_OK) return rc;
-    const int n = S->nbasis;
-    const size_t nn = (size_t)n * n;
+    const int64_t npc = S ? (int64_t)(S->pc.size() / 4) : 0;
     DevBuf dD;
-    if (dD.alloc(nspin * nn) != QC_OK) return QC_ERR_HIP;
-    QC_HIP_CHECK(hipMemcpyAsync(dD.p, D, nspin * nn * sizeof(double), hipMemcpyHostToDevice, S->stream));
-    if (nspin == 2) qc_axpby(S->stream, n, 1.0, dD.p, 1.0, dD.p + nn, dD.p);
+    int rc = density_to_device(S, terms != nullptr, npc == 0, nspin, D, dD);
+    if (rc != QC_OK || !dD.p) return rc;
     std::vector<double> xyz(3 * (size_t)npc);
     for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) xyz[3 * c + k] = S->pc[4 * c + k];
     if ((rc = qc_points_field_device(S, dD.p, npc, xyz.data(), terms + 3 * npc, S->pc_ms)) != QC_OK) return rc;

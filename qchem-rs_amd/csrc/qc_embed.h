@@ -23,5 +23,3 @@ int qc_pc_matrix_device(qc_system *S, const std::vector<double> &pc, double *d_o
 // d tr(P_t V_pc)/dR_A at fixed charges from the device density dPt (n*n, P_alpha + P_beta), 3 natoms doubles on the host (basis-function
 // derivatives only); phase times into S->pc_ms
 int qc_pc_atom_gradient_device(qc_system *S, const std::vector<double> &pc, const double *dPt, double *grad);
-// e_elec = -grad v_elec of the device density dD on npts > 0 host points, npts x 3 on the host; phase times into ms[4]
-int qc_points_field_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *e_elec, double *ms);

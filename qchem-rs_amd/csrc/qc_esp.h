@@ -1,8 +1,11 @@
-// qc_esp.h - what the kernels of the potential on points (qc_points.hip) and of the point-charge embedding (qc_embed.hip) share: the
-// compile-time plan of the Hermite-Coulomb table R^0_tuv in registers, the rescaling of the stored expansion blocks to the
-// nuclear-attraction prefactor, the layout of the Hermite records of a density, the phase clock of a call.
+// qc_esp.h - what the kernels of the potential and the field on points (qc_points.hip) and of the point-charge embedding (qc_embed.hip)
+// share: the compile-time plan of the Hermite-Coulomb table R^0_tuv in registers, the dispatch of a run-time table order to its instance,
+// the rescaling of the stored expansion blocks to the nuclear-attraction prefactor, the layout of records grouped by pair order, the
+// Hermite records of a density, the ordered sum of tile sums, the phase clock of a call.
 #pragma once
+#include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "qc_fock_kernel.h"
 #include "qc_md.h"
@@ -60,6 +63,41 @@ __device__ __forceinline__ void esp_table(double p, const double (&X)[3], const 
     esp_rtable<L>(R, seed, X, std::make_integer_sequence<int, qc_rwork(L)>{});
 }
 
+// A run-time order (of a table, a pair or a shell) as a compile-time one: f(std::integral_constant<int, L>) for order == L in
+// 0 .. MAXL - 1; every other order takes the instance of MAXL (the orders the callers can reach end there).  Host launchers and kernels.
+template <int MAXL, int L = 0, class F>
+__host__ __device__ inline void esp_dispatch(int order, F &&f) {
+    if constexpr (L == MAXL) f(std::integral_constant<int, MAXL>{});
+    else if (order == L) f(std::integral_constant<int, L>{});
+    else esp_dispatch<MAXL, L + 1>(order, f);
+}
+
+// Records grouped by the pair order L: add() them pair by pair, then close() with the doubles a record of order L takes.  cnt[L] records,
+// group L begins at record first[L] of the list and at double g.off[L]; nrec / words in all.
+struct EspLayout {
+    int64_t cnt[QC_LPAIR + 1] = {};
+    EspGroups g{};
+    int first[QC_LPAIR + 1] = {}, nrec = 0;
+    size_t words = 0;
+    int add(int L, int K) { const int at = (int)cnt[L]; cnt[L] += K; return at; }      // K more records of order L -> index of the first in its group
+    template <class W> void close(W record_words) {
+        for (int L = 0; L <= QC_LPAIR; ++L) {
+            g.off[L] = (long long)words; words += (size_t)cnt[L] * record_words(L);
+            first[L] = nrec; nrec += (int)cnt[L];
+        }
+    }
+    // the stored primitive pairs of a handle, in list order: -> the first record of every stored shell pair in its group
+    template <class W> std::vector<int> stored_pairs(const qc_system *S, W record_words) {
+        std::vector<int> recstart(S->pairs.size());
+        for (size_t i = 0; i < S->pairs.size(); ++i) recstart[i] = add(S->pairs[i].L, S->pairs[i].K);
+        close(record_words);
+        return recstart;
+    }
+};
+
+// out[i] = ((out[i] + t_0[i]) + t_1[i]) + ..., i < words: the sums of ntiles tiles, `words` doubles each, in ascending order (qc_points.hip)
+void esp_tile_sum(hipStream_t st, size_t words, int ntiles, const double *partial, double *out);
+
 // records of order L per LDS tile (16 KB at the most); a tile is also the unit of the fixed summation order of the potential
 __host__ __device__ constexpr int esp_tile(int L) { return 2048 / (4 + qc_nherm(L)); }
 
@@ -77,12 +115,11 @@ struct PhaseClock {
 };
 
 // The Hermite records of a density on the device (qc_points.hip): per stored primitive pair [p, P(3), -Lambda_h ...], grouped by the pair
-// order L; cnt / ntiles / tile0: records, LDS tiles and first tile of each group.  build: enqueued on the handle's stream and waited for;
+// order L (lay); ntiles / tile0: LDS tiles and first tile of each group.  build: enqueued on the handle's stream and waited for;
 // clk: phases 0 (upload) and 1 (the kernel).
 struct EspRecords {
     DevBuf rec;
-    EspGroups g{};
-    int64_t cnt[QC_LPAIR + 1];
+    EspLayout lay;
     int ntiles[QC_LPAIR + 1], tile0[QC_LPAIR + 1], tiles_all = 0;
     int build(qc_system *S, const double *dD, PhaseClock &clk);
 };

@@ -44,11 +44,6 @@ constexpr HermTab make_htab() {
 }
 __constant__ HermTab c_htab = make_htab();
 
-__device__ inline double wave_sum(double v) {        // fixed butterfly: every lane ends with the same, order-independent value
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- density transform ---------------------------------------------------------------------------------------------------------
 // dst[m][i][j] (nc x nc, Cartesian) = sum_{f,g} T_A[f][x] src[m][offA + f][offB + g] T_B[g][y] for Cartesian i = coffA + x, j = coffB + y
 __global__ __launch_bounds__(256) void cart_transform_kernel(int n, int nc, const QcDevShell *__restrict__ sh, const int *__restrict__ cshell,
@@ -102,9 +97,8 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const QcDevSh
     __syncthreads();
     const int npairs = nshells * (nshells + 1) / 2;
     for (int pr = blockIdx.x; pr < npairs; pr += gridDim.x) {
-        int a = 0, rem = pr;
-        while (rem > a) { rem -= a + 1; ++a; }
-        const int b = rem;
+        int a, b;
+        qc_tri_pair(pr, a, b);
         const QcDevShell A = sh[a], B = sh[b];
         const double f = a == b ? 1.0 : 2.0;
         const int npp = A.nprim * B.nprim;
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const QcDevSh
                 }
             }
         }
-        for (int k = 0; k < 3; ++k) { sA[k] = wave_sum(sA[k]); tA[k] = wave_sum(tA[k]); }
+        for (int k = 0; k < 3; ++k) { sA[k] = qc_wave_sum(sA[k]); tA[k] = qc_wave_sum(tA[k]); }
         if (lane == 0)
             for (int k = 0; k < 3; ++k) {
                 row[3 * A.atom + k] += f * tA[k]; row[3 * B.atom + k] -= f * tA[k];
@@ -159,30 +153,9 @@ __global__ __launch_bounds__(64) void qc_grad1_kernel(int nshells, const QcDevSh
                     Rn[0] = pow(-2.0 * p, n) * F[n];          // (the seeds: pow here, see qc_md.h)
                     for (int h = 1; h < qc_nherm(L - n); ++h) Rn[h] = qc_md_r_step(Rn1, c_htab.t[h], c_htab.u[h], c_htab.v[h], PC);
                 }
-                const double *R = Rb[0];
-                for (int x = 0; x < A.ncart; ++x) {
-                    const unsigned char *ax = qc_md_cart(A.L, x);
-                    for (int y = 0; y < B.ncart; ++y) {
-                        const unsigned char *by = qc_md_cart(B.L, y);
-                        const double pv = cc * Pc[(size_t)(A.coff + x) * nc + B.coff + y];
-                        for (int k = 0; k < 3; ++k) {
-                            int ai[3] = {ax[0], ax[1], ax[2]}, bi[3] = {by[0], by[1], by[2]};
-                            ++ai[k];
-                            double dA = 2.0 * ea * qc_md_nuc(E, ai, bi, R);
-                            ai[k] -= 2;
-                            if (ax[k]) dA -= ax[k] * qc_md_nuc(E, ai, bi, R);
-                            ai[k] += 1;
-                            ++bi[k];
-                            double dB = 2.0 * eb * qc_md_nuc(E, ai, bi, R);
-                            bi[k] -= 2;
-                            if (by[k]) dB -= by[k] * qc_md_nuc(E, ai, bi, R);
-                            vA[k] += pv * dA;
-                            vB[k] += pv * dB;
-                        }
-                    }
-                }
+                qc_md_nuc_grad(E, A.L, A.ncart, B.L, B.ncart, ea, eb, Rb[0], cc, Pc + (size_t)A.coff * nc + B.coff, nc, vA, vB);
             }
-            for (int k = 0; k < 3; ++k) { vA[k] = wave_sum(vA[k]); vB[k] = wave_sum(vB[k]); }
+            for (int k = 0; k < 3; ++k) { vA[k] = qc_wave_sum(vA[k]); vB[k] = qc_wave_sum(vB[k]); }
             if (lane == 0)
                 for (int k = 0; k < 3; ++k) {
                     row[3 * A.atom + k] += f * vA[k];
@@ -319,7 +292,7 @@ __global__ __launch_bounds__(64) void qc_grad2_kernel(const GTask *__restrict__ 
                 __syncthreads();
             }
         }
-        for (int x = 0; x < 9; ++x) acc[x] = wave_sum(acc[x]);
+        for (int x = 0; x < 9; ++x) acc[x] = qc_wave_sum(acc[x]);
         if (lane == 0) {
             // degeneracy of the unique quartet (pair A>=B, pair C>=D, bra pair vs ket pair) x the 1/2 of the energy expression
             const bool bra_eq_ket = (tk.sa == tk.sc && tk.sb == tk.sd) || (tk.sa == tk.sd && tk.sb == tk.sc);

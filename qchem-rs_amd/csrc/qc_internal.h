@@ -413,6 +413,8 @@ int qc_polarizability_device(qc_system *S, bool uhf, const int *nocc, const doub
 int qc_points_density_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *rho);
 int qc_points_orbitals_device(qc_system *S, int m, const double *dC, int ldc, int64_t npts, const double *xyz, double *out);
 int qc_points_esp_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *v_elec);
+// e_elec = -grad v_elec of the device density dD on npts > 0 host points, npts x 3 on the host; phase times into ms[4]
+int qc_points_field_device(qc_system *S, const double *dD, int64_t npts, const double *xyz, double *e_elec, double *ms);
 void qc_points_vnuc(const qc_system *S, int64_t npts, const double *xyz, double *v);
 void qc_esp_record_counts(const qc_system *S, int64_t counts[QC_LPAIR + 1]);
 int qc_launch_fock_classes(qc_system *S, const QcFockArgs &a, float *class_ms /*nullable*/, float *unit_ms = nullptr /*nullable, 14*/, bool nofork = false);

@@ -166,3 +166,45 @@ template <class E1> __host__ __device__ inline double qc_md_nuc(const E1 *E, con
             for (int v = 0; v <= a[2] + b[2]; ++v) acc += E[0].g(a[0], b[0], t) * E[1].g(a[1], b[1], u) * E[2].g(a[2], b[2], v) * R[qc_hidx(t, u, v)];
     return acc;
 }
+
+// ---- what the gradient kernels of the nuclear attraction share (qc_grad1_kernel: R of one nucleus; qc_pc_grad_kernel: Lambda, the sum over
+// the point charges).  For every Cartesian pair (x | y) of a shell pair and every axis k, d/dA_k and d/dB_k of its integral by the Gaussian
+// rule - E filled to la + 1, lb + 1, R of order la + lb + 1 - weighted with cc P[x * ldp + y]:  vA[k] += pv dA,  vB[k] += pv dB.
+template <class E1>
+__device__ __forceinline__ void qc_md_nuc_grad(const E1 *E, int la, int nca, int lb, int ncb, double ea, double eb, const double *R, double cc,
+                                               const double *P, int ldp, double (&vA)[3], double (&vB)[3]) {
+    for (int x = 0; x < nca; ++x) {
+        const unsigned char *ax = qc_md_cart(la, x);
+        for (int y = 0; y < ncb; ++y) {
+            const unsigned char *by = qc_md_cart(lb, y);
+            const double pv = cc * P[(size_t)x * ldp + y];
+            for (int k = 0; k < 3; ++k) {
+                int ai[3] = {ax[0], ax[1], ax[2]}, bi[3] = {by[0], by[1], by[2]};
+                ++ai[k];
+                double dA = 2.0 * ea * qc_md_nuc(E, ai, bi, R);
+                ai[k] -= 2;
+                if (ax[k]) dA -= ax[k] * qc_md_nuc(E, ai, bi, R);
+                ai[k] += 1;
+                ++bi[k];
+                double dB = 2.0 * eb * qc_md_nuc(E, ai, bi, R);
+                bi[k] -= 2;
+                if (by[k]) dB -= by[k] * qc_md_nuc(E, ai, bi, R);
+                vA[k] += pv * dA;
+                vB[k] += pv * dB;
+            }
+        }
+    }
+}
+#ifdef __HIPCC__                                     // (the host tests compile this header with a plain C++ compiler)
+// sum over the lanes of a wave by a fixed butterfly: every lane ends with the same, order-independent value
+__device__ inline double qc_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+#endif
+// shell pair pr = a (a + 1) / 2 + b of the triangle a >= b
+__host__ __device__ inline void qc_tri_pair(int pr, int &a, int &b) {
+    a = 0;
+    while (pr > a) { pr -= a + 1; ++a; }
+    b = pr;
+}

@@ -1011,20 +1011,25 @@ int qc_scf_esp_charges(qc_scf_state *st, qc_esp_fit *io, int64_t npts, const dou
 }
 // ---- values on points from the state's own densities and orbitals (qc_points.hip): they are read where they lie on the device; no Fock
 // build runs and nothing of the state or of a prepared build is written, so a following qc_scf_iterate is unchanged.
+// The state's density P_alpha + w P_beta on the device: the RHF pointer where it lies (its density is the total one), or the UHF sum,
+// enqueued on the handle's stream, in `sum`.  Null: the allocation failed.
+static const double *state_density(qc_scf_state *st, double w, DevBuf &sum) {
+    if (!st->uhf) return st->D[0].p;
+    qc_system *S = st->S;
+    if (sum.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return nullptr;
+    qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, w, st->D[1].p, sum.p);
+    return sum.p;
+}
 // which 0: P_alpha + P_beta, 1: P_alpha - P_beta (an RHF state: exactly zero, nothing is launched)
 int qc_scf_density_on_points(qc_scf_state *st, int which, int64_t npts, const double *xyz, double *rho) {
     if (!st || !xyz || !rho || npts < 0 || which < 0 || which > 1) return QC_ERR_INVALID;
     qc_system *S = st->S;
     if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
     if (npts == 0) return QC_OK;
-    if (!st->uhf) {
-        if (which == 1) { std::fill(rho, rho + npts, 0.0); return QC_OK; }
-        return qc_points_density_device(S, st->D[0].p, npts, xyz, rho);
-    }
-    DevBuf P;
-    if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
-    qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, which ? -1.0 : 1.0, st->D[1].p, P.p);
-    return qc_points_density_device(S, P.p, npts, xyz, rho);
+    if (!st->uhf && which == 1) { std::fill(rho, rho + npts, 0.0); return QC_OK; }
+    DevBuf sum;
+    const double *P = state_density(st, which ? -1.0 : 1.0, sum);
+    return P ? qc_points_density_device(S, P, npts, xyz, rho) : QC_ERR_HIP;
 }
 // v_total = v_nuc + v_elec of P_alpha + P_beta; the nuclear part on the host, as in qc_scf_dipole
 int qc_scf_esp_on_points(qc_scf_state *st, int64_t npts, const double *xyz, double *v_total, double *v_elec) {
@@ -1032,13 +1037,11 @@ int qc_scf_esp_on_points(qc_scf_state *st, int64_t npts, const double *xyz, doub
     qc_system *S = st->S;
     if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
     if (npts == 0) return QC_OK;
-    DevBuf P;
-    if (st->uhf) {
-        if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
-        qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, 1.0, st->D[1].p, P.p);
-    }
+    DevBuf sum;
+    const double *P = state_density(st, 1.0, sum);
+    if (!P) return QC_ERR_HIP;
     std::vector<double> ve(npts);
-    const int rc = qc_points_esp_device(S, st->uhf ? P.p : st->D[0].p, npts, xyz, ve.data());
+    const int rc = qc_points_esp_device(S, P, npts, xyz, ve.data());
     if (rc != QC_OK) return rc;
     qc_points_vnuc(S, npts, xyz, v_total);
     for (int64_t k = 0; k < npts; ++k) { v_total[k] += ve[k]; if (v_elec) v_elec[k] = ve[k]; }
@@ -1050,13 +1053,11 @@ int qc_scf_field_on_points(qc_scf_state *st, int64_t npts, const double *xyz, do
     qc_system *S = st->S;
     if (S->comm || S->nranks != 1) return QC_ERR_UNSUPPORTED;
     if (npts == 0) return QC_OK;
-    DevBuf P;
-    if (st->uhf) {
-        if (P.alloc((size_t)S->nbasis * S->nbasis) != QC_OK) return QC_ERR_HIP;
-        qc_axpby(S->stream, S->nbasis, 1.0, st->D[0].p, 1.0, st->D[1].p, P.p);
-    }
+    DevBuf sum;
+    const double *P = state_density(st, 1.0, sum);
+    if (!P) return QC_ERR_HIP;
     std::vector<double> ee(3 * (size_t)npts);
-    const int rc = qc_points_field_device(S, st->uhf ? P.p : st->D[0].p, npts, xyz, ee.data(), S->points_ms);
+    const int rc = qc_points_field_device(S, P, npts, xyz, ee.data(), S->points_ms);
     if (rc != QC_OK) return rc;
     qc_points_enuc(S, npts, xyz, e_total);
     for (int64_t k = 0; k < 3 * npts; ++k) { e_total[k] += ee[k]; if (e_elec) e_elec[k] = ee[k]; }

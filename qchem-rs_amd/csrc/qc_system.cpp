@@ -470,42 +470,56 @@ void qc_host_basis_on_points(const qc_system *S, int64_t npts, const double *xyz
         }
 }
 
-// ---- the potential of a unit point charge at r in the basis: out_ab = (a| 1/|r' - r| |b), positive - the nuclear-attraction sum of
-// qc_host_one_electron for one centre without its -Z; exactly symmetric (diagonal blocks: one triangle, mirrored)
-void qc_host_potential_matrix(const qc_system *S, const double *r, double *out) {
+// ---- matrices of Coulomb operators in the basis, one skeleton: NM matrices out[m] (n x n each) at once, element ab of matrix m
+//   sign sum_prim c_a c_b 2 pi / p sum_tuv E^ab_tuv R^m_tuv,
+// the nuclear-attraction sum of qc_host_one_electron with the tables R^m (order la + lb, indexed by qc_hidx) that `tables(L, p, P, R)` fills
+// for the primitive pair of exponent p at P.  Per shell pair a >= b: the Cartesian block over the primitive pairs in list order, then the
+// Cartesian -> pure transform; exactly symmetric (diagonal blocks: one triangle, mirrored).
+template <int NM, class Tables>
+static void host_coulomb_matrices(const qc_system *S, double sign, double *out, Tables tables) {
     const int n = S->nbasis;
-    std::fill(out, out + (size_t)n * n, 0.0);
-    std::vector<double> R0;
+    const size_t nn = (size_t)n * n;
+    std::fill(out, out + NM * nn, 0.0);
+    std::vector<double> R[NM];
     for (int a = 0; a < S->nshells; ++a)
         for (int b = 0; b <= a; ++b) {
             const QcShell &A = S->shells[a], &B = S->shells[b];
             const size_t nca = A.ncart, ncb = B.ncart;
-            std::vector<double> cart(nca * ncb, 0.0);
+            std::vector<double> cart(NM * nca * ncb, 0.0);
             for (int i = 0; i < A.nprim; ++i)
                 for (int j = 0; j < B.nprim; ++j) {
                     const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
-                    double PC[3];
-                    for (int k = 0; k < 3; ++k) PC[k] = (ea * A.A[k] + eb * B.A[k]) / p - r[k];
+                    double P[3];
+                    for (int k = 0; k < 3; ++k) P[k] = (ea * A.A[k] + eb * B.A[k]) / p;
                     E1 E[3];
                     for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
-                    hermite_r_host(A.L + B.L, p, PC, R0);
+                    tables(A.L + B.L, p, P, R);
                     for (size_t x = 0; x < nca; ++x)
                         for (size_t y = 0; y < ncb; ++y) {
                             const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
                             const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
-                            cart[x * ncb + y] += cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, R0.data()));
+                            for (int m = 0; m < NM; ++m) cart[(m * nca + x) * ncb + y] += sign * (cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, R[m].data())));
                         }
                 }
-            for (int fa = 0; fa < A.nfunc; ++fa)
-                for (int fb = 0; fb < B.nfunc; ++fb) {
-                    if (a == b && fb > fa) continue;
-                    double v = 0.0;
-                    for (size_t x = 0; x < nca; ++x)
-                        for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * ncb + y];
-                    out[(size_t)(A.off + fa) * n + B.off + fb] = v;
-                    out[(size_t)(B.off + fb) * n + A.off + fa] = v;
-                }
+            for (int m = 0; m < NM; ++m)
+                for (int fa = 0; fa < A.nfunc; ++fa)
+                    for (int fb = 0; fb < B.nfunc; ++fb) {
+                        if (a == b && fb > fa) continue;
+                        double v = 0.0;
+                        for (size_t x = 0; x < nca; ++x)
+                            for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[(m * nca + x) * ncb + y];
+                        out[m * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
+                        out[m * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
+                    }
         }
+}
+
+// the potential of a unit point charge at r in the basis: out_ab = (a| 1/|r' - r| |b), positive - one centre without its -Z
+void qc_host_potential_matrix(const qc_system *S, const double *r, double *out) {
+    host_coulomb_matrices<1>(S, 1.0, out, [r](int L, double p, const double *P, std::vector<double> *R) {
+        const double PC[3] = {P[0] - r[0], P[1] - r[1], P[2] - r[2]};
+        hermite_r_host(L, p, PC, R[0]);
+    });
 }
 
 // ---- point-charge embedding on the host (qc_embed.h): the reference statements of what qc_embed.hip computes
@@ -533,96 +547,36 @@ void qc_pc_nuclear_gradient(const qc_system *S, const std::vector<double> &pc, d
         }
 }
 
-// V_pc = -sum_c q_c A(R_c): the nuclear-attraction sum of qc_host_one_electron with the charges as centres - per primitive pair the
-// Hermite-Coulomb tables of all charges summed first, then one contraction; exactly symmetric (diagonal blocks: one triangle, mirrored)
+// V_pc = -sum_c q_c A(R_c): the charges as centres - per primitive pair the Hermite-Coulomb tables of all charges summed first, in list
+// order, then one contraction
 void qc_host_point_charge_matrix(const qc_system *S, const std::vector<double> &pc, double *out) {
-    const int n = S->nbasis;
-    std::fill(out, out + (size_t)n * n, 0.0);
-    std::vector<double> R0, Rs;
-    for (int a = 0; a < S->nshells; ++a)
-        for (int b = 0; b <= a; ++b) {
-            const QcShell &A = S->shells[a], &B = S->shells[b];
-            const size_t nca = A.ncart, ncb = B.ncart;
-            std::vector<double> cart(nca * ncb, 0.0);
-            for (int i = 0; i < A.nprim; ++i)
-                for (int j = 0; j < B.nprim; ++j) {
-                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
-                    double P[3];
-                    for (int k = 0; k < 3; ++k) P[k] = (ea * A.A[k] + eb * B.A[k]) / p;
-                    E1 E[3];
-                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
-                    Rs.assign(qc_nherm(A.L + B.L), 0.0);
-                    for (size_t c = 0; c < pc.size() / 4; ++c) {
-                        const double PC[3] = {P[0] - pc[4 * c], P[1] - pc[4 * c + 1], P[2] - pc[4 * c + 2]};
-                        hermite_r_host(A.L + B.L, p, PC, R0);
-                        for (size_t h = 0; h < Rs.size(); ++h) Rs[h] += pc[4 * c + 3] * R0[h];
-                    }
-                    for (size_t x = 0; x < nca; ++x)
-                        for (size_t y = 0; y < ncb; ++y) {
-                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
-                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
-                            cart[x * ncb + y] -= cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, Rs.data()));
-                        }
-                }
-            for (int fa = 0; fa < A.nfunc; ++fa)
-                for (int fb = 0; fb < B.nfunc; ++fb) {
-                    if (a == b && fb > fa) continue;
-                    double v = 0.0;
-                    for (size_t x = 0; x < nca; ++x)
-                        for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[x * ncb + y];
-                    out[(size_t)(A.off + fa) * n + B.off + fb] = v;
-                    out[(size_t)(B.off + fb) * n + A.off + fa] = v;
-                }
+    std::vector<double> R0;
+    host_coulomb_matrices<1>(S, -1.0, out, [&](int L, double p, const double *P, std::vector<double> *R) {
+        R[0].assign(qc_nherm(L), 0.0);
+        for (size_t c = 0; c < pc.size() / 4; ++c) {
+            const double PC[3] = {P[0] - pc[4 * c], P[1] - pc[4 * c + 1], P[2] - pc[4 * c + 2]};
+            hermite_r_host(L, p, PC, R0);
+            for (size_t h = 0; h < R[0].size(); ++h) R[0][h] += pc[4 * c + 3] * R0[h];
         }
+    });
 }
 
 // B^k_ab = dA_ab(r)/dr_k, k = x, y, z: qc_host_potential_matrix with the table of order L + 1 shifted by one unit along k,
-// d/dr_x R_tuv(P - r) = -R_{t+1,u,v}; exactly symmetric
+// d/dr_x R_tuv(P - r) = -R_{t+1,u,v}
 void qc_host_field_matrix(const qc_system *S, const double *r, double *out) {
-    const int n = S->nbasis;
-    const size_t nn = (size_t)n * n;
-    std::fill(out, out + 3 * nn, 0.0);
-    std::vector<double> R0, Rk[3];
-    for (int a = 0; a < S->nshells; ++a)
-        for (int b = 0; b <= a; ++b) {
-            const QcShell &A = S->shells[a], &B = S->shells[b];
-            const size_t nca = A.ncart, ncb = B.ncart;
-            const int L = A.L + B.L;
-            std::vector<double> cart(3 * nca * ncb, 0.0);
-            for (int i = 0; i < A.nprim; ++i)
-                for (int j = 0; j < B.nprim; ++j) {
-                    const double ea = A.exps[i], eb = B.exps[j], p = ea + eb, cc = A.coefs[i] * B.coefs[j];
-                    double PC[3];
-                    for (int k = 0; k < 3; ++k) PC[k] = (ea * A.A[k] + eb * B.A[k]) / p - r[k];
-                    E1 E[3];
-                    for (int k = 0; k < 3; ++k) E[k].fill(A.L, B.L, ea, eb, A.A[k] - B.A[k]);
-                    hermite_r_host(L + 1, p, PC, R0);
-                    for (int k = 0; k < 3; ++k) Rk[k].assign(qc_nherm(L), 0.0);
-                    for (int t = 0; t <= L; ++t)
-                        for (int u = 0; t + u <= L; ++u)
-                            for (int v = 0; t + u + v <= L; ++v) {
-                                Rk[0][qc_hidx(t, u, v)] = -R0[qc_hidx(t + 1, u, v)];
-                                Rk[1][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u + 1, v)];
-                                Rk[2][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u, v + 1)];
-                            }
-                    for (size_t x = 0; x < nca; ++x)
-                        for (size_t y = 0; y < ncb; ++y) {
-                            const unsigned char *ca = qc_md_cart(A.L, (int)x), *cb = qc_md_cart(B.L, (int)y);
-                            const int ai[3] = {ca[0], ca[1], ca[2]}, bi[3] = {cb[0], cb[1], cb[2]};
-                            for (int k = 0; k < 3; ++k) cart[(k * nca + x) * ncb + y] += cc * (2.0 * M_PI / p * qc_md_nuc(E, ai, bi, Rk[k].data()));
-                        }
+    std::vector<double> R0;
+    host_coulomb_matrices<3>(S, 1.0, out, [&](int L, double p, const double *P, std::vector<double> *R) {
+        const double PC[3] = {P[0] - r[0], P[1] - r[1], P[2] - r[2]};
+        hermite_r_host(L + 1, p, PC, R0);
+        for (int k = 0; k < 3; ++k) R[k].assign(qc_nherm(L), 0.0);
+        for (int t = 0; t <= L; ++t)
+            for (int u = 0; t + u <= L; ++u)
+                for (int v = 0; t + u + v <= L; ++v) {
+                    R[0][qc_hidx(t, u, v)] = -R0[qc_hidx(t + 1, u, v)];
+                    R[1][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u + 1, v)];
+                    R[2][qc_hidx(t, u, v)] = -R0[qc_hidx(t, u, v + 1)];
                 }
-            for (int k = 0; k < 3; ++k)
-                for (int fa = 0; fa < A.nfunc; ++fa)
-                    for (int fb = 0; fb < B.nfunc; ++fb) {
-                        if (a == b && fb > fa) continue;
-                        double v = 0.0;
-                        for (size_t x = 0; x < nca; ++x)
-                            for (size_t y = 0; y < ncb; ++y) v += A.T[(size_t)fa * A.ncart + x] * B.T[(size_t)fb * B.ncart + y] * cart[(k * nca + x) * ncb + y];
-                        out[k * nn + (size_t)(A.off + fa) * n + B.off + fb] = v;
-                        out[k * nn + (size_t)(B.off + fb) * n + A.off + fa] = v;
-                    }
-        }
+    });
 }
 
 void qc_points_enuc(const qc_system *S, int64_t npts, const double *xyz, double *e) {

@@ -123,6 +123,21 @@ def test_field_matches_the_host_field_matrix_and_numpy(name):
     # up to 4096 points the record list is spread over workgroups and the tiles' sums are added in a second pass (all calls above);
     # larger batches walk the list in one workgroup per 256 points: the same bits
     assert np.array_equal(s.field_on_points(D, np.tile(P, (14, 1)), parts=True)[1], np.tile(c["ee"], (14, 1)))
+    # The field batches and splits by the potential's rule (test_points_gpu): QC_POINTS_SPLIT=0 forces the walk, QC_POINTS_BATCH=64 forces
+    # five batches, each transposed from component-major to point-major on its own (the switches are read by a handle at its first point
+    # call): the same bits every way.
+    import qchem_rs_amd as q
+    for env in ({}, {"QC_POINTS_SPLIT": "0"}, {"QC_POINTS_BATCH": "64"}, {"QC_POINTS_BATCH": "64", "QC_POINTS_SPLIT": "0"},
+                {"QC_POINTS_BATCH": "256", "QC_POINTS_SPLIT": "100"}):
+        os.environ.update(env)
+        try:
+            h = q.System(m)
+            got = h.field_on_points(D, P, parts=True)[1]
+            h.close()
+        finally:
+            for key in env:
+                del os.environ[key]
+        assert np.array_equal(got, c["ee"]), env
 
 
 def _four(s, D, C):
