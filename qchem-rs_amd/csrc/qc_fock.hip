@@ -39,46 +39,44 @@ static Seg seg_of(const QcClass &c) {
 
 void qc_drop_launch_plan(qc_system *S) { delete S->launch_plan; S->launch_plan = nullptr; }
 
-static int launch_segments(qc_system *S, int unit, const std::vector<Seg> &segs, hipStream_t st, const QcKernelArgs &base) {
-    if (unit >= 2 * (QC_LPAIR + 1)) {      // bra-major launch
-        QcBmArgs t{};
-        t.base = base; t.pairdataT = S->dev.d_pairdataT.p; t.pspack = S->dev.d_pspack.p;
-        t.base.tl = S->tl.cur ? S->tl.cur + QC_TL_W * unit : nullptr;
-        const int v = unit - 2 * (QC_LPAIR + 1);
-        const int lds_max = 160 * 1024 - 512;
-        int nw = qc_bm_waves(v / 2, v % 2), iblock = 0, rows = 0;
-        for (const Seg &sg : segs) { iblock = std::max(iblock, sg.lds); rows = std::max(rows, sg.c->bm_rows); }
-        // exchange rows of a wave's current bra in LDS: (na + nb) rows x n columns per spin
-        const int rowbytes = (base.Dk1 ? 2 : 1) * rows * S->nbasis * 8;
-        // (QC_BM_NO_ROWBUF forces the large-n fallback - direct global atomics per bundle - so that tests can reach it)
-        t.use_rowbuf = (base.eri_out == nullptr && base.schwarz_out == nullptr && QC_BM_LDS_TABLE + 2 * (iblock + rowbytes) <= lds_max && S->ds_order_ok && !getenv("QC_BM_NO_ROWBUF")) ? 1 : 0;
-        const int wbytes = iblock + (t.use_rowbuf ? rowbytes : 0);
-        while (nw > 1 && QC_BM_LDS_TABLE + nw * wbytes > lds_max) nw = nw > 4 ? nw - 1 : nw / 2;   // Cartesian d / f bras: 36+ rows of I per wave
-        {   // (QC_BM_NW: experiment switch - at most that many waves per workgroup, so that two workgroups of different launches fit a CU's LDS)
-            static const int nw_env = getenv("QC_BM_NW") ? atoi(getenv("QC_BM_NW")) : 0;
-            if (nw_env > 0) nw = std::min(nw, nw_env);
-        }
-        int grid = 0, k = 0;
-        for (const Seg &sg : segs) {
-            // persistent workgroups of `nw` waves: at most ~12 waves per CU, each wave strides through the bundle list
-            static const int capw = getenv("QC_BM_WAVES_PER_CU") ? std::max(4, atoi(getenv("QC_BM_WAVES_PER_CU"))) : 12;   // (A/B switch)
-            grid += std::min((sg.nslots + nw - 1) / nw, 256 * capw / nw);
-            t.seg_end[k] = grid; t.seg_lab[k] = sg.c->LAB; t.seg_lcd[k] = sg.c->LCD; t.seg_bundles[k] = sg.d_bundles; t.seg_ketlist[k] = sg.d_ketlist;
-            t.seg_nbundles[k] = sg.nslots; t.seg_iwords[k] = sg.lds / 8;
-            t.seg_rows[k] = rows;
-            ++k;
-        }
-        t.nseg = k;
-        const int lds = QC_BM_LDS_TABLE + nw * wbytes;
-        static const bool lds_dbg = getenv("QC_LDS_DEBUG") != nullptr;
-        if (lds_dbg) fprintf(stderr, "[lds] bm<%d,%d>: %d workgroups x %d waves, %d bytes of LDS per workgroup (table %d, per wave %d)\n", v / 2, v % 2, grid, nw, lds, QC_BM_LDS_TABLE, wbytes);
-        {   // ss-ket segments in the launch of the ps kets / low bras: the merged kernel
-            bool mixed = false;
-            for (const Seg &sg : segs) mixed = mixed || sg.c->LCD != v / 2;
-            if (mixed) return (v == 2 && k <= QC_MAXSEG) ? qc_launch_bm(3, 0, grid, nw, (size_t)lds, st, t) : QC_ERR_UNSUPPORTED;
-        }
-        return qc_launch_bm(v / 2, v % 2, grid, nw, (size_t)lds, st, t);
+// One launch of the bra-major kernels: workgroups of up to QC_BM_WAVES waves, as many as the LDS blocks of the segments allow
+static int launch_bm_segments(qc_system *S, int unit, const std::vector<Seg> &segs, hipStream_t st, const QcKernelArgs &base) {
+    QcBmArgs t{};
+    t.base = base; t.pairdataT = S->dev.d_pairdataT.p; t.pspack = S->dev.d_pspack.p;
+    t.base.tl = S->tl.cur ? S->tl.cur + QC_TL_W * unit : nullptr;
+    const int v = unit - 2 * (QC_LPAIR + 1);
+    const int lds_max = 160 * 1024 - 512;
+    int nw = QC_BM_WAVES, iblock = 0, rows = 0;
+    for (const Seg &sg : segs) { iblock = std::max(iblock, sg.lds); rows = std::max(rows, sg.c->bm_rows); }
+    // exchange rows of a wave's current bra in LDS: (na + nb) rows x n columns per spin
+    const int rowbytes = (base.Dk1 ? 2 : 1) * rows * S->nbasis * 8;
+    // (QC_BM_NO_ROWBUF forces the large-n fallback - direct global atomics per bundle - so that tests can reach it)
+    t.use_rowbuf = (base.eri_out == nullptr && base.schwarz_out == nullptr && QC_BM_LDS_TABLE + 2 * (iblock + rowbytes) <= lds_max && S->ds_order_ok && !getenv("QC_BM_NO_ROWBUF")) ? 1 : 0;
+    const int wbytes = iblock + (t.use_rowbuf ? rowbytes : 0);
+    while (nw > 1 && QC_BM_LDS_TABLE + nw * wbytes > lds_max) nw = nw > 4 ? nw - 1 : nw / 2;   // Cartesian d / f bras: 36+ rows of I per wave
+    int grid = 0, k = 0;
+    for (const Seg &sg : segs) {
+        // persistent workgroups of `nw` waves: at most ~12 waves per CU, each wave strides through the bundle list
+        grid += std::min((sg.nslots + nw - 1) / nw, 256 * 12 / nw);
+        t.seg_end[k] = grid; t.seg_lab[k] = sg.c->LAB; t.seg_lcd[k] = sg.c->LCD; t.seg_bundles[k] = sg.d_bundles; t.seg_ketlist[k] = sg.d_ketlist;
+        t.seg_nbundles[k] = sg.nslots; t.seg_iwords[k] = sg.lds / 8;
+        t.seg_rows[k] = rows;
+        ++k;
     }
+    t.nseg = k;
+    const int lds = QC_BM_LDS_TABLE + nw * wbytes;
+    static const bool lds_dbg = getenv("QC_LDS_DEBUG") != nullptr;
+    if (lds_dbg) fprintf(stderr, "[lds] bm<%d,%d>: %d workgroups x %d waves, %d bytes of LDS per workgroup (table %d, per wave %d)\n", v / 2, v % 2, grid, nw, lds, QC_BM_LDS_TABLE, wbytes);
+    {   // ss-ket segments in the launch of the ps kets / low bras: the merged kernel
+        bool mixed = false;
+        for (const Seg &sg : segs) mixed = mixed || sg.c->LCD != v / 2;
+        if (mixed) return (v == 2 && k <= QC_MAXSEG) ? qc_launch_bm(3, 0, grid, nw, (size_t)lds, st, t) : QC_ERR_UNSUPPORTED;
+    }
+    return qc_launch_bm(v / 2, v % 2, grid, nw, (size_t)lds, st, t);
+}
+
+// One launch of the column kernels: one-wave workgroups, every segment with the largest segment's LDS
+static int launch_column_segments(qc_system *S, int unit, const std::vector<Seg> &segs, hipStream_t st, const QcKernelArgs &base) {
     QcTierArgs t{};
     t.base = base;
     t.base.tl = S->tl.cur ? S->tl.cur + QC_TL_W * unit : nullptr;
@@ -125,6 +123,10 @@ static int launch_segments(qc_system *S, int unit, const std::vector<Seg> &segs,
         fprintf(stderr, "\n");
     }
     return launch_tier(unit / 2, tier, grid, (size_t)lds, st, t);
+}
+
+static int launch_segments(qc_system *S, int unit, const std::vector<Seg> &segs, hipStream_t st, const QcKernelArgs &base) {
+    return unit >= 2 * (QC_LPAIR + 1) ? launch_bm_segments(S, unit, segs, st, base) : launch_column_segments(S, unit, segs, st, base);
 }
 
 // Launch units of one build: per bra class LAB, tier 0 (LCD <= 3) and tier 1 (LCD >= 4) of the column kernels, plus

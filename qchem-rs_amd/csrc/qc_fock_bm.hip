@@ -23,27 +23,12 @@
 // coefficients and exp(-x_k)): with one quartet per lane every table access is a 64-address gather, and the texture path
 // - not the VALU - was what these kernels waited for when the rows came from global memory (rocprofv3: 60 % of the
 // wave-cycles waiting to issue).  Same evaluation as qc_boys<L>.
-// f64 add into LDS through the DS unit (a generic pointer would make it a flat atomic)
-typedef __attribute__((address_space(3))) double qc_lds_double;
-// (the row buffer belongs to one wave and every add to it is an instruction of that wave: the DS unit serves the lanes of an
-// instruction in a fixed order, so these sums do not depend on timing - f64 is fine here in the fixed-point mode too)
-__device__ __forceinline__ void qc_lds_add(double *p, double v) { (void)__builtin_amdgcn_ds_atomic_fadd_f64((qc_lds_double *)p, v); }
 // Wave-uniform reads of the bra's pair data go through the scalar unit: a pointer taken from the kernel's argument struct carries no
 // no-alias information, so the compiler reads `pd[uniform]` with a 64-lane vector load per two values (10 loads and a full memory
 // latency per row of step 3); the same address in the constant address space is an s_load.  (The pair data are written by the host
 // before any launch.)
 typedef const __attribute__((address_space(4))) double qc_cdouble;
 
-// -DQC_BM_TIMING (tools/build_variant_lib.sh): wave 0 of the first workgroups of a segment prints where its time went (10 ns units)
-#ifdef QC_BM_TIMING
-#define QC_BT(i) do { const long long t_ = wall_clock64(); tph[i] += t_ - tlast; tlast = t_; } while (0)
-#define QC_BT_ARGS , long long *tph, long long &tlast
-#define QC_BT_PASS , tph, tlast
-#else
-#define QC_BT(i) do {} while (0)
-#define QC_BT_ARGS
-#define QC_BT_PASS
-#endif
 constexpr int QC_BM_TROW = 9;
 constexpr int QC_BM_TWORDS = QC_BOYS_NGRID * QC_BM_TROW;
 
@@ -122,170 +107,175 @@ __device__ __forceinline__ void qc_step2_pp(double (&W)[3][qc_nherm(LAB)], const
     }
 }
 
-// One pass over the ket primitives for NIJ consecutive bra primitive pairs (NIJ = 2 shares every ket load between two
-// primitive quartets), followed by step 3 with the wave-uniform bra blocks.
-// Latencies a pass used to expose, and what hides them now (round 3; with ket chunks of <= 8 primitives a pass is only ~16 primitive
-// quartets long, so they were a third to a half of a wave's life): the bra headers of the NEXT pass are requested before the
-// primitive loop (`hd` carries them from pass to pass); the first ket record is loaded once per bundle (`hk0`, `ek0`); the rows of
-// step 3 come in pieces of QC_BM_PIECE scalars, each requested while the previous one is being used.
-constexpr int QC_BM_PIECE = 10;
-#ifndef QC_BM_AHEAD
-#define QC_BM_AHEAD 1
-#endif
-template <int LAB, int LCD, int NIJ, int CAX = 0>
-__device__ __forceinline__ void qc_bm_pass(const double *__restrict__ pd, const double *__restrict__ pdT, const double *__restrict__ Tb,
-                                           const int bdoff, const int strideB, const int ij, const int ij_last, const int nab,
-                                           const double *__restrict__ ketBase, const double4 hk0, const double4 ek0, const double4 ek0b, const double4 ek0c,
-                                           const int K_cd, const int Kc1, const int maxK, double *const I, double (&hd)[2][4] QC_BT_ARGS) {
-    constexpr int L = LAB + LCD, HAB = qc_nherm(LAB), NC = (LCD == 0) ? 1 : 3;
-    constexpr int strideK = (LCD == 0) ? qc_pair_stride(0, 1) : (LCD == 1 ? 8 : 16);
-    constexpr int LS = 65;
-    double p[NIJ], Px[NIJ], Py[NIJ], Pz[NIJ];
+// Device records of the work lists (built by qc_bm_device_lists, qc_fock.hip): the bundle carries what the kernel needs of its bra pair,
+// the unit what it needs of the lane's ket pair - a wave used to start with three dependent trips to memory (bundle -> pair descriptors
+// -> first ket record); now the bundle comes through the scalar unit and both records of the NEXT bundle are requested while the current
+// one is being digested (qc_bm_segment).
+typedef int qc_v4i __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) qc_v4i qc_cv4i;
+struct QcBmBundleRegs { int bra, ij_lo, ij_hi, first, nket, maxK, bdoff, offa, offb, na, nb, eq, cax; };   // wave-uniform (cax: p.p kets, axis of the first function)
+__device__ __forceinline__ QcBmBundleRegs qc_bm_load_bundle(const QcBundleDev *bundles, const int b) {
+    const qc_cv4i *bp = (const qc_cv4i *)(bundles + b);
+    const qc_v4i x = bp[0], y = bp[1], z = bp[2];
+    return QcBmBundleRegs{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y & 0xff, (z.y >> 8) & 0xff, (z.y >> 16) & 1, z.z};
+}
+
+// ---- what the pieces of a bundle's body share
+constexpr int QC_BM_LS = 65;                                  // row stride (doubles) of a wave's I block in LDS
+constexpr int qc_bm_nc(int lcd) { return lcd == 0 ? 1 : 3; }  // ket columns of a lane: one (ss), or the three of an axis (ps, p.p)
+// The wave's side of a bundle: its bra pair (wave-uniform) and its block I[ab * NC + col][lane]
+struct QcBmView {
+    const double *pd, *pdT, *Tb;                              // pair data, the same with the expansions stored [ab][h], the Boys table (LDS)
+    int lane, n;
+    int bdoff, strideB, ij_lo, ij_hi, maxK;                   // the bra's pair-data block, its primitive pairs [ij_lo, ij_hi), longest ket chunk
+    int na, nb, nab, offa, offb;
+    double *Iw, *I;                                           // the wave's block; this lane's column of it, I[x * QC_BM_LS]
+};
+// The lane's side: its ket pair, decoded from the unit (ket pair | offset of its (chunk of) primitive records | c0, d0 | primitives, shape)
+template <int LCD>
+struct QcBmKetView {
+    const double *base;                                       // first primitive record of the chunk (ss: pair data; ps, p.p: packed records)
+    int ket, K_cd, Kc1;                                       // ket pair; primitives of the chunk (0: idle lane) and the index of its last
+    bool active, nd1, keq;                                    // (nc, nd) = (1,1), (3,1) [nd1] or (1,3); keq: one shell twice
+    int c0, d0, kc[qc_bm_nc(LCD)], lc[qc_bm_nc(LCD)];         // column c of the lane is the function pair (c0 + kc[c], d0 + lc[c])
+};
+template <int LCD>
+__device__ __forceinline__ QcBmKetView<LCD> qc_bm_ket_view(const QcBmView &v, const double *pspack, const QcBmBundleRegs &bd, const QcKetUnit ue) {
+    QcBmKetView<LCD> k;
+    k.active = v.lane < bd.nket;
+    k.ket = ue.ket;
+    k.K_cd = k.active ? (ue.info & 0xffff) : 0; k.Kc1 = max(k.K_cd - 1, 0);
+    k.nd1 = (ue.info >> 16) & 1;
+    k.keq = (ue.info >> 17) & 1;
+    // (p.p kets: the lane's three columns share the function of the wave's axis in the first shell - it moves into the column base)
+    k.c0 = (ue.cd & 0xffff) + (LCD == 2 ? ((ue.info >> (24 + 2 * bd.cax)) & 3) : 0); k.d0 = (int)((unsigned)ue.cd >> 16);
+    k.base = ((LCD == 0) ? v.pd : pspack) + ue.koff;
 #pragma unroll
-    for (int u = 0; u < NIJ; ++u) { p[u] = hd[u][0]; Px[u] = hd[u][1]; Py[u] = hd[u][2]; Pz[u] = hd[u][3]; }
-    // headers of the bra primitive pairs after this pass (clamped: the last pass re-reads its own)
-    double hn[2][4];
+    for (int c = 0; c < qc_bm_nc(LCD); ++c) {
+        const int fc = (LCD == 0) ? 0 : (ue.info >> (18 + 2 * c)) & 3;   // ps kets: column c = axis c = p function fc
+        k.kc[c] = k.nd1 ? fc : 0; k.lc[c] = k.nd1 ? 0 : fc;
+    }
+    return k;
+}
+
+// One ket primitive record.  ss kets: pair-data block [q, Q | E] (h, e); ps kets: packed record [q, Q | e0x, e0y, e0z, e1] (h, e4; stride
+// 8); p.p kets: [q, Q | A_x, A_y, A_z, kh | D_x, D_y, D_z, khh | hq A_x, hq A_y, hq A_z, -] (h, e4, e4b, e4c; stride 16).
+struct QcBmKetRec { double4 h; double e; double4 e4, e4b, e4c; };
+template <int LCD>
+__device__ __forceinline__ QcBmKetRec qc_bm_fetch(const double *__restrict__ kb) {
+    QcBmKetRec r{};
+    r.h = *reinterpret_cast<const double4 *>(kb);
+    if constexpr (LCD == 0) r.e = kb[4];
+    else r.e4 = *reinterpret_cast<const double4 *>(kb + 4);
+    if constexpr (LCD == 2) { r.e4b = *reinterpret_cast<const double4 *>(kb + 8); r.e4c = *reinterpret_cast<const double4 *>(kb + 12); }
+    return r;
+}
+// the headers (p, P) of the bra primitive pairs ij and ij + 1, clamped to the bundle's last
+__device__ __forceinline__ void qc_bm_bra_headers(const QcBmView &v, const int ij, double (&hd)[2][4]) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        qc_cdouble *bh = (qc_cdouble *)(pd + bdoff + (size_t)min(ij + NIJ + u, ij_last) * strideB);
-        hn[u][0] = bh[0]; hn[u][1] = bh[1]; hn[u][2] = bh[2]; hn[u][3] = bh[3];
+        qc_cdouble *bh = (qc_cdouble *)(v.pd + v.bdoff + (size_t)min(ij + u, v.ij_hi - 1) * v.strideB);
+        hd[u][0] = bh[0]; hd[u][1] = bh[1]; hd[u][2] = bh[2]; hd[u][3] = bh[3];
     }
-    double W[NIJ][NC][HAB];
+}
+
+// The primitive step: the primitive quartets of ket record `rc` with the NIJ bra primitive pairs of the pass (headers hd) - Boys values,
+// R table, and step 2 in the form of the ket type: W[u][c][h] += sum_h' E_cd[c][h'] R_{h + h'} (`valid`: the record is one of the lane's)
+template <int LAB, int LCD, int NIJ, int CAX>
+__device__ __forceinline__ void qc_bm_prim(const QcBmKetRec &rc, const bool valid, const double (&hd)[2][4], const double *__restrict__ Tb,
+                                           double (&W)[NIJ][qc_bm_nc(LCD)][qc_nherm(LAB)]) {
+    constexpr int L = LAB + LCD;
+    const double4 ck = rc.h;
+    const double q = ck.x;
 #pragma unroll
-    for (int u = 0; u < NIJ; ++u)
+    for (int u = 0; u < NIJ; ++u) {
+        const double p = hd[u][0], X = hd[u][1] - ck.y, Y = hd[u][2] - ck.z, Z = hd[u][3] - ck.w;
+        const double pref = qc_rsqrt(p + q);
+        const double alpha = p * q * (pref * pref);
+        double F[L + 1], Rr[qc_nherm(L)];
+        qc_boys_lds<L>(alpha * (X * X + Y * Y + Z * Z), Tb, F);
+        qc_rtab<L>(alpha, X, Y, Z, F, Rr);
+        const double sc = valid ? pref : 0.0;
+        if constexpr (LCD == 0) {
+            const double e = rc.e * sc;               // ss ket: a single Hermite function, W[h] += e R_h
 #pragma unroll
-        for (int c = 0; c < NC; ++c)
+            for (int h = 0; h < qc_nherm(LAB); ++h) W[u][0][h] = fma(e, Rr[h], W[u][0][h]);
+        } else if constexpr (LCD == 1) {
+            const double e0[3] = {rc.e4.x * sc, rc.e4.y * sc, rc.e4.z * sc};
+            qc_step2_ps<LAB>(W[u], e0, -(rc.e4.w * sc), Rr);
+        } else {
+            const double Ac = (CAX == 0 ? rc.e4.x : (CAX == 1 ? rc.e4.y : rc.e4.z)) * sc, hAc = (CAX == 0 ? rc.e4c.x : (CAX == 1 ? rc.e4c.y : rc.e4c.z)) * sc;
+            const double kh = rc.e4.w * sc;
+            const double c0[3] = {fma(Ac, rc.e4b.x, CAX == 0 ? kh : 0.0), fma(Ac, rc.e4b.y, CAX == 1 ? kh : 0.0), fma(Ac, rc.e4b.z, CAX == 2 ? kh : 0.0)};
+            const double cc[3] = {-(kh * rc.e4b.x), -(kh * rc.e4b.y), -(kh * rc.e4b.z)};
+            qc_step2_pp<LAB, CAX>(W[u], c0, cc, -hAc, rc.e4b.w * sc, Rr);
+        }
+    }
+}
+
+// Step 3 of the high bras against ss kets (HAB = 20 / 35, up to 36 function pairs), I[ab] += sum_h E_ab,ij[ab][h] W[h]: a row is 2-4
+// scalar pieces, and one piece ahead leaves the step bound by the scalar-load latency (17 us of a 36 us bundle for the (dd|ss) class).  The
+// block is staged in the wave's LDS - coalesced loads, one latency - and read back as wave-uniform (broadcast) DS reads.
+// (ps kets, three columns per lane: measured slower staged - 17 vs 10 us per bundle on H2O/cc-pVTZ)
+constexpr bool qc_bm_staged(int lab, int lcd) { return lab >= 3 && lcd == 0; }
+// LAB = 3: the block is requested BEFORE the primitive loop - NV values per lane held in registers through it (at most 18 function pairs
+// x 20 = 6 per lane) - and stored to LDS after it.  LAB = 4 would need 20 - that costs the ss-ket launch its second wave per SIMD - and
+// its bras are mostly single primitive pairs, one pass per bundle: staged after the loop, one exposed latency.
+constexpr int qc_bm_nprestage(int lab) { return lab == 3 ? (18 * 20 + 63) / 64 : 1; }
+template <int LAB>
+__device__ __forceinline__ void qc_bm_prestage(const QcBmView &v, const int ij, double (&est)[qc_bm_nprestage(LAB)]) {
+    if constexpr (LAB == 3) {
+        const double *__restrict__ Eg = v.pdT + v.bdoff + (size_t)ij * v.strideB + 4;
+        const int ne = v.nab * qc_nherm(LAB);
 #pragma unroll
-            for (int h = 0; h < HAB; ++h) W[u][c][h] = 0.0;
-    // high bras: the expansion block of this bra primitive pair (step 3 below) is requested now - coalesced, NV values per lane held in
-    // registers through the primitive loop - and staged in the wave's LDS afterwards
-    // (LAB = 3: at most 18 function pairs x 20 = 6 values per lane; LAB = 4 would need 20 - that costs the ss-ket launch its second wave
-    // per SIMD - and its bras are mostly single primitive pairs, one pass per bundle: staged after the loop, one exposed latency)
-    constexpr bool STAGE = LAB >= 3 && LCD == 0;     // (ps kets, three columns per lane: measured slower staged - 17 vs 10 us per bundle on H2O/cc-pVTZ)
-    constexpr int NV = (LAB == 3) ? (18 * 20 + 63) / 64 : 1;
-    constexpr bool PRE = STAGE && LAB == 3;
-    const int lane = threadIdx.x & 63;
-    const double *__restrict__ Eg = pdT + bdoff + (size_t)ij * strideB + 4;
-    const int ne = nab * HAB;
-    double est[NV];
+        for (int k = 0; k < qc_bm_nprestage(LAB); ++k) est[k] = (k * 64 < ne) ? Eg[min(v.lane + k * 64, ne - 1)] : 0.0;
+    }
+}
+template <int LAB>
+__device__ __forceinline__ void qc_bm_step3_staged(const QcBmView &v, const int ij, const double (&est)[qc_bm_nprestage(LAB)],
+                                                   const double (&W)[1][1][qc_nherm(LAB)]) {
+    constexpr int HAB = qc_nherm(LAB), NV = qc_bm_nprestage(LAB), LS = QC_BM_LS;
+    constexpr bool PRE = LAB == 3;
+    const int lane = v.lane, nab = v.nab, ne = nab * HAB;
+    const double *__restrict__ Eg = v.pdT + v.bdoff + (size_t)ij * v.strideB + 4;
+    double *const I = v.I;
+    double *const Es = v.Iw + nab * LS;                       // behind the wave's I block (qc_bm_wave_words)
     if constexpr (PRE) {
 #pragma unroll
-        for (int k = 0; k < NV; ++k) est[k] = (k * 64 < ne) ? Eg[min(lane + k * 64, ne - 1)] : 0.0;
+        for (int k = 0; k < NV; ++k)
+            if (k * 64 < ne) Es[min(lane + k * 64, ne - 1)] = est[k];   // (lanes past the end rewrite the last element with its own value)
     }
-    // The ket primitives' records are requested QC_BM_AHEAD iterations ahead (round 4).  ss kets: pair-data block [q, Q | E]; ps kets: packed
-    // record [q, Q | e0x, e0y, e0z, e1] (ketBase points into pspack, stride 8).  One iteration ahead - rounds 1-3 - left every iteration
-    // waiting for its record: per-wave phase timing (-DQC_BM_TIMING) shows 0.47-0.74 us per iteration for EVERY class, (ss|ss) with its
-    // 130 instructions per iteration as well as (pp|ps) with 217 - the latency of an L2 hit under load, not the arithmetic (0.15-0.3 us
-    // of issue).  The loop is unrolled by the depth so that the staged records rotate through fixed registers.
-    struct Rec { double4 h; double e; double4 e4, e4b, e4c; };
-    auto fetch = [&](const int kl) -> Rec {
-        Rec r{};
-        const double *__restrict__ kbn = ketBase + (size_t)min(kl, Kc1) * strideK;
-        r.h = *reinterpret_cast<const double4 *>(kbn);
-        if constexpr (LCD == 0) r.e = kbn[4];
-        else r.e4 = *reinterpret_cast<const double4 *>(kbn + 4);
-        if constexpr (LCD == 2) { r.e4b = *reinterpret_cast<const double4 *>(kbn + 8); r.e4c = *reinterpret_cast<const double4 *>(kbn + 12); }
-        return r;
-    };
-    auto step = [&](const int kl, const Rec &rc) {
-        const bool valid = kl < K_cd;
-        const double4 ck = rc.h;
-        const double q = ck.x;
+    for (int x0 = lane + (PRE ? NV * 64 : 0); x0 < ne; x0 += 4 * 64) {  // what the register stage does not hold
+        double e[4];
 #pragma unroll
-        for (int u = 0; u < NIJ; ++u) {
-            const double X = Px[u] - ck.y, Y = Py[u] - ck.z, Z = Pz[u] - ck.w;
-            const double pref = qc_rsqrt(p[u] + q);
-            const double alpha = p[u] * q * (pref * pref);
-            double F[L + 1], Rr[qc_nherm(L)];
-            qc_boys_lds<L>(alpha * (X * X + Y * Y + Z * Z), Tb, F);
-            qc_rtab<L>(alpha, X, Y, Z, F, Rr);
-            const double sc = valid ? pref : 0.0;
-            if constexpr (LCD == 0) {
-                const double e = rc.e * sc;               // ss ket: a single Hermite function, W[h] += e R_h
+        for (int k = 0; k < 4; ++k) e[k] = Eg[min(x0 + k * 64, ne - 1)];
 #pragma unroll
-                for (int h = 0; h < qc_nherm(LAB); ++h) W[u][0][h] = fma(e, Rr[h], W[u][0][h]);
-            } else if constexpr (LCD == 1) {
-                const double e0[3] = {rc.e4.x * sc, rc.e4.y * sc, rc.e4.z * sc};
-                qc_step2_ps<LAB>(W[u], e0, -(rc.e4.w * sc), Rr);
-            } else {
-                // packed p.p record: e4 = (A_x, A_y, A_z, kh), e4b = (D_x, D_y, D_z, khh), e4c = (hq A_x, hq A_y, hq A_z, -)
-                const double Ac = (CAX == 0 ? rc.e4.x : (CAX == 1 ? rc.e4.y : rc.e4.z)) * sc, hAc = (CAX == 0 ? rc.e4c.x : (CAX == 1 ? rc.e4c.y : rc.e4c.z)) * sc;
-                const double kh = rc.e4.w * sc;
-                const double c0[3] = {fma(Ac, rc.e4b.x, CAX == 0 ? kh : 0.0), fma(Ac, rc.e4b.y, CAX == 1 ? kh : 0.0), fma(Ac, rc.e4b.z, CAX == 2 ? kh : 0.0)};
-                const double cc[3] = {-(kh * rc.e4b.x), -(kh * rc.e4b.y), -(kh * rc.e4b.z)};
-                qc_step2_pp<LAB, CAX>(W[u], c0, cc, -hAc, rc.e4b.w * sc, Rr);
-            }
-        }
-    };
-    Rec r0{};
-    r0.h = hk0; r0.e = ek0.x; r0.e4 = ek0; r0.e4b = ek0b; r0.e4c = ek0c;
-    // (p.p kets keep one record ahead: their 16-double records would push the kernel past 256 registers - one wave per SIMD)
-    constexpr int AHEAD = (LCD == 2) ? 1 : QC_BM_AHEAD;
-    if constexpr (AHEAD == 1) {
-        for (int kl = 0; kl < maxK; ++kl) {
-            const Rec cur = r0;
-            r0 = fetch(kl + 1);
-            step(kl, cur);
-        }
-    } else if constexpr (AHEAD == 2) {
-        Rec r1 = fetch(1);
-        for (int kl = 0; kl < maxK; kl += 2) {
-            { const Rec cur = r0; r0 = fetch(kl + 2); step(kl, cur); }
-            if (kl + 1 < maxK) { const Rec cur = r1; r1 = fetch(kl + 3); step(kl + 1, cur); }
-        }
-    } else {
-        Rec r1 = fetch(1), r2 = fetch(2);
-        for (int kl = 0; kl < maxK; kl += 3) {
-            { const Rec cur = r0; r0 = fetch(kl + 3); step(kl, cur); }
-            if (kl + 1 < maxK) { const Rec cur = r1; r1 = fetch(kl + 4); step(kl + 1, cur); }
-            if (kl + 2 < maxK) { const Rec cur = r2; r2 = fetch(kl + 5); step(kl + 2, cur); }
-        }
+        for (int k = 0; k < 4; ++k)
+            if (x0 + k * 64 < ne) Es[x0 + k * 64] = e[k];
     }
-    QC_BT(1);
-#ifdef QC_BM_TIMING
-    tph[6] += maxK; tph[7] += 1;      // (iterations of the primitive loop, passes)
-#endif
-    // step 3 with the wave-uniform bra blocks: I[ab][c] += sum_u sum_h E_ab,ij+u[ab][h] W[u][c][h]
-    if constexpr (STAGE) {
-        // High bras (HAB = 20 / 35, up to 36 function pairs): a row is 2-4 scalar pieces, and one piece ahead leaves the step bound by the
-        // scalar-load latency (17 us of a 36 us bundle for the (dd|ss) class).  The block is staged in the wave's LDS - coalesced
-        // loads, one latency - and read back as wave-uniform (broadcast) DS reads.
-        static_assert(NIJ == 1, "high bras run one bra primitive pair per pass");
-        double *const Es = I - lane + nab * NC * LS;            // behind the wave's I block (qc_bm_wave_words)
-        if constexpr (PRE) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int ab = 0; ab < nab; ++ab) {
+        const double *row = Es + ab * HAB;
+        double acc = 0.0;
 #pragma unroll
-            for (int k = 0; k < NV; ++k)
-                if (k * 64 < ne) Es[min(lane + k * 64, ne - 1)] = est[k];   // (lanes past the end rewrite the last element with its own value)
-        }
-        for (int x0 = lane + (PRE ? NV * 64 : 0); x0 < ne; x0 += 4 * 64) {  // what the register stage does not hold
-            double v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = Eg[min(x0 + k * 64, ne - 1)];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x0 + k * 64 < ne) Es[x0 + k * 64] = v[k];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int ab = 0; ab < nab; ++ab) {
-            const double *row = Es + ab * HAB;
-            double acc[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-#pragma unroll
-            for (int h = 0; h < HAB; ++h) {            // (one chain in ascending h, as in the scalar form: same roundings)
-                const double e = row[h];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) acc[c] = fma(e, W[0][c][h], acc[c]);
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) qc_lds_add(&I[(ab * NC + c) * LS], acc[c]);
-        }
-        // (the next pass overwrites Es only after these reads: DS operations of a wave execute in order)
-    } else {
+        for (int h = 0; h < HAB; ++h) acc = fma(row[h], W[0][0][h], acc);   // (one chain in ascending h, as in the scalar form: same roundings)
+        qc_ds_add(&I[ab * LS], acc);
+    }
+    // (the next pass overwrites Es only after these reads: DS operations of a wave execute in order)
+}
+
+// Step 3 with the bra blocks through the scalar unit, I[ab][c] += sum_u sum_h E_ab,ij+u[ab][h] W[u][c][h]: the rows come in pieces of
+// QC_BM_PIECE scalars, each requested while the previous one is being used
+constexpr int QC_BM_PIECE = 10;
+template <int LAB, int LCD, int NIJ>
+__device__ __forceinline__ void qc_bm_step3_scalar(const QcBmView &v, const int ij, const double (&W)[NIJ][qc_bm_nc(LCD)][qc_nherm(LAB)]) {
+    constexpr int HAB = qc_nherm(LAB), NC = qc_bm_nc(LCD), LS = QC_BM_LS;
     constexpr int PL = QC_BM_PIECE, NPC = (HAB + PL - 1) / PL, NP = NIJ * NPC;
-    qc_cdouble *ET = (qc_cdouble *)(pdT + bdoff + (size_t)ij * strideB + 4);
+    const int nab = v.nab, strideB = v.strideB;
+    double *const I = v.I;
+    qc_cdouble *ET = (qc_cdouble *)(v.pdT + v.bdoff + (size_t)ij * strideB + 4);
     auto load_piece = [&](double (&e)[PL], const int ab, const int u, const int pc) {
         qc_cdouble *row = ET + (size_t)u * strideB + ab * HAB + pc * PL;
 #pragma unroll
@@ -316,203 +306,194 @@ __device__ __forceinline__ void qc_bm_pass(const double *__restrict__ pd, const 
             for (int k = 0; k < PL; ++k) cur[k] = nxt[k];
         }
 #pragma unroll
-        for (int c = 0; c < NC; ++c) qc_lds_add(&I[(ab * NC + c) * LS], acc[c]);
+        for (int c = 0; c < NC; ++c) qc_ds_add(&I[(ab * NC + c) * LS], acc[c]);
     }
+}
+
+// One pass over the ket primitives for NIJ consecutive bra primitive pairs (NIJ = 2 shares every ket load between two
+// primitive quartets), followed by step 3 with the wave-uniform bra blocks.
+// Latencies a pass used to expose, and what hides them now (round 3; with ket chunks of <= 8 primitives a pass is only ~16 primitive
+// quartets long, so they were a third to a half of a wave's life): the bra headers of the NEXT pass are requested before the
+// primitive loop (`hd` carries them from pass to pass); the first ket record is loaded once per bundle (`first`); the expansion block
+// of step 3 is pre-staged or comes in pieces, each requested while the previous one is being used.
+template <int LAB, int LCD, int NIJ, int CAX = 0>
+__device__ __forceinline__ void qc_bm_pass(const QcBmView &v, const QcBmKetView<LCD> &kv, const int ij, const QcBmKetRec &first, double (&hd)[2][4]) {
+    constexpr int HAB = qc_nherm(LAB), NC = qc_bm_nc(LCD);
+    constexpr int strideK = (LCD == 0) ? qc_pair_stride(0, 1) : (LCD == 1 ? 8 : 16);
+    // headers of the bra primitive pairs after this pass (clamped: the last pass re-reads its own)
+    double hn[2][4];
+    qc_bm_bra_headers(v, ij + NIJ, hn);
+    double W[NIJ][NC][HAB];
+#pragma unroll
+    for (int u = 0; u < NIJ; ++u)
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int h = 0; h < HAB; ++h) W[u][c][h] = 0.0;
+    double est[qc_bm_nprestage(LAB)];
+    if constexpr (qc_bm_staged(LAB, LCD)) qc_bm_prestage<LAB>(v, ij, est);
+    // The ket primitives' records are requested one iteration ahead.  An iteration takes 0.47-0.74 us in EVERY class, (ss|ss) with its 130
+    // instructions as well as (pp|ps) with 217, against 0.15-0.3 us of issue - but two or three records ahead (round 4) gained nothing:
+    // the loop takes turns with the SIMD's other waves, it does not wait for its record.
+    QcBmKetRec next = first;
+    for (int kl = 0; kl < v.maxK; ++kl) {
+        const QcBmKetRec cur = next;
+        next = qc_bm_fetch<LCD>(kv.base + (size_t)min(kl + 1, kv.Kc1) * strideK);
+        qc_bm_prim<LAB, LCD, NIJ, CAX>(cur, kl < kv.K_cd, hd, v.Tb, W);
     }
+    if constexpr (qc_bm_staged(LAB, LCD)) {
+        static_assert(NIJ == 1, "high bras run one bra primitive pair per pass");
+        qc_bm_step3_staged<LAB>(v, ij, est, W);
+    } else qc_bm_step3_scalar<LAB, LCD, NIJ>(v, ij, W);
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int k = 0; k < 4; ++k) hd[u][k] = hn[u][k];
-    QC_BT(2);
 }
 
-// Device records of the work lists (built by qc_bm_device_lists, qc_fock.hip): the bundle carries what the kernel needs of its bra pair,
-// the unit what it needs of the lane's ket pair - a wave used to start with three dependent trips to memory (bundle -> pair descriptors
-// -> first ket record); now the bundle comes through the scalar unit and both records of the NEXT bundle are requested while the current
-// one is being digested (qc_bm_segment).
-typedef int qc_v4i __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) qc_v4i qc_cv4i;
-struct QcBmBundleRegs { int bra, ij_lo, ij_hi, first, nket, maxK, bdoff, offa, offb, na, nb, eq, cax; };   // wave-uniform (cax: p.p kets, axis of the first function)
-__device__ __forceinline__ QcBmBundleRegs qc_bm_load_bundle(const QcBundleDev *bundles, const int b) {
-    const qc_cv4i *bp = (const qc_cv4i *)(bundles + b);
-    const qc_v4i x = bp[0], y = bp[1], z = bp[2];
-    return QcBmBundleRegs{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y & 0xff, (z.y >> 8) & 0xff, (z.y >> 16) & 1, z.z};
+// The passes of a bundle: two bra primitive pairs per pass while W[2][NC][HAB] fits the registers, then one; p.p kets: the instance of
+// the wave's axis (wave-uniform)
+template <int LAB, int LCD, int NIJ, int CAX = 0>
+__device__ __forceinline__ void qc_bm_pass_run(const QcBmView &v, const QcBmKetView<LCD> &kv, int &ij, const QcBmKetRec &first, double (&hd)[2][4]) {
+    for (; ij + NIJ <= v.ij_hi; ij += NIJ) qc_bm_pass<LAB, LCD, NIJ, CAX>(v, kv, ij, first, hd);
 }
-
 template <int LAB, int LCD>
-__device__ __forceinline__ void qc_bm_body(const QcKernelArgs &a, const double *__restrict__ pdT, const QcBmBundleRegs &bd, const QcKetUnit ue,
-                                           const int blk, const double *__restrict__ Tb, double *const Iw,
-                                           const double *__restrict__ pspack, double *const rowbuf, const int rowcap QC_BT_ARGS) {
-    constexpr int HAB = qc_nherm(LAB), NC = (LCD == 0) ? 1 : 3;
-    constexpr int LS = 65;                                    // LDS row stride (doubles)
-    constexpr bool PAIRED = 2 * NC * HAB <= 24;               // two bra primitive pairs per pass when W[2][NC][HAB] fits
-    const int lane = threadIdx.x & 63;
-    const double *__restrict__ pd = a.pairdata;
-    const int n = a.n;
-    const bool uhf = a.Dk1 != nullptr;
-    const double fxscale = a.fxs ? a.fxs[0] : 0.0;           // 0: f64 atomics
-
-    const int bra = bd.bra, ij_lo = bd.ij_lo, ij_hi = bd.ij_hi, nket = bd.nket, maxK = bd.maxK;
-    const int na = bd.na, nb = bd.nb, offa = bd.offa, offb = bd.offb, bdoff = bd.bdoff;
-    const int nab = na * nb;
-    const int strideB = qc_pair_stride(LAB, nab);
-
-    const bool active = lane < nket;
-    // unit: ket pair | offset of its (chunk of) primitive records | c0, d0 | primitives, shape - QcKetUnit
-    const int ket = ue.ket;
-    const int K_cd = active ? (ue.info & 0xffff) : 0, Kc1 = max(K_cd - 1, 0);
-    const bool nd1 = (ue.info >> 16) & 1;                      // (nc, nd) = (1,1), (3,1) [nd1] or (1,3)
-    const bool keq = (ue.info >> 17) & 1;
-    const int psperm = (ue.info >> 18) & 63;
-    // (p.p kets: the lane's three columns share the function of the wave's axis in the first shell - it moves into the column base)
-    const int c0 = (ue.cd & 0xffff) + (LCD == 2 ? ((ue.info >> (24 + 2 * bd.cax)) & 3) : 0), d0 = (int)((unsigned)ue.cd >> 16);
-    const double *__restrict__ ketBase = ((LCD == 0) ? pd : pspack) + ue.koff;
-    double *const I = Iw + lane;                              // I[x * LS], x = ab * NC + col
-
-    for (int x = 0; x < nab * NC; ++x) I[x * LS] = 0.0;
-
+__device__ __forceinline__ void qc_bm_passes(const QcBmView &v, const QcBmKetView<LCD> &kv, const int cax) {
+    constexpr bool PAIRED = 2 * qc_bm_nc(LCD) * qc_nherm(LAB) <= 24;
     // first ket record of the lane's chunk (the same for every pass) and the headers of the first two bra primitive pairs
-    const double4 hk0 = *reinterpret_cast<const double4 *>(ketBase);
-    const double4 ek0 = (LCD >= 1) ? *reinterpret_cast<const double4 *>(ketBase + 4) : double4{ketBase[4], 0.0, 0.0, 0.0};
-    const double4 ek0b = (LCD == 2) ? *reinterpret_cast<const double4 *>(ketBase + 8) : double4{0.0, 0.0, 0.0, 0.0};
-    const double4 ek0c = (LCD == 2) ? *reinterpret_cast<const double4 *>(ketBase + 12) : double4{0.0, 0.0, 0.0, 0.0};
+    const QcBmKetRec first = qc_bm_fetch<LCD>(kv.base);
     double hd[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        qc_cdouble *bh = (qc_cdouble *)(pd + bdoff + (size_t)min(ij_lo + u, ij_hi - 1) * strideB);
-        hd[u][0] = bh[0]; hd[u][1] = bh[1]; hd[u][2] = bh[2]; hd[u][3] = bh[3];
-    }
-    QC_BT(0);
-    int ij = ij_lo;
+    qc_bm_bra_headers(v, v.ij_lo, hd);
+    int ij = v.ij_lo;
     if constexpr (LCD == 2) {
-        // (the axis is wave-uniform: one of three instances of the pass)
-        if (bd.cax == 0) for (; ij < ij_hi; ++ij) qc_bm_pass<LAB, LCD, 1, 0>(pd, pdT, Tb, bdoff, strideB, ij, ij_hi - 1, nab, ketBase, hk0, ek0, ek0b, ek0c, K_cd, Kc1, maxK, I, hd QC_BT_PASS);
-        else if (bd.cax == 1) for (; ij < ij_hi; ++ij) qc_bm_pass<LAB, LCD, 1, 1>(pd, pdT, Tb, bdoff, strideB, ij, ij_hi - 1, nab, ketBase, hk0, ek0, ek0b, ek0c, K_cd, Kc1, maxK, I, hd QC_BT_PASS);
-        else for (; ij < ij_hi; ++ij) qc_bm_pass<LAB, LCD, 1, 2>(pd, pdT, Tb, bdoff, strideB, ij, ij_hi - 1, nab, ketBase, hk0, ek0, ek0b, ek0c, K_cd, Kc1, maxK, I, hd QC_BT_PASS);
+        if (cax == 0) qc_bm_pass_run<LAB, LCD, 1, 0>(v, kv, ij, first, hd);
+        else if (cax == 1) qc_bm_pass_run<LAB, LCD, 1, 1>(v, kv, ij, first, hd);
+        else qc_bm_pass_run<LAB, LCD, 1, 2>(v, kv, ij, first, hd);
     } else {
-    if constexpr (PAIRED)
-        for (; ij + 1 < ij_hi; ij += 2) qc_bm_pass<LAB, LCD, 2>(pd, pdT, Tb, bdoff, strideB, ij, ij_hi - 1, nab, ketBase, hk0, ek0, ek0b, ek0c, K_cd, Kc1, maxK, I, hd QC_BT_PASS);
-    for (; ij < ij_hi; ++ij) qc_bm_pass<LAB, LCD, 1>(pd, pdT, Tb, bdoff, strideB, ij, ij_hi - 1, nab, ketBase, hk0, ek0, ek0b, ek0c, K_cd, Kc1, maxK, I, hd QC_BT_PASS);
+        if constexpr (PAIRED) qc_bm_pass_run<LAB, LCD, 2>(v, kv, ij, first, hd);
+        qc_bm_pass_run<LAB, LCD, 1>(v, kv, ij, first, hd);
     }
+}
 
-    if (a.schwarz_out != nullptr) {
-        // Schwarz factors: the bundles are (P|P) quartets, one ket per bundle; the largest element of the block is on its diagonal
-        if (active) {
-            double m = 0.0;
-            for (int x = 0; x < nab * NC; ++x) m = fmax(m, fabs(I[x * LS]));
-            a.schwarz_out[ket] = sqrt(m);
-        }
-        return;
+// Output: Schwarz factors - the bundles are (P|P) quartets, one ket per bundle; the largest element of the block is on its diagonal
+template <int LCD>
+__device__ __forceinline__ void qc_bm_out_schwarz(const QcKernelArgs &a, const QcBmView &v, const QcBmKetView<LCD> &kv) {
+    if (!kv.active) return;
+    double m = 0.0;
+    for (int x = 0; x < v.nab * qc_bm_nc(LCD); ++x) m = fmax(m, fabs(v.I[x * QC_BM_LS]));
+    a.schwarz_out[kv.ket] = sqrt(m);
+}
+// Output: (ij|kl) materialised with its 8 symmetry images (qc_eri_full, MP2, stored-tensor mode; bundles are not cut along ij there)
+template <int LCD>
+__device__ __forceinline__ void qc_bm_out_tensor(const QcKernelArgs &a, const QcBmView &v, const QcBmKetView<LCD> &kv) {
+    constexpr int NC = qc_bm_nc(LCD);
+    if (!kv.active) return;
+    const QcTensorOut out(a.eri_out, v.n);
+    for (int ab = 0; ab < v.nab; ++ab)
+        for (int c = 0; c < NC; ++c)
+            out.store8(v.offa + ab / v.nb, v.offb + ab % v.nb, kv.c0 + kv.kc[c], kv.d0 + kv.lc[c], v.I[(ab * NC + c) * QC_BM_LS]);
+}
+
+// Where a bundle's Fock contributions go: the wave's replica of G (both spins) and, for the exchange rows of the bra's functions, the
+// wave's row buffer in LDS (null: none - they go to G directly)
+struct QcBmSink {
+    double *G0, *G1, *rowbuf;
+    int rowcap, n;
+    double fxscale;                                           // 0: f64 atomics
+    size_t fx_lo;
+};
+// Exchange contributions land in the rows of the bra's functions (r = i, or na + j; `grow` in G) at the columns of this lane's ket
+// functions.  With a row buffer they are DS atomics and the rows leave as one global atomic per touched element after the bundle
+// (qc_bm_flush_rows); without one they go to global memory directly.
+__device__ __forceinline__ void qc_bm_kadd(const QcBmSink &g, int sp, int r, int grow, int col, double val) {
+    if (g.rowbuf) qc_ds_add(&g.rowbuf[((size_t)sp * g.rowcap + r) * g.n + col], val);
+    else qc_gadd(&(sp ? g.G1 : g.G0)[(size_t)grow * g.n + col], val, g.fxscale, g.fx_lo);
+}
+// the partial sums of one target row: G[target, c_k] (accK) and G[target, d_l] (accL) over the lane's columns
+template <int LCD>
+__device__ __forceinline__ void qc_bm_kadd3(const QcBmSink &g, const QcBmKetView<LCD> &kv, const double fk, int sp, int r, int grow,
+                                            const double (&accK)[qc_bm_nc(LCD)], const double (&accL)[qc_bm_nc(LCD)]) {
+    const int c0 = kv.c0, d0 = kv.d0;
+    if constexpr (LCD == 0) {
+        qc_bm_kadd(g, sp, r, grow, c0, fk * accK[0]);
+        qc_bm_kadd(g, sp, r, grow, d0, fk * accL[0]);
+    } else if (kv.nd1) {                                      // columns differ in k, share l
+        qc_bm_kadd(g, sp, r, grow, c0 + kv.kc[0], fk * accK[0]); qc_bm_kadd(g, sp, r, grow, c0 + kv.kc[1], fk * accK[1]); qc_bm_kadd(g, sp, r, grow, c0 + kv.kc[2], fk * accK[2]);
+        qc_bm_kadd(g, sp, r, grow, d0, fk * (accL[0] + accL[1] + accL[2]));
+    } else {                                                  // columns differ in l, share k
+        qc_bm_kadd(g, sp, r, grow, c0, fk * (accK[0] + accK[1] + accK[2]));
+        qc_bm_kadd(g, sp, r, grow, d0 + kv.lc[0], fk * accL[0]); qc_bm_kadd(g, sp, r, grow, d0 + kv.lc[1], fk * accL[1]); qc_bm_kadd(g, sp, r, grow, d0 + kv.lc[2], fk * accL[2]);
     }
-    if (a.eri_out != nullptr) {
-        // materialise (ij|kl) with its 8 symmetry images (qc_eri_full, MP2, stored-tensor mode; bundles are not cut along ij there)
-        if (active) {
-            const size_t n1 = n, n2 = n1 * n1, n3 = n2 * n1;
-            double *o = a.eri_out;
-            for (int ab = 0; ab < nab; ++ab) {
-                const size_t i = offa + ab / nb, j = offb + ab % nb;
-                for (int c = 0; c < NC; ++c) {
-                    const int fc = (LCD == 0) ? 0 : (psperm >> (2 * c)) & 3;    // ps kets: column c = axis c = p function fc
-                    const size_t k = c0 + (nd1 ? fc : 0), l = d0 + (nd1 ? 0 : fc);
-                    const double v = I[(ab * NC + c) * LS];
-                    o[i * n3 + j * n2 + k * n1 + l] = v; o[j * n3 + i * n2 + k * n1 + l] = v;
-                    o[i * n3 + j * n2 + l * n1 + k] = v; o[j * n3 + i * n2 + l * n1 + k] = v;
-                    o[k * n3 + l * n2 + i * n1 + j] = v; o[l * n3 + k * n2 + i * n1 + j] = v;
-                    o[k * n3 + l * n2 + j * n1 + i] = v; o[l * n3 + k * n2 + j * n1 + i] = v;
-                }
+}
+// One half of a spin's exchange blocks: the targets are the functions of one bra shell (on_a: a_i, with D[b_j, d_l] and D[b_j, c_k];
+// else b_j, with D[a_i, .]).  The density rows of the functions of the OTHER bra shell are gathered first (one memory latency per half
+// instead of one per target row: the elements do not depend on the target), then every target row is a loop over LDS reads.  RB covers
+// a whole shell, so a target element is ONE sum over the other shell's functions in ascending order (the O2 triplet run of the tests
+// sits on a saddle and follows these roundings).
+// (Not force-inlined: inlined before the optimiser runs, both halves of the ss-ket instances compile to 40 % more register moves and
+// another branch structure, and bm<0,1> ran 2 % longer on benzene/cc-pVDZ; inlined in its turn - it always is, the kernels have no
+// calls and no scratch - it is the code of the lambda it replaces, profiles/r20_bm_body_kernel_resources.md.)
+template <int LAB, int LCD>
+__device__ inline void qc_bm_exchange_half(const QcBmView &v, const QcBmKetView<LCD> &kv, const QcBmSink &g, const double fk,
+                                                    const double *__restrict__ Dk, const int s, const bool on_a) {
+    constexpr int NC = qc_bm_nc(LCD), LS = QC_BM_LS, RB = (LAB <= 2) ? 6 : 10;
+    const int na = v.na, nb = v.nb, n = v.n;
+    const int nt = on_a ? na : nb, no = on_a ? nb : na;      // target shell / other shell (wave-uniform)
+    const int offo = on_a ? v.offb : v.offa;
+    const double *const I = v.I;
+    for (int o0 = 0; o0 < no; o0 += RB) {
+        double dK[RB][NC], dL[RB][NC];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) dK[r][c] = dL[r][c] = 0.0;
+            if (o0 + r < no) {
+                const double *__restrict__ Drow = Dk + (size_t)(offo + o0 + r) * n;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) { dK[r][c] = Drow[kv.d0 + kv.lc[c]]; dL[r][c] = Drow[kv.c0 + kv.kc[c]]; }
             }
         }
-        return;
-    }
-
-    const size_t rep = (size_t)(blk % a.nrep) * a.rep_stride;
-    double *G0 = a.G0 + rep, *G1 = a.G1 + rep;
-    const double f = active ? (bd.eq ? 0.5 : 1.0) * (keq ? 0.5 : 1.0) * (bra == ket ? 0.5 : 1.0) : 0.0;
-    // column c of this lane's ket is the function pair (c0 + kc[c], d0 + lc[c])
-    int kc[NC], lc[NC];
+        for (int t = 0; t < nt; ++t) {
+            double accK[NC], accL[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int fc = (LCD == 0) ? 0 : (psperm >> (2 * c)) & 3;     // ps kets: column c = axis c = p function fc
-        kc[c] = nd1 ? fc : 0; lc[c] = nd1 ? 0 : fc;
-    }
-    // this lane's ket-side density elements (Coulomb part below): requested here, used after the exchange blocks
-    double dcd[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) dcd[c] = active ? a.Dj[(size_t)(c0 + kc[c]) * n + d0 + lc[c]] : 0.0;
-
-    const double fk = -a.cK * f;
-    // Exchange contributions land in the rows of the bra's functions (r = i, or na + j) at the columns of this lane's ket
-    // functions.  With a row buffer (LDS, per wave) they are DS atomics and the rows leave as one global atomic per
-    // touched element after the bundle; without one they go to global memory directly.
-    auto kadd = [&](int sp, int r, int grow, int col, double v) {
-        if (rowbuf) qc_lds_add(&rowbuf[((size_t)sp * rowcap + r) * n + col], v);
-        else qc_gadd(&(sp ? G1 : G0)[(size_t)grow * n + col], v, fxscale, a.fx_lo);
-    };
-    auto kadd3 = [&](int sp, int r, int grow, const double (&accK)[NC], const double (&accL)[NC]) {
-        if constexpr (NC == 1) {
-            kadd(sp, r, grow, c0, fk * accK[0]);
-            kadd(sp, r, grow, d0, fk * accL[0]);
-        } else if (nd1) {                                     // columns differ in k, share l
-            kadd(sp, r, grow, c0 + kc[0], fk * accK[0]); kadd(sp, r, grow, c0 + kc[1], fk * accK[1]); kadd(sp, r, grow, c0 + kc[2], fk * accK[2]);
-            kadd(sp, r, grow, d0, fk * (accL[0] + accL[1] + accL[2]));
-        } else {                                              // columns differ in l, share k
-            kadd(sp, r, grow, c0, fk * (accK[0] + accK[1] + accK[2]));
-            kadd(sp, r, grow, d0 + lc[0], fk * accL[0]); kadd(sp, r, grow, d0 + lc[1], fk * accL[1]); kadd(sp, r, grow, d0 + lc[2], fk * accL[2]);
-        }
-    };
-    // ---- exchange blocks first (they read I), per spin: Gt_ik -= cK f sum_jl I D_jl and the il / jk / jl images.
-    // The density rows of the functions of the OTHER bra shell are gathered first (one memory latency per half instead of one per
-    // target row: the elements do not depend on the target), then every target row is a loop over LDS reads.  RB covers a whole
-    // shell, so a target element is ONE sum over the other shell's functions in ascending order, as before (the O2 triplet run of
-    // the tests sits on a saddle and follows these roundings).
-    constexpr int RB = (LAB <= 2) ? 6 : 10;
-    auto exchange_half = [&](const double *__restrict__ Dk, const int s, const bool on_a) {
-        const int nt = on_a ? na : nb, no = on_a ? nb : na;              // target shell / other shell (wave-uniform)
-        const int offo = on_a ? offb : offa;
-        for (int o0 = 0; o0 < no; o0 += RB) {
-            double dK[RB][NC], dL[RB][NC];
+            for (int c = 0; c < NC; ++c) accK[c] = accL[c] = 0.0;
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) dK[r][c] = dL[r][c] = 0.0;
                 if (o0 + r < no) {
-                    const double *__restrict__ Drow = Dk + (size_t)(offo + o0 + r) * n;
+                    const int o = o0 + r;
+                    const int ab = on_a ? t * nb + o : o * nb + t;
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) { dK[r][c] = Drow[d0 + lc[c]]; dL[r][c] = Drow[c0 + kc[c]]; }
-                }
-            }
-            for (int t = 0; t < nt; ++t) {
-                double accK[NC], accL[NC];                   // G[target, c_k] and G[target, d_l] partial sums
-#pragma unroll
-                for (int c = 0; c < NC; ++c) accK[c] = accL[c] = 0.0;
-#pragma unroll
-                for (int r = 0; r < RB; ++r) {
-                    if (o0 + r < no) {
-                        const int o = o0 + r;
-                        const int ab = on_a ? t * nb + o : o * nb + t;
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            const double v = I[(ab * NC + c) * LS];
-                            accK[c] = fma(v, dK[r][c], accK[c]);
-                            accL[c] = fma(v, dL[r][c], accL[c]);
-                        }
+                    for (int c = 0; c < NC; ++c) {
+                        const double val = I[(ab * NC + c) * LS];
+                        accK[c] = fma(val, dK[r][c], accK[c]);
+                        accL[c] = fma(val, dL[r][c], accL[c]);
                     }
                 }
-                kadd3(s, on_a ? t : na + t, (on_a ? offa : offb) + t, accK, accL);
             }
-        }
-    };
-    if (active) {
-        for (int s = 0; s < (uhf ? 2 : 1); ++s) {
-            const double *__restrict__ Dk = s ? a.Dk1 : a.Dk0;
-            exchange_half(Dk, s, true);                       // targets on the bra functions a_i: D[b_j, d_l] and D[b_j, c_k]
-            exchange_half(Dk, s, false);                      // targets on the bra functions b_j: D[a_i, d_l] and D[a_i, c_k]
+            qc_bm_kadd3<LCD>(g, kv, fk, s, on_a ? t : na + t, (on_a ? v.offa : v.offb) + t, accK, accL);
         }
     }
+}
+// Exchange blocks (they read I), per spin: Gt_ik -= cK f sum_jl I D_jl and the il / jk / jl images (fk = -cK f)
+template <int LAB, int LCD>
+__device__ __forceinline__ void qc_bm_exchange(const QcKernelArgs &a, const QcBmView &v, const QcBmKetView<LCD> &kv, const QcBmSink &g, const double fk) {
+    if (!kv.active) return;
+    for (int s = 0; s < (a.Dk1 != nullptr ? 2 : 1); ++s) {
+        const double *__restrict__ Dk = s ? a.Dk1 : a.Dk0;
+        qc_bm_exchange_half<LAB, LCD>(v, kv, g, fk, Dk, s, true);
+        qc_bm_exchange_half<LAB, LCD>(v, kv, g, fk, Dk, s, false);
+    }
+}
 
-    QC_BT(3);
-    // ---- Coulomb blocks: Gt_cd += 2f sum_ab I D_ab (per lane);  Gt_ab += 2f sum_cd I D_cd (reduced over the wave)
-    const double fj = 2.0 * f;
+// Coulomb blocks: Gt_cd += fj sum_ab I D_ab (per lane);  Gt_ab += fj sum_cd I D_cd (reduced over the wave); fj = 2f, dcd = the lane's
+// ket-side density elements
+template <int LCD>
+__device__ __forceinline__ void qc_bm_coulomb(const QcKernelArgs &a, const QcBmView &v, const QcBmKetView<LCD> &kv, const QcBmSink &g, const double fj,
+                                              const double (&dcd)[qc_bm_nc(LCD)]) {
+    constexpr int NC = qc_bm_nc(LCD), LS = QC_BM_LS;
+    const int n = v.n, na = v.na, nb = v.nb, nab = v.nab, offa = v.offa, offb = v.offb;
+    const bool uhf = a.Dk1 != nullptr;
+    double *const I = v.I;
     double jcd[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) jcd[c] = 0.0;
@@ -529,63 +510,112 @@ __device__ __forceinline__ void qc_bm_body(const QcKernelArgs &a, const double *
             double t = 0.0;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const double v = I[(ab * NC + c) * LS];
-                jcd[c] = fma(v, dab, jcd[c]);
-                t = fma(v, dcd[c], t);
+                const double val = I[(ab * NC + c) * LS];
+                jcd[c] = fma(val, dab, jcd[c]);
+                t = fma(val, dcd[c], t);
             }
             I[(ab * NC) * LS] = fj * t;                       // own column: this lane's share of Gt_ab
             dab = dnx; bi = bin; bj = bjn;
         }
     }
-    if (active) {
+    if (kv.active) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const size_t o = (size_t)(c0 + kc[c]) * n + d0 + lc[c];
-            qc_gadd2(&G0[o], &G1[o], uhf, fj * jcd[c], fxscale, a.fx_lo);
+            const size_t o = (size_t)(kv.c0 + kv.kc[c]) * n + kv.d0 + kv.lc[c];
+            qc_gadd2(&g.G0[o], &g.G1[o], uhf, fj * jcd[c], g.fxscale, g.fx_lo);
         }
     }
     // same-wave LDS hand-off (DS operations of a wave execute in order): lane ab sums row ab over the 64 columns
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int ab = lane; ab < nab; ab += 64) {
-        const double *row = Iw + (size_t)(ab * NC) * LS;
+    for (int ab = v.lane; ab < nab; ab += 64) {
+        const double *row = v.Iw + (size_t)(ab * NC) * LS;
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll 8
         for (int j = 0; j < 64; j += 2) { s0 += row[j]; s1 += row[j + 1]; }
         const size_t o = (size_t)(offa + ab / nb) * n + offb + ab % nb;
-        qc_gadd2(&G0[o], &G1[o], uhf, s0 + s1, fxscale, a.fx_lo);
+        qc_gadd2(&g.G0[o], &g.G1[o], uhf, s0 + s1, g.fxscale, g.fx_lo);
     }
-    QC_BT(4);
 }
 
-// Workgroup = qc_bm_waves(LCD, HI) independent waves sharing the LDS Boys table of their segment's Hermite order; every wave
-// walks the segment's bundle list with the stride of the launch (bundles are sorted longest first).
-template <int LAB, int LCD, int NW>
-__device__ __forceinline__ void qc_bm_segment(const QcBmArgs &a, const int s, const int wg, const int nwg) {
-    extern __shared__ double lds[];
-    constexpr int L = LAB + LCD;
-    const int tid = threadIdx.x, wave = tid >> 6;
-    {
-        const double *__restrict__ rows = a.base.boys + (size_t)L * QC_BOYS_NGRID * 8;
-        const double *__restrict__ exk = a.base.boys + (size_t)(QC_LTOT + 1) * QC_BOYS_NGRID * 8;
-        // eight loads of a thread in flight together (an L2 round trip per batch, not per element)
-        const int nt = blockDim.x;
-        for (int i0 = tid; i0 < QC_BM_TWORDS; i0 += 8 * nt) {
-            double v[8];
+// One bundle: the lane's quartet block I through the passes, then one output - Schwarz factor, the materialised tensor, or digestion
+template <int LAB, int LCD>
+__device__ __forceinline__ void qc_bm_body(const QcKernelArgs &a, const double *__restrict__ pdT, const QcBmBundleRegs &bd, const QcKetUnit ue,
+                                           const int blk, const double *__restrict__ Tb, double *const Iw,
+                                           const double *__restrict__ pspack, double *const rowbuf, const int rowcap) {
+    constexpr int NC = qc_bm_nc(LCD);
+    const int lane = threadIdx.x & 63, nab = bd.na * bd.nb;
+    const QcBmView v{a.pairdata, pdT, Tb, lane, a.n, bd.bdoff, qc_pair_stride(LAB, nab), bd.ij_lo, bd.ij_hi, bd.maxK,
+                     bd.na, bd.nb, nab, bd.offa, bd.offb, Iw, Iw + lane};
+    const QcBmKetView<LCD> kv = qc_bm_ket_view<LCD>(v, pspack, bd, ue);
+    const double fxscale = a.fxs ? a.fxs[0] : 0.0;            // 0: f64 atomics
+    for (int x = 0; x < nab * NC; ++x) v.I[x * QC_BM_LS] = 0.0;
+    qc_bm_passes<LAB, LCD>(v, kv, bd.cax);
+
+    if (a.schwarz_out != nullptr) { qc_bm_out_schwarz<LCD>(a, v, kv); return; }
+    if (a.eri_out != nullptr) { qc_bm_out_tensor<LCD>(a, v, kv); return; }
+
+    const size_t rep = (size_t)(blk % a.nrep) * a.rep_stride;
+    const QcBmSink g{a.G0 + rep, a.G1 + rep, rowbuf, rowcap, a.n, fxscale, a.fx_lo};
+    const double f = kv.active ? (bd.eq ? 0.5 : 1.0) * (kv.keq ? 0.5 : 1.0) * (bd.bra == kv.ket ? 0.5 : 1.0) : 0.0;
+    // this lane's ket-side density elements (Coulomb part): requested here, used after the exchange blocks
+    double dcd[NC];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = min(i0 + j * nt, QC_BM_TWORDS - 1);
-                const int k = i / QC_BM_TROW, r = i - k * QC_BM_TROW;
-                v[j] = (r < 8) ? rows[k * 8 + r] : exk[k];
+    for (int c = 0; c < NC; ++c) dcd[c] = kv.active ? a.Dj[(size_t)(kv.c0 + kv.kc[c]) * a.n + kv.d0 + kv.lc[c]] : 0.0;
+    qc_bm_exchange<LAB, LCD>(a, v, kv, g, -a.cK * f);
+    qc_bm_coulomb<LCD>(a, v, kv, g, 2.0 * f, dcd);
+}
+
+// The Boys table of Hermite order L into the head of the workgroup's LDS, QC_BM_TROW words per grid point (every thread of the workgroup)
+template <int L>
+__device__ __forceinline__ void qc_bm_load_boys_table(const double *__restrict__ boys, double *const lds) {
+    const double *__restrict__ rows = boys + (size_t)L * QC_BOYS_NGRID * 8;
+    const double *__restrict__ exk = boys + (size_t)(QC_LTOT + 1) * QC_BOYS_NGRID * 8;
+    // eight loads of a thread in flight together (an L2 round trip per batch, not per element)
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int i0 = tid; i0 < QC_BM_TWORDS; i0 += 8 * nt) {
+        double e[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = min(i0 + j * nt, QC_BM_TWORDS - 1);
+            const int k = i / QC_BM_TROW, r = i - k * QC_BM_TROW;
+            e[j] = (r < 8) ? rows[k * 8 + r] : exk[k];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (i0 + j * nt < QC_BM_TWORDS) lds[i0 + j * nt] = e[j];
+    }
+}
+// The rows a wave has accumulated for the bundle `pb` leave as one global atomic per touched element (g: the wave's row buffer and its
+// replica of G): the 64 kets of a bundle share most of their functions, so the lanes' contributions combine 2-5x in LDS first
+__device__ __forceinline__ void qc_bm_flush_rows(const QcBmSink &g, const int nsp, const QcBmBundleRegs &pb, const int lane) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int sp = 0; sp < nsp; ++sp) {
+        double *G = sp ? g.G1 : g.G0;
+        for (int r = 0; r < pb.na + pb.nb; ++r) {
+            const int grow = r < pb.na ? pb.offa + r : pb.offb + r - pb.na;
+            double *row = g.rowbuf + ((size_t)sp * g.rowcap + r) * g.n;
+            for (int col = lane; col < g.n; col += 64) {
+                const double val = row[col];
+                if (val != 0.0) { qc_gadd(&G[(size_t)grow * g.n + col], val, g.fxscale, g.fx_lo); row[col] = 0.0; }
             }
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (i0 + j * nt < QC_BM_TWORDS) lds[i0 + j * nt] = v[j];
         }
     }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Workgroup = up to QC_BM_WAVES independent waves sharing the LDS Boys table of their segment's Hermite order; every wave
+// walks the segment's bundle list with the stride of the launch (bundles are sorted longest first).
+template <int LAB, int LCD>
+__device__ __forceinline__ void qc_bm_segment(const QcBmArgs &a, const int s, const int wg, const int nwg) {
+    extern __shared__ double lds[];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    qc_bm_load_boys_table<LAB + LCD>(a.base.boys, lds);
     __syncthreads();
-    const int nw = blockDim.x >> 6;                           // <= NW: fewer when the LDS blocks of NW waves would not fit
+    const int nw = blockDim.x >> 6;                           // <= QC_BM_WAVES: fewer when the LDS blocks of that many waves would not fit
     const int n = a.base.n, lane = tid & 63;
     const int rowcap = a.seg_rows[s], nsp = a.base.Dk1 ? 2 : 1;
     const int rowwords = a.use_rowbuf ? nsp * rowcap * n : 0;
@@ -595,31 +625,9 @@ __device__ __forceinline__ void qc_bm_segment(const QcBmArgs &a, const int s, co
     for (int x = lane; x < rowwords; x += 64) rowbuf[x] = 0.0;
     const QcBundleDev *__restrict__ bundles = a.seg_bundles[s];
     const QcKetUnit *__restrict__ units = a.seg_ketlist[s];
-    // the rows a wave has accumulated for the bundle of bra pair `bra` leave as one global atomic per touched element:
-    // the 64 kets of a bundle share most of their functions, so the lanes' contributions combine 2-5x in LDS first
-    const double fxscale = a.base.fxs ? a.base.fxs[0] : 0.0;
-    auto flush_rows = [&](const QcBmBundleRegs &pb) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int sp = 0; sp < nsp; ++sp) {
-            double *G = (sp ? a.base.G1 : a.base.G0) + (size_t)(((wg * nw + wave) % a.base.nrep)) * a.base.rep_stride;
-            for (int r = 0; r < pb.na + pb.nb; ++r) {
-                const int grow = r < pb.na ? pb.offa + r : pb.offb + r - pb.na;
-                double *row = rowbuf + ((size_t)sp * rowcap + r) * n;
-                for (int col = lane; col < n; col += 64) {
-                    const double v = row[col];
-                    if (v != 0.0) { qc_gadd(&G[(size_t)grow * n + col], v, fxscale, a.base.fx_lo); row[col] = 0.0; }
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
+    const size_t wrep = (size_t)((wg * nw + wave) % a.base.nrep) * a.base.rep_stride;
+    const QcBmSink rows{a.base.G0 + wrep, a.base.G1 + wrep, rowbuf, rowcap, n, a.base.fxs ? a.base.fxs[0] : 0.0, a.base.fx_lo};
     const int nb = a.seg_nbundles[s];
-#ifdef QC_BM_TIMING
-    long long tph[8] = {}, tlast = wall_clock64();
-    int nbun = 0;
-#endif
     const int b0 = __builtin_amdgcn_readfirstlane(wg * nw + wave), bstep = nwg * nw;
     if (b0 >= nb) return;
     QcBmBundleRegs bd = qc_bm_load_bundle(bundles, b0);
@@ -627,30 +635,19 @@ __device__ __forceinline__ void qc_bm_segment(const QcBmArgs &a, const int s, co
     for (int b = b0; b < nb; b += bstep) {
         // records of the wave's next bundle: the bundle now (scalar), its unit while the rows of this one are flushed
         const QcBmBundleRegs bdn = qc_bm_load_bundle(bundles, min(b + bstep, nb - 1));
-        qc_bm_body<LAB, LCD>(a.base, a.pairdataT, bd, ue, b, lds, Iw, a.pspack, rowbuf, rowcap QC_BT_PASS);
+        qc_bm_body<LAB, LCD>(a.base, a.pairdataT, bd, ue, b, lds, Iw, a.pspack, rowbuf, rowcap);
         const QcKetUnit uen = units[bdn.first + min(lane, bdn.nket - 1)];
-        if (rowbuf) flush_rows(bd);
+        if (rowbuf) qc_bm_flush_rows(rows, nsp, bd, lane);
         bd = bdn; ue = uen;
-        QC_BT(5);
-#ifdef QC_BM_TIMING
-        ++nbun;
-#endif
     }
-#ifdef QC_BM_TIMING
-    if (lane == 0 && wave == 0 && wg < 2 && a.base.eri_out == nullptr && a.base.schwarz_out == nullptr)
-        printf("bm<%d,%d> seg wg %d: %d bundles (of %d)  setup %lld  k-loop %lld  step3 %lld  digestK %lld  digestJ %lld  flush %lld  [10 ns]  k-iterations %lld in %lld passes: %.0f ns per iteration\n", LAB, LCD, wg, nbun, nb,
-               tph[0], tph[1], tph[2], tph[3], tph[4], tph[5], tph[6], tph[7], tph[6] ? 10.0 * (double)tph[1] / (double)tph[6] : 0.0);
-#endif
 }
 
 template <int LCD, int HI>
-__global__ __launch_bounds__(qc_bm_waves(LCD, HI) * 64) void qc_fock_bm_kernel(const QcBmArgs a) {
+__global__ __launch_bounds__(QC_BM_WAVES * 64) void qc_fock_bm_kernel(const QcBmArgs a) {
     qc_tl_stamp(a.base.tl, 0);
-    int s = 0;
-    while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg_end[s]) ++s;
-    const int b0 = s ? a.seg_end[s - 1] : 0;
-    const int wg = blockIdx.x - b0, nwg = a.seg_end[s] - b0;
-#define QC_BM_CASE(LAB) case LAB: qc_bm_segment<LAB, LCD, qc_bm_waves(LCD, HI)>(a, s, wg, nwg); break;
+    const QcSegment sg = qc_find_segment(a);
+    const int s = sg.s;
+#define QC_BM_CASE(LAB) case LAB: qc_bm_segment<LAB, LCD>(a, s, sg.blk, sg.nblk); break;
     if constexpr (LCD == 0 && HI == 0) { switch (a.seg_lab[s]) { QC_BM_CASE(0) QC_BM_CASE(1) QC_BM_CASE(2) default: break; } }
     if constexpr (LCD == 0 && HI == 1) { switch (a.seg_lab[s]) { QC_BM_CASE(3) QC_BM_CASE(4) default: break; } }
     if constexpr (LCD == 1 && HI == 0) { switch (a.seg_lab[s]) { QC_BM_CASE(1) QC_BM_CASE(2) default: break; } }
@@ -662,30 +659,17 @@ __global__ __launch_bounds__(qc_bm_waves(LCD, HI) * 64) void qc_fock_bm_kernel(c
     // chip together instead of following each other on a stream (50 + 83 us in-build there)
     if constexpr (LCD == 3 && HI == 0) {
         switch ((a.seg_lcd[s] << 4) | a.seg_lab[s]) {
-            case 0x03: qc_bm_segment<3, 0, qc_bm_waves(0, 1)>(a, s, wg, nwg); break;
-            case 0x04: qc_bm_segment<4, 0, qc_bm_waves(0, 1)>(a, s, wg, nwg); break;
-            case 0x11: qc_bm_segment<1, 1, qc_bm_waves(1, 0)>(a, s, wg, nwg); break;
-            case 0x12: qc_bm_segment<2, 1, qc_bm_waves(1, 0)>(a, s, wg, nwg); break;
+            case 0x03: qc_bm_segment<3, 0>(a, s, sg.blk, sg.nblk); break;
+            case 0x04: qc_bm_segment<4, 0>(a, s, sg.blk, sg.nblk); break;
+            case 0x11: qc_bm_segment<1, 1>(a, s, sg.blk, sg.nblk); break;
+            case 0x12: qc_bm_segment<2, 1>(a, s, sg.blk, sg.nblk); break;
             default: break;
         }
     }
     qc_tl_stamp(a.base.tl, 1);
 }
 
-template <int LCD, int HI>
-static int launch_bm(int grid, int nwaves, size_t lds, hipStream_t st, const QcBmArgs &a) {
-    auto kern = qc_fock_bm_kernel<LCD, HI>;
-    static std::atomic<bool> raised{false};       // once per instantiation, to the device maximum (see qc_launch_tier)
-    if (lds > 48 * 1024 && !raised.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, QC_LDS_MAX);
-        if (e != hipSuccess) return QC_ERR_HIP;
-        raised.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nwaves * 64), lds, st, a);
-    return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
-}
-
-// The exchange rows of a bundle are summed in LDS with f64 DS atomics, several lanes of ONE instruction adding to one address (qc_lds_add):
+// The exchange rows of a bundle are summed in LDS with f64 DS atomics, several lanes of ONE instruction adding to one address (qc_ds_add):
 // bitwise reproducible builds need the DS unit to serve such lanes in an order that does not depend on timing.  No manual says so; every
 // device seen does it.  This probe asks the device at hand: 64 lanes add values of very different magnitudes (the sum depends on the
 // order) to one word, 64 times over, with another wave of the workgroup hammering the same LDS bank meanwhile; all 64 sums must be the same
@@ -694,7 +678,7 @@ __global__ __launch_bounds__(128) void qc_ds_order_probe_kernel(double *out) {
     __shared__ double acc[64 + 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave == 1) {                                   // traffic on the same banks, other addresses
-        for (int rep = 0; rep < 4096; ++rep) qc_lds_add(&acc[64 + ((lane * 7 + rep) & 63)], 1.0);
+        for (int rep = 0; rep < 4096; ++rep) qc_ds_add(&acc[64 + ((lane * 7 + rep) & 63)], 1.0);
         return;
     }
     const double v = ldexp(1.0 + 0.001 * lane, (lane * 37) % 53 - 20) * ((lane & 1) ? -1.0 : 1.0);
@@ -703,8 +687,8 @@ __global__ __launch_bounds__(128) void qc_ds_order_probe_kernel(double *out) {
         if (lane == 0) *word = 0.0;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if ((lane + rep) & 3) qc_lds_add(&acc[2 + (lane & 31)], 1.0);      // (an unrelated add with a partial mask in front)
-        qc_lds_add(word, v);                           // the probed instruction: 64 lanes, one address
+        if ((lane + rep) & 3) qc_ds_add(&acc[2 + (lane & 31)], 1.0);       // (an unrelated add with a partial mask in front)
+        qc_ds_add(word, v);                            // the probed instruction: 64 lanes, one address
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) out[rep] = *word;
@@ -715,6 +699,10 @@ int qc_ds_order_probe(hipStream_t st, double *d_out64) {
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
 
+template <int LCD, int HI>
+static int launch_bm(int grid, int nwaves, size_t lds, hipStream_t st, const QcBmArgs &a) {
+    return qc_launch_column<qc_fock_bm_kernel<LCD, HI>>(grid, nwaves * 64, lds, st, a);
+}
 int qc_launch_bm(int lcd, int hi, int grid, int nwaves, size_t lds, hipStream_t st, const QcBmArgs &a) {
     if (lcd == 3) return hi ? QC_ERR_UNSUPPORTED : launch_bm<3, 0>(grid, nwaves, lds, st, a);
     if (lcd == 2) return hi ? QC_ERR_UNSUPPORTED : launch_bm<2, 0>(grid, nwaves, lds, st, a);

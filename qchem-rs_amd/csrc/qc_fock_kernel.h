@@ -537,22 +537,27 @@ __device__ __forceinline__ void qc_out_schwarz(const QcKernelArgs &a, const QcSl
     for (int o = C / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, C));
     if (v.li == 0) a.schwarz_out[v.sl.bra] = sqrt(m);
 }
-// Output: (ij|kl) materialised with its 8 symmetry images: the tensor molint::eri returns (qc_eri_full, MP2, stored Fock mode; the host
-// hands this mode unsplit slots, so plain stores are complete values)
-template <int C>
-__device__ __forceinline__ void qc_out_tensor(const QcKernelArgs &a, const QcSlotView &v) {
-    const int nb = v.nb, nd = v.nd, nab = v.nab, ncd = v.ncd;
-    const QcPairDesc &pb = v.pb, &pk = v.pk;
-    const size_t n1 = v.n, n2 = n1 * n1, n3 = n2 * n1;
-    for (int x = v.li; x < nab * ncd; x += C) {
-        const int ab = x / ncd, cd = x - ab * ncd;
-        const size_t i = pb.offa + ab / nb, j = pb.offb + ab % nb, k = pk.offa + cd / nd, l = pk.offb + cd % nd;
-        const double val = v.Iblk[x];
-        double *o = a.eri_out;
+// The n^4 tensor molint::eri returns, as the kernels write it: an element (ij|kl) goes to its 8 symmetry images (both kernel families)
+struct QcTensorOut {
+    double *o; size_t n1, n2, n3;
+    __device__ __forceinline__ QcTensorOut(double *out, int n) : o(out), n1(n), n2(n1 * n1), n3(n2 * n1) {}
+    __device__ __forceinline__ void store8(size_t i, size_t j, size_t k, size_t l, double val) const {
         o[i * n3 + j * n2 + k * n1 + l] = val; o[j * n3 + i * n2 + k * n1 + l] = val;
         o[i * n3 + j * n2 + l * n1 + k] = val; o[j * n3 + i * n2 + l * n1 + k] = val;
         o[k * n3 + l * n2 + i * n1 + j] = val; o[l * n3 + k * n2 + i * n1 + j] = val;
         o[k * n3 + l * n2 + j * n1 + i] = val; o[l * n3 + k * n2 + j * n1 + i] = val;
+    }
+};
+// Output: (ij|kl) materialised with its 8 symmetry images (qc_eri_full, MP2, stored Fock mode; the host hands this mode unsplit slots, so
+// plain stores are complete values)
+template <int C>
+__device__ __forceinline__ void qc_out_tensor(const QcKernelArgs &a, const QcSlotView &v) {
+    const int nb = v.nb, nd = v.nd, nab = v.nab, ncd = v.ncd;
+    const QcPairDesc &pb = v.pb, &pk = v.pk;
+    const QcTensorOut out(a.eri_out, v.n);
+    for (int x = v.li; x < nab * ncd; x += C) {
+        const int ab = x / ncd, cd = x - ab * ncd;
+        out.store8(pb.offa + ab / nb, pb.offb + ab % nb, pk.offa + cd / nd, pk.offb + cd % nd, v.Iblk[x]);
     }
 }
 
@@ -974,13 +979,15 @@ struct QcTierArgs {
     int seg_words[QC_MAXSEG];
     const QcSlot *seg_slots[QC_MAXSEG];
 };
-// the segment s that workgroup blockIdx.x belongs to, the workgroup's place blk among the segment's nblk, and the segment's slot list
-struct QcSegment { int s, blk, nblk, nslots, words; const QcSlot *slots; };
-__device__ __forceinline__ QcSegment qc_find_segment(const QcTierArgs &a) {
+// the segment s that workgroup blockIdx.x belongs to and the workgroup's place blk among the segment's nblk (any launch arguments with
+// nseg and seg_end: the column kernels' and the bra-major kernels')
+struct QcSegment { int s, blk, nblk; };
+template <class ARGS>
+__device__ __forceinline__ QcSegment qc_find_segment(const ARGS &a) {
     int s = 0;
     while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg_end[s]) ++s;
     const int b0 = s ? a.seg_end[s - 1] : 0;
-    return QcSegment{s, (int)blockIdx.x - b0, a.seg_end[s] - b0, a.seg_nslots[s], a.seg_words[s], a.seg_slots[s]};
+    return QcSegment{s, (int)blockIdx.x - b0, a.seg_end[s] - b0};
 }
 
 // (TIER 2 = the tier-1 launch of a build without f-ket classes - every segment an LCD = 4 bucket, any basis without f functions: the same
@@ -994,13 +1001,15 @@ void qc_fock_tier_kernel(const QcTierArgs a) {
     // low-L waves they share a SIMD with
     if constexpr (TIER >= 1) __builtin_amdgcn_s_setprio(3);
     const QcSegment sg = qc_find_segment(a);
-#define QC_CASE(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
+    const int nslots = a.seg_nslots[sg.s], words = a.seg_words[sg.s];
+    const QcSlot *const slots = a.seg_slots[sg.s];
+#define QC_CASE(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, slots, nslots, words, sg.blk, sg.nblk); break;
     if constexpr (TIER == 0) {
         switch (a.seg_code[sg.s]) { QC_CASE(2, 4) QC_CASE(3, 4) QC_CASE(3, 5) default: break; }
     } else if constexpr (TIER == 1) {
         switch (a.seg_code[sg.s]) { QC_CASE(4, 5) QC_CASE(4, 6) QC_CASE(5, 6) QC_CASE(6, 6) default: break; }
     } else {
-#define QC_CASE_V(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC, false>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
+#define QC_CASE_V(LCD, LGC) case ((LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC, false>(a.base, slots, nslots, words, sg.blk, sg.nblk); break;
         switch (a.seg_code[sg.s]) { QC_CASE_V(4, 5) QC_CASE_V(4, 6) default: break; }
 #undef QC_CASE_V
     }
@@ -1022,7 +1031,9 @@ void qc_fock_tier1_low_kernel(const QcTierArgs a) {
     qc_tl_stamp(a.base.tl, 0);
     __builtin_amdgcn_s_setprio(3);
     const QcSegment sg = qc_find_segment(a);
-#define QC_CASE(LAB, LCD, LGC) case ((LAB) << 8 | (LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, sg.slots, sg.nslots, sg.words, sg.blk, sg.nblk); break;
+    const int nslots = a.seg_nslots[sg.s], words = a.seg_words[sg.s];
+    const QcSlot *const slots = a.seg_slots[sg.s];
+#define QC_CASE(LAB, LCD, LGC) case ((LAB) << 8 | (LCD) << 4 | (LGC)): qc_fock_body<LAB, LCD, LGC>(a.base, slots, nslots, words, sg.blk, sg.nblk); break;
     // V = 0: bra classes 0, 1, 2;  V = 1: 3 and 4 (994 + 350 workgroups on H2O/cc-pVTZ, 22 / 31 KB of LDS: still four per CU);  V = 2: 5 and 6
     // (46 + 4 workgroups, 42 / 56 KB) - the f.d / f.f bras stay out of the launch of classes 3 and 4 because their LDS would halve its waves
     if constexpr (V == 0) {
@@ -1048,20 +1059,21 @@ void qc_fock_tier1_low_kernel(const QcTierArgs a) {
 #undef QC_CASE
     qc_tl_stamp(a.base.tl, 1);
 }
-// One launch of a column kernel.  The dynamic-LDS cap of the instantiation is raised once, to the device maximum (the attribute is
-// process-wide, so a per-handle high-water mark would let one handle lower another's cap; the flag only saves the repeated call).
-template <void (*KERN)(const QcTierArgs)>
-int qc_launch_column(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) {
+// One launch of a Fock kernel (column: one wave per workgroup; bra-major: up to QC_BM_WAVES).  The dynamic-LDS cap of the instantiation
+// is raised once, to the device maximum (the attribute is process-wide, so a per-handle high-water mark would let one handle lower
+// another's cap; the flag only saves the repeated call).
+template <auto KERN, class ARGS>
+int qc_launch_column(int grid, int block, size_t lds, hipStream_t st, const ARGS &a) {
     static std::atomic<bool> raised{false};
     if (lds > 48 * 1024 && !raised.load(std::memory_order_acquire)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, QC_LDS_MAX);
         if (e != hipSuccess) return QC_ERR_HIP;
         raised.store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), lds, st, a);
     return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
 }
 template <int V>
-int qc_launch_tier1_low_impl(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier1_low_kernel<V>>(grid, lds, st, a); }
+int qc_launch_tier1_low_impl(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier1_low_kernel<V>>(grid, 64, lds, st, a); }
 template <int LAB, int TIER>
-int qc_launch_tier(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier_kernel<LAB, TIER>>(grid, lds, st, a); }
+int qc_launch_tier(int grid, size_t lds, hipStream_t st, const QcTierArgs &a) { return qc_launch_column<qc_fock_tier_kernel<LAB, TIER>>(grid, 64, lds, st, a); }
