@@ -101,8 +101,25 @@ __global__ __launch_bounds__(QC_EIG_THREADS) void qc_jacobi_kernel(int n, const 
         double off2 = 0.0;
         for (int k = 0; k < nt / 64; ++k) off2 += red[k];
         __syncthreads();
-        // Jacobi converges quadratically: a sweep that met a relative off-norm <= done_tol (1e-9) leaves <= ~done_tol^2 behind
-        if (2.0 * off2 <= done_tol * done_tol * normF2) { conv = true; break; }
+        // Jacobi converges quadratically: a sweep that met a relative off-norm <= done_tol (1e-9) leaves <= ~done_tol^2 behind - when
+        // every rotation of it was a small one.  A pair inside a cluster of equal eigenvalues is turned by up to 45 degrees however small
+        // its element, and such a turn moves what rows p and q still hold into positions the sweep has already visited: `seen` is what
+        // the sweep removed, not what it left (multiplicity 2 at n = 58 left 4e-10, multiplicity 7 at n = 64 left 4e-10 of a scale of 10
+        // to 30).  So the sweep that looks like the last one is believed only if what it left is small, element by element.
+        if (2.0 * off2 <= done_tol * done_tol * normF2) {
+            double left = 0.0;
+            for (int x = tid; x < m * m; x += nt) {
+                const int i = x / m, j = x - i * m;
+                if (i != j) left = fmax(left, fabs(A[i * ld + j]));
+            }
+            for (int o = 32; o > 0; o >>= 1) left = fmax(left, __shfl_down(left, o, 64));
+            if ((tid & 63) == 0) red[tid >> 6] = left;
+            __syncthreads();
+            left = 0.0;
+            for (int k = 0; k < nt / 64; ++k) left = fmax(left, red[k]);
+            __syncthreads();
+            if (left * left <= QC_JACOBI_LEFT_TOL * QC_JACOBI_LEFT_TOL * normF2) { conv = true; break; }
+        }
     }
     if (!conv && notconv && tid == 0) *notconv = 1;         // sweeps exhausted: the caller reports it instead of using the vectors
     // ascending order (utils.rs:28): rank sort, then permute columns
@@ -238,7 +255,8 @@ __global__ __launch_bounds__(QC_EIG1_THREADS) void qc_jacobi1_kernel(int n, cons
                         const int r = tl + k * QC_EIG1_TEAM;
                         if (r < n) { gp[r] = cs * xp[k] - sn * xq[k]; gq[r] = sn * xp[k] + cs * xq[k]; }
                     }
-                    // quadratic convergence: pairs whose relative coupling |c| / sqrt(a b) is below done_tol (1e-9) are done after this rotation
+                    // pairs whose relative coupling |c| / sqrt(a b) is below done_tol are done after this rotation (QC_JACOBI_LEFT_TOL: a sweep
+                    // may leave what it met - qc_internal.h - so what it met has to be as small as what may be left)
                     if (tl == 0 && c * c > done_tol * done_tol * (a * b)) *flag = 1;
                 }
             }
@@ -346,14 +364,14 @@ int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, QcE
         if (l1 <= QC_LDS_MAX) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(qc_jacobi1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
             if (e != hipSuccess) return QC_ERR_HIP;
-            hipLaunchKernelGGL(qc_jacobi1_kernel, dim3(1), dim3(QC_EIG1_THREADS), l1, st, n, dA, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_DONE_TOL, notconv);
+            hipLaunchKernelGGL(qc_jacobi1_kernel, dim3(1), dim3(QC_EIG1_THREADS), l1, st, n, dA, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_LEFT_TOL, notconv);
             return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
         }
     }
     const size_t lds = v_in_lds ? lds2 : lds1;
     if (lds > QC_LDS_MAX || !v_in_lds) {                // n > 128: the global-memory variant
         if (n > 3000) return QC_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(qc_jacobi1g_kernel, dim3(1), dim3(QC_EIG_THREADS), (size_t)n * 12 + 16, st, n, dA, d_work, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_DONE_TOL, notconv);
+        hipLaunchKernelGGL(qc_jacobi1g_kernel, dim3(1), dim3(QC_EIG_THREADS), (size_t)n * 12 + 16, st, n, dA, d_work, dV, dw, QC_JACOBI_MAX_SWEEPS, QC_JACOBI_LEFT_TOL, notconv);
         return hipGetLastError() == hipSuccess ? QC_OK : QC_ERR_HIP;
     }
     auto kern = v_in_lds ? qc_jacobi_kernel<true> : qc_jacobi_kernel<false>;

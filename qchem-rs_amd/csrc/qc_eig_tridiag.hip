@@ -4,16 +4,22 @@
 // does the same thing: tridiagonalise, then iterate on the tridiagonal matrix).  The parallel Jacobi kernels of qc_eig_jacobi.hip
 // touch the whole matrix in every one of their ~6 (n-1) steps and are bound by the LDS port of the single CU they run on
 // (2 n^2 doubles read and written per step: 1.8 us per step at n = 114, 1.1-1.6 ms per eigensolve).  Here
-//   1. qc_tridiag_kernel      A + pert = Q T Q^T: n-2 Householder steps in ONE workgroup, matrix resident in LDS (n <= 139, else in
-//                             global memory), 4 barriers per step, every access along rows (both triangles are kept);
+//   1. qc_tridiag_kernel      A + pert = Q T Q^T: n-2 Householder steps in ONE workgroup, matrix resident in LDS (n <= 142 by the launch
+//                             rule of qc_eig_tridiag_start, under QC_TRI_LDS only; else in global memory: n > 192), 4 barriers per step,
+//                             every access along rows (both triangles are kept); qc_tridiag_reg_kernel: the same in registers, n <= 192;
 //   2. qc_tri_eig_kernel      eigenvalues of T by 9-way multisection on division-free Sturm sequences (8 lanes per eigenvalue),
 //                             eigenvectors by twisted factorisation (one lane per eigenvalue, four O(n) sweeps);
 //   3. qc_backtransform_kernel  X0 = Q Z: one wave per eigenvector applies the n-2 reflectors (whole chip);
 // and the result goes into the Ogita-Aishima refinement (qc_eig_refine_async: f64 MFMA GEMMs), which converges quadratically
 // and therefore only needs X0 to ~1e-3: that is why none of the delicate parts of a tridiagonal eigensolver are needed -
 //   * exactly degenerate eigenvalues (benzene's E-type orbital pairs) would leave the twisted vectors of a pair parallel.  A
-//     diagonal pseudo-random perturbation of relative size 1e-9 splits them first (any basis of a degenerate subspace is a valid
-//     answer); the refinement then works on the unperturbed matrix and treats what is left as its "strong pairs";
+//     diagonal pseudo-random perturbation P of relative size 1e-11 splits them first (any basis of a degenerate subspace is a valid
+//     answer); the refinement then works on the unperturbed matrix, where what P left inside a pair stays below QC_REF_CLEAN.  How far P
+//     splits a pair depends on its vectors: by the eigenvalue difference of the 2 x 2 block x^T P x, ~1e-11 max|a| / sqrt(n) when they
+//     are spread over all rows.  The eigenvalues are located to a few eps max|w| ~ 1e-14 (the rounding of a Sturm count, not the 65^-9
+//     of the multisection), so the vectors of a pair come out mixed by 1e-14 / split: good enough for the refinement (< 1e-3) on
+//     matrices with exact pairs at n = 24, not from n = 58 on, where random matrices with exact pairs, multiplets and clusters below
+//     ~1e-8 of the scale go on to the Jacobi kernels (tests/test_eigensolver_gpu.py records which inputs do);
 //   * a start that is not good enough (orthogonality > 1e-3, clusters the refinement cannot rotate) is detected by the
 //     refinement's control word and answered with the Jacobi kernels - correctness never rests on this file.
 #include <algorithm>

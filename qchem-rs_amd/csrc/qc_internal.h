@@ -497,9 +497,14 @@ struct QcEigWork {
     int alloc(int n);
 };
 // Jacobi kernels: at most this many sweeps; they end after one that met no relative coupling above the tolerance (the sweep itself
-// leaves ~tolerance^2 behind).  notconv (device int, nullable): set to 1 when the sweeps ran out before the criterion was met.
+// leaves ~tolerance^2 behind) - unless the spectrum has clusters of equal eigenvalues: a pair inside a cluster is turned by a large
+// angle however small its coupling, which carries the couplings the sweep started with into pairs it has already been to, so that such a
+// sweep leaves up to what it met.  The two-sided kernel therefore also looks at what is left (largest off-diagonal element <=
+// QC_JACOBI_LEFT_TOL ||A||_F, 100 times its rounding floor at n = 100); the one-sided kernels, for which that look costs a sweep, end on
+// a sweep that met nothing above QC_JACOBI_LEFT_TOL (their inner products carry ~sqrt(n) eps of rounding: 3e-15 at n = 512).
+// notconv (device int, nullable): set to 1 when the sweeps ran out before the criterion was met.
 constexpr int QC_JACOBI_MAX_SWEEPS = 40;
-constexpr double QC_JACOBI_DONE_TOL = 1e-9;
+constexpr double QC_JACOBI_DONE_TOL = 1e-9, QC_JACOBI_LEFT_TOL = 1e-13;
 bool qc_eig_force_jacobi();              // QC_EIG_JACOBI (A/B switch): no tridiagonal path, the single-workgroup Jacobi kernels only
 int qc_eig_device(hipStream_t st, int n, double *dA, double *dV, double *dw, QcEigWork &E, int *notconv = nullptr);
 int qc_eig_device_warm(hipStream_t st, int n, double *dA, const double *dV0, double *dV, double *dw, QcEigWork &E, int *notconv = nullptr);
