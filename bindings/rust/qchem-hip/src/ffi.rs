@@ -81,6 +81,24 @@ pub struct QcPolarizability {
 /// qc_multipoles (include/qchem_hip.h): in order (0..4), origin; out the total, nuclear and electronic Cartesian moments of the
 /// orders 0..order (components by order ascending, then x power descending, then y power descending; the rest zero) and the traceless
 /// quadrupole xx xy xz yy yz zz of the total second moments.
+/// Conductor-like continuum (C-PCM x = 0, COSMO x = 0.5); 0 in scale / density: the defaults 1.2 and 5 points per Angstrom^2.
+#[repr(C)]
+pub struct QcSolvent {
+    pub epsilon: f64,
+    pub x: f64,
+    pub scale: f64,
+    pub density: f64,
+}
+
+/// 1/2 q.v_nuc, 1/2 q.v_elec, sum q and the number of surface elements.
+#[repr(C)]
+pub struct QcSolventEnergy {
+    pub nuclear: f64,
+    pub electronic: f64,
+    pub total_charge: f64,
+    pub npoints: i64,
+}
+
 #[repr(C)]
 pub struct QcMultipoles {
     pub order: i32,
@@ -275,6 +293,25 @@ extern "C" {
     pub fn qc_scf_point_charge_gradient(st: *mut QcScfState, grad: *mut f64) -> c_int;
     /// Phase times (ms) of the handle's last embedding call: upload, Hermite sums over the charges, assembly or contraction, download.
     pub fn qc_point_charge_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
+    /// Ainv = A^-1 of a symmetric positive-definite n x n matrix (host pointers) by the device Cholesky factorisation, exactly symmetric;
+    /// QC_ERR_INVALID when a pivot is <= 0 or not finite.
+    pub fn qc_spd_inverse(sys: *mut QcSystem, n: c_int, a: *const f64, ainv: *mut f64) -> c_int;
+    /// Conductor-like continuum of the handle: cfg null removes it; radii (nullable): natoms doubles, bohr, before scaling.  Host only.
+    /// SCF states begun afterwards are solvated; states that are alive keep theirs.
+    pub fn qc_set_solvent(sys: *mut QcSystem, cfg: *const QcSolvent, radii: *const f64) -> c_int;
+    /// Returns M; with capacity >= M also writes xyz (M x 3), area (M) and the owning atoms (M), each nullable.  Host only.
+    pub fn qc_solvent_surface(sys: *const QcSystem, capacity: i64, xyz: *mut f64, area: *mut f64, atom: *mut i32) -> i64;
+    /// S of the cavity, M x M: the host statement, and S and K = -f S^-1 by the device kernels (either nullable).
+    pub fn qc_solvent_matrix(sys: *const QcSystem, s: *mut f64) -> c_int;
+    pub fn qc_solvent_matrix_gpu(sys: *mut QcSystem, s: *mut f64, k: *mut f64) -> c_int;
+    /// At the total density d (n*n): the charges q (M, nullable), V_R (n*n, nullable) and energy = {1/2 q.v_nuc, 1/2 q.v_elec}.
+    pub fn qc_solvent_response(sys: *mut QcSystem, d: *const f64, q: *mut f64, v: *mut f64, energy: *mut f64) -> c_int;
+    /// The reaction field of the state's current density; q (nullable): M doubles.
+    pub fn qc_scf_solvent(st: *mut QcScfState, out: *mut QcSolventEnergy, q: *mut f64) -> c_int;
+    /// The same at the end of the last one-shot run on the handle.
+    pub fn qc_solvent_last(sys: *const QcSystem, out: *mut QcSolventEnergy) -> c_int;
+    /// ms: set-up (S, factorisation, inverse); of the last response: potential, reaction kernel, V_R.
+    pub fn qc_solvent_timings(sys: *const QcSystem, ms: *mut f64) -> c_int;
     pub fn qc_set_fock_mode(sys: *mut QcSystem, mode: c_int) -> c_int;
     /// 1 (default): exact, order-independent accumulation of G; 0: f64 atomics.
     pub fn qc_set_accumulation(sys: *mut QcSystem, fixed_point: c_int) -> c_int;

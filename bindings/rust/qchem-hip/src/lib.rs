@@ -149,6 +149,24 @@ pub fn excited_states(st: *mut ffi::QcScfState, tdhf: bool, triplets: bool, nroo
     }
 }
 
+/// Put the molecule of a handle into a conductor-like continuum of dielectric constant `epsilon` (`qc_set_solvent`; C-PCM, or COSMO with
+/// `cosmo`; default cavity: van der Waals radii times 1.2, 5 points per Angstrom^2).  SCF states begun afterwards are solvated; their total
+/// energy is electronic + nuclear repulsion + `solvent_energy(st).nuclear`.  False on a bad epsilon.
+pub fn set_solvent(system: &GpuSystem, epsilon: f64, cosmo: bool) -> bool {
+    let cfg = ffi::QcSolvent { epsilon, x: if cosmo { 0.5 } else { 0.0 }, scale: 0.0, density: 0.0 };
+    unsafe { ffi::qc_set_solvent(system.as_ptr(), &cfg, std::ptr::null()) == ffi::QC_OK }
+}
+
+/// 1/2 q.v_nuc, 1/2 q.v_elec, sum q and the number of surface elements for a solvated state's current density (`qc_scf_solvent`).
+/// None for a state in vacuum.
+pub fn solvent_energy(st: *mut ffi::QcScfState) -> Option<ffi::QcSolventEnergy> {
+    let mut out = ffi::QcSolventEnergy { nuclear: 0.0, electronic: 0.0, total_charge: 0.0, npoints: 0 };
+    match unsafe { ffi::qc_scf_solvent(st, &mut out, null_mut()) } {
+        ffi::QC_OK => Some(out),
+        _ => None,
+    }
+}
+
 /// Static dipole polarizability (bohr^3, row-major 3 x 3, symmetrised) of a state that has done at least one pass
 /// (`qc_scf_polarizability`, default tolerance).  None on any error or when the response equations do not converge.  The state is left
 /// as it was.

@@ -452,6 +452,65 @@ int qc_scf_point_charge_gradient(qc_scf_state *st, double *grad);
  * of a gradient call): upload, Hermite sums over the charges, assembly or contraction, download. */
 int qc_point_charge_timings(const qc_system *sys, double ms[4]);
 
+/* ---- dense symmetric positive-definite inverse on the GPU (qc_chol.hip; what the continuum below needs, exported for tests).  A, Ainv:
+ * n x n f64 on the host, row-major, n >= 1; only A's lower triangle is read.  Blocked Cholesky A = L L^T (64 x 64 diagonal blocks factored
+ * and inverted by one workgroup in LDS, panels and trailing updates by the MFMA GEMM), X = L^-1 by block forward substitution,
+ * Ainv = X^T X, mirrored so that it is exactly symmetric.  Every sum has a fixed order and there are no atomics: two calls give the same
+ * bits.  A pivot that is <= 0 or not finite is replaced by 1, the factorisation runs to its end and the call returns QC_ERR_INVALID
+ * (Ainv is then meaningless).  QC_ERR_INVALID also for null pointers or n < 1; QC_ERR_NO_DEVICE without a device. */
+int qc_spd_inverse(qc_system *sys, int n, const double *A, double *Ainv);
+
+/* ---- conductor-like continuum solvation, C-PCM / COSMO (not in the reference).  Atomic units.
+ * Surface: one sphere per atom, radius R_I = scale * r_I with r_I the van der Waals radius of qc_esp_fit_points (or the caller's radii,
+ * bohr, before scaling); on it N_I = ceil(density 4 pi R_I^2) golden-angle points (the rule of qc_esp_fit_points); a point of sphere I
+ * is kept if and only if its distance to the centre of every other sphere J is >= R_J.  Order: atom, then k.  A kept point is a surface
+ * element at s_i with area a_i = 4 pi R_I^2 / N_I, owned by atom I.  The cut is hard (no switching function): the energy is not smooth
+ * in the geometry, and there are no gradients.
+ * Cavity matrix, Gaussian-blurred charges (York-Karplus): zeta_i = c / sqrt(a_i), c = 1.0694 pi sqrt 2; S_ii = zeta_i sqrt(2 / pi)
+ * (= Klamt's 1.0694 sqrt(4 pi / a_i)); S_ij = erf(zeta_ij r_ij) / r_ij, zeta_ij = zeta_i zeta_j / sqrt(zeta_i^2 + zeta_j^2).  S is a
+ * Gram matrix, positive definite for any point set; the point-charge form 1 / r_ij is not.
+ * Reaction field: f = (epsilon - 1) / (epsilon + x), x = 0 C-PCM, x = 0.5 COSMO.  v_i = v_nuc(s_i) + v_elec(s_i), the point potentials of
+ * qc_esp_on_points for the TOTAL density;  q = K v, K = -f S^-1;  G_pol = 1/2 q.v;  V_R = -sum_i q_i A(s_i) (the matrix of
+ * qc_point_charge_matrix for the charges q) = dG_pol/dD, so E_HF[D] + G_pol[D] is variational.
+ * SCF: the reference's loop with electronic_hamiltonian := G(D) + V_R(D) (UHF: V_R of the total density in both spins' Fock matrices).
+ * A pass reports 1/2 tr[D_new (2 H + G(D_old) + V_R(D_old))] with H the vacuum core Hamiltonian (rhf.rs:84-85 with that substitution);
+ * at convergence this is E_HF,el + 1/2 q.v_elec, and the total energy is electronic + nuclear repulsion + 1/2 q.v_nuc.
+ *
+ * qc_set_solvent (host only): cfg NULL removes the solvent; 0 in scale / density: the defaults 1.2 and 5 points per Angstrom^2 (density is
+ * in points per Angstrom^2).  QC_ERR_INVALID, the handle left as it was: epsilon not finite or <= 1, x < 0 or not finite, a negative or
+ * non-finite scale or density, a radius <= 0 or not finite, an empty surface.  QC_ERR_UNSUPPORTED: more than 16384 elements.
+ * qc_solvent_surface (host only): returns M (QC_ERR_INVALID without a solvent); when capacity >= M also writes xyz (M x 3), area (M)
+ * and the owning atoms (M), each nullable.  qc_solvent_matrix (host only): S, M x M, the reference statement. */
+typedef struct { double epsilon, x, scale, density; } qc_solvent;   /* 0 in scale / density: defaults 1.2, 5 per A^2 */
+int     qc_set_solvent(qc_system *sys, const qc_solvent *cfg /* NULL removes */, const double *radii /* nullable, natoms, bohr */);
+int64_t qc_solvent_surface(const qc_system *sys, int64_t capacity, double *xyz, double *area, int32_t *atom);  /* returns M */
+int     qc_solvent_matrix(const qc_system *sys, double *S);        /* host statement of S, M x M */
+/* GPU (qc_solvent.hip).  matrix_gpu: S by the assembly kernel (device erf; an element and its mirror are one value) and K = -f S^-1 by
+ * qc_spd_inverse's kernels, both exactly symmetric, either nullable; K is built once per qc_set_solvent, at its first use, and kept on
+ * the handle.  response: at the total density D (host, n x n) the charges q (M), V_R (n x n, exactly symmetric) and
+ * energy = {1/2 q.v_nuc, 1/2 q.v_elec}; v_elec by the potential kernels of qc_esp_on_points, q and the dot products by one reaction
+ * kernel (fixed summation order), V_R by the kernels of qc_point_charge_matrix_gpu.  Bitwise reproducible from call to call and across
+ * fresh handles.  QC_ERR_INVALID: null sys / D / energy, no solvent; QC_ERR_UNSUPPORTED on a sharded handle or one with a communicator. */
+int qc_solvent_matrix_gpu(qc_system *sys, double *S /* nullable */, double *K /* nullable */);
+int qc_solvent_response(qc_system *sys, const double *D /* host, n*n, total density */, double *q /* M, nullable */,
+                        double *V /* n*n, nullable */, double energy[2] /* 1/2 q.v_nuc, 1/2 q.v_elec */);
+/* SCF.  States begun while a solvent is set take it with them (like the point charges) and keep it when the handle's is changed.
+ * qc_scf_begin_* and the one-shot drivers return QC_ERR_UNSUPPORTED, before the device is touched, for a solvent together with a sharded
+ * handle or a communicator, the stored-tensor mode, or point charges.  On a solvated state qc_scf_gradient (no cavity derivative),
+ * qc_scf_stability, qc_scf_rotated_density, qc_scf_polarizability, qc_scf_excitations and qc_scf_excitation_matrices (no solvent response
+ * term) return QC_ERR_UNSUPPORTED; the properties of the density (dipole, multipoles, populations, points, ESP charges) read the solvated
+ * density; qc_scf_mp2 is the correlation energy on the solvated orbitals; qc_scf_matrix(.., 1) is the vacuum H.
+ * qc_scf_solvent: 1/2 q.v_nuc, 1/2 q.v_elec, sum q and M for the state's current density (after scf_begin: the guess; after a pass: its
+ * new density), q (nullable) the charges.  qc_solvent_last: the same of the last one-shot run on the handle that ended with QC_OK
+ * (QC_ERR_INVALID if there is none).  qc_solvent_timings (ms): [0] the one-off set-up (S, factorisation, inverse; host clock), then of the last
+ * response evaluation [1] the potential call and [3] the V_R call (host clock around calls that end in a wait: kernels, copies and
+ * allocations) and [2] the reaction kernel alone (device events; its copies and the wait behind it are in none of the three).  Without a solvent nothing is launched or allocated and every result
+ * keeps its bits. */
+typedef struct { double nuclear, electronic, total_charge; int64_t npoints; } qc_solvent_energy;  /* 1/2 q.v_nuc, 1/2 q.v_elec, sum q */
+int qc_scf_solvent(qc_scf_state *st, qc_solvent_energy *out, double *q /* nullable, M */);   /* of the last pass */
+int qc_solvent_last(const qc_system *sys, qc_solvent_energy *out);                           /* of the last one-shot run on the handle */
+int qc_solvent_timings(const qc_system *sys, double ms[4]);   /* set-up (S, factor, inverse); per pass: potential, reaction, matrix */
+
 /* ---- excited states of an RHF state (after SCF, not in the reference): configuration interaction singles (CIS, the Tamm-Dancoff
  * approximation) and time-dependent Hartree-Fock (TDHF, the random-phase approximation), singlets or triplets, at the state's last C and
  * orbital energies.  With (pq|rs) in chemists' notation, i j occupied, a b virtual, Delta = delta_ij delta_ab (e_a - e_i), rows and columns

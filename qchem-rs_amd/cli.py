@@ -40,6 +40,12 @@ Three additions, all opt-in:
     their sum plus E_nq (never the charge-charge energy).  With `--gradient` the atoms' rows are the full dE/dR_A and one row per charge
     follows - `qI gx gy gz`, dE/dR_c; `--json` then carries a "point_charges" object (count, nuclear_energy, gradient).  Does not
     combine with `--follow`.  Output without the flag is unchanged.
+  * `--solvent EPS [--solvent-model cpcm|cosmo] [--solvent-density D]` solvates the molecule in a conductor-like continuum (C-PCM, the
+    default, or COSMO) of dielectric constant EPS with D surface points per Angstrom^2 (default 5).  One line comes first, `solvent: MODEL,
+    epsilon EPS, surface elements: M`; the `electronic energy` then contains 1/2 q.v_elec and `hartree fock energy` is electronic +
+    nuclear repulsion + 1/2 q.v_nuc; two lines follow the orbital energies, `solvent 1/2 q.v: nuclei .., electrons .., total ..` and
+    `solvent surface charge: sum q`; `--json` carries a "solvent" object.  `--mp2` is then the correlation energy on the solvated
+    orbitals.  Does not combine with `--point-charges`, `--gradient`, `--stability`, `--follow`, `--polarizability`, `--cis`, `--tdhf`.
 Host-side plumbing only: loaders (loader.py) -> C ABI (hf.py) -> HIP kernels; nothing here computes.
 """
 from __future__ import annotations
@@ -125,6 +131,10 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--cube-spacing", type=float, default=0.2, metavar="BOHR", help="grid spacing of --cube along x, y and z (default 0.2)")
         s.add_argument("--point-charges", default=None, metavar="FILE",
                        help='embed the molecule in external point charges: a JSON list of {"charge": q, "position": [x, y, z]} (bohr)')
+        s.add_argument("--solvent", type=float, default=None, metavar="EPS",
+                       help="solvate the molecule in a conductor-like continuum of dielectric constant EPS (> 1)")
+        s.add_argument("--solvent-model", choices=("cpcm", "cosmo"), default="cpcm", help="f = (eps - 1) / (eps + x): cpcm x = 0 (default), cosmo x = 0.5")
+        s.add_argument("--solvent-density", type=float, default=0.0, metavar="D", help="surface points per Angstrom^2 (default 5)")
         s.add_argument("--cube-margin", type=float, default=4.0, metavar="BOHR", help="margin of --cube around the bounding box of the nuclei (default 4.0)")
     return p
 
@@ -163,6 +173,16 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--follow cannot be combined with --cis or --tdhf")
     if args.follow and args.point_charges:
         p.error("--follow cannot be combined with --point-charges")
+    if args.solvent is None and (args.solvent_model != "cpcm" or args.solvent_density != 0.0):
+        p.error("--solvent-model and --solvent-density require --solvent")
+    if args.solvent is not None:
+        if not (1.0 < args.solvent < float("inf")) or not (0.0 <= args.solvent_density < float("inf")):
+            p.error("--solvent takes a dielectric constant above 1, --solvent-density must not be negative")
+        for flag, on in (("--point-charges", args.point_charges), ("--gradient", args.gradient), ("--stability", args.stability),
+                         ("--follow", args.follow), ("--polarizability", args.polarizability), ("--cis", getattr(args, "cis", 0)),
+                         ("--tdhf", getattr(args, "tdhf", 0))):
+            if on:
+                p.error("--solvent cannot be combined with " + flag)
     if args.cube is not None:
         if cube_what(args.cube, args.command == "uhf") is None:
             p.error("--cube takes density, %sesp, homo, lumo or mo:K" % ("spin, " if args.command == "uhf" else ""))
@@ -198,6 +218,11 @@ def load_point_charges(path: str):
 
 def _embedded(system: MolecularSystem, args):
     """what the drivers run on: the molecule itself, or with --point-charges a handle that carries the charges (one line is printed)"""
+    if args.solvent is not None:
+        handle = hf.System(system)
+        handle.set_solvent(args.solvent, model=args.solvent_model, density=args.solvent_density)
+        print("solvent: %s, epsilon %s, surface elements: %d" % (args.solvent_model, fmt_f(args.solvent), handle.solvent_points()))
+        return handle
     if not args.point_charges:
         return system
     pos, q = load_point_charges(args.point_charges)
@@ -205,6 +230,16 @@ def _embedded(system: MolecularSystem, args):
     handle.set_point_charges(pos, q)
     print("point charges: %d, nuclei-charges energy: %s" % (len(q), fmt_f(handle.point_charge_nuclear_energy())))
     return handle
+
+
+def _solvent_json(sv: "hf.SolventOutput", args) -> dict:
+    return {"model": args.solvent_model, "epsilon": args.solvent, "points": sv.npoints, "nuclear_energy": sv.nuclear,
+            "electronic_energy": sv.electronic, "polarization_energy": sv.polarization_energy(), "total_charge": sv.total_charge}
+
+
+def _print_solvent(sv: "hf.SolventOutput") -> None:
+    print("solvent 1/2 q.v: nuclei %s, electrons %s, total %s" % (fmt_f(sv.nuclear), fmt_f(sv.electronic), fmt_f(sv.polarization_energy())))
+    print("solvent surface charge: " + fmt_f(sv.total_charge))
 
 
 def _gradient(st, pc_rows: list):
@@ -537,6 +572,9 @@ def run_rhf(args) -> int:
     print("nuclear repulsion energy: " + fmt_f(out.nuclear_repulsion))
     print("hartree fock energy: " + fmt_f(out.total_energy()))
     print("orbital energies: " + fmt_vec(out.orbital_energies))
+    solv = system.last_solvent if args.solvent is not None else None
+    if solv is not None:
+        _print_solvent(solv)
     if mp2 is not None:
         _print_mp2(mp2, out.total_energy())
     if grad is not None:
@@ -561,6 +599,8 @@ def run_rhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if solv is not None:
+            doc["solvent"] = _solvent_json(solv, args)
         if args.point_charges:
             doc["point_charges"] = {"count": system.point_charge_count(), "nuclear_energy": out.embedding_nuclear_energy}
             if pc_rows:
@@ -593,15 +633,16 @@ def run_uhf(args) -> int:
     if args.follow:
         return run_follow(args, True, n_alpha, n_beta)
     start = time.perf_counter()
-    s2 = mp2 = grad = stab = dip = pol = cube = chg = None
+    s2 = mp2 = grad = stab = dip = pol = cube = chg = solv = None
     pc_rows = []
     embedded = _embedded(system, args)
     if (not extension and not args.mp2 and not args.gradient and not args.stability and not args.dipole and not args.polarizability and not args.cube
             and not wants_charge_properties(args)):
         out = hf.unrestricted_hartree_fock(embedded, hf.HartreeFockConfig(args.max_iterations, args.epsilon))
+        solv = embedded.last_solvent if args.solvent is not None else None
     else:
         # the same loop (uhf.rs:82-160) driven pass by pass, so that <S^2> and the MP2 energy of the final determinant can be read
-        handle = embedded if args.point_charges else hf.System(system)
+        handle = embedded if args.point_charges or args.solvent is not None else hf.System(system)
         st = hf.ScfStepper(handle, uhf=True, n_alpha=n_alpha, n_beta=n_beta)
         out = None
         try:
@@ -612,7 +653,9 @@ def run_uhf(args) -> int:
                         s2 = st.spin_square()
                     out = hf.UnrestrictedHartreeFockOutput(list(st.orbital_energies(0)), list(st.orbital_energies(1)), e,
                                                            handle.nuclear_repulsion(), it,
-                                                           embedding_nuclear_energy=st.embedding_nuclear_energy())
+                                                           embedding_nuclear_energy=st.embedding_nuclear_energy(),
+                                                           solvent_nuclear_energy=st.solvent_nuclear_energy())
+                    solv = st.solvent()
                     if args.mp2:
                         mp2 = st.mp2(args.frozen_core or 0)
                     if args.gradient:
@@ -636,6 +679,8 @@ def run_uhf(args) -> int:
     print("hartree fock energy: " + fmt_f(out.total_energy()))
     print("orbital energies alpha spin:   " + fmt_vec(out.orbital_energies_alpha))
     print("orbital energies beta spin: " + fmt_vec(out.orbital_energies_beta))
+    if solv is not None:
+        _print_solvent(solv)
     if s2 is not None:
         print("<S^2>: %s (n_alpha %d, n_beta %d)" % (fmt_f(s2), n_alpha, n_beta))
     if mp2 is not None:
@@ -662,6 +707,8 @@ def run_uhf(args) -> int:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
+        if solv is not None:
+            doc["solvent"] = _solvent_json(solv, args)
         if args.point_charges:
             doc["point_charges"] = {"count": len(load_point_charges(args.point_charges)[1]), "nuclear_energy": out.embedding_nuclear_energy}
             if pc_rows:

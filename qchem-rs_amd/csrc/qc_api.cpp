@@ -80,6 +80,7 @@ struct ShardScope {
 
 void qc_system_free(qc_system *S) {
     if (S->comm) { qc_rccl().CommDestroy((ncclComm_t)S->comm); S->comm = nullptr; }
+    S->solvent.reset();                      // (its device buffers go before the device side does)
     qc_device_free(S);
     delete S;
 }

@@ -2,7 +2,7 @@
 // Waals spheres and the constrained least-squares fit.  The potential itself is the point code's (qc_points.hip).
 #include <cmath>
 
-#include "qc_internal.h"
+#include "qc_solvent.h"
 #include "qc_subspace_host.h"
 
 namespace {
@@ -33,27 +33,41 @@ bool qc_espfit_config(const qc_esp_fit *cfg, int *nscales, double *scales, doubl
     return true;
 }
 
+// van der Waals radius in bohr (the table of qchem_hip.h)
+double qc_vdw_radius_bohr(int Z) { return vdw_radius(Z) / QC_BOHR_ANGSTROM; }
+
+// The sphere-point rule, stated once for the ESP-fit grid and the solvent cavity (qc_solvent.h): on the sphere of radius R[A] around atom A
+// the N = ceil(density 4 pi R^2) golden-angle points k = 0 .. N - 1; a point is kept iff its distance to every other atom B is >= R[B].
+// Appends to xyz (and to atom / area) in the order atom, k.
+void qc_sphere_points(const qc_system *S, const double *Rs, double density, std::vector<double> &xyz, std::vector<int32_t> *atom, std::vector<double> *area) {
+    const double golden = M_PI * (3.0 - std::sqrt(5.0));
+    for (int A = 0; A < S->natoms; ++A) {
+        const double R = Rs[A];
+        const long N = (long)std::ceil(density * 4.0 * M_PI * R * R);
+        for (long k = 0; k < N; ++k) {
+            const double z = 1.0 - (2.0 * k + 1.0) / N, rho = std::sqrt(1.0 - z * z), phi = k * golden;
+            const double r[3] = {S->xyz[3 * A] + R * (rho * std::cos(phi)), S->xyz[3 * A + 1] + R * (rho * std::sin(phi)), S->xyz[3 * A + 2] + R * z};
+            bool keep = true;
+            for (int B = 0; B < S->natoms && keep; ++B) {
+                if (B == A) continue;
+                const double d[3] = {r[0] - S->xyz[3 * B], r[1] - S->xyz[3 * B + 1], r[2] - S->xyz[3 * B + 2]};
+                keep = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) >= Rs[B];
+            }
+            if (!keep) continue;
+            xyz.insert(xyz.end(), r, r + 3);
+            if (atom) atom->push_back(A);
+            if (area) area->push_back(4.0 * M_PI * R * R / (double)N);
+        }
+    }
+}
+
 // the grid, in the order scale, atom, k (qchem_hip.h)
 void qc_espfit_grid(const qc_system *S, int nscales, const double *scales, double density, std::vector<double> &xyz) {
     xyz.clear();
-    const double golden = M_PI * (3.0 - std::sqrt(5.0));
+    std::vector<double> R(S->natoms);
     for (int s = 0; s < nscales; ++s) {
-        const double f = scales[s];
-        for (int A = 0; A < S->natoms; ++A) {
-            const double R = f * (vdw_radius(S->Z[A]) / QC_BOHR_ANGSTROM);
-            const long N = (long)std::ceil(density * 4.0 * M_PI * R * R);
-            for (long k = 0; k < N; ++k) {
-                const double z = 1.0 - (2.0 * k + 1.0) / N, rho = std::sqrt(1.0 - z * z), phi = k * golden;
-                const double r[3] = {S->xyz[3 * A] + R * (rho * std::cos(phi)), S->xyz[3 * A + 1] + R * (rho * std::sin(phi)), S->xyz[3 * A + 2] + R * z};
-                bool keep = true;
-                for (int B = 0; B < S->natoms && keep; ++B) {
-                    if (B == A) continue;
-                    const double d[3] = {r[0] - S->xyz[3 * B], r[1] - S->xyz[3 * B + 1], r[2] - S->xyz[3 * B + 2]};
-                    keep = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) >= f * (vdw_radius(S->Z[B]) / QC_BOHR_ANGSTROM);
-                }
-                if (keep) xyz.insert(xyz.end(), r, r + 3);
-            }
-        }
+        for (int A = 0; A < S->natoms; ++A) R[A] = scales[s] * qc_vdw_radius_bohr(S->Z[A]);
+        qc_sphere_points(S, R.data(), density, xyz, nullptr, nullptr);
     }
 }
 

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -274,6 +275,7 @@ struct qc_system {
     double pc_ms[4] = {0, 0, 0, 0};           // phase times of the last embedding call (qc_point_charge_timings)
     long pc_batch = -1;                         // QC_PC_BATCH: charges per batch of the embedding calls (0: the default; -1: not read yet)
     int pc_orient = 0;                          // QC_PC_ORIENT (read with it): 0 chosen from the sizes, 1 lane = record, 2 lane = charge
+    std::shared_ptr<struct QcSolvent> solvent;  // continuum solvation (qc_solvent.h): the cavity of the last qc_set_solvent, null without one
     std::vector<double> pairQ;                  // Schwarz factor sqrt(max_ab (ab|ab)) of each stored pair (empty until the device pass has run)
     double imax = 0.0;                          // max pairQ^2: bound on every |(ij|kl)|
     double schwarz_tau = QC_SCHWARZ_TAU;        // 0: no screening

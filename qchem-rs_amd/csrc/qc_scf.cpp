@@ -12,6 +12,7 @@
 #include <new>
 
 #include "qc_embed.h"
+#include "qc_solvent.h"
 
 namespace {
 
@@ -219,6 +220,12 @@ struct qc_scf_state {
     unsigned pass_seq = 0;                     // sequence number of the last pass whose end the host saw through the pinned word
     bool event_wait = getenv("QC_EVENT_WAIT") != nullptr;      // (A/B switch, read per SCF state: the stream's event instead)
     std::vector<double> pc;                    // the handle's point charges when the state began ([x, y, z, q] each): what its H contains
+    // continuum solvation: the handle's cavity when the state began.  W.H is then H_eff = Hvac + V_R(q) of the state's current
+    // density, renewed behind every pass (solvent_update); solv_q / solv_out: the charges and {1/2 q.v_nuc, 1/2 q.v_elec, sum q} that go with it
+    std::shared_ptr<QcSolvent> solv;
+    DevBuf Hvac, VR, Dsum;                     // (Dsum: the total density of a UHF state, formed per pass)
+    std::vector<double> solv_q, solv_ve;
+    double solv_out[3] = {0.0, 0.0, 0.0};
     ~qc_scf_state() {
         if (S && S->prep.owner == this) { S->prep.prepared = false; S->prep.owner = nullptr; }
         delete diis[0]; delete diis[1];
@@ -418,12 +425,43 @@ int density_and_scalars(qc_system *S, ScfWork &W, const PassPlan &plan, SpinStep
 
 }  // namespace
 
+// A solvated state's reaction field for its current density D: v_elec(D) -> q = K v -> V_R(q) -> W.H = Hvac + V_R, so that the next pass's
+// F = H + G and its energy 1/2 tr[D_new (2 H + G)] contain V_R(D).  That energy counts V_R twice - the definition is
+// 1/2 tr[D_new (2 Hvac + G + V_R)] - and tr(D_new V_R(q_old)) = q_old . v_elec(D_new): *correction = -1/2 q_old . v_elec(D), summed on the
+// host in element order, with q_old the charges in force before this call (`correction` null: the first call, from scf_begin).
+// Synchronous: the handle's stream is drained when it returns.
+static int solvent_update(qc_scf_state *st, double *correction) {
+    qc_system *S = st->S;
+    QcSolvent &Q = *st->solv;
+    const int n = S->nbasis;
+    const double *P = st->D[0].p;
+    if (st->uhf) {
+        qc_axpby(S->stream, n, 1.0, st->D[0].p, 1.0, st->D[1].p, st->Dsum.p);
+        P = st->Dsum.p;
+    }
+    std::vector<double> q(Q.M);
+    st->solv_ve.resize(Q.M);
+    const int rc = qc_solvent_response_device(S, Q, P, q.data(), st->solv_ve.data(), st->VR.p, st->solv_out);
+    if (rc != QC_OK) return rc;
+    if (correction) {
+        double dot = 0.0;
+        for (int64_t i = 0; i < Q.M; ++i) dot += st->solv_q[i] * st->solv_ve[i];
+        *correction = -0.5 * dot;
+    }
+    st->solv_q.swap(q);
+    qc_axpby(S->stream, n, 1.0, st->Hvac.p, 1.0, st->VR.p, st->W.H.p);
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    return QC_OK;
+}
+
 // (hDa / hDb non-null: the caller's densities, host, in place of the Hueckel guess - qc_scf_begin_*_from)
 static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_state **out, const double *hDa = nullptr, const double *hDb = nullptr) {
     if (!S || !out) return QC_ERR_INVALID;
     const double t0 = qc_now_ms();
     static const bool sdbg = getenv("QC_SETUP_DEBUG") != nullptr;
     QcLap lap{"setup", sdbg, t0};
+    // a continuum goes with one whole direct build in vacuum: no shards, no stored tensor, no point charges (checked before the device is touched)
+    if (S->solvent && (S->comm || S->nranks != 1 || S->fock_mode == 1 || !S->pc.empty())) return QC_ERR_UNSUPPORTED;
     int rc = qc_device_init(S);
     if (rc != QC_OK) return rc;
     lap("qc_device_init (total)");
@@ -462,6 +500,13 @@ static int scf_begin(qc_system *S, bool uhf, int n_alpha, int n_beta, qc_scf_sta
         else if ((rc = huckel_density(S, st->W, h_eht, st->nocc[s], uhf ? 1.0 : 2.0, st->D[s].p)) != QC_OK) return rc;
     }
     lap("Hueckel guess");
+    if (S->solvent) {                                                    // the reaction field of the starting density (the guess itself is the vacuum one)
+        st->solv = S->solvent;
+        if (st->Hvac.alloc(nn) != QC_OK || st->VR.alloc(nn) != QC_OK || (uhf && st->Dsum.alloc(nn) != QC_OK)) return QC_ERR_HIP;
+        QC_HIP_CHECK(hipMemcpyAsync(st->Hvac.p, st->W.H.p, nn * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+        if ((rc = solvent_update(st, nullptr)) != QC_OK) return rc;
+        lap("solvent: K, first reaction field");
+    }
     if (S->fock_mode == 1) {
         // the reference's conventional SCF: ERI tensor once (rhf.rs:45), antisymmetrised copy (rhf.rs:58-62), dense
         // contraction per pass.  8 n^4 bytes per tensor; two of them live during the build.
@@ -742,6 +787,11 @@ static int scf_iterate(qc_scf_state *st, double *energy, double *rms_out) {
     st->tm.pass_seen();
     if ((rc = repeat_eigensolves(st, plan, sp, ev, &redo)) != QC_OK) return rc;
     accept_pass(st, redo, energy, rms_out);
+    if (st->solv) {                                                       // the reaction field of the new density, and this pass's energy by its definition
+        double corr = 0.0;
+        if ((rc = solvent_update(st, &corr)) != QC_OK) return rc;
+        if (energy) *energy += corr;
+    }
     qc_stamp("pass end");
     qc_stamp_flush();
     return QC_OK;
@@ -771,6 +821,7 @@ static int scf_run(qc_system *S, const qc_hf_config *cfg, qc_hf_output *out, boo
             out->electronic_energy = e; out->iterations = it;
             QC_HIP_CHECK(hipMemcpy(out->orbital_energies, st->ws.p, n * sizeof(double), hipMemcpyDeviceToHost));
             if (uhf) QC_HIP_CHECK(hipMemcpy(out->orbital_energies_beta, st->ws.p + n, n * sizeof(double), hipMemcpyDeviceToHost));
+            if (st->solv) { st->solv->last = {st->solv_out[0], st->solv_out[1], st->solv_out[2], st->solv->M}; st->solv->have_last = true; }
             status = QC_OK;
             break;
         }
@@ -866,6 +917,7 @@ int qc_scf_mp2(qc_scf_state *st, int32_t n_frozen, qc_mp2_output *out) {
 }
 int qc_scf_gradient(qc_scf_state *st, double *grad) {
     if (!st || !grad) return QC_ERR_INVALID;
+    if (st->solv) return QC_ERR_UNSUPPORTED;                             // (no cavity derivative)
     int rc = ran_on_one_rank(st);
     if (rc != QC_OK) return rc;
     qc_system *S = st->S;
@@ -906,6 +958,7 @@ int qc_scf_stability_dim(qc_scf_state *st, int kind) {
 }
 int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors) {
     if (!st || !io) return QC_ERR_INVALID;
+    if (st->solv) return QC_ERR_UNSUPPORTED;                             // (the Hessian lacks the solvent's response term; so do the four below)
     if (io->kind < 0 || io->kind > (st->uhf ? 0 : 1) || io->nroots < 1 || io->nroots > 8 || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
     qc_system *S = st->S;
     const int dim = qc_stability_dim(S->nbasis, st->uhf, st->nocc);
@@ -917,6 +970,7 @@ int qc_scf_stability(qc_scf_state *st, qc_stability *io, double *vectors) {
 }
 int qc_scf_rotated_density(qc_scf_state *st, int kind, const double *x, double angle, double *Da, double *Db, double *energy) {
     if (!st || !x || !Da || !Db || kind < 0 || kind > (st->uhf ? 0 : 1) || angle != angle) return QC_ERR_INVALID;
+    if (st->solv) return QC_ERR_UNSUPPORTED;
     qc_system *S = st->S;
     if (qc_stability_dim(S->nbasis, st->uhf, st->nocc) <= 0) return QC_ERR_INVALID;
     const int rc = ran_on_one_rank(st);
@@ -1077,6 +1131,13 @@ int qc_scf_point_charge_gradient(qc_scf_state *st, double *grad) {
     for (int64_t c = 0; c < npc; ++c) for (int k = 0; k < 3; ++k) grad[3 * c + k] *= -st->pc[4 * c + 3];
     return QC_OK;
 }
+// the reaction field that goes with the state's current density (solvent_update)
+int qc_scf_solvent(qc_scf_state *st, qc_solvent_energy *out, double *q) {
+    if (!st || !out || !st->solv) return QC_ERR_INVALID;
+    *out = {st->solv_out[0], st->solv_out[1], st->solv_out[2], st->solv->M};
+    if (q) std::copy(st->solv_q.begin(), st->solv_q.end(), q);
+    return QC_OK;
+}
 int64_t qc_scf_point_charge_count(const qc_scf_state *st) { return st ? (int64_t)(st->pc.size() / 4) : QC_ERR_INVALID; }
 double qc_scf_point_charge_nuclear_energy(const qc_scf_state *st) { return st ? qc_pc_nuclear_energy(st->S, st->pc) : 0.0; }
 // orbitals first .. first + count - 1 of `spin`, counted from 0 in the order of qc_scf_orbital_energies; out: count x npts
@@ -1092,6 +1153,7 @@ int qc_scf_orbitals_on_points(qc_scf_state *st, int spin, int first, int count, 
 
 int qc_scf_polarizability(qc_scf_state *st, qc_polarizability *io, double *response) {
     if (!st || !io || io->max_iterations < 0 || !(io->tol >= 0.0)) return QC_ERR_INVALID;
+    if (st->solv) return QC_ERR_UNSUPPORTED;
     qc_system *S = st->S;
     const int rc = ran_on_one_rank(st);
     if (rc != QC_OK) return rc;
@@ -1103,7 +1165,7 @@ int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors) {
     if (!st || !io || st->passes == 0) return QC_ERR_INVALID;
     if (io->method < 0 || io->method > 1 || io->kind < 0 || io->kind > 1 || io->nroots < 1 || io->nroots > 8 || io->max_iterations < 0 || !(io->tol >= 0.0))
         return QC_ERR_INVALID;
-    if (st->uhf) return QC_ERR_UNSUPPORTED;
+    if (st->uhf || st->solv) return QC_ERR_UNSUPPORTED;
     qc_system *S = st->S;
     const int dim = qc_stability_dim(S->nbasis, false, st->nocc);
     if (dim <= 0 || io->nroots > dim) return QC_ERR_INVALID;
@@ -1112,7 +1174,7 @@ int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors) {
 }
 int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *AmB) {
     if (!st || st->passes == 0 || kind < 0 || kind > 1) return QC_ERR_INVALID;
-    if (st->uhf) return QC_ERR_UNSUPPORTED;
+    if (st->uhf || st->solv) return QC_ERR_UNSUPPORTED;
     qc_system *S = st->S;
     if (qc_stability_dim(S->nbasis, false, st->nocc) <= 0) return QC_ERR_INVALID;
     if (const int rc = ran_on_one_rank(st)) return rc;                  // (a pass has run, see above: the number of ranks)
@@ -1129,7 +1191,7 @@ int qc_scf_begin_uhf_from(qc_system *S, int n_alpha, int n_beta, const double *D
 int qc_scf_matrix(qc_scf_state *st, int which, double *out) {
     if (!st || !out || which < 0 || which > 2) return QC_ERR_INVALID;
     const size_t nn = (size_t)st->S->nbasis * st->S->nbasis;
-    const double *src = which == 0 ? st->W.S.p : which == 1 ? st->W.H.p : st->W.X.p;
+    const double *src = which == 0 ? st->W.S.p : which == 1 ? (st->solv ? st->Hvac.p : st->W.H.p) : st->W.X.p;   // (a solvated state: the vacuum H)
     QC_HIP_CHECK(hipMemcpy(out, src, nn * sizeof(double), hipMemcpyDeviceToHost));
     return QC_OK;
 }

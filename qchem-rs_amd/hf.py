@@ -55,13 +55,18 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_set_point_charges", "qc_point_charge_count", "qc_point_charge_nuclear_energy", "qc_scf_point_charge_count",
            "qc_scf_point_charge_nuclear_energy", "qc_point_charge_matrix", "qc_point_charge_matrix_gpu", "qc_field_matrix",
            "qc_field_on_points", "qc_scf_field_on_points", "qc_point_charge_gradient", "qc_scf_point_charge_gradient",
-           "qc_point_charge_timings"]
+           "qc_point_charge_timings",
+           "qc_spd_inverse", "qc_set_solvent", "qc_solvent_surface", "qc_solvent_matrix", "qc_solvent_matrix_gpu", "qc_solvent_response",
+           "qc_scf_solvent", "qc_solvent_last", "qc_solvent_timings"]
 
 POPULATION_SCHEMES = {"mulliken": 0, "lowdin": 1}
 BOHR_ANGSTROM = 0.529177210903   # QC_BOHR_ANGSTROM in include/qchem_hip.h
 
 
 EXCITATION_METHODS = {"cis": 0, "tdhf": 1}
+
+
+SOLVENT_MODELS = {"cpcm": 0.0, "cosmo": 0.5}     # x of f = (eps - 1) / (eps + x)
 
 
 class QcError(RuntimeError):
@@ -253,6 +258,32 @@ class ExcitationsOutput:
     vectors: Optional[np.ndarray] = None
 
 
+class _Solvent(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("x", C.c_double), ("scale", C.c_double), ("density", C.c_double)]
+
+
+class _SolventEnergy(C.Structure):
+    _fields_ = [("nuclear", C.c_double), ("electronic", C.c_double), ("total_charge", C.c_double), ("npoints", C.c_int64)]
+
+
+@dataclass
+class SolventOutput:
+    """The reaction field of a density (qc_scf_solvent / qc_solvent_last): nuclear = 1/2 q.v_nuc, electronic = 1/2 q.v_elec (their sum is
+    G_pol), total_charge = sum q, npoints = M; charges: q (M,) where the call returns them."""
+    nuclear: float
+    electronic: float
+    total_charge: float
+    npoints: int
+    charges: Optional[np.ndarray] = None
+
+    def polarization_energy(self) -> float:
+        return self.nuclear + self.electronic
+
+    @classmethod
+    def _from(cls, o: "_SolventEnergy", q=None) -> "SolventOutput":
+        return cls(o.nuclear, o.electronic, o.total_charge, int(o.npoints), q)
+
+
 class WorkStats(C.Structure):
     _fields_ = [("quartets", C.c_int64), ("prim_quartets", C.c_int64), ("bytes_alg", C.c_double),
                 ("flops_alg", C.c_double), ("nclasses", C.c_int32), ("quartets_enumerated", C.c_int64),
@@ -375,6 +406,15 @@ def lib():
         L.qc_point_charge_gradient.argtypes = [vp, C.c_int, vp, vp]
         L.qc_scf_point_charge_gradient.argtypes = [vp, vp]
         L.qc_point_charge_timings.argtypes = [vp, vp]
+        L.qc_spd_inverse.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_set_solvent.argtypes = [vp, C.POINTER(_Solvent), vp]
+        L.qc_solvent_surface.argtypes = [vp, C.c_int64, vp, vp, vp]; L.qc_solvent_surface.restype = C.c_int64
+        L.qc_solvent_matrix.argtypes = [vp, vp]
+        L.qc_solvent_matrix_gpu.argtypes = [vp, vp, vp]
+        L.qc_solvent_response.argtypes = [vp, vp, vp, vp, vp]
+        L.qc_scf_solvent.argtypes = [vp, C.POINTER(_SolventEnergy), vp]
+        L.qc_solvent_last.argtypes = [vp, C.POINTER(_SolventEnergy)]
+        L.qc_solvent_timings.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -401,6 +441,7 @@ class System:
                                       mol.shell_L, mol.shell_pure, mol.shell_nprim, mol.exponents, mol.coefficients,
                                       C.byref(self._h)), "qc_system_create")
         self.n = lib().qc_nbasis(self._h)
+        self.last_solvent = None     # SolventOutput of the last run of this module's drivers on the handle (None: in vacuum, or that run did not converge)
 
     def close(self):
         if self._h:
@@ -597,6 +638,78 @@ class System:
     def point_charge_timings(self):
         """Phase times (ms) of the handle's last embedding call: upload, Hermite sums over the charges, assembly or contraction, download."""
         ms = np.zeros(4); _check(lib().qc_point_charge_timings(self._h, _ptr(ms)), "qc_point_charge_timings"); return ms
+
+    # ---- conductor-like continuum solvation (DESIGN.md 3.14)
+    def set_solvent(self, epsilon=None, model: str = "cpcm", scale: float = 0.0, density: float = 0.0, radii=None, x=None):
+        """Put the molecule into a conductor-like continuum of dielectric constant `epsilon` (qc_set_solvent, host only), or with
+        epsilon=None take it out again.  model: "cpcm" (x = 0) or "cosmo" (x = 0.5), or x itself; scale: factor of the radii (0: 1.2);
+        density: surface points per Angstrom^2 (0: 5); radii: per-atom radii in bohr before scaling (None: the van der Waals table).
+        SCF states begun afterwards are solvated; states that are alive keep theirs."""
+        if epsilon is None:
+            _check(lib().qc_set_solvent(self._h, None, None), "qc_set_solvent")
+            return
+        if x is None:
+            if model not in SOLVENT_MODELS:
+                raise QcError(f"qc_set_solvent: model must be one of {sorted(SOLVENT_MODELS)}")
+            x = SOLVENT_MODELS[model]
+        cfg = _Solvent(float(epsilon), float(x), float(scale), float(density))
+        r = None
+        if radii is not None:
+            r = np.ascontiguousarray(radii, np.float64).reshape(-1)
+            if len(r) != len(self.mol.atoms):
+                raise QcError("qc_set_solvent: one radius per atom")
+        _check(lib().qc_set_solvent(self._h, C.byref(cfg), _ptr(r) if r is not None else None), "qc_set_solvent")
+
+    def solvent_points(self) -> int:
+        """M, the number of surface elements of the handle's cavity."""
+        return int(_check(lib().qc_solvent_surface(self._h, 0, None, None, None), "qc_solvent_surface"))
+
+    def solvent_surface(self):
+        """(xyz (M, 3), area (M,), atom (M,) int32): the surface elements of the handle's cavity (qc_solvent_surface)."""
+        M = self.solvent_points()
+        xyz, area, atom = np.zeros((M, 3)), np.zeros(M), np.zeros(M, np.int32)
+        _check(lib().qc_solvent_surface(self._h, M, _ptr(xyz), _ptr(area), _ptr(atom)), "qc_solvent_surface")
+        return xyz, area, atom
+
+    def solvent_matrix(self, gpu: bool = False, inverse: bool = False):
+        """(M, M): S of the cavity - qc_solvent_matrix on the host, or with gpu=True the assembly kernel; inverse=True (GPU): (S, K) with
+        K = -f S^-1 as the SCF uses it (qc_solvent_matrix_gpu)."""
+        M = self.solvent_points()
+        Sm = np.zeros((M, M))
+        if not gpu and not inverse:
+            _check(lib().qc_solvent_matrix(self._h, _ptr(Sm)), "qc_solvent_matrix")
+            return Sm
+        K = np.zeros((M, M)) if inverse else None
+        _check(lib().qc_solvent_matrix_gpu(self._h, _ptr(Sm), _ptr(K) if inverse else None), "qc_solvent_matrix_gpu")
+        return (Sm, K) if inverse else Sm
+
+    def solvent_response(self, D):
+        """(q (M,), V_R (n, n), (1/2 q.v_nuc, 1/2 q.v_elec)) of the total density D (qc_solvent_response, GPU)."""
+        Dm = self._density_arg(D, "qc_solvent_response")
+        q, V, e = np.zeros(self.solvent_points()), np.zeros((self.n, self.n)), np.zeros(2)
+        _check(lib().qc_solvent_response(self._h, _ptr(Dm), _ptr(q), _ptr(V), _ptr(e)), "qc_solvent_response")
+        return q, V, (float(e[0]), float(e[1]))
+
+    def solvent_last(self) -> "SolventOutput":
+        """The reaction field at the end of the last one-shot run on this handle (qc_solvent_last)."""
+        o = _SolventEnergy()
+        _check(lib().qc_solvent_last(self._h, C.byref(o)), "qc_solvent_last")
+        return SolventOutput._from(o)
+
+    def solvent_timings(self):
+        """ms: the one-off set-up (S, factorisation, inverse), then of the last response: the potential call, the reaction kernel
+        alone (device events), the V_R call."""
+        ms = np.zeros(4); _check(lib().qc_solvent_timings(self._h, _ptr(ms)), "qc_solvent_timings"); return ms
+
+    def spd_inverse(self, A):
+        """The inverse of a symmetric positive-definite matrix by the device Cholesky factorisation (qc_spd_inverse); QcError when a pivot
+        is <= 0 or not finite."""
+        Am = np.ascontiguousarray(A, np.float64)
+        if Am.ndim != 2 or Am.shape[0] != Am.shape[1] or Am.shape[0] < 1:
+            raise QcError("qc_spd_inverse: A must be n x n, n >= 1")
+        out = np.zeros_like(Am)
+        _check(lib().qc_spd_inverse(self._h, Am.shape[0], _ptr(Am), _ptr(out)), "qc_spd_inverse")
+        return out
 
     def eri(self):
         I = np.zeros((self.n,) * 4); _check(lib().qc_eri_full(self._h, I.reshape(-1)), "qc_eri_full"); return I
@@ -921,6 +1034,22 @@ class ScfStepper:
         """E_nq of the charges the state began with: total energy = electronic + nuclear repulsion + this."""
         return lib().qc_scf_point_charge_nuclear_energy(self._st)
 
+    def solvent(self, charges: bool = False) -> Optional["SolventOutput"]:
+        """The reaction field that goes with the state's current density (qc_scf_solvent), or None for a state in vacuum."""
+        o = _SolventEnergy()
+        if lib().qc_scf_solvent(self._st, C.byref(o), None) != QC_OK:
+            return None
+        q = None
+        if charges:
+            q = np.zeros(int(o.npoints))
+            _check(lib().qc_scf_solvent(self._st, C.byref(o), _ptr(q)), "qc_scf_solvent")
+        return SolventOutput._from(o, q)
+
+    def solvent_nuclear_energy(self) -> float:
+        """1/2 q.v_nuc of a solvated state (0 in vacuum): what the total energy adds to electronic + nuclear repulsion."""
+        s = self.solvent()
+        return s.nuclear if s is not None else 0.0
+
     def point_charge_gradient(self):
         """(npc, 3): dE/dR_c at the state for the charges it began with, -q_c E(R_c) (qc_scf_point_charge_gradient); the state is left
         as it was."""
@@ -1066,9 +1195,10 @@ class RestrictedHartreeFockOutput:
     iterations: int
     timings_ms: dict = field(default_factory=dict)
     embedding_nuclear_energy: float = 0.0    # E_nq of the point charges the run was embedded in (System.set_point_charges)
+    solvent_nuclear_energy: float = 0.0      # 1/2 q.v_nuc of the continuum the run was solvated in (System.set_solvent)
 
     def total_energy(self) -> float:
-        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy
+        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy + self.solvent_nuclear_energy
 
 
 @dataclass
@@ -1080,9 +1210,10 @@ class UnrestrictedHartreeFockOutput:
     iterations: int
     timings_ms: dict = field(default_factory=dict)
     embedding_nuclear_energy: float = 0.0    # E_nq of the point charges the run was embedded in (System.set_point_charges)
+    solvent_nuclear_energy: float = 0.0      # 1/2 q.v_nuc of the continuum the run was solvated in (System.set_solvent)
 
     def total_energy(self) -> float:
-        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy
+        return self.electronic_energy + self.nuclear_repulsion + self.embedding_nuclear_energy + self.solvent_nuclear_energy
 
 
 def _as_system(system) -> System:
@@ -1091,6 +1222,7 @@ def _as_system(system) -> System:
 
 def _run(fn, system, config, uhf):
     sysh = _as_system(system)
+    sysh.last_solvent = None
     n = sysh.n
     wa, wb = np.zeros(n), np.zeros(n)
     cfg = _Config(int(config.max_iterations), float(config.epsilon), int(config.n_alpha), int(config.n_beta))
@@ -1104,11 +1236,14 @@ def _run(fn, system, config, uhf):
     if rc == QC_NOT_CONVERGED:
         return None                                       # rhf.rs:106-107
     t = dict(setup=out.ms_setup, fock=out.ms_fock_total, linalg=out.ms_linalg_total, total=out.ms_total, tuner=out.ms_tuner)
+    o = _SolventEnergy()
+    sysh.last_solvent = SolventOutput._from(o) if lib().qc_solvent_last(sysh.handle, C.byref(o)) == QC_OK else None   # (None: no solvent)
+    e_solv = sysh.last_solvent.nuclear if sysh.last_solvent is not None else 0.0
     if uhf:
         return UnrestrictedHartreeFockOutput(wa.tolist(), wb.tolist(), out.electronic_energy, out.nuclear_repulsion,
-                                             int(out.iterations), t, sysh.point_charge_nuclear_energy())
+                                             int(out.iterations), t, sysh.point_charge_nuclear_energy(), e_solv)
     return RestrictedHartreeFockOutput(wa.tolist(), out.electronic_energy, out.nuclear_repulsion, int(out.iterations), t,
-                                       sysh.point_charge_nuclear_energy())
+                                       sysh.point_charge_nuclear_energy(), e_solv)
 
 
 def restricted_hartree_fock(system, config: HartreeFockConfig) -> Optional[RestrictedHartreeFockOutput]:
@@ -1123,6 +1258,7 @@ def _stepped(system, config: HartreeFockConfig, uhf: bool, after):
     """The reference's loop (rhf.rs:67-108 / uhf.rs:82-167) driven pass by pass, as cli.run_uhf does, then `after` (MP2, gradient) on the
     converged state."""
     sysh = _as_system(system)
+    sysh.last_solvent = None
     if uhf:
         n_alpha, n_beta = int(config.n_alpha), int(config.n_beta)
         st = ScfStepper(sysh, uhf=True, n_alpha=n_alpha, n_beta=n_beta, stop_rule=float(config.epsilon))
@@ -1133,12 +1269,13 @@ def _stepped(system, config: HartreeFockConfig, uhf: bool, after):
             e, rms = st.iterate()
             if (rms / 2.0 if uhf else rms) < config.epsilon:                # uhf.rs:139 / rhf.rs:94
                 t = st.timings()
+                sysh.last_solvent = st.solvent()
                 if uhf:
                     out = UnrestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), st.orbital_energies(1).tolist(), e,
-                                                        sysh.nuclear_repulsion(), it, t, st.embedding_nuclear_energy())
+                                                        sysh.nuclear_repulsion(), it, t, st.embedding_nuclear_energy(), st.solvent_nuclear_energy())
                 else:
                     out = RestrictedHartreeFockOutput(st.orbital_energies(0).tolist(), e, sysh.nuclear_repulsion(), it, t,
-                                                      st.embedding_nuclear_energy())
+                                                      st.embedding_nuclear_energy(), st.solvent_nuclear_energy())
                 return out, after(st)
         return None
     finally:

@@ -42,7 +42,8 @@ def kernels(obj):
 
 def demangle(names):
     p = subprocess.run(["c++filt"], input="\n".join(names), stdout=subprocess.PIPE, text=True)
-    return dict(zip(names, (re.sub(r"^void |\(.*$", "", l) for l in p.stdout.splitlines())))
+    # (kernels in an unnamed namespace demangle to "(anonymous namespace)::name<..>(args)": that prefix goes, then the argument list)
+    return dict(zip(names, (re.sub(r"^void |\(.*$", "", l.replace("(anonymous namespace)::", "")) for l in p.stdout.splitlines())))
 
 
 def waves(vgpr, agpr):
