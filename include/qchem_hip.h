@@ -555,6 +555,40 @@ int qc_scf_excitations(qc_scf_state *st, qc_excitations *io, double *vectors /* 
  * qc_scf_excitations (kind 0 or 1). */
 int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *AmB);
 
+/* ---- closed-shell coupled cluster with singles and doubles (CCSD) of an RHF state (after SCF, not in the reference), at the state's last C
+ * and orbital energies as qc_scf_mp2.  The canonical-orbital formula is used: the occupied-virtual block of the Fock matrix and the
+ * off-diagonal elements of its diagonal blocks are taken as zero, which they are at convergence (as for qc_scf_stability); on a state that
+ * is not converged the result is the CCSD of that approximation.  Spin-adapted amplitudes t1[i, a] and t2[i, j, a, b] with
+ * t_ij^ab = t_ji^ba over o = nocc - n_frozen active occupied and v virtual orbitals;
+ *   E = sum_ijab (2 (ia|jb) - (ib|ja)) (t_ij^ab + t_i^a t_j^b).
+ * The AO tensor is built in HBM (as qc_scf_mp2) and transformed to the blocks (ij|kl), (ia|jk), (ij|ab), (ia|jb), (ia|bc), (ab|cd); the
+ * call needs about 8 max(n^4 + (o + v) n^3, 2 v^4 + ...) bytes of free HBM, QC_ERR_UNSUPPORTED when the device cannot hold them.  Nothing is
+ * cached between calls.  The iteration starts from t1 = 0, t2 = (ia|jb) / D, updates by the denominators and extrapolates by DIIS over
+ * the vectors [t1 | t2] with the error t_new - t_old.
+ * In:  n_frozen (lowest orbitals left out), max_iterations (0: 100), diis_size (0: 8; 1: no extrapolation; at most 12), tol: the largest
+ *      |t_new - t_old| over T1 and T2 at which the iteration stops (0: 1e-8).
+ * Out: e_mp2 (from the first T2) and e_ccsd, correlation energies in Eh; t1_diagnostic = sqrt(sum t1^2 / o), the largest |t1| and |t2|,
+ *      the last max |t_new - t_old|; iterations, converged; wall times of the call, the AO tensor, the transformation and the iteration (ms).
+ * t1 (o x v) and t2 (o^2 x v^2), nullable, host: the last amplitudes.
+ * QC_NOT_CONVERGED when the iterations run out (the outputs are filled).  QC_ERR_INVALID, checked before the device is touched: a null st
+ * or io, a state before its first qc_scf_iterate, n_frozen < 0 or >= nocc, no virtual orbital, a negative or NaN tol, a negative
+ * max_iterations, diis_size < 0 or > 12.  QC_ERR_UNSUPPORTED: a UHF state, a solvated state, a sharded handle or one with a communicator, too
+ * little free memory.  Bitwise reproducible from call to call and across fresh handles (no atomics, fixed-order reductions, a split-k
+ * GEMM whose slice count depends on the shape alone).  The state is left exactly as it was (no Fock build runs). */
+typedef struct {
+    int32_t n_frozen, max_iterations, diis_size, reserved0;
+    double tol;
+    double e_mp2, e_ccsd;
+    double t1_diagnostic, t1_max, t2_max, residual;
+    int32_t iterations, converged, reserved1[2];
+    double ms_total, ms_tensor, ms_transform, ms_solve;
+} qc_ccsd;
+int qc_scf_ccsd(qc_scf_state *st, qc_ccsd *io, double *t1 /* nullable, host, o_act x v */, double *t2 /* nullable, host, o_act^2 x v^2 */);
+/* For tests and timing: C = alpha A B + beta C of dense row-major host matrices (m x k, k x n, m x n) on the GPU, which 0 through the
+ * one-wave-per-tile GEMM, 1 through the split-k GEMM of the CCSD ladder.  reps > 1 repeats the product on the same device buffers; ms
+ * (nullable, max(reps, 1) doubles) takes the device time of each.  QC_ERR_INVALID: a bad which, m, n, k < 1, null pointers, reps < 0. */
+int qc_debug_gemm(int which, int m, int n, int k, double alpha, const double *A, const double *B, double beta, double *C, int reps, double *ms);
+
 /* qc_scf_begin_rhf / qc_scf_begin_uhf with the caller's densities (host, n*n, in the convention of qc_scf_density: the RHF density carries
  * the factor 2) in place of the Hueckel guess: DIIS windows empty, first eigensolve cold.  Null densities are QC_ERR_INVALID (checked
  * before the device is touched). */

@@ -9,6 +9,9 @@ Three additions, all opt-in:
     0 the behaviour is the reference's N/2 rule (uhf.rs:43-45);
   * `--mp2 [--frozen-core N]` adds the MP2 correlation energy of the converged determinant after the reference's lines (the SCF
     then runs pass by pass through hf.ScfStepper; its lines are those of the run without the flag);
+  * `rhf --ccsd [--frozen-core N]` adds the closed-shell CCSD correlation energy of the converged determinant after any MP2 lines: the
+    MP2 (from the first T2, under a name of its own) and CCSD correlation energies, the total energy, the T1 diagnostic and the iteration count; `--json` then carries a "ccsd"
+    object; the exit status is 101 when the amplitudes do not converge;
   * `--gradient` adds the analytic nuclear gradient of the converged determinant (Eh/bohr), one line per atom - index, Z, gx, gy,
     gz - after the reference's lines and any MP2 lines; `--json` then carries a "gradient" array;
   * `--stability` adds the lowest eigenvalue of the orbital Hessian of the converged determinant (rhf: triplet and singlet kind; uhf:
@@ -110,7 +113,7 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--json", action="store_true", help="also print one JSON object with full-precision fields")
         s.add_argument("--mp2", action="store_true", help="also compute the MP2 correlation energy of the converged determinant")
         s.add_argument("--frozen-core", type=int, default=None, metavar="N",
-                       help="leave the lowest N orbitals of each spin out of the MP2 sums (requires --mp2)")
+                       help="leave the lowest N orbitals of each spin out of the MP2 and CCSD sums (requires --mp2 or --ccsd)")
         s.add_argument("--gradient", action="store_true", help="also print the analytic nuclear gradient (Eh/bohr) of the converged determinant")
         s.add_argument("--stability", action="store_true", help="also print the lowest eigenvalue(s) of the orbital Hessian and whether the determinant is a minimum")
         s.add_argument("--dipole", action="store_true", help="also print the dipole moment of the converged determinant (a.u. and Debye)")
@@ -120,6 +123,7 @@ def build_parser() -> argparse.ArgumentParser:
         s.add_argument("--charges", default=None, metavar="SCHEMES", help="also print atomic charges: a comma list of mulliken, lowdin, esp")
         s.add_argument("--bond-orders", action="store_true", help="also print the Mayer bond orders above 0.05")
         if name == "rhf":
+            s.add_argument("--ccsd", action="store_true", help="also compute the CCSD correlation energy of the converged determinant (combines with --frozen-core)")
             s.add_argument("--cis", type=int, default=0, metavar="N", help="also print the lowest N CIS excited states (1..8)")
             s.add_argument("--tdhf", type=int, default=0, metavar="N", help="also print the lowest N TDHF (RPA) excited states (1..8)")
             s.add_argument("--triplets", action="store_true", help="triplet instead of singlet excited states (requires --cis or --tdhf)")
@@ -151,8 +155,8 @@ def cube_what(text: str, uhf: bool):
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p = build_parser()
     args = p.parse_args(argv)
-    if args.frozen_core is not None and not args.mp2:
-        p.error("--frozen-core requires --mp2")
+    if args.frozen_core is not None and not (args.mp2 or getattr(args, "ccsd", False)):
+        p.error("--frozen-core requires --mp2" + (" or --ccsd" if args.command == "rhf" else ""))
     if args.frozen_core is not None and args.frozen_core < 0:
         p.error("--frozen-core must not be negative")
     if args.follow and (args.mp2 or args.gradient or args.dipole or args.polarizability):
@@ -171,6 +175,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--triplets requires --cis or --tdhf")
         if args.follow and (args.cis or args.tdhf):
             p.error("--follow cannot be combined with --cis or --tdhf")
+        if args.follow and args.ccsd:
+            p.error("--follow cannot be combined with --ccsd")
     if args.follow and args.point_charges:
         p.error("--follow cannot be combined with --point-charges")
     if args.solvent is None and (args.solvent_model != "cpcm" or args.solvent_density != 0.0):
@@ -180,7 +186,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--solvent takes a dielectric constant above 1, --solvent-density must not be negative")
         for flag, on in (("--point-charges", args.point_charges), ("--gradient", args.gradient), ("--stability", args.stability),
                          ("--follow", args.follow), ("--polarizability", args.polarizability), ("--cis", getattr(args, "cis", 0)),
-                         ("--tdhf", getattr(args, "tdhf", 0))):
+                         ("--tdhf", getattr(args, "tdhf", 0)), ("--ccsd", getattr(args, "ccsd", False))):
             if on:
                 p.error("--solvent cannot be combined with " + flag)
     if args.cube is not None:
@@ -200,6 +206,21 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
 def _print_mp2(mp2: "hf.Mp2Output", e_hf: float) -> None:
     print("mp2 correlation energy: " + fmt_f(mp2.e_corr))
     print("mp2 total energy: " + fmt_f(e_hf + mp2.e_corr))
+
+
+def _print_ccsd(cc: "hf.CcsdOutput", e_hf: float) -> None:
+    # (ten decimals: the lines are not the reference's, and a correlation energy to three decimals is of little use)
+    print("ccsd first-iteration (mp2) correlation energy: %.10f" % cc.e_mp2)
+    print("ccsd correlation energy: %.10f" % cc.e_ccsd)
+    print("ccsd total energy: %.10f" % (e_hf + cc.e_ccsd))
+    print("ccsd t1 diagnostic: %.6f" % cc.t1_diagnostic)
+    print("ccsd %s after %d iterations" % ("converged" if cc.converged else "did not converge", cc.iterations))
+
+
+def _ccsd_json(cc: "hf.CcsdOutput", e_hf: float) -> dict:
+    return {"e_mp2": cc.e_mp2, "e_ccsd": cc.e_ccsd, "e_total": e_hf + cc.e_ccsd, "t1_diagnostic": cc.t1_diagnostic, "t1_max": cc.t1_max,
+            "t2_max": cc.t2_max, "residual": cc.residual, "iterations": cc.iterations, "converged": cc.converged, "n_frozen": cc.n_frozen,
+            "timings_ms": {"total": cc.ms_total, "tensor": cc.ms_tensor, "transform": cc.ms_transform, "solve": cc.ms_solve}}
 
 
 def _mp2_json(mp2: "hf.Mp2Output", e_hf: float) -> dict:
@@ -545,17 +566,17 @@ def run_rhf(args) -> int:
     basis = BasisSet.load(args.basis_set)                                   # main.rs:76
     system = MolecularSystem.load(args.molecule, basis)                     # main.rs:77
     start = time.perf_counter()
-    mp2 = grad = stab = dip = pol = cube = chg = None
+    mp2 = grad = stab = dip = pol = cube = chg = cc = None
     exc, pc_rows = [], []
     molecule, system = system, _embedded(system, args)
     config = hf.HartreeFockConfig(args.max_iterations, args.epsilon)
-    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.cube or wants_charge_properties(args):
+    if args.stability or args.dipole or args.polarizability or args.cis or args.tdhf or args.ccsd or args.cube or wants_charge_properties(args):
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None,
                                                              _gradient(st, pc_rows) if args.gradient else None,
                                                              _stability(st, False) if args.stability else None) + _properties(st, args)
                                                             + (_excitations(st, args), _cube(st, molecule, args, False) if args.cube else None,
-                                                               _charge_properties(st, args)))
-        out, (mp2, grad, stab, dip, pol, exc, cube, chg) = res if res is not None else (None, (None,) * 5 + ([], None, None))
+                                                               _charge_properties(st, args), st.ccsd(args.frozen_core or 0) if args.ccsd else None))
+        out, (mp2, grad, stab, dip, pol, exc, cube, chg, cc) = res if res is not None else (None, (None,) * 5 + ([], None, None, None))
     elif args.gradient:
         res = hf._stepped(system, config, False, lambda st: (st.mp2(args.frozen_core or 0) if args.mp2 else None, _gradient(st, pc_rows)))
         out, (mp2, grad) = res if res is not None else (None, (None, None))
@@ -577,6 +598,8 @@ def run_rhf(args) -> int:
         _print_solvent(solv)
     if mp2 is not None:
         _print_mp2(mp2, out.total_energy())
+    if cc is not None:
+        _print_ccsd(cc, out.total_energy())
     if grad is not None:
         _print_gradient(molecule, grad)
     for rows in pc_rows:
@@ -597,6 +620,8 @@ def run_rhf(args) -> int:
                "orbital_energies": list(out.orbital_energies), "seconds": elapsed, "timings_ms": out.timings_ms}
         if mp2 is not None:
             doc["mp2"] = _mp2_json(mp2, out.total_energy())
+        if cc is not None:
+            doc["ccsd"] = _ccsd_json(cc, out.total_energy())
         if grad is not None:
             doc["gradient"] = grad.tolist()
         if solv is not None:
@@ -618,6 +643,9 @@ def run_rhf(args) -> int:
         if chg is not None:
             doc.update(chg)
         print(json.dumps(doc))
+    if cc is not None and not cc.converged:
+        print("ccsd did not converge", file=sys.stderr)
+        return 101                                                          # (as an SCF that does not converge)
     if any(not e["converged"] for e in exc):
         return EXCITATIONS_FAILED
     return 0

@@ -371,6 +371,19 @@ void qc_quarter_last(hipStream_t st, int n, int rows, const double *C, int c0, i
 // caller has checked io's inputs.  matrices: the two d x d matrices of `kind` copied to the host (either nullable).
 int qc_excitations_device(qc_system *S, int nocc, const double *dC, const double *dEps, qc_excitations *io, double *vectors);
 int qc_excitation_matrices_device(qc_system *S, int nocc, const double *dC, const double *dEps, int kind, double *ApB, double *AmB);
+// closed-shell CCSD of an RHF state (qc_ccsd.hip): io's inputs have been checked by the caller; t1 (o x v) and t2 (o^2 x v^2) nullable, host.
+int qc_ccsd_device(qc_system *S, int nocc, const double *dC, const double *dEps, qc_ccsd *io, double *t1, double *t2);
+// C = alpha A B + beta C (row-major) for few rows and a long k: (tiles of C) x (k slices) workgroups sum their slices in ascending k into
+// `work` (qc_gemm_splitk_work doubles), a second launch adds the slices in slice order; a product of one slice writes C itself and
+// needs no work.  The slice count is a function of (m, n, k) alone.
+int qc_gemm_splitk_slices(int m, int n, int k, int *slice_len);
+size_t qc_gemm_splitk_work(int m, int n, int k);
+bool qc_gemm_splitk_pays(int m, int n, int k);          // qc_gemm would run under one wave per CU and k spans at least two slices
+void qc_gemm_splitk(hipStream_t st, int m, int n, int k, double alpha, const double *A, int64_t lda, const double *B, int64_t ldb, double beta,
+                    double *C, int64_t ldc, double *work);
+// out = alpha perm(in) + beta out of a dense four-index tensor: axis x of `out` is axis p[x] of `in` (dimensions d)
+void qc_permute4(hipStream_t st, const int d[4], const int p[4], double alpha, const double *in, double beta, double *out);
+int qc_debug_gemm_device(int which, int m, int n, int k, double alpha, const double *A, const double *B, double beta, double *C, int reps, double *ms);
 // nuclear gradient (qc_grad.hip): terms3 = [core | overlap | two-electron] x 3 natoms (host) from device densities dP (RHF D, UHF [Da; Db])
 // and dW; ms[4] = phase times (transform, one-electron, two-electron, sum) or null.  w: W of an SCF state's orbitals (enqueued).
 int qc_gradient_device(qc_system *S, int nspin, const double *dP, const double *dW, double *terms3, double *ms);

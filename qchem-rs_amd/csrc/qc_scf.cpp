@@ -1180,6 +1180,27 @@ int qc_scf_excitation_matrices(qc_scf_state *st, int kind, double *ApB, double *
     if (const int rc = ran_on_one_rank(st)) return rc;                  // (a pass has run, see above: the number of ranks)
     return qc_excitation_matrices_device(S, st->nocc[0], st->Cs.p, st->ws.p, kind, ApB, AmB);
 }
+// closed-shell CCSD from MO integrals: like qc_scf_mp2 the call reads Cs / ws and runs no Fock build
+int qc_scf_ccsd(qc_scf_state *st, qc_ccsd *io, double *t1, double *t2) {
+    if (!st || !io || st->passes == 0) return QC_ERR_INVALID;
+    const int n = st->S->nbasis, nocc = st->nocc[0];
+    if (io->n_frozen < 0 || io->n_frozen >= nocc || n - nocc <= 0 || io->max_iterations < 0 || io->diis_size < 0 || io->diis_size > 12 || !(io->tol >= 0.0))
+        return QC_ERR_INVALID;
+    if (st->uhf || st->solv) return QC_ERR_UNSUPPORTED;
+    if (const int rc = ran_on_one_rank(st)) return rc;
+    qc_system *S = st->S;
+    std::vector<double> eps(n);
+    QC_HIP_CHECK(hipStreamSynchronize(S->stream));
+    QC_HIP_CHECK(hipMemcpy(eps.data(), st->ws.p, eps.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int32_t no[2] = {nocc, 0};
+    if (const int rc = qc_mp2_validate(n, 1, eps.data(), no, io->n_frozen)) return rc;       // (a denominator >= 0)
+    return qc_ccsd_device(S, nocc, st->Cs.p, st->ws.p, io, t1, t2);
+}
+int qc_debug_gemm(int which, int m, int n, int k, double alpha, const double *A, const double *B, double beta, double *C, int reps, double *ms) {
+    if (which < 0 || which > 1 || m < 1 || n < 1 || k < 1 || !A || !B || !C || reps < 0) return QC_ERR_INVALID;
+    if (qc_device_ready() != QC_OK) return QC_ERR_NO_DEVICE;
+    return qc_debug_gemm_device(which, m, n, k, alpha, A, B, beta, C, reps, ms);
+}
 int qc_scf_begin_rhf_from(qc_system *S, const double *D, qc_scf_state **out) {
     if (!S || !D || !out) return QC_ERR_INVALID;
     return scf_begin(S, false, 0, 0, out, D, nullptr);

@@ -47,7 +47,7 @@ EXPORTS = ["qc_system_create", "qc_system_destroy", "qc_nbasis", "qc_nelectrons"
            "qc_scf_coefficients", "qc_scf_mp2", "qc_mp2", "qc_gradient", "qc_scf_gradient", "qc_gradient_timings",
            "qc_scf_stability_dim", "qc_scf_stability", "qc_scf_rotated_density", "qc_scf_begin_rhf_from", "qc_scf_begin_uhf_from",
            "qc_dipole_matrices", "qc_dipole_matrices_gpu", "qc_scf_dipole", "qc_scf_polarizability",
-           "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors",
+           "qc_scf_excitations", "qc_scf_excitation_matrices", "qc_schwarz_factors", "qc_scf_ccsd", "qc_debug_gemm",
            "qc_basis_on_points", "qc_potential_matrix", "qc_esp_records", "qc_density_on_points", "qc_esp_on_points", "qc_orbitals_on_points",
            "qc_scf_density_on_points", "qc_scf_esp_on_points", "qc_scf_orbitals_on_points", "qc_points_timings",
            "qc_multipole_count", "qc_multipole_matrices", "qc_multipole_matrices_gpu", "qc_scf_multipoles",
@@ -258,6 +258,35 @@ class ExcitationsOutput:
     vectors: Optional[np.ndarray] = None
 
 
+class _Ccsd(C.Structure):
+    _fields_ = [("n_frozen", C.c_int32), ("max_iterations", C.c_int32), ("diis_size", C.c_int32), ("reserved0", C.c_int32), ("tol", C.c_double),
+                ("e_mp2", C.c_double), ("e_ccsd", C.c_double), ("t1_diagnostic", C.c_double), ("t1_max", C.c_double), ("t2_max", C.c_double),
+                ("residual", C.c_double), ("iterations", C.c_int32), ("converged", C.c_int32), ("reserved1", C.c_int32 * 2),
+                ("ms_total", C.c_double), ("ms_tensor", C.c_double), ("ms_transform", C.c_double), ("ms_solve", C.c_double)]
+
+
+@dataclass
+class CcsdOutput:
+    """qc_ccsd: the MP2 (from the first T2) and CCSD correlation energies (Eh) of an RHF determinant, the T1 diagnostic
+    sqrt(sum t1^2 / o), the largest |t1| and |t2|, the last max |t_new - t_old|, and the wall times of the phases (ms).  t1 (o, v) and
+    t2 (o, o, v, v) with t2[i, j, a, b] = t2[j, i, b, a], when asked for; o counts the active occupied orbitals."""
+    e_mp2: float
+    e_ccsd: float
+    t1_diagnostic: float
+    t1_max: float
+    t2_max: float
+    residual: float
+    iterations: int
+    converged: bool
+    n_frozen: int
+    ms_total: float
+    ms_tensor: float
+    ms_transform: float
+    ms_solve: float
+    t1: Optional[np.ndarray] = None
+    t2: Optional[np.ndarray] = None
+
+
 class _Solvent(C.Structure):
     _fields_ = [("epsilon", C.c_double), ("x", C.c_double), ("scale", C.c_double), ("density", C.c_double)]
 
@@ -374,6 +403,8 @@ def lib():
         L.qc_scf_polarizability.argtypes = [vp, C.POINTER(_Polarizability), vp]
         L.qc_scf_excitations.argtypes = [vp, C.POINTER(_Excitations), vp]
         L.qc_scf_excitation_matrices.argtypes = [vp, C.c_int, vp, vp]
+        L.qc_scf_ccsd.argtypes = [vp, C.POINTER(_Ccsd), vp, vp]
+        L.qc_debug_gemm.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, C.c_double, vp, C.c_int, vp]
         L.qc_basis_on_points.argtypes = [vp, C.c_int64, vp, vp]
         L.qc_potential_matrix.argtypes = [vp, vp, vp]
         L.qc_esp_records.argtypes = [vp, vp]
@@ -1101,6 +1132,20 @@ class ScfStepper:
                                  np.array(io.transition_dipole[:3 * nroots]).reshape(nroots, 3), rc == QC_OK, bool(io.reference_unstable),
                                  int(io.nconverged), int(io.iterations), int(io.products), io.ms_total, io.ms_tensor, io.ms_transform, io.ms_solve, X)
 
+    def ccsd(self, n_frozen: int = 0, tol: float = 0.0, max_iterations: int = 0, diis_size: int = 0, amplitudes: bool = False) -> "CcsdOutput":
+        """Closed-shell CCSD correlation energy of an RHF state at its last orbitals (qc_scf_ccsd); the state is left as it was.
+        tol 0: 1e-8 on max |t_new - t_old|; max_iterations 0: 100; diis_size 0: 8 (1: no extrapolation)."""
+        io = _Ccsd(n_frozen=int(n_frozen), max_iterations=int(max_iterations), diis_size=int(diis_size), tol=float(tol))
+        t1 = t2 = None
+        if amplitudes:
+            nocc = self.system.n_electrons() // 2
+            o, v = nocc - int(n_frozen), self.system.n - nocc
+            t1, t2 = np.zeros((max(o, 0), max(v, 0))), np.zeros((max(o, 0), max(o, 0), max(v, 0), max(v, 0)))
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        rc = _check(lib().qc_scf_ccsd(self._st, C.byref(io), p(t1), p(t2)), "qc_scf_ccsd")
+        return CcsdOutput(io.e_mp2, io.e_ccsd, io.t1_diagnostic, io.t1_max, io.t2_max, io.residual, int(io.iterations), rc == QC_OK, int(io.n_frozen),
+                          io.ms_total, io.ms_tensor, io.ms_transform, io.ms_solve, t1, t2)
+
     def excitation_matrices(self, kind: int = 0):
         """(A + B, A - B) of an RHF state, (dim, dim) each, rows and columns [i * v + a] (qc_scf_excitation_matrices): kind 0 singlets,
         1 triplets.  Both exactly symmetric."""
@@ -1280,6 +1325,19 @@ def _stepped(system, config: HartreeFockConfig, uhf: bool, after):
         return None
     finally:
         st.close()
+
+
+def debug_gemm(A, B, Cm=None, alpha: float = 1.0, beta: float = 0.0, splitk: bool = True, reps: int = 0):
+    """alpha A B + beta C on the GPU through the split-k GEMM of the CCSD ladder (splitk) or the one-wave-per-tile GEMM (qc_debug_gemm).
+    Returns the product, or (product, times in ms) when reps > 0."""
+    A, B = np.ascontiguousarray(A, np.float64), np.ascontiguousarray(B, np.float64)
+    m, k = A.shape
+    n = B.shape[1]
+    out = np.zeros((m, n)) if Cm is None else np.array(Cm, np.float64, order="C")
+    ms = np.zeros(max(int(reps), 1))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib().qc_debug_gemm(1 if splitk else 0, m, n, k, float(alpha), p(A), p(B), float(beta), p(out), int(reps), p(ms)), "qc_debug_gemm")
+    return (out, ms) if reps > 0 else out
 
 
 def restricted_mp2(system, config: HartreeFockConfig, n_frozen: int = 0):
